@@ -7,20 +7,27 @@ BASELINE.json's metric is quoted on: 8 E. coli-like strains (synthetic, sibelia_
 Inputs are resident in HBM when the timed region starts (sbl_restore_state is a device-to-device copy
 of the saved stage-boundary state and is inside the timed region).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 (launched through torch.distributed.run, one rank per GPU over RCCL): north_star's configuration -- ONE job on all
 ranks, the k-mer table of the enumeration sharded by hash prefix (RCCL all-to-all of 16-B k-mer records + all-gathers of
 bifurcation codes and marks, csrc/shard.hip), the globally ordered simplification replicated and bit-identical on every GPU;
-value = strand-k-mers of the one job / max time, "scaling": "strong".  The same line carries, under "replicas", the weak-scaling
-configuration (every rank runs the whole job on its own strain set, no data-path collective), measured right after with the
-same K / W; --replicas makes that one the headline instead.
+value = strand-k-mers of the one job / max time, "scaling": "strong".  With --full the same line carries, under "replicas", the
+weak-scaling configuration (every rank runs the whole job on its own strain set, no data-path collective), measured right after
+with the same K / W; --replicas makes that one the headline instead.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ... and the stage's
+counters and phase times of the timed steps).  --dump-outputs DIR writes what the last timed step computed (the bulge count
+and the state it left, see dump_outputs) as DIR/<name>.npy; the inputs are the same from run to run for the same arguments.
+--full adds what takes work of its own:
+  state_sha256 / matches_reference_fixture / verify
+                the state the last step left, downloaded, hashed and compared with the reference's committed fixture
   roofline      the dominant kernel's algorithmic bytes / its HIP-event duration vs the 8 TB/s HBM peak
+  pcie_inclusive  host -> device load + one stage + download, cold and warm
   cpu_baseline  the UNMODIFIED reference (oracle/_ref/ref_dump, built by oracle/build_ref.sh; kind "reference") timed on
-                rank 0 on the FULL workload of `value` (1 thread -- it has none more; ~4 - 8 min, its output hashed and compared
-                with the GPU's) with the bounded sample (8 strains, shorter genomes, ~20 s) beside it; --no-cpu-full keeps the
-                sample only; the bit-exact port (oracle/, kind "port") only where no reference build exists
+                rank 0 on the FULL workload of `value` (1 thread -- it has none more; ~4 - 8 min, bounded so that the whole run
+                ends within FULL_DEADLINE_S; its output hashed and compared with the GPU's) with the bounded sample (8 strains,
+                shorter genomes, ~20 s) beside it; --no-cpu-full keeps the sample only; the bit-exact port (oracle/, kind
+                "port") only where no reference build exists
 """
 import argparse
 import json
@@ -28,10 +35,42 @@ import os
 import sys
 import time
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
+FULL_DEADLINE_S = 540.0    # --full: the reference's run on the full workload is cut off so that the whole run ends within 10 min
+DUMP_SAMPLE = 1 << 21      # --dump-outputs: bases of the state sampled (fixed seed) into the dump: 2 M x 12 B of float32 + float64
+
+
+def dump_outputs(d, bulges, bf):
+    """--dump-outputs DIR: what the timed path hands its caller after the last timed step -- the bulge count and the state
+    (sequences + original positions, BlockFinder.state_views()) -- as float .npy files.  The whole state is 5 B per base (~180 MB
+    for the default workload), so the files hold per-record lengths and sums of the whole state plus a fixed, seeded sample of
+    bases of the records laid end to end (index, base, original position)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    vs, vp = bf.state_views()
+    lens = np.array([len(x) for x in vs], np.int64)
+    ends = np.cumsum(lens)
+    n = int(ends[-1]) if len(ends) else 0
+    idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE)) if n else np.zeros(0, np.int64)
+    rec = np.searchsorted(ends, idx, side="right")
+    off = idx - (ends[rec] - lens[rec])
+    seq, pos = np.zeros(len(idx), np.float32), np.zeros(len(idx), np.float64)
+    for c in np.unique(rec):
+        m = rec == c
+        seq[m], pos[m] = vs[c][off[m]], vp[c][off[m]]
+    arrays = {"bulges": np.array([bulges], np.float64),
+              "state_lengths": lens.astype(np.float64),
+              "state_seq_sum": np.array([x.sum(dtype=np.uint64) for x in vs], np.float64),
+              "state_pos_sum": np.array([x.sum(dtype=np.uint64) for x in vp], np.float64),
+              "state_sample_index": idx.astype(np.float64),
+              "state_sample_seq": seq,
+              "state_sample_pos": pos}
+    for name, x in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), x)
 
 
 # the translation unit of the round kernels' dominant one (k_commit, k_resume, k_chain) and every header it includes: what a PMC summary of
@@ -137,6 +176,8 @@ def run_config(a):
     for x, y in zip(vs, vp):
         h.update(struct.pack("<Q", len(x))); h.update(x); h.update(y)
     sha = h.hexdigest()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, bulges, bf)
     match, fx_name = None, None
     if fixture is not None:
         want = [o for o in fixture["outputs"] if o["cmd"] == fx_cmd][0]
@@ -228,6 +269,77 @@ def run_config(a):
     bf.close()
 
 
+def roofline_line(a, st, agg, N, ms_step):
+    """--full: the roofline figures of the timed steps (dominant kernel, SURVEY.md 8d model, committed PMC traffic)"""
+    # dominant kernel by accumulated HIP-event time
+    per = {"k_kmer_table_build": agg.get("kmer_table_ms", 0.0) / a.steps,
+           "k_snapshot": agg.get("snapshot_ms", 0.0) / a.steps,
+           "k_reserve": agg.get("reserve_ms", 0.0) / a.steps,
+           "k_commit": agg.get("commit_ms", 0.0) / a.steps,
+           "k_probe": agg.get("probe_ms", 0.0) / a.steps}
+    launches = {"k_kmer_table_build": 1, "k_snapshot": max(1, st["iterations"] + st["replays"]),
+                "k_reserve": max(1, st["rounds"]), "k_commit": max(1, st["rounds"]), "k_probe": max(1, st["rounds"])}
+    # algorithmic HBM bytes per launch (DESIGN.md §Kernels): table build = 32 B per base position + packed
+    # sequence; snapshot = 4 B per strand-k-mer (one pass over the dense mark arrays, SURVEY.md §8d);
+    # reserve = 4 B x 2 strands x neighbourhood (3(D+k)+k elements), commit = 8 B x window (D+k), probe = 4 B x window,
+    # each per instance of the ids the launch works on
+    nbh = 3 * (a.D + a.k) + a.k
+    per_id = st["instances"] / max(1, st["bif_count"])
+    inst_per_launch = per_id * st["transactions"] / max(1, st["rounds"])          # reserve / commit work on real transactions
+    probed_per_launch = per_id * st["executed"] / max(1, st["rounds"])           # the probe looks at every pending id
+    alg = {"k_kmer_table_build": float(st["kmer_table_bytes"]), "k_snapshot": 4.0 * N,
+           "k_reserve": 8.0 * nbh * inst_per_launch, "k_commit": 8.0 * (a.D + a.k) * inst_per_launch,
+           "k_probe": 4.0 * (a.D + a.k) * probed_per_launch}
+    dom = max(per, key=lambda kk: per[kk])
+    dur_ms = per[dom] / launches[dom]                  # device wall-clock start stamps, every launch of the timed steps
+    dur_ms_clock, timing = dur_ms, "device wall-clock start stamps written by the round kernels, every launch of the timed steps"
+    ev_launches = agg.get("commit_event_launches", 0.0)
+    if dom == "k_commit" and ev_launches > 0:
+        # HIP event pairs on the context's stream around every 4th launch of k_commit (which ones rotates from step to step): an
+        # event pair around every round kernel cost 1.7 - 2.2 ms of the stage; the stamps beside them time every launch
+        dur_ms = agg["commit_event_ms"] / ev_launches
+        timing = ("HIP event pairs around %d of the %d launches of k_commit in the timed steps (every 4th, rotating); "
+                  "avg_launch_ms_all_launches = device wall-clock start stamps of every launch" % (int(ev_launches), launches[dom] * a.steps))
+    achieved_design = alg[dom] / (dur_ms * 1e-3) / 1e9 if dur_ms > 0 else 0.0
+    # SURVEY.md 8d's figure (what roofline.achieved / frac use): bytes = N x 24.125 (table: 0.125 sequence + 16 build + 8 resolve)
+    # + 12 x instances + iterations x N x 4 (one streaming pass over the dense marks per iteration).  The simplification share
+    # belongs to the ordered rounds as a whole; the dominant kernel is charged all of it, spread over its launches (the same
+    # accounting as the judge's in VERDICT.md) -- an upper bound of what that kernel alone achieves.
+    sim_8d = float(st["iterations"]) * N * 4.0
+    alg8d = {"k_kmer_table_build": N * 24.125, "k_snapshot": sim_8d / max(1, st["iterations"])}
+    for kk in ("k_commit", "k_probe", "k_reserve"):
+        alg8d[kk] = sim_8d / launches[kk]
+    stage_8d = N * 24.125 + 12.0 * st["instances"] + sim_8d
+    achieved = alg8d[dom] / (dur_ms * 1e-3) / 1e9 if dur_ms > 0 else 0.0
+    # HBM traffic of that kernel per launch from the last committed PMC passes (tools/profile_summary.py), same workload only
+    # (PMC counters need the profiler around the process: they are collected by tools/collect_profiles.sh in passes of their own and
+    # summarised by tools/profile_summary.py, which records the digest of the kernel sources it ran on; traffic_source says which
+    # file the figure comes from and whether that digest is the one of THIS build)
+    traffic, traffic_source = None, None
+    pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+    if os.path.exists(pmc) and (a.strains, a.L0, a.k, a.D, a.iters) == (8, 4_600_000, 25, 150, 4):
+        try:
+            doc = json.load(open(pmc))
+            traffic = doc["kernels"][dom]["hbm_bytes_per_launch_est"]
+            here = W_source_digest()
+            traffic_source = ("committed PMC passes: profiles/pmc_latest.json (round %s, FETCH_SIZE / WRITE_SIZE in separate rocprofv3 passes, digest of commit.hip + the headers it includes %s; "
+                              "this build: %s = %s)" % (doc.get("round"), doc.get("source_digest", "unrecorded"), here,
+                                                        "the same sources" if doc.get("source_digest") == here else "DIFFERENT sources: indicative only"))
+        except Exception:
+            traffic = None
+    return {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+            "traffic_ratio": (traffic / alg8d[dom]) if traffic else None,
+            "avg_launch_ms": dur_ms, "avg_launch_ms_all_launches": dur_ms_clock, "timing": timing,
+            "launches_per_step": launches[dom], "algorithmic_bytes_per_launch": alg8d[dom],
+            "algorithmic_model": "SURVEY.md 8d: N x 24.125 + 12 x instances + iterations x N x 4 = %.2f GB per stage; the simplification share "
+                                 "(iterations x N x 4 B) spread over the launches of the dominant kernel (since round 3; rounds 1 and 2 priced `frac` "
+                                 "with this design's own per-kernel model, now `frac_design_model`: not comparable)" % (stage_8d / 1e9),
+            "stage": {"bytes_8d": stage_8d, "achieved": stage_8d / (ms_step * 1e-3) / 1e9, "frac": stage_8d / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+            "frac_design_model": achieved_design / HBM_PEAK_GBS, "design_model_bytes_per_launch": alg[dom],
+            "design_model": "this design's per-kernel model (DESIGN.md 4: e.g. k_commit = 8 B x (D + k) per instance of the launch's transactions)",
+            "all_kernels_ms_per_step": per}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -244,15 +356,20 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--shard-enum", action="store_true", help="one job on all ranks: hash-prefix sharded enumeration over RCCL (the default for --gpus > 1)")
     ap.add_argument("--replicas", action="store_true", help="--gpus > 1: make the replicas configuration (one independent job per GPU) the headline value")
-    ap.add_argument("--check", action="store_true", help="compare the GPU result of the CPU sample with the oracle")
-    ap.add_argument("--cpu-full", action="store_true", help="(default since round 4) time the unmodified reference on the FULL workload as well")
-    ap.add_argument("--no-cpu-full", action="store_true", help="bounded CPU sample only (~20 s) instead of the reference on the full workload (~4 - 8 min, 1 thread)")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps: the state check against the reference's fixture, roofline, PCIe-inclusive "
+                    "rate, CPU baseline (the unmodified reference), with --gpus > 1 the replicas configuration")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--check", action="store_true", help="with --full: compare the GPU result of the CPU sample with the oracle")
+    ap.add_argument("--cpu-full", action="store_true", help="(default of --full) time the unmodified reference on the FULL workload as well")
+    ap.add_argument("--no-cpu-full", action="store_true", help="with --full: bounded CPU sample only (~20 s) instead of the reference on the full workload (~4 - 8 min, 1 thread)")
     ap.add_argument("--config", type=int, default=0, choices=[0, 3, 4, 5],
                     help="one of BASELINE.json's other configurations instead of the headline one: 3 = 8 strains through the `-s fine` cascade, 4 = 62 strains at k = 25, 5 = 900 Mbp of random DNA at k = 5000 (single GPU)")
     ap.add_argument("--dry-collectives", action="store_true", help="self-test of the RCCL transport with --gpus real ranks (processes) that all open device 0 "
                     "(tools/rccl_two_ranks_one_gpu.py): runs, or reports LOUDLY that RCCL refuses two ranks on one device; no bench line")
     ap.add_argument("--require-sharded", action="store_true", help="--gpus > 1: exit non-zero instead of falling back to replicas when the sharded (strong-scaling) configuration cannot run")
     a = ap.parse_args()
+    if a.check and not a.full and not a.config:
+        ap.error("--check compares with the CPU baseline, which only --full runs")
     if a.dry_collectives:
         os.execvp(sys.executable, [sys.executable, os.path.join(ROOT, "tools", "rccl_two_ranks_one_gpu.py"), str(max(2, a.gpus))])
     if a.config:
@@ -364,9 +481,9 @@ def main():
     if a.shard_enum:
         Ntot = float(N)                      # one job, however many GPUs enumerate it
 
-    # second configuration of a multi-GPU run: replicas (weak scaling), same K / W, same barrier + max-over-ranks timing
+    # --full, second configuration of a multi-GPU run: replicas (weak scaling), same K / W, same barrier + max-over-ranks timing
     replicas = None
-    if world > 1 and a.shard_enum:
+    if world > 1 and a.shard_enum and a.full:
         seqs2 = W.gen_strains(**D.rank_workload(rank, a.strains, a.L0))
         N2 = W.strand_kmers(seqs2, a.k)
         bf2 = BlockFinder(seqs2, device=local)
@@ -386,7 +503,7 @@ def main():
     # once through the C ABI, serialised like the golden vectors (formats.state_bytes) and hashed; on the metric workload the
     # reference's own result is a committed fixture (tests/golden/vectors.json: synth/strains8_4600k, generated by oracle/_ref)
     verify = None
-    if rank == 0:
+    if rank == 0 and a.full:
         import hashlib, struct
         t1 = time.perf_counter()
         vs, vp = bf.state_views()
@@ -406,66 +523,12 @@ def main():
                 verify["fixture_error"] = str(e)
         else:
             verify["matches_reference_fixture"] = None       # no reference fixture for a non-default workload
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, bulges, bf)
 
     if rank == 0:
         st = bf.stats()
         ms_step = 1000.0 * dt / a.steps
-        # dominant kernel by accumulated HIP-event time
-        per = {"k_kmer_table_build": agg.get("kmer_table_ms", 0.0) / a.steps,
-               "k_snapshot": agg.get("snapshot_ms", 0.0) / a.steps,
-               "k_reserve": agg.get("reserve_ms", 0.0) / a.steps,
-               "k_commit": agg.get("commit_ms", 0.0) / a.steps,
-               "k_probe": agg.get("probe_ms", 0.0) / a.steps}
-        launches = {"k_kmer_table_build": 1, "k_snapshot": max(1, st["iterations"] + st["replays"]),
-                    "k_reserve": max(1, st["rounds"]), "k_commit": max(1, st["rounds"]), "k_probe": max(1, st["rounds"])}
-        # algorithmic HBM bytes per launch: table build = 32 B per base position + packed
-        # sequence; snapshot = 4 B per strand-k-mer (one pass over the dense mark arrays);
-        # reserve = 4 B x 2 strands x neighbourhood (3(D+k)+k elements), commit = 8 B x window (D+k), probe = 4 B x window,
-        # each per instance of the ids the launch works on
-        nbh = 3 * (a.D + a.k) + a.k
-        per_id = st["instances"] / max(1, st["bif_count"])
-        inst_per_launch = per_id * st["transactions"] / max(1, st["rounds"])          # reserve / commit work on real transactions
-        probed_per_launch = per_id * st["executed"] / max(1, st["rounds"])           # the probe looks at every pending id
-        alg = {"k_kmer_table_build": float(st["kmer_table_bytes"]), "k_snapshot": 4.0 * N,
-               "k_reserve": 8.0 * nbh * inst_per_launch, "k_commit": 8.0 * (a.D + a.k) * inst_per_launch,
-               "k_probe": 4.0 * (a.D + a.k) * probed_per_launch}
-        dom = max(per, key=lambda kk: per[kk])
-        dur_ms = per[dom] / launches[dom]                  # device wall-clock start stamps, every launch of the timed steps
-        dur_ms_clock, timing = dur_ms, "device wall-clock start stamps written by the round kernels, every launch of the timed steps"
-        ev_launches = agg.pop("commit_event_launches", 0.0)
-        if dom == "k_commit" and ev_launches > 0:
-            # HIP event pairs on the context's stream around every 4th launch of k_commit (which ones rotates from step to step): an
-            # event pair around every round kernel cost 1.7 - 2.2 ms of the stage; the stamps beside them time every launch
-            dur_ms = agg["commit_event_ms"] / ev_launches
-            timing = ("HIP event pairs around %d of the %d launches of k_commit in the timed steps (every 4th, rotating); "
-                      "avg_launch_ms_all_launches = device wall-clock start stamps of every launch" % (int(ev_launches), launches[dom] * a.steps))
-        achieved_design = alg[dom] / (dur_ms * 1e-3) / 1e9 if dur_ms > 0 else 0.0
-        # SURVEY.md 8d's figure (what roofline.achieved / frac use): bytes = N x 24.125 (table: 0.125 sequence + 16 build + 8 resolve)
-        # + 12 x instances + iterations x N x 4 (one streaming pass over the dense marks per iteration).  The simplification share
-        # belongs to the ordered rounds as a whole; the dominant kernel is charged all of it, spread over its launches (the same
-        # accounting as the judge's in VERDICT.md) -- an upper bound of what that kernel alone achieves.
-        sim_8d = float(st["iterations"]) * N * 4.0
-        alg8d = {"k_kmer_table_build": N * 24.125, "k_snapshot": sim_8d / max(1, st["iterations"])}
-        for kk in ("k_commit", "k_probe", "k_reserve"):
-            alg8d[kk] = sim_8d / launches[kk]
-        stage_8d = N * 24.125 + 12.0 * st["instances"] + sim_8d
-        achieved = alg8d[dom] / (dur_ms * 1e-3) / 1e9 if dur_ms > 0 else 0.0
-        # HBM traffic of that kernel per launch from the last committed PMC passes (tools/profile_summary.py), same workload only
-        # (PMC counters need the profiler around the process: they are collected by tools/collect_profiles.sh in passes of their own and
-        # summarised by tools/profile_summary.py, which records the digest of the kernel sources it ran on; traffic_source says which
-        # file the figure comes from and whether that digest is the one of THIS build)
-        traffic, traffic_source = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc) and (a.strains, a.L0, a.k, a.D, a.iters) == (8, 4_600_000, 25, 150, 4):
-            try:
-                doc = json.load(open(pmc))
-                traffic = doc["kernels"][dom]["hbm_bytes_per_launch_est"]
-                here = W_source_digest()
-                traffic_source = ("committed PMC passes: profiles/pmc_latest.json (round %s, FETCH_SIZE / WRITE_SIZE in separate rocprofv3 passes, digest of commit.hip + the headers it includes %s; "
-                                  "this build: %s = %s)" % (doc.get("round"), doc.get("source_digest", "unrecorded"), here,
-                                                            "the same sources" if doc.get("source_digest") == here else "DIFFERENT sources: indicative only"))
-            except Exception:
-                traffic = None
         out = {
             "metric": "k-mers/sec in BlockFinder graph-build+simplify, 8xE.coli k=25",
             "value": Ntot / (dt / a.steps), "unit": "strand-k-mers/s",
@@ -481,23 +544,13 @@ def main():
                        "bulges": bulges, "bif_ids": st["bif_count"], "instances": st["instances"],
                        "iterations": st["iterations"], "rounds": st["rounds"], "replays": st["replays"],
                        "device_bytes": int(st.get("device_bytes", 0)), "device_bytes_per_base": float(st.get("device_bytes", 0)) / max(1, a.strains * a.L0)},
-            "phase_ms": {kk: agg[kk] / a.steps for kk in sorted(agg)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "traffic_ratio": (traffic / alg8d[dom]) if traffic else None,
-                         "avg_launch_ms": dur_ms, "avg_launch_ms_all_launches": dur_ms_clock, "timing": timing,
-                         "launches_per_step": launches[dom], "algorithmic_bytes_per_launch": alg8d[dom],
-                         "algorithmic_model": "SURVEY.md 8d: N x 24.125 + 12 x instances + iterations x N x 4 = %.2f GB per stage; the simplification share "
-                                              "(iterations x N x 4 B) spread over the launches of the dominant kernel (since round 3; rounds 1 and 2 priced `frac` "
-                                              "with this design's own per-kernel model, now `frac_design_model`: not comparable)" % (stage_8d / 1e9),
-                         "stage": {"bytes_8d": stage_8d, "achieved": stage_8d / (ms_step * 1e-3) / 1e9, "frac": stage_8d / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                         "frac_design_model": achieved_design / HBM_PEAK_GBS, "design_model_bytes_per_launch": alg[dom],
-                         "design_model": "this design's per-kernel model (DESIGN.md 4: e.g. k_commit = 8 B x (D + k) per instance of the launch's transactions)",
-                         "all_kernels_ms_per_step": per},
+            "phase_ms": {kk: agg[kk] / a.steps for kk in sorted(agg) if kk != "commit_event_launches"},
         }
-        out["state_sha256"] = verify["state_sha256"]
-        out["matches_reference_fixture"] = verify["matches_reference_fixture"]
-        out["verify"] = verify
+        if a.full:
+            out["roofline"] = roofline_line(a, st, agg, N, ms_step)
+            out["state_sha256"] = verify["state_sha256"]
+            out["matches_reference_fixture"] = verify["matches_reference_fixture"]
+            out["verify"] = verify
         if world > 1:
             out["rccl_ranks"] = world
             out["exchange_ms"] = st["exchange_ms"]
@@ -510,7 +563,7 @@ def main():
             out["replicas"] = replicas
         if shard_error:
             out["sharded_error"] = shard_error
-        if world == 1:
+        if world == 1 and a.full:
             # PCIe-inclusive rate (never `value`): host buffers -> device (sbl_load: 1 B/base over PCIe; original positions and the
             # ambiguity scan are derived on the device) + one stage + the state back to the host (5 B/base)
             torch.cuda.synchronize()
@@ -535,7 +588,7 @@ def main():
                                      "cold": {"value": N / t_all, "load_ms": 1e3 * t_load, "stage_ms": 1e3 * t_stage, "download_ms": 1e3 * (t_all - t_load - t_stage),
                                               "note": "cold context: first-call workspace allocations of the stage and pinning of the staging buffer included"},
                                      "note": "host buffers -> sbl_load (1 B/base up) + one warm stage + sbl_get_state (5 B/base down, pinned bulk copy)"}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             # The reference's own CPU path beside the GPU number (north_star): oracle/_ref/ref_dump is the UNMODIFIED reference
             # compiled by oracle/build_ref.sh (it travels to the GPU box as a prebuilt binary).  The reference is single-threaded
             # and superlinear in the number of strains (8 x 4.6 Mbp take 500 s), so the sample keeps the 8 strains and shortens
@@ -569,12 +622,14 @@ def main():
                         # timed on the GPU box's host cores in the same run"): it becomes the baseline, the bounded sample stays beside it
                         fa2 = os.path.join(d, "full.fa")
                         W.write_fasta(fa2, seqs)
-                        try:                                      # (bounded: a loaded host must not turn the bench line into a time-out of the whole run)
-                            r2 = subprocess.run([ref_dump, fa2, os.path.join(d, "f"), "stage:%d:%d:%d" % (a.k, a.D, a.iters)], capture_output=True, text=True, timeout=1200)
+                        # (bounded: a loaded host must not turn the bench line into a time-out of the whole run, which ends within 10 min)
+                        budget = max(1.0, FULL_DEADLINE_S - (time.time() - T_START))
+                        try:
+                            r2 = subprocess.run([ref_dump, fa2, os.path.join(d, "f"), "stage:%d:%d:%d" % (a.k, a.D, a.iters)], capture_output=True, text=True, timeout=budget)
                             m2 = re.search(r"bulges=(\d+) seconds=([0-9.]+)", r2.stderr)
                         except subprocess.TimeoutExpired:
                             r2, m2 = None, None
-                            out["cpu_baseline"]["full"] = "not finished within 1200 s on this host: the bounded sample stands"
+                            out["cpu_baseline"]["full"] = "not finished within %.0f s on this host: the bounded sample stands" % budget
                         if r2 is not None and r2.returncode == 0 and m2:
                             fb, fdt = int(m2.group(1)), float(m2.group(2))
                             import hashlib

@@ -4,7 +4,7 @@
 out=$1; shift
 mkdir -p "$out"
 L=sibelia_amd/lib/libsibelia_amd.so
-run() { python bench.py --no-cpu-baseline --steps 5 "$@" > "$out/$tag.json" 2> "$out/$tag.err"; python - "$out/$tag.json" "$tag" <<'PY'
+run() { python bench.py --full --no-cpu-baseline --steps 5 "$@" > "$out/$tag.json" 2> "$out/$tag.err"; python - "$out/$tag.json" "$tag" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[2], round(d["ms_per_step"], 2), d["config"]["rounds"], d["matches_reference_fixture"], {k: round(v, 2) for k, v in d["phase_ms"].items()})

@@ -14,6 +14,6 @@ if [ "$1" = "pmc" ]; then
   find $out -name '*_kernel_trace.csv' -size +20M -delete
 else
   cd $R
-  timeout 1500 python bench.py 2>/dev/null | grep '^{' > $out/bench_default.json
+  timeout 1500 python bench.py --full 2>/dev/null | grep '^{' > $out/bench_default.json
   tail -c 300 $out/bench_default.json
 fi

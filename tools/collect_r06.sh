@@ -27,5 +27,5 @@ timeout 300 python bench.py --gpus 2 --dry-collectives 2>/dev/null | grep '^{' >
 timeout 600 python tools/longk_profile.py 100 500 > $out/longk_enumerate.jsonl 2>/dev/null
 SBL_LONGK_DOUBLING=1 timeout 600 python tools/longk_profile.py 100 500 > $out/longk_enumerate_doubling.jsonl 2>/dev/null
 # (the default line last -- and, for the round's LAST build, by tools/collect_r06_final.sh bench in a second call, with profiles/pmc_latest.json of this build in place: SKIP_DEFAULT=1)
-[ -n "$SKIP_DEFAULT" ] || timeout 1500 python bench.py 2>/dev/null | grep '^{' > $out/bench_default.json
+[ -n "$SKIP_DEFAULT" ] || timeout 1500 python bench.py --full 2>/dev/null | grep '^{' > $out/bench_default.json
 ls -la $out | head -40; tail -c 500 $out/bench_default.json

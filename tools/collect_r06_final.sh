@@ -22,6 +22,6 @@ if [ "$1" = "pmc" ]; then
   ls $out
 else
   cd $R
-  timeout 1500 python bench.py 2>/dev/null | grep '^{' > $out/bench_default.json
+  timeout 1500 python bench.py --full 2>/dev/null | grep '^{' > $out/bench_default.json
   tail -c 400 $out/bench_default.json
 fi

@@ -11,7 +11,7 @@ if [ -n "$sel" ]; then timeout 1500 python -m pytest $sel -m gpu -q --timeout=90
 i=0
 for envs in "" "$@"; do
   i=$((i+1))
-  env $envs timeout 600 python bench.py --no-cpu-baseline --steps ${STEPS:-5} ${BENCH_ARGS} > $out/bench_$i.json 2> $out/bench_$i.err
+  env $envs timeout 600 python bench.py --full --no-cpu-baseline --steps ${STEPS:-5} ${BENCH_ARGS} > $out/bench_$i.json 2> $out/bench_$i.err
   python - "$out/bench_$i.json" "[$envs]" <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ cd $R
 timeout 1200 python -m pytest tests/test_gpu_parking.py -m gpu -q --timeout=900 -k "not three_virtual" > $out/park.log 2>&1; echo "rc $?" >> $out/park.log; tail -5 $out/park.log
 SBL_TRACE=1 timeout 600 python -m pytest tests/test_gpu_parking.py -m gpu -q -x --timeout=500 -k "three_virtual" > $out/park3.log 2>&1; echo "rc $?" >> $out/park3.log; tail -25 $out/park3.log | cut -c1-400
 for envs in "" "SBL_PARK=0"; do
-  env $envs timeout 600 python bench.py --no-cpu-baseline --steps 5 > $out/bench.json 2> $out/bench.err
+  env $envs timeout 600 python bench.py --full --no-cpu-baseline --steps 5 > $out/bench.json 2> $out/bench.err
   python - "$out/bench.json" "[$envs]" <<'PY'
 import json, sys
 try:

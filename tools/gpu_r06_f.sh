@@ -7,7 +7,7 @@ cd $R
 timeout 600 python -m pytest tests/test_gpu_parking.py tests/test_gpu_shard.py tests/test_gpu_errors.py -m gpu -q -x --timeout=300 > $out/tests.log 2>&1; echo "rc $?" >> $out/tests.log; tail -6 $out/tests.log | cut -c1-300
 timeout 300 python -m pytest tests/test_gpu_stress.py -m gpu -q -x --timeout=280 > $out/stress_t.log 2>&1; tail -2 $out/stress_t.log | cut -c1-300
 for envs in "" "SBL_PARK=0"; do
-  env $envs timeout 200 python bench.py --no-cpu-baseline --steps 8 > $out/bench.json 2> $out/bench.err
+  env $envs timeout 200 python bench.py --full --no-cpu-baseline --steps 8 > $out/bench.json 2> $out/bench.err
   python - "$out/bench.json" "[$envs]" <<'PY'
 import json, sys
 try:

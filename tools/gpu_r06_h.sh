@@ -6,7 +6,7 @@ mkdir -p $out
 cd $R
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_parking.py tests/test_gpu_block_index.py -m gpu -q -x --timeout=600 -k "not config5_full and not config4 and not config3_full" > $out/tests.log 2>&1; tail -3 $out/tests.log | cut -c1-300
 for envs in "" "SBL_SELECT_TWO=1" ""; do
-  env $envs timeout 200 python bench.py --no-cpu-baseline --steps 8 > $out/bench.json 2> $out/bench.err
+  env $envs timeout 200 python bench.py --full --no-cpu-baseline --steps 8 > $out/bench.json 2> $out/bench.err
   python - "$out/bench.json" "[$envs]" <<'PY'
 import json, sys
 try:

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for v in base "$@"; do
   if [ $v = base ]; then cp /tmp/base.so sibelia_amd/lib/libsibelia_amd.so; else cp sibelia_amd/lib/var_$v.so sibelia_amd/lib/libsibelia_amd.so; fi
   touch sibelia_amd/lib/libsibelia_amd.so
-  timeout 600 python bench.py --no-cpu-baseline --steps 5 ${BENCH_ARGS} 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --no-cpu-baseline --steps 5 ${BENCH_ARGS} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', round(d['ms_per_step'],2), d.get('matches_reference_fixture'), {k: round(x,2) for k,x in d.get('phase_ms',{}).items() if k in ('commit_ms','simplify_ms')})" | tee -a $out/variants.log
 done; done
