@@ -128,6 +128,9 @@ struct GraphView {
 // every round until the transaction is through -- and whoever would read such a size waits, exactly as for an id inside the core.
 // (Found by tools/stress.py seed 93194: a neighbour read a size one too high, collapsed in the other direction and counted one bulge less.)
 #define PARK_IMG 12288u
+#ifndef COMMIT_FAST_BYTES
+#define COMMIT_FAST_BYTES 8192               // LDS scratch of a transaction; with Txn / BulgeWork ~9 KB per workgroup = 17 workgroups per CU (12 KB: 12, and 4 % slower)
+#endif
 #define CTR_PARKED (CTR_DETAIL + 8)      // parked transactions at the moment
 #define CTR_PLIST (CTR_DETAIL + 10)      // entries of GraphView::park_list in this round (reset behind every round by k_select_write)
 // (the tag is 11 bits of a 12-bit round: finished markers are swept every 1024 rounds, DeviceBackend::commit, so that none survives to the round with the same tag)
@@ -555,7 +558,9 @@ __host__ __device__ inline uint32_t bt_count_instances(const GraphView &g, uint3
 }
 
 // ListPositions (bulgeremoval.cpp:335) + all scratch of the transaction.  False when fewer than two instances.
-__host__ __device__ inline bool bt_setup(Txn &t, BulgeWork &w, bool lite = false, bool fill_list = true)
+// park_aware: with parked transactions about (GraphView::any_parked) an id may have fewer live nodes than its list sizes say -- the erased
+// nodes of a parked transaction leave the sizes at its Cleanup (PARK_IMG); as wave_setup<PARK_AWARE> (tests/hostsim's parking model)
+__host__ __device__ inline bool bt_setup(Txn &t, BulgeWork &w, bool lite = false, bool fill_list = true, bool park_aware = false)
 {
 	GraphView &g = t.g;
 	uint32_t k = g.k, D = g.D;
@@ -604,6 +609,7 @@ __host__ __device__ inline bool bt_setup(Txn &t, BulgeWork &w, bool lite = false
 	for (uint32_t s = 0; s < 2; s++)
 		for (uint32_t nd = g.head[s][t.id]; nd != BT_NONE; nd = g.nnext[nd])
 			if (!g.ndead[nd] && m < n) { w.start[m] = (nd << 1) | s; w.sel[m] = g.nslot[nd]; m++; }
+	if (park_aware && m < n) { w.n = m; return m >= 2; }
 	if (m != n) { t.err |= BT_ERR_SCRATCH; return false; }     // cannot happen on a consistent graph
 	return true;
 }

@@ -1191,9 +1191,6 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 
 // One wave per window entry: ownership check on the claim list (64 lanes), then RemoveBulges with lane 0 taking
 // the decisions on the cached windows and all lanes rescanning them after every collapse.
-#ifndef COMMIT_FAST_BYTES
-#define COMMIT_FAST_BYTES 8192               // LDS scratch of a transaction; with Txn / BulgeWork ~9 KB per workgroup = 17 workgroups per CU (12 KB: 12, and 4 % slower)
-#endif
 // ---- parked transactions (GraphView::park_of): the LDS state of a transaction at the end of its arena slice (PARK_IMG bytes, bulge_txn.h)
 // The image holds raw LDS addresses (t.fscr, the w.* arrays laid out in `fast`, absh.skey / sval): it is only valid in a kernel that
 // places t, w, absh and fast where the parking kernel had them.  k_commit and k_resume instantiate the same declarations

@@ -60,7 +60,7 @@ __host__ __device__ inline bool ss_probe(const GraphView &g, uint32_t widx, uint
 	BulgeWork w;
 	t.init(g, id, widx, 3, arena, arena_bytes);
 	bool has = false;
-	if (bt_setup(t, w, true)) { bt_scan_all(t, w); bt_end_chars(t, w); has = bt_any_bulges(t, w, true); }
+	if (bt_setup(t, w, true, true, g.any_parked != 0)) { bt_scan_all(t, w); bt_end_chars(t, w); has = bt_any_bulges(t, w, true); }
 	if (err_out) *err_out = t.err;
 	if (t.err) return true;                    // undecidable here: let the commit path sort it out
 	if (!has) { g.need[id] = 0; g.touch[id] = 0; bt_atomic_add(&g.ctr[CTR_COMMITTED], 1u); }   // verdict taken now: clean until touched again
@@ -71,27 +71,30 @@ __host__ __device__ inline bool ss_probe(const GraphView &g, uint32_t widx, uint
 // alone: nothing else is in flight (solo round / serial chain) -- the precondition of lazy windows in the kernels, where an ordered
 // round needs the set of windows a collapse dirtied for its reservation check; this one-thread form has no such check and takes
 // lazy windows whenever the id is large enough (g.lazy_min lets the tests force them everywhere)
-__host__ __device__ inline void ss_commit_run(const GraphView &g, uint32_t widx, uint8_t *arena, uint32_t arena_bytes,
-                                              uint8_t *fast = nullptr, uint32_t fast_bytes = 0)
+// Resumable in three parts, in the caller's Txn / BulgeWork (the kernels' LDS): ss_commit_begin (verdict pass, writer pass up to its
+// loops), ss_commit_loop (until the loops are over, or -- park_cap != 0 -- until a collapse beyond park_cap is decided: the caller may
+// then park t, w and the fast scratch and call the loop again later with decided = true, as commit.hip's park_store / park_load do),
+// ss_commit_end (Cleanup if deferred, counters).  lazy_ok: the kernels take lazy windows only when the id runs alone (tests/hostsim's
+// parking model); defer_cleanup: Cleanup at the END of the transaction, not when the loops finish.
+// ss_commit_begin: < 0 the transaction is over already (counted), else the loop's first `more`; *dirty: the loop's dirty-window bits
+__host__ __device__ inline int ss_commit_begin(const GraphView &g, Txn &t, BulgeWork &w, uint32_t widx, uint8_t *arena, uint32_t arena_bytes,
+                                               uint8_t *fast, uint32_t fast_bytes, bool lazy_ok, bool defer_cleanup, uint64_t **dirty)
 {
 	uint32_t id = g.win[widx];
 	g.need[id] = 0;                            // cleared BEFORE running: a later push must survive
 	g.touch[id] = 1;                           // whatever it leaves behind is examined again by the next snapshot
-	Txn t;
-	BulgeWork w;
 	t.init(g, id, widx, 1, arena, arena_bytes);
 	bool has = false;
-	if (bt_setup(t, w)) { bt_scan_all(t, w); bt_end_chars(t, w); has = bt_any_bulges(t, w, true); }
-	if (t.err & BT_ERR_SCRATCH) { ss_mark_big(g, id); return; }   // nothing written yet: big-arena path
-	bt_atomic_add(&g.ctr[CTR_COMMITTED], 1u);
-	bt_atomic_add(&g.ctr[CTR_TXN], 1u);
-	if (!has) return;
+	if (bt_setup(t, w, false, true, g.any_parked != 0)) { bt_scan_all(t, w); bt_end_chars(t, w); has = bt_any_bulges(t, w, true); }
+	if (t.err & BT_ERR_SCRATCH) { ss_mark_big(g, id); return -1; }   // nothing written yet: big-arena path
+	if (!has) { bt_atomic_add(&g.ctr[CTR_COMMITTED], 1u); bt_atomic_add(&g.ctr[CTR_TXN], 1u); return -1; }
 	t.init(g, id, widx, 2, arena, arena_bytes);                   // writer pass: publish reads and writes
 	t.fscr = fast; t.fscr_cap = fast_bytes;                       // (the kernels put summaries, mark lists and the AnyBulges map in LDS)
+	t.defer_cleanup = defer_cleanup;
 	w.ret = 0;
-	bt_setup(t, w);
+	bt_setup(t, w, false, true, g.any_parked != 0);
 	bt_scan_all(t, w);
-	w.lazy = !t.err && w.wep != nullptr;
+	w.lazy = lazy_ok && !t.err && w.wep != nullptr;
 	w.jscan = w.lazy;                                              // (exercises the caller-side J search of the kernels)
 	w.wfill = w.lazy;                                              // (... and the caller-side FillVisit)
 	w.pscan = w.lazy;                                              // (... and the caller-side search for the next I that has a J)
@@ -99,11 +102,17 @@ __host__ __device__ inline void ss_commit_run(const GraphView &g, uint32_t widx,
 	int more = !t.err && bt_rb_begin(t, w) ? 1 : 0;
 	// windows that see the region a collapse rewrites (target start .. end of its look-forward flank) are the only ones whose
 	// cache changes: like k_commit (simplify.hip), only those are rescanned -- normally just the target's own window
-	uint64_t *dirty = more && !w.lazy ? (uint64_t *)t.alloc(((w.n + 63) / 64) * 8) : nullptr;
-	if (more && !w.lazy && !dirty) more = 0;
+	*dirty = more && !w.lazy ? (uint64_t *)t.alloc(((w.n + 63) / 64) * 8) : nullptr;
+	if (more && !w.lazy && !*dirty) more = 0;
 	w.use_stale = more && !w.lazy && g.test_lazy_map != 0 && w.n <= 256;      // (tests/hostsim, HOSTSIM_LAZY_MAP: ... and stale-marking instead of eager rescans)
+	return more;
+}
+// true: parked with its next collapse decided (w.ret - w.ret0 > park_cap, never with lazy windows), nothing of it done yet
+__host__ __device__ inline bool ss_commit_loop(const GraphView &g, Txn &t, BulgeWork &w, int more, uint64_t *dirty, uint32_t park_cap = 0, bool decided = false)
+{
 	while (more) {
-		more = bt_rb_run(t, w);
+		if (!decided) more = bt_rb_run(t, w);
+		decided = false;
 		if (t.err) break;
 		if (more == 3) bt_rb_next_j(t, w);
 		else if (more == 4) bt_rb_mults(t, w);
@@ -120,6 +129,8 @@ __host__ __device__ inline void ss_commit_run(const GraphView &g, uint32_t widx,
 				w.stale[0] = w.stale[1] = w.stale[2] = w.stale[3] = 0;
 			}
 			if (t.err) break;
+		} else if (more && park_cap && !w.lazy && w.ret - w.ret0 > park_cap) {
+			return true;                                               // (commit.hip: the condition of park_store)
 		} else if (more && w.lazy) {
 			bt_collapse(t, w, w.c_src, w.c_dS, w.c_tgt, w.c_dT);
 			if (t.err) break;
@@ -148,11 +159,29 @@ __host__ __device__ inline void ss_commit_run(const GraphView &g, uint32_t widx,
 			if (w.mk_overflow) { bt_marks_to_arena(t, w); if (!t.err) for (uint32_t i = 0; i < w.n; i++) bt_scan_instance(t, w, i); }
 		}
 	}
+	return false;
+}
+__host__ __device__ inline void ss_commit_end(const GraphView &g, Txn &t, BulgeWork &w)
+{
+	if (t.defer_cleanup && !t.err) t.cleanup();                    // (k_commit: Cleanup by all lanes once the loops are over)
+	bt_atomic_add(&g.ctr[CTR_COMMITTED], 1u);
+	bt_atomic_add(&g.ctr[CTR_TXN], 1u);
 	if (t.err) {
-		if (!t.wrote && t.err == BT_ERR_SCRATCH) { ss_mark_big(g, id); return; }
+		if (!t.wrote && t.err == BT_ERR_SCRATCH) { ss_mark_big(g, t.id); return; }
 		bt_atomic_or(&g.ctr[CTR_ERR], t.err);
 	}
 	bt_atomic_add(&g.ctr[CTR_BULGES], w.ret);
+}
+__host__ __device__ inline void ss_commit_run(const GraphView &g, uint32_t widx, uint8_t *arena, uint32_t arena_bytes,
+                                              uint8_t *fast = nullptr, uint32_t fast_bytes = 0)
+{
+	Txn t;
+	BulgeWork w;
+	uint64_t *dirty = nullptr;
+	const int more = ss_commit_begin(g, t, w, widx, arena, arena_bytes, fast, fast_bytes, true, false, &dirty);
+	if (more < 0) return;
+	ss_commit_loop(g, t, w, more, dirty);
+	ss_commit_end(g, t, w);
 }
 
 // ---- the block index (GraphView::bidx) read by ONE thread: reference forms of what k_probe / k_reserve evaluate with 64 lanes

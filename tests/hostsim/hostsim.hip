@@ -6,10 +6,18 @@
 //
 // The window entries of a round are executed in ascending, descending or shuffled order to show
 // that the committed result does not depend on the execution order inside a round.
+//
+// Parking (park_cap != 0; tests/test_hostsim_parking.py) follows the device protocol of GraphView::park_of: a transaction that has
+// decided a collapse beyond park_cap stops, its Txn, BulgeWork and fast scratch are COPIED to the end of its window position's arena
+// slice (commit.hip: park_store) and copied back into the same objects in a later round (park_load); fresh and resumed entries of a
+// round run interleaved in the round's order (k_commit and k_resume on two streams).  The protocol's invariants are checked on the way
+// (SblError, like idx_check).
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #include <set>
+#include <string>
+#include <algorithm>
 
 #include "../../sibelia_amd/csrc/sbl_common.h"
 #include "../../sibelia_amd/csrc/simplify_driver.h"
@@ -73,10 +81,12 @@ struct HostBackend {
 		g.nblk = (g.cap_e >> BT_BLOCK_SHIFT) + 1;
 		g.win = win.data();
 		g.bidx = bidx.empty() ? nullptr : bidx.data();
+		g.park_of = park_of.empty() ? nullptr : park_of.data();
 	}
 	uint32_t nid() { return nid_; }
 	void checkpoint()
 	{
+		if (!parked_ids.empty()) fail("something is parked at the end of an iteration");
 		ck.ne = ctr[CTR_NE]; ck.nn = ctr[CTR_NN];
 		ck.ch = ch; ck.ndead = ndead; ck.touch = touch; ck.op = op; ck.nx = nx; ck.pv = pv; ck.nslot = nslot; ck.nnext = nnext;
 		for (int s = 0; s < 2; s++) { ck.bif[s] = bif[s]; ck.nodeof[s] = nodeof[s]; ck.head[s] = head[s]; ck.lsize[s] = lsize[s]; }
@@ -88,13 +98,16 @@ struct HostBackend {
 		for (int s = 0; s < 2; s++) { cp(bif[s], ck.bif[s]); cp(nodeof[s], ck.nodeof[s]); cp(head[s], ck.head[s]); cp(lsize[s], ck.lsize[s]); }
 		ctr[CTR_NE] = ck.ne; ctr[CTR_NN] = ck.nn;
 		if (g.bidx) idx_build(bidx, false);
+		drop_parked();
 	}
 	void snapshot_all(bool incremental)
 	{
+		if (!parked_ids.empty()) fail("something is parked when a snapshot runs");
 		for (uint32_t id = 0; id < nid_; id++) ss_snapshot(g, id, arena.data(), 1u << 14, incremental);
 	}
 	void reset_round_state(bool stamps_too)
 	{
+		if (stamps_too) { drop_parked(); iter_rounds = 0; }
 		std::fill(own.begin(), own.end(), 0xFFFFFFFFu);
 		std::fill(lock.begin(), lock.end(), 0xFFFFFFFFu);
 		if (stamps_too) {
@@ -136,19 +149,149 @@ struct HostBackend {
 	std::vector<uint32_t> dbg_bif0, dbg_bif1; uint32_t dbg_nn = 0;
 	alignas(16) uint8_t fastbuf[24576];      // stands in for the kernels' LDS scratch
 	std::vector<uint8_t> live;
-	bool chain(uint32_t, uint32_t) { return false; }      // the host driver always runs ordered rounds
+
+	// ---- parked transactions (GraphView::park_of; commit.hip: park_store / park_load / commit_body<RESUME>, rounds.hip: k_reserve)
+	uint32_t park_cap = 0;                        // 0: off -- the transactions run to their end (ss_commit_run), as before the model existed
+	uint32_t claim_cap = 0xFFFFFFFFu;             // claims a window entry can list (CLAIM_CAP); beyond that ownership is re-walked (ss_owns_footprint)
+	bool ctl_no_chain_claim = false, ctl_cleanup_at_park = false;      // negative controls of the tests (environment switches, see hostsim_stage)
+	uint32_t nslots = 0, parked_known = 0;        // window positions (own slice w, shadow slice nslots + w); CTR_PARKED as of the last counters()
+	std::vector<uint32_t> park_of;
+	std::vector<uint8_t> slice_busy, busy_snap, overflow;
+	std::vector<std::vector<uint8_t>> slices;
+	std::vector<uint32_t> park_list, parked_ids, finished, touched_ids;
+	std::vector<uint64_t> park_round, fin_round;
+	std::vector<uint32_t> park_count;
+	Txn pt;                                       // the transaction's "LDS": parked and resumed at these very addresses (and fastbuf)
+	BulgeWork pw;
+	uint64_t abs_round = 0, iter_rounds = 0;
+	uint64_t n_parks = 0, n_resumes = 0, max_parks = 0, n_shadow = 0, n_fallbacks = 0, n_parked_fallbacks = 0, max_iter_rounds = 0;
+	// the image at the end of a slice: Txn, BulgeWork, fast scratch, then where the dirty-window bits are and which objects it was taken from
+	static constexpr uint32_t IMG_W = (uint32_t)((sizeof(Txn) + 15) & ~(size_t)15), IMG_FAST = IMG_W + (uint32_t)((sizeof(BulgeWork) + 15) & ~(size_t)15), IMG_TAIL = PARK_IMG - 16u;
+	static_assert(IMG_FAST + COMMIT_FAST_BYTES <= IMG_TAIL, "the image of a transaction must fit PARK_IMG");
+	[[noreturn]] static void fail(const char *msg) { throw SblError{SBL_ERR_INTERNAL, std::string("parking model: ") + msg}; }
+	uint32_t tag() const { return bt_round_tag(g); }
+	uint8_t *slice(uint32_t s)
+	{
+		if (slices[s].empty()) slices[s].assign(arena_bytes, 0);
+		return slices[s].data();
+	}
+	uint8_t *image_of(uint32_t id) { return slice((park_of[id] & 0xFFFFFu) - 1u) + arena_bytes - PARK_IMG; }
+	template <class F> void chain_ids(const Txn &t, F f) const { for (uint32_t nd = t.tc_head; nd != BT_NONE; nd = nclr[nd]) f(nidst[nd] >> 1); }
+	void drop_parked()                            // start of an iteration, replay, grow: nothing is parked (DeviceBackend::reset_round_state)
+	{
+		if (!park_cap) return;
+		std::fill(park_of.begin(), park_of.end(), 0u);
+		std::fill(slice_busy.begin(), slice_busy.end(), 0);
+		parked_ids.clear(); finished.clear(); touched_ids.clear();
+		parked_known = 0; ctr[CTR_PARKED] = 0; g.park_hold = 0; g.any_parked = 0;
+	}
+	void park_store(uint32_t id, uint32_t slc, uint64_t *dirty)
+	{
+		if (slc >= nslots) fail("an entry of a shadow slice parked");
+		if (ctl_cleanup_at_park) pt.cleanup();                       // (negative control: Cleanup when the transaction stops, not at its end)
+		chain_ids(pt, [&](uint32_t b) { touched_ids.push_back(b); });
+		uint8_t *img = slice(slc) + arena_bytes - PARK_IMG;
+		memcpy(img, &pt, sizeof pt); memcpy(img + IMG_W, &pw, sizeof pw); memcpy(img + IMG_FAST, fastbuf, COMMIT_FAST_BYTES);
+		const uint64_t tail[2] = {(uint64_t)(uintptr_t)dirty, (uint64_t)(uintptr_t)&pt};
+		memcpy(img + IMG_TAIL, tail, sizeof tail);
+		memset((void *)&pt, 0xA5, sizeof pt); memset((void *)&pw, 0xA5, sizeof pw); memset(fastbuf, 0xA5, sizeof fastbuf);   // nothing may live on outside the image
+		park_of[id] = (slc + 1u) | (tag() << 20); slice_busy[slc] = 1; need[id] = 2; ctr[CTR_PARKED]++;
+		parked_ids.push_back(id); park_round[id] = abs_round;
+		n_parks++; max_parks = std::max<uint64_t>(max_parks, ++park_count[id]);
+	}
+	// runs the loops of pt / pw from `more` (decided: a parked transaction's next collapse); parks or ends it
+	void txn_finish(uint32_t id, uint32_t slc, int more, uint64_t *dirty, bool may_park, bool decided, bool resumed)
+	{
+		if (ss_commit_loop(g, pt, pw, more, dirty, may_park && !g.park_hold ? park_cap : 0u, decided)) { park_store(id, slc, dirty); return; }
+		chain_ids(pt, [&](uint32_t b) { touched_ids.push_back(b); });
+		ss_commit_end(g, pt, pw);
+		if (resumed) { slice_busy[slc] = 0; park_of[id] = 0x80000000u | (tag() << 20); finished.push_back(id); fin_round[id] = abs_round; }
+	}
+	void commit_fresh(uint32_t w, bool solo)
+	{
+		const uint32_t id = win[w];
+		if (!solo) {
+			const uint32_t pk = park_of[id];
+			if (pk && (!(pk >> 31) || ((pk >> 20) & 0x7FFu) == tag())) return;      // parked (the resume's), or finished in this round
+		}
+		const bool shadow = !solo && busy_snap[w] != 0;
+		if (shadow) n_shadow++;
+		const uint32_t slc = shadow ? nslots + w : w;
+		uint8_t *ar = solo ? big_arena.data() : slice(slc);
+		uint32_t ab = solo ? big_arena_bytes : arena_bytes;
+		const bool can_park = !solo && !shadow && ab >= 4u * PARK_IMG;
+		if (can_park) ab -= PARK_IMG;
+		park_count[id] = 0;
+		uint64_t *dirty = nullptr;
+		const int more = ss_commit_begin(g, pt, pw, w, ar, ab, fastbuf, COMMIT_FAST_BYTES, solo, true, &dirty);
+		if (more < 0) return;
+		txn_finish(id, slc, more, dirty, can_park, false, false);
+	}
+	void commit_resume(uint32_t w)
+	{
+		const uint32_t id = win[w], pk = park_of[id];
+		if (!pk || (pk >> 31) || ((pk >> 20) & 0x7FFu) == tag()) return;         // not parked / parked in this very launch
+		if (park_round[id] == abs_round) fail("a transaction resumed in the round it parked in");
+		const uint32_t slc = (pk & 0xFFFFFu) - 1u;
+		const uint8_t *img = slice(slc) + arena_bytes - PARK_IMG;
+		uint64_t tail[2];
+		memcpy(tail, img + IMG_TAIL, sizeof tail);
+		if (tail[1] != (uint64_t)(uintptr_t)&pt) fail("an image of other objects");
+		need[id] = 0; touch[id] = 1;
+		memcpy((void *)&pt, img, sizeof pt); memcpy((void *)&pw, img + IMG_W, sizeof pw); memcpy(fastbuf, img + IMG_FAST, COMMIT_FAST_BYTES);
+		pt.g = g; pt.stamp = g.round_bits | w; pw.ret0 = pw.ret - 1; ctr[CTR_PARKED]--;       // what belongs to the round is renewed (park_load)
+		parked_ids.erase(std::find(parked_ids.begin(), parked_ids.end(), id));
+		n_resumes++;
+		txn_finish(id, slc, 1, (uint64_t *)(uintptr_t)tail[0], true, true, true);
+	}
+	// at the end of every round: the ids whose nodes were erased have list sizes = live nodes, unless a parked transaction erased them
+	void sizes_check()
+	{
+		if (!park_cap || touched_ids.empty()) return;
+		if (ctr[CTR_ERR]) { touched_ids.clear(); return; }          // (a capacity error: Cleanup skipped, the driver replays the iteration)
+		std::set<uint32_t> held;
+		for (uint32_t id : parked_ids) chain_ids(*reinterpret_cast<const Txn *>(image_of(id)), [&](uint32_t b) { held.insert(b); });
+		std::sort(touched_ids.begin(), touched_ids.end());
+		touched_ids.erase(std::unique(touched_ids.begin(), touched_ids.end()), touched_ids.end());
+		for (uint32_t id : touched_ids) {
+			if (held.count(id)) continue;
+			uint32_t m = 0;
+			for (int s = 0; s < 2; s++) for (uint32_t nd = head[s][id]; nd != BT_NONE; nd = nnext[nd]) m += ndead[nd] ? 0u : 1u;
+			if (m != lsize[0][id] + lsize[1][id]) {
+				char msg[160];
+				snprintf(msg, sizeof msg, "id %u has %u live nodes and list sizes %u at the end of round %llu", id, m, lsize[0][id] + lsize[1][id], (unsigned long long)abs_round);
+				fail(msg);
+			}
+		}
+		touched_ids.clear();
+	}
+	void round_begin()
+	{
+		abs_round++; iter_rounds++;
+		max_iter_rounds = std::max(max_iter_rounds, iter_rounds);
+		g.any_parked = parked_known != 0;
+	}
+	bool chain(uint32_t, uint32_t)                // the host driver always runs ordered rounds; with something parked it waits for that to drain
+	{
+		if (park_cap && parked_known) g.park_hold = 1;
+		return false;
+	}
 	void probe(uint32_t nwin, uint32_t round)
 	{
 		g.round_bits = (SS_ROUND_MAX - round) << 20;
+		round_begin();
 		live.assign(nwin, 0);
 		for (uint32_t w : order(nwin)) {
 			// the verdict the index gives (ss_verdict_idx: what k_probe's probe_idx evaluates) must be the walking probe's wherever it gives one
 			const uint32_t id = win[w];
+			if (need[id] == 2 && bt_parked(g, id)) { live[w] = 1; continue; }      // parked: live without a verdict (k_probe_idx / k_probe)
+			uint8_t *ar = arena.data();
+			if (park_cap) ar = slice(slice_busy[w] ? nslots + w : w);            // (a slice that holds a parked transaction: the spare one)
 			const uint32_t viol_before = ctr[CTR_VIOL];
 			const int vi = ss_verdict_idx(g, id, id + 1);
 			uint8_t need_before = need[id];
 			uint32_t perr = 0;
-			const bool has = ss_probe(g, w, arena.data(), arena_bytes, &perr);
+			const bool has = ss_probe(g, w, ar, arena_bytes, &perr);
 			live[w] = has ? 1 : 0;
 			idx_probe_checked++;
 			if (vi >= 0 && ctr[CTR_VIOL] == viol_before && !perr) {
@@ -162,16 +305,24 @@ struct HostBackend {
 			}
 		}
 	}
-	void mark_live(uint32_t nwin) { live.assign(nwin, 1); }
+	void mark_live(uint32_t nwin) { round_begin(); live.assign(nwin, 1); }
 	void reserve(uint32_t nwin, uint32_t round)
 	{
 		g.round_bits = (SS_ROUND_MAX - round) << 20;
 		claims.assign(nwin, {});
+		park_list.clear();
 		if (getenv("HOSTSIM_DEBUG")) { dbg_bif0 = bif[0]; dbg_bif1 = bif[1]; dbg_nn = ctr[CTR_NN]; }
 		for (uint32_t w : order(nwin)) {
 			if (!live[w]) continue;
 			uint32_t st = g.round_bits | w;
 			uint32_t me = win[w];
+			if (park_cap) {
+				if (bt_parked(g, me)) park_list.push_back(w);
+				busy_snap[w] = slice_busy[w];                  // (k_reserve's copy: own slice or the shadow slice is decided from it)
+				// the ids a parked transaction has erased instances of: exclusively, from the image's erase chain
+				if (bt_parked(g, me) && !ctl_no_chain_claim)
+					chain_ids(*reinterpret_cast<const Txn *>(image_of(me)), [&](uint32_t b) { bt_atomic_min(&g.own[b], st); claims[w].push_back(b); });
+			}
 			std::set<std::pair<uint32_t, uint32_t>> walked, indexed;
 			bt_footprint(g, me, [&](uint32_t b, uint32_t kind) {
 				walked.insert({b, kind});
@@ -191,18 +342,60 @@ struct HostBackend {
 			}
 		}
 	}
+	void park_list_sort() { std::sort(park_list.begin(), park_list.end()); }
+	bool owns(uint32_t w)
+	{
+		const uint32_t st = g.round_bits | w;
+		if (claims[w].size() > claim_cap) {                                   // list overflowed: serial re-walk (commit.hip, commit_kernel)
+			n_fallbacks++;
+			if (bt_parked(g, win[w])) n_parked_fallbacks++;
+			return ss_owns_footprint(g, w);
+		}
+		for (uint32_t b : claims[w]) {
+			if (b & 0x80000000u) { uint32_t x = b & 0x7FFFFFFFu; if (own[x] != st && bt_order_blocked(g, x)) return false; }
+			else if (own[b] != st) return false;
+		}
+		return true;
+	}
+	// the round with parking: k_commit's fresh entries and k_resume's parked ones, interleaved in the round's order
+	void commit_parking(uint32_t nwin, uint32_t round, bool solo)
+	{
+		if (!solo && (round & 1023u) == 0u)                                   // the finished-marker sweep, on DeviceBackend::commit's schedule
+			for (uint32_t &pk : park_of) if (pk >> 31) pk = 0u;
+		size_t keep = 0;
+		for (uint32_t id : finished) {                                          // bt_round_tag: no marker survives to a round with its tag
+			const uint32_t pk = park_of[id];
+			if (!(pk >> 31)) continue;
+			if (((pk >> 20) & 0x7FFu) == tag() && fin_round[id] != abs_round) {
+				char msg[200];
+				snprintf(msg, sizeof msg, "the finished marker of id %u (round %llu) is still there in round %llu, which has the same tag %u", id,
+				         (unsigned long long)fin_round[id], (unsigned long long)abs_round, tag());
+				fail(msg);
+			}
+			finished[keep++] = id;
+		}
+		finished.resize(keep);
+		if (solo) { commit_fresh(0, true); return; }
+		park_list_sort();
+		std::vector<uint64_t> ev;                                               // (w << 1) | resume
+		for (uint32_t w = 0, p = 0; w < nwin; w++) {
+			if (p < park_list.size() && park_list[p] == w) { ev.push_back((uint64_t)w << 1 | 1u); p++; }
+			ev.push_back((uint64_t)w << 1);
+		}
+		for (uint32_t e : order((uint32_t)ev.size())) {
+			const uint32_t w = (uint32_t)(ev[e] >> 1);
+			if (!live[w] || !owns(w)) continue;
+			if (ev[e] & 1u) commit_resume(w); else commit_fresh(w, false);
+		}
+	}
 	void commit(uint32_t nwin, uint32_t round, bool solo)
 	{
 		g.round_bits = (SS_ROUND_MAX - round) << 20;
+		if (park_cap) { commit_parking(nwin, round, solo); return; }
 		if (solo) { ss_commit_run(g, 0, big_arena.data(), big_arena_bytes, fastbuf, sizeof fastbuf); return; }
 		for (uint32_t w : order(nwin)) {
 			if (!live[w]) continue;
-			uint32_t st = g.round_bits | w;
-			bool owner = true;
-			for (uint32_t b : claims[w]) {
-				if (b & 0x80000000u) { uint32_t x = b & 0x7FFFFFFFu; if (own[x] != st && bt_order_blocked(g, x)) { owner = false; break; } }
-				else if (own[b] != st) { owner = false; break; }
-			}
+			const bool owner = owns(w);
 			uint32_t before = ctr[CTR_VIOL];
 			if (owner) ss_commit_run(g, w, arena.data(), arena_bytes, fastbuf, sizeof fastbuf);
 			if (getenv("HOSTSIM_DEBUG") && ctr[CTR_VIOL] != before) {
@@ -244,9 +437,15 @@ struct HostBackend {
 			}
 		}
 	}
-	SimplifyCounters counters() { SimplifyCounters c; memcpy(c.v, ctr.data(), sizeof c.v); return c; }
+	SimplifyCounters counters()
+	{
+		sizes_check();
+		parked_known = ctr[CTR_PARKED];
+		SimplifyCounters c; memcpy(c.v, ctr.data(), sizeof c.v); return c;
+	}
 	bool grow(uint32_t err)
 	{
+		drop_parked();
 		if (err & BT_ERR_ELEM_CAP) {
 			size_t n = ch.size() * 2;
 			ch.resize(n); op.resize(n); nx.resize(n); pv.resize(n);
@@ -264,11 +463,15 @@ struct HostBackend {
 
 // Input: sanitised sequences + original positions, the enumeration (instances sorted by (chr,pos) per strand,
 // negative strand in reverse-complement coordinates).  Output: post-stage sequences / positions.
-// stats: [0]=iterations [1]=rounds [2]=replays [3]=solo rounds [4]=executed transactions
+// stats: [0]=iterations [1]=rounds [2]=replays [3]=solo rounds [4]=executed transactions [5]=grow replays
+// parking (park_cap != 0): [6]=parks [7]=resumes [8]=most parks of one transaction [9]=shadow-slice runs [10]=claim-cap fallbacks
+// [11]=... of parked entries [12]=most rounds of one iteration (attempt).  claim_cap: 0xFFFFFFFF = unlimited.
+// Negative controls of the tests (environment): HOSTSIM_NO_CHAIN_CLAIM -- a parked entry does not claim the ids of its erase chain;
+// HOSTSIM_CLEANUP_AT_PARK -- Cleanup runs when a transaction parks instead of at its end.
 extern "C" int hostsim_stage(uint32_t nchr, const uint8_t *const *seq, const uint32_t *const *opos, const uint64_t *len,
                              uint32_t k, uint32_t D, uint32_t max_iter, uint32_t bif_count,
                              const uint32_t *pos_inst, uint64_t n0, const uint32_t *neg_inst, uint64_t n1,
-                             uint32_t window, int order_mode, uint32_t arena_bytes, uint32_t slack_elems,
+                             uint32_t window, int order_mode, uint32_t arena_bytes, uint32_t slack_elems, uint32_t park_cap, uint32_t claim_cap,
                              uint8_t **out_seq, uint32_t **out_op, uint64_t *out_len, uint64_t *bulges, uint64_t *stats)
 {
 	try {
@@ -322,7 +525,18 @@ extern "C" int hostsim_stage(uint32_t nchr, const uint8_t *const *seq, const uin
 			be.idx_build(be.bidx, false);
 			be.bind();
 		}
+		if (park_cap) {
+			const size_t W = window ? window : 1;
+			be.park_cap = park_cap; be.claim_cap = claim_cap; be.nslots = (uint32_t)W;
+			be.ctl_no_chain_claim = getenv("HOSTSIM_NO_CHAIN_CLAIM") != nullptr;
+			be.ctl_cleanup_at_park = getenv("HOSTSIM_CLEANUP_AT_PARK") != nullptr;
+			be.park_of.assign((size_t)bif_count + 1, 0u); be.park_round.assign((size_t)bif_count + 1, ~0ull); be.fin_round.assign((size_t)bif_count + 1, 0ull);
+			be.park_count.assign((size_t)bif_count + 1, 0u);
+			be.slice_busy.assign(2 * W, 0); be.busy_snap.assign(W, 0); be.slices.assign(2 * W, {});
+			be.bind();
+		} else be.claim_cap = claim_cap;
 		SimplifyReport rep = simplify_graph(be, max_iter, window, nullptr, nullptr);
+		if (!be.parked_ids.empty()) throw SblError{SBL_ERR_INTERNAL, "parking model: something is parked at the end of the stage"};
 		be.idx_check("end of the stage");
 		if (getenv("HOSTSIM_INDEX_STATS")) fprintf(stderr, "[hostsim] index served %llu of %llu probes, %llu of %llu footprints\n", (unsigned long long)be.idx_probe_served,
 		                                           (unsigned long long)be.idx_probe_checked, (unsigned long long)be.idx_fp_served, (unsigned long long)be.idx_fp_checked);
@@ -335,6 +549,8 @@ extern "C" int hostsim_stage(uint32_t nchr, const uint8_t *const *seq, const uin
 		}
 		*bulges = rep.bulges;
 		stats[0] = rep.iterations; stats[1] = rep.rounds; stats[2] = rep.replays; stats[3] = rep.solo; stats[4] = rep.executed; stats[5] = rep.grow_replays;
+		stats[6] = be.n_parks; stats[7] = be.n_resumes; stats[8] = be.max_parks; stats[9] = be.n_shadow; stats[10] = be.n_fallbacks; stats[11] = be.n_parked_fallbacks;
+		stats[12] = be.max_iter_rounds;
 		return 0;
 	} catch (const SblError &err) {
 		fprintf(stderr, "hostsim: %s\n", err.msg.c_str());

@@ -35,7 +35,7 @@ def lib():
 
 def stage(seqs: Sequence[bytes], opos: Sequence[np.ndarray], k: int, D: int, max_iter: int, bif_count: int,
           pos: np.ndarray, neg: np.ndarray, window: int = 64, order_mode: int = 0, arena_bytes: int = 1 << 16,
-          slack: int = 1 << 16) -> Tuple[int, List[bytes], List[np.ndarray], dict]:
+          slack: int = 1 << 16, park_cap: int = 0, claim_cap: int = None) -> Tuple[int, List[bytes], List[np.ndarray], dict]:
     L = lib()
     n = len(seqs)
     sarr = (C.c_char_p * n)(*[bytes(s) for s in seqs])
@@ -48,10 +48,11 @@ def stage(seqs: Sequence[bytes], opos: Sequence[np.ndarray], k: int, D: int, max
     oop = (C.c_void_p * n)()
     olen = (C.c_uint64 * n)()
     bulges = C.c_uint64()
-    stats = (C.c_uint64 * 8)()
+    stats = (C.c_uint64 * 16)()
     rc = L.hostsim_stage(C.c_uint32(n), sarr, oarr, lens, C.c_uint32(k), C.c_uint32(D), C.c_uint32(max_iter), C.c_uint32(bif_count),
                          C.c_void_p(p3.ctypes.data), C.c_uint64(len(p3)), C.c_void_p(n3.ctypes.data), C.c_uint64(len(n3)),
                          C.c_uint32(window), C.c_int(order_mode), C.c_uint32(arena_bytes), C.c_uint32(slack),
+                         C.c_uint32(park_cap), C.c_uint32(0xFFFFFFFF if claim_cap is None else claim_cap),
                          oseq, oop, olen, C.byref(bulges), stats)
     if rc:
         raise RuntimeError("hostsim_stage failed: %d" % rc)
@@ -62,4 +63,6 @@ def stage(seqs: Sequence[bytes], opos: Sequence[np.ndarray], k: int, D: int, max
         rp.append(np.frombuffer(C.string_at(oop[i], 4 * m), dtype=np.uint32).copy())
         L.hostsim_free(oseq[i])
         L.hostsim_free(oop[i])
-    return bulges.value, rs, rp, {"iterations": stats[0], "rounds": stats[1], "replays": stats[2], "solo": stats[3], "executed": stats[4], "grow_replays": stats[5]}
+    return bulges.value, rs, rp, {"iterations": stats[0], "rounds": stats[1], "replays": stats[2], "solo": stats[3], "executed": stats[4], "grow_replays": stats[5],
+                                      "parks": stats[6], "resumes": stats[7], "max_parks": stats[8], "shadow": stats[9], "fallbacks": stats[10],
+                                      "parked_fallbacks": stats[11], "max_iter_rounds": stats[12]}

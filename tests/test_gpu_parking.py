@@ -240,3 +240,23 @@ def test_rounds_that_turn_into_a_slow_serial_chain_give_way_to_the_one_launch_pa
     _same_state(a, ref, "seed 67012, switch to the one-launch path")
     assert a[0][1] == 0, "the stage finished in the ordered rounds (%d rounds): the switch did not happen" % a[0][1]
     assert dt < 10.0, "seed 67012 took %.1f s" % dt
+
+
+def test_parking_across_the_round_tag_wrap(monkeypatch):
+    """A window of one entry and a park after every collapse: one iteration takes more than SS_ROUND_MAX = 4095 rounds (tests/hostsim
+    counts 6 231 for this case), so the round counter wraps (4095 -> 1) and every 11-bit round tag of park_of comes round again --
+    a finished marker that survived its sweep would make k_commit skip an id as "finished in this round".  Same state as the oracle."""
+    from sibelia_amd import BlockFinder, workloads as W
+    seqs = W.gen_strains(L0=20_000, n=6, seed=3, snp=0.03, indel_every=1000, inv_min=200, inv_max=1000)
+    ref = _oracle(seqs, [(25, 150)])
+    monkeypatch.setenv("SBL_PARK", "1")
+    bf = BlockFinder(seqs, device=0)
+    try:
+        bf.set_window(1)
+        n = bf.simplify_stage(25, 150, 4)
+        rounds = int(bf.stats()["rounds"])
+        seq, pos = bf.state()
+    finally:
+        bf.close()
+    _same_state([(n, rounds, seq, pos)], ref, "window 1, SBL_PARK=1")
+    assert rounds > 4095, "%d rounds: the round counter never wrapped" % rounds
