@@ -23,9 +23,7 @@
 #define BT_DEAD_CHAR 0            // ch[] of an element that was erased from the list
 #define BT_POS_MASK 0x1FFFFFFFu   // 29-bit original positions (reference src/stranditerator.cpp:19-27)
 #define BT_MAX_BREAKS 16u
-#ifndef BT_LDS_MARKS
 #define BT_LDS_MARKS 48u
-#endif
 #define BT_BLOCK_SHIFT 0          // validation granularity: single elements (coarser blocks flag neighbours across a chromosome boundary)
 // Fresh element slots per insertion are a multiple of this.  Validation works on single elements (BT_BLOCK_SHIFT 0), so an
 // insertion takes exactly the slots it needs: low-complexity inputs make tens of thousands of 1-3 element insertions per
@@ -37,22 +35,32 @@
 // 110 MB of counter traffic per launch of k_commit).  NEGATIVE: two transactions of one round own disjoint ids but abut inside a
 // 64-slot block all the time; every such pair is a false violation, the attempt replays with a fence, and the next pair is already
 // there -- 409 013 rounds on a stage that takes 100.  Read stamps stay per element (0); the shift is kept for the record.
-#ifndef BT_RSHIFT
 #define BT_RSHIFT 0u
-#endif
 #define BT_LAZY_MIN 64u           // see BulgeWork::lazy
-#define BT_ACT_FAST 64u           // see BulgeWork::act_fast
 #define BT_MSCAN_MIN 6u           // see BulgeWork::mscan
 __host__ __device__ __forceinline__ uint32_t bt_insert_span(uint32_t m) { return (m + BT_INSERT_ALIGN - 1u) & ~(BT_INSERT_ALIGN - 1u); }
 
 // Counter block.  Every counter has a 128-byte line of its own: thousands of workgroups per launch bump them (retired entries,
 // transactions, bulges) or reserve pool ranges through them with RETURNING atomics (element / node slots of a collapse), and all
 // atomics on one line queue up behind each other in the L2 (~11 ns each) -- on one shared line a collapse waited for everybody's
-// bookkeeping.  CTR_DETAIL .. +4: first violation (kind, resource, other, id, info), debugging only.
+// bookkeeping.  The last line, CTR_DETAIL, holds the rarely written words below.
 enum { CTR_STRIDE = 32,
        CTR_NE = 0 * CTR_STRIDE, CTR_NN = 1 * CTR_STRIDE, CTR_ERR = 2 * CTR_STRIDE, CTR_BULGES = 3 * CTR_STRIDE, CTR_VIOL = 4 * CTR_STRIDE,
        CTR_NWIN = 5 * CTR_STRIDE, CTR_LO = 6 * CTR_STRIDE, CTR_COMMITTED = 7 * CTR_STRIDE, CTR_BIG = 8 * CTR_STRIDE, CTR_PUSHED = 9 * CTR_STRIDE,
        CTR_TXN = 10 * CTR_STRIDE, CTR_DETAIL = 11 * CTR_STRIDE, CTR_COUNT = 12 * CTR_STRIDE };
+// The words of the CTR_DETAIL line.  k_clear_counters zeroes all of them before the first round of an iteration attempt.
+enum { CTR_VDETAIL = CTR_DETAIL + 0, CTR_VDETAIL_N = 5,   // first violation (kind, resource, other, id, info), debugging only
+       CTR_DENSE_ITER = CTR_DETAIL + 0,                   // iterations of the one-launch path (k_dense_stage has no violations: the reuse is by design)
+       CTR_PARKED = CTR_DETAIL + 8,                       // parked transactions at the moment
+       CTR_PLIST = CTR_DETAIL + 10,                       // entries of GraphView::park_list in this round (reset behind every round by k_select_write)
+       CTR_TOUCHED = CTR_DETAIL + 12,                     // host scratch: ids touched since their last verdict (DeviceBackend::few_touched, snapshot_idx)
+       CTR_IDXCHECK = CTR_DETAIL + 16, CTR_IDXCHECK_N = 2 };   // SBL_CHECK_INDEX: blocks that differ from a rebuild, the first of them
+static_assert(CTR_VDETAIL + CTR_VDETAIL_N <= CTR_PARKED && CTR_PARKED < CTR_PLIST && CTR_PLIST < CTR_TOUCHED && CTR_TOUCHED < CTR_IDXCHECK &&
+              CTR_IDXCHECK + CTR_IDXCHECK_N <= CTR_DETAIL + CTR_STRIDE, "the words of the CTR_DETAIL line overlap or leave it");
+// GraphView::test_flags (SBL_TEST_FLAGS): the step-wise walks in place of the burst walks of the reservation (k_reserve) and of the
+// publish of a collapse (wave_publish_collapse) -- tests/test_gpu_burst_walks.py checks both forms agree --, and statistics of the
+// block index and of the reservation's phases, reported at the end of a stage (sbl_rounds_stats_report)
+enum { BT_TF_STEPWISE_RESERVE = 4, BT_TF_STEPWISE_PUBLISH = 8, BT_TF_STATS = 32 };
 enum { BT_ERR_SCRATCH = 1, BT_ERR_ELEM_CAP = 2, BT_ERR_NODE_CAP = 4, BT_ERR_LAYOUT = 8 /* a parked image from another LDS layout (commit.hip: park_load) */ };
 
 // optional cycle counters of the decision loops (simplify.hip defines them for SBL_PHASES=1; nothing elsewhere)
@@ -79,13 +87,7 @@ struct GraphView {
 	uint32_t round_bits;                // (ROUND_MAX - round) << 20
 	const uint32_t *win;                // ids of the current window
 	uint32_t lazy_min;                  // a run with more instances than this that has the graph to itself rescans windows on demand (0: default, BT_LAZY_MIN)
-	uint32_t test_flags;                // A/B switches of experiments (SBL_TEST_FLAGS)
-	uint32_t lazy_rescan;               // ordered rounds: dirty windows are marked stale instead of rescanned at once (BulgeWork::use_stale)
-	uint32_t collapse_g;                // ordered rounds / chain: the gather-first collapse (simplify.hip: wave_collapse_g)
-	uint32_t ab_estimate;               // AnyBulges of ids with more than 32 instances sizes its tables by an estimate instead of a counting pass (simplify.hip)
-	uint32_t jscan_rounds;              // ordered rounds: ids with more than 24 instances hand the search for the next J to 64 lanes (BulgeWork::jscan)
-	uint32_t probe_pre;                 // the probe of a round first looks at the endChars alone (simplify.hip: probe_endchars)
-	uint32_t lazy_map;                  // the kernels' AnyBulges logs its map insertions and builds the Boost-ordered map only for calls with >= 2 groups (ABuild::lazy)
+	uint32_t test_flags;                // test and diagnostic switches (SBL_TEST_FLAGS): the BT_TF_* bits
 	uint32_t test_lazy_map;             // tests/hostsim: bt_any_bulges (one thread) builds its map lazily too (ABuild::lazy), look-ups by linear search
 	// start stamps of the round kernels (device wall clock; simplify.hip: DeviceBackend::stamp_*): 4 slots per round, nullptr = off
 	unsigned long long *tstamp; uint32_t tslot;
@@ -128,11 +130,7 @@ struct GraphView {
 // every round until the transaction is through -- and whoever would read such a size waits, exactly as for an id inside the core.
 // (Found by tools/stress.py seed 93194: a neighbour read a size one too high, collapsed in the other direction and counted one bulge less.)
 #define PARK_IMG 12288u
-#ifndef COMMIT_FAST_BYTES
 #define COMMIT_FAST_BYTES 8192               // LDS scratch of a transaction; with Txn / BulgeWork ~9 KB per workgroup = 17 workgroups per CU (12 KB: 12, and 4 % slower)
-#endif
-#define CTR_PARKED (CTR_DETAIL + 8)      // parked transactions at the moment
-#define CTR_PLIST (CTR_DETAIL + 10)      // entries of GraphView::park_list in this round (reset behind every round by k_select_write)
 // (the tag is 11 bits of a 12-bit round: finished markers are swept every 1024 rounds, DeviceBackend::commit, so that none survives to the round with the same tag)
 __host__ __device__ __forceinline__ uint32_t bt_round_tag(const GraphView &g) { return (g.round_bits >> 20) & 0x7FFu; }
 // index of a resource's read stamp: element resources (r < nblk) by 64-slot block, id resources as they are
@@ -527,7 +525,8 @@ struct BulgeWork {
 	// member with another endChar (pj = the first such J) -- see bt_rb_next_pair; pready = idI / pj are such a pair (or idI is the group's end)
 	bool pscan, pready, pjknown; uint32_t pj;
 	uint32_t ret0;               // parked transactions (GraphView::park_of): value of ret when this launch took the transaction up
-	uint32_t mscan_min;          // ... with more than this many marks inside the two branches together
+	uint32_t mscan_min;          // ... with more than this many marks inside the two branches together (BT_MSCAN_MIN; read as a member, the
+	                             // constant itself made k_resume spill 16 B more)
 	uint32_t mq_i, mq_di, mq_j, mq_dj, mres[2];
 	uint64_t *visit; uint32_t nvisit, visit_cap;      // FillVisit result sorted by (bif, distance)
 	uint32_t *occ; uint32_t occ_cap;
@@ -540,7 +539,6 @@ struct BulgeWork {
 	// the collapse bt_rb_run has decided on (performed by the caller: bt_collapse on one thread, or 64 lanes in simplify.hip)
 	uint32_t c_src, c_dS, c_tgt, c_dT;
 	uint32_t *act;               // scratch for the wave-wide collapse: (strand, element, id) AddPoint actions
-	uint32_t *act_fast;          // ... up to BT_ACT_FAST of them in the fast scratch
 };
 
 __host__ __device__ __forceinline__ SIt bt_deref(Txn &t, uint32_t packed) { SIt a; a.e = t.g.nslot[packed >> 1]; a.d = packed & 1; return a; }
@@ -585,7 +583,7 @@ __host__ __device__ inline bool bt_setup(Txn &t, BulgeWork &w, bool lite = false
 	w.mks = BT_LDS_MARKS;
 	if (!w.wmk) { w.wmk = (uint64_t *)t.alloc(n * w.ws * 8); w.mks = w.ws; }
 	w.lite = lite;
-	w.wel = w.wbf = nullptr; w.wch = nullptr; w.wbk = w.wnb = w.wdel = nullptr; w.visit = nullptr; w.occ = nullptr; w.lb = w.lf = nullptr; w.act = nullptr; w.act_fast = nullptr; w.dirty_big = nullptr;
+	w.wel = w.wbf = nullptr; w.wch = nullptr; w.wbk = w.wnb = w.wdel = nullptr; w.visit = nullptr; w.occ = nullptr; w.lb = w.lf = nullptr; w.act = nullptr; w.dirty_big = nullptr;
 	w.visit_cap = D; w.occ_cap = D + k;
 	if (!lite) {
 		w.wel = (uint32_t *)t.alloc(n * w.ws * 4);
@@ -599,7 +597,6 @@ __host__ __device__ inline bool bt_setup(Txn &t, BulgeWork &w, bool lite = false
 		w.occ = (uint32_t *)t.alloc(w.occ_cap * 4);
 		w.lb = (uint32_t *)t.alloc2(k * 8); w.lf = (uint32_t *)t.alloc2(k * 8);   // flank lists of a collapse: read back by other lanes, LDS when it fits
 		w.act = (uint32_t *)t.alloc((2 * D + 4) * 12);
-		w.act_fast = g.test_flags & 1u ? (uint32_t *)t.falloc(BT_ACT_FAST * 12) : nullptr;      // the usual few dozen AddPoint actions of a collapse stay in the fast scratch (nullptr: no room)
 		if (n > 256) w.dirty_big = (unsigned long long *)t.alloc(((n + 63) / 64) * 8);
 		if (n > lazy_min) { w.wep = (uint32_t *)t.alloc(n * 4); if (w.wep) for (uint32_t i = 0; i < n; i++) w.wep[i] = 0; }
 	}

@@ -27,7 +27,7 @@ __device__ __forceinline__ void wave_stamp_id_write(const GraphView &g, unsigned
 	atomicMax(&g.wmax[r], tid);
 	if (bad) {
 		atomicMin(&g.ctr[CTR_VIOL], id);
-		if (atomicCAS(&g.ctr[CTR_DETAIL], 0u, 3u) == 0u) { g.ctr[CTR_DETAIL + 1] = r; g.ctr[CTR_DETAIL + 2] = (wm > rm ? wm : rm) - 1; g.ctr[CTR_DETAIL + 3] = id; g.ctr[CTR_DETAIL + 4] = (wm > tid ? 1u : 0u) | (rm > tid ? 2u : 0u) | (ow != stampv ? 4u : 0u); }
+		if (atomicCAS(&g.ctr[CTR_VDETAIL], 0u, 3u) == 0u) { g.ctr[CTR_VDETAIL + 1] = r; g.ctr[CTR_VDETAIL + 2] = (wm > rm ? wm : rm) - 1; g.ctr[CTR_VDETAIL + 3] = id; g.ctr[CTR_VDETAIL + 4] = (wm > tid ? 1u : 0u) | (rm > tid ? 2u : 0u) | (ow != stampv ? 4u : 0u); }
 	}
 }
 // ErasePoint (bifurcationstorage.cpp:144-155) for one (strand, element) per lane; the lazy-erase chain head lives in LDS
@@ -73,9 +73,7 @@ __device__ unsigned long long g_round_span[4096 * 3];   // SBL_PHASES=1, per lau
 __device__ unsigned long long g_round_few[4096 * 2];    // ... and the slowest transaction with at most one / at most two collapses
 #define PH_T0() unsigned long long ph_t = prof ? __builtin_readcyclecounter() : 0ull; const unsigned long long ph_start = ph_t; const unsigned long long ph_wall = prof ? wall_clock64() : 0ull
 #define PH_ADD(i) do { if (prof && lane == 0) { unsigned long long n_ = __builtin_readcyclecounter(); atomicAdd(&g_phase_cycles[i], n_ - ph_t); ph_t = n_; } } while (0)
-#ifndef AP_CHUNKS
 #define AP_CHUNKS 4                          // AddPoints of a collapse handled one per lane: up to AP_CHUNKS x 64 (more: one lane, one after the other)
-#endif
 #define PC_T0() unsigned long long pc_t = prof ? __builtin_readcyclecounter() : 0ull
 #define PC_ADD(i) do { if (prof && lane == 0) { unsigned long long n_ = __builtin_readcyclecounter(); atomicAdd(&g_phase_cycles[i], n_ - pc_t); pc_t = n_; } } while (0)
 // The AddPoints of a collapse, one per lane and chunk of 64 lanes (NC chunks: instantiated for 1 -- the usual few dozen -- and for AP_CHUNKS).
@@ -84,12 +82,6 @@ __device__ __forceinline__ void wave_add_points(const GraphView &g, Txn &t, Bulg
                                                 unsigned dS, unsigned nlb, unsigned nlf, unsigned total, unsigned s_nodebase, const unsigned *actp)
 {
 	const unsigned t0 = T[0];
-	// place of a restored flank mark in the reference's order = its place in its own list + the entries of the OTHER list it comes after:
-	// with both lists in one wave's registers (k <= 64) that count is a loop of shuffles, not a walk over the list in memory per lane
-	const bool inreg = nlb <= 64u && nlf <= 64u && (g.test_flags & 2u);
-	const unsigned my_lb = inreg && lane < nlb ? w.lb[2 * lane] : ~0u, my_lf = inreg && lane < nlf ? w.lf[2 * lane] : ~0u;
-	unsigned cnt_lb = 0;                                                   // lookForward entries with a smaller index than my lookBack entry
-	if (inreg) for (unsigned y = 0; y < nlf; y++) cnt_lb += __shfl(my_lf, y) < my_lb ? 1u : 0u;
 	// One AddPoint per lane and chunk of 64 (up to NC x 64 of them: with dozens of strains half of all positions are
 	// bifurcations and a collapse copies 60 - 150 marks -- one lane doing them one after the other was 12 % of k_commit at 62 strains).
 	// seq = its place in the reference's order (flanks merged by index, look-back first at equal index, then the copied source
@@ -102,18 +94,14 @@ __device__ __forceinline__ void wave_add_points(const GraphView &g, Txn &t, Bulg
 	for (int c = 0; c < NC; c++) {
 		const unsigned x = lane + 64u * c;
 		unsigned sq = BT_NONE, ad = 0, ae = 0, ab = BT_NONE;
-		// (uniform part: the index of my lookForward entry and how many lookBack entries come before it)
-		const unsigned bi_u = x >= nlb && x < nlb + nlf ? x - nlb : 0u;
-		const unsigned idx_lf = inreg ? __shfl(my_lf, bi_u & 63u) : 0u;
-		unsigned cnt_lf = 0;
-		if (inreg) for (unsigned y = 0; y < nlb; y++) cnt_lf += __shfl(my_lb, y) <= idx_lf ? 1u : 0u;
+		// place of a restored flank mark in the reference's order = its place in its own list + the entries of the OTHER list it comes after
 		if (x < nlb) {
-			unsigned idx = inreg ? my_lb : w.lb[2 * x], cc = cnt_lb;
-			if (!inreg) for (unsigned y = 0; y < nlf; y++) cc += w.lf[2 * y] < idx;
+			unsigned idx = w.lb[2 * x], cc = 0;
+			for (unsigned y = 0; y < nlf; y++) cc += w.lf[2 * y] < idx;
 			sq = x + cc; ad = opp; ae = T[k - 1 - idx]; ab = w.lb[2 * x + 1];
 		} else if (x < nlb + nlf) {
-			unsigned bi = x - nlb, idx = inreg ? idx_lf : w.lf[2 * bi], cc = cnt_lf;
-			if (!inreg) for (unsigned y = 0; y < nlb; y++) cc += w.lb[2 * y] <= idx;
+			unsigned bi = x - nlb, idx = w.lf[2 * bi], cc = 0;
+			for (unsigned y = 0; y < nlb; y++) cc += w.lb[2 * y] <= idx;
 			sq = bi + cc; ad = d; ae = newT(dS + idx); ab = w.lf[2 * bi + 1];
 		} else if (x < total) {
 			unsigned xa = x - nlb - nlf;
@@ -352,9 +340,7 @@ __device__ __forceinline__ void wave_collapse(const GraphView &g, Txn &t, BulgeW
 //   4  checks, then nothing but stores (erase, characters, links, new elements, positions), the AddPoint list, and the AddPoints.
 // Same effect as wave_collapse (the two erase loops fuse: the flank marks of the first are a subset of the range of the second, and
 // the order of erasure is unobservable -- lazy-erase chain and list sizes are order-free).  NC = 64-step chunks per window (1 or 3).
-#ifndef GATHER_CHUNKS_MAX
 #define GATHER_CHUNKS_MAX 1
-#endif
 template <int NC>
 __device__ __forceinline__ unsigned gsel(const unsigned (&r)[NC], unsigned x)      // r "at step x": every lane must take part
 {
@@ -468,7 +454,7 @@ __device__ __forceinline__ void wave_collapse_g(const GraphView &g, Txn &t, Bulg
 				atomicMax(&g.wmax[r], tid);
 				if (bad) {
 					atomicMin(&g.ctr[CTR_VIOL], id);
-					if (atomicCAS(&g.ctr[CTR_DETAIL], 0u, 3u) == 0u) { g.ctr[CTR_DETAIL + 1] = r; g.ctr[CTR_DETAIL + 2] = (wm > rm ? wm : rm) - 1; g.ctr[CTR_DETAIL + 3] = id; g.ctr[CTR_DETAIL + 4] = (wm > tid ? 1u : 0u) | (rm > tid ? 2u : 0u) | (ow != stampv ? 4u : 0u); }
+					if (atomicCAS(&g.ctr[CTR_VDETAIL], 0u, 3u) == 0u) { g.ctr[CTR_VDETAIL + 1] = r; g.ctr[CTR_VDETAIL + 2] = (wm > rm ? wm : rm) - 1; g.ctr[CTR_VDETAIL + 3] = id; g.ctr[CTR_VDETAIL + 4] = (wm > tid ? 1u : 0u) | (rm > tid ? 2u : 0u) | (ow != stampv ? 4u : 0u); }
 				}
 			}
 		}
@@ -564,7 +550,7 @@ __device__ __forceinline__ void wave_collapse_g(const GraphView &g, Txn &t, Bulg
 		return (s >= k && s < k + dS && fj >= common) ? newbase + (fj - dT) : v;
 	};
 	// ---- 4c: the AddPoint actions of the copied source marks, in the reference's order (own strand, then opposite, per index)
-	unsigned *const act = w.act_fast && nact <= BT_ACT_FAST ? w.act_fast : w.act;      // (the usual few dozen: through LDS, not through the arena)
+	unsigned *const act = w.act;
 #pragma unroll
 	for (int u = 0; u < NC; u++) {
 		const unsigned x = lane + 64u * u, i = x <= dS ? x : 0u;
@@ -610,8 +596,8 @@ __device__ __forceinline__ void wave_collapse_any(const GraphView &g, Txn &t, Bu
 	const unsigned span = (w.c_dT > w.c_dS ? w.c_dT : w.c_dS) + g.k + 1u;
 	// (one chunk only: the three-chunk instantiation needs ~60 more registers, and inlined into k_commit it made EVERY transaction spill --
 	// 504 B of scratch, commit 40 -> 52 ms; longer branches keep the round-3 form)
-	if (prof && lane == 0 && (!g.collapse_g || span > 64u * GATHER_CHUNKS_MAX)) w.nold++;
-	if (!g.collapse_g || span > 64u * GATHER_CHUNKS_MAX) wave_collapse(g, t, w, lane, stampv, prof);
+	if (prof && lane == 0 && span > 64u * GATHER_CHUNKS_MAX) w.nold++;
+	if (span > 64u * GATHER_CHUNKS_MAX) wave_collapse(g, t, w, lane, stampv, prof);
 	else if (span <= 64u) wave_collapse_g<1>(g, t, w, lane, stampv, prof);
 	else wave_collapse_g<GATHER_CHUNKS_MAX>(g, t, w, lane, stampv, prof);
 }
@@ -782,9 +768,7 @@ __device__ __forceinline__ void wave_fill_visit(Txn &t, BulgeWork &w, unsigned D
 {
 	const unsigned nm = ldx(&w.wmn[w.fill_i]);
 	if (nm <= 64u) wave_fill_visit_t<1>(t, w, D, lane);
-#ifndef SBL_VAR_NOFV3
 	else if (nm <= 192u) wave_fill_visit_t<3>(t, w, D, lane);                // (62 strains: ~90 marks per window, lists in the arena -- one thread's sort there was 330 k cycles per transaction)
-#endif
 	else {                                                                 // (longer than any window of D <= 150 steps: the one-thread form)
 		if (lane == 0) { if (bt_scratch_in_lds(w)) bt_fill_visit<true>(t, w, w.fill_i); else bt_fill_visit<false>(t, w, w.fill_i); w.need_fill = false; }
 		WSYNC();
@@ -1006,7 +990,7 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 	// the estimate was too low (ids of low-complexity sequence, whose instances are not homologous; never on the 62-strain workload).
 	// (Round 4's first version let the overflow surface as a scratch error: the id was sent to the big arena, overflowed there again,
 	// was sent again ... -- the `-s far` hierarchy case of the drop-in tests never came back.)
-	const bool estimate = attempt == 0 && g.ab_estimate && (n > 32u || !(g.test_flags & 2048u));      // (round 5: small ids too -- the counting pass was 4 % of a transaction; 2048: measurement switch)
+	const bool estimate = attempt == 0;                               // (round 5: small ids too -- the counting pass was 4 % of a transaction)
 	if (sh.mode && estimate) {
 		unsigned mx = 0;
 		for (unsigned i = lane; i < n; i += 64) { const unsigned v = ldx(&endc[i]) == ' ' ? 0u : ldx(&wmn[i]); mx = v > mx ? v : mx; }
@@ -1021,7 +1005,7 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 			sh.bits = bits; sh.distinct = distinct;
 			sh.skey = (unsigned *)t.alloc2((2u << bits) * 4);
 			sh.sval = sh.skey ? sh.skey + (1u << bits) : nullptr;
-			if (!sh.skey || !bt_ab_prepare(t, w, distinct, g.lazy_map != 0)) sh.mode = -1;
+			if (!sh.skey || !bt_ab_prepare(t, w, distinct, true)) sh.mode = -1;
 		}
 		WSYNC();
 	} else if (sh.mode) {
@@ -1066,7 +1050,7 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 				sh.bits = bits; sh.distinct = distinct;
 				sh.skey = (unsigned *)t.alloc2((2u << bits) * 4);
 				sh.sval = sh.skey ? sh.skey + (1u << bits) : nullptr;
-				if (!sh.skey || !bt_ab_prepare(t, w, distinct, g.lazy_map != 0)) sh.mode = -1;      // log the insertions, build the Boost map only if the call has >= 2 groups (bulge_txn.h: ABuild::lazy)
+				if (!sh.skey || !bt_ab_prepare(t, w, distinct, true)) sh.mode = -1;      // log the insertions, build the Boost map only if the call has >= 2 groups (bulge_txn.h: ABuild::lazy)
 			}
 		}
 		WSYNC();
@@ -1087,9 +1071,7 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 	// of instances the lists live in the arena, and every instance used to begin with a memory round trip of its own, and with another
 	// one per further chunk of 64 marks (62 strains: ~90 marks per window); a chunk that starts in the middle of a block of 64 -- after
 	// an event -- is put together from two of the registers)
-#ifndef ABPF_N
 #define ABPF_N 1             // (3 = a whole window of the next instance in flight: -0.7 % at 62 strains, + 0.3 ms of k_commit at 8 -- registers)
-#endif
 	enum { ABPF = ABPF_N };
 	unsigned long long vpre[ABPF];
 #pragma unroll
@@ -1143,7 +1125,7 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 			// a run of consecutive new ids (the first instance of every endChar brings ~all its marks) is handed to lane 0 at once
 			unsigned long long ins = __ballot(ev == 1u) >> f;
 			unsigned run = eev == 1u ? (ins == ~0ull ? 64u - f : (unsigned)__builtin_ctzll(~ins)) : 0u;
-			if (w.abb.lazy && eev == 1u && !(g.test_flags & 512u)) {              // the run by the lanes that hold its ids
+			if (w.abb.lazy && eev == 1u) {                                      // the run by the lanes that hold its ids
 				const int m = ab_lazy_wave(t, w, sh, lane, i, ec, f, run, b, slots, shift, estimate);
 				WSYNC();
 				if (lane == 0) sh.mode = m;
@@ -1316,8 +1298,8 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 		// lazy windows (bulge_txn.h: BulgeWork::lazy) when the id is large and has the graph to itself: the set of windows a collapse
 		// dirties -- O(instances) to compute, and nearly all of them in the dense regime -- is only needed by the reservation check of
 		// an ordered round
-		if (lane == 0) { flag = bt_rb_begin(t, w, any) && !t.err ? 1 : 0; w.lazy = solo && w.wep != nullptr; w.jscan = w.lazy || (w.n > 24u && g.jscan_rounds); w.mscan = (w.n > 24u || (g.test_flags & 16u)) && g.jscan_rounds; if (g.test_flags & 16u) w.mscan_min = (g.test_flags >> 8) & 15u;
-			                 w.use_stale = !w.lazy && w.n <= 256u && g.lazy_rescan && w.wdel != nullptr; w.wfill = !(g.test_flags & 64u); w.pscan = false; }      // (pscan: measured -1.2 % at 62 strains, +1.4 % of k_commit at 8 -- the handler's registers; the one-launch kernel uses it)      // (many strains: groups of dozens of members, the J search with 64 lanes -- wave_next_j)
+		if (lane == 0) { flag = bt_rb_begin(t, w, any) && !t.err ? 1 : 0; w.lazy = solo && w.wep != nullptr; w.jscan = w.lazy || w.n > 24u; w.mscan = w.n > 24u;
+			                 w.use_stale = !w.lazy && w.n <= 256u && w.wdel != nullptr; w.wfill = true; w.pscan = false; }      // (pscan: measured -1.2 % at 62 strains, +1.4 % of k_commit at 8 -- the handler's registers; the one-launch kernel uses it)      // (many strains: groups of dozens of members, the J search with 64 lanes -- wave_next_j)
 		WSYNC();
 		PH_ADD(2);
 		}

@@ -345,16 +345,14 @@ void sbl_run_enumeration_longk(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 	HIP_TRY(hipMemcpyAsync(L.sym.p, rank, np * 4, hipMemcpyDeviceToDevice, s));
 	size_t h = 1;
 	unsigned maxrank = 4;                                            // symbols 0 .. 4
-	const bool first27 = k >= LK_FIRST_H && getenv("SBL_LONGK_FROM_1") == nullptr && getenv("SBL_LONGK_NO_DISCARD") == nullptr && getenv("SBL_LONGK_FROM_8") == nullptr;      // (SBL_LONGK_FROM_8: A/B switch, the round-4 start)
-	if (k >= 16 && getenv("SBL_LONGK_FROM_1") == nullptr) {          // (k > 32 here: always; the switch is for A/B tests)
-		rank = L.rank[1].as<unsigned>();
-		if (!first27) {
-			k_lk_rank8<<<nblocks(np, 256), 256, 0, s>>>(L.sym.as<unsigned>(), (unsigned)np, L.rank[1].as<unsigned>());
-			h = 8; maxrank = 390624;
-		}
+	const bool discard = getenv("SBL_LONGK_NO_DISCARD") == nullptr;
+	const bool first27 = k >= LK_FIRST_H && discard;
+	rank = L.rank[1].as<unsigned>();                                 // (k > 32 here: the doubling starts from rank_8 or rank_27)
+	if (!first27) {
+		k_lk_rank8<<<nblocks(np, 256), 256, 0, s>>>(L.sym.as<unsigned>(), (unsigned)np, L.rank[1].as<unsigned>());
+		h = 8; maxrank = 390624;
 	}
-	const bool by_sort = np >= (1u << 22) && getenv("SBL_LONGK_SCATTER") == nullptr;      // small inputs: the scatter stays in cache
-	const bool discard = k >= 16 && getenv("SBL_LONGK_FROM_1") == nullptr && getenv("SBL_LONGK_NO_DISCARD") == nullptr;
+	const bool by_sort = np >= (1u << 22);                           // small inputs: the scatter stays in cache
 	unsigned nv = 0;                                                 // valid windows at the front of the sorted (skeys, sidx)
 	bool plain = !discard;
 	unsigned na_final = 0;

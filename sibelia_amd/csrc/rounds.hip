@@ -97,9 +97,7 @@ __device__ __forceinline__ int wave_probe_window(const GraphView &g, const ScanB
 // The windows of a probed id, PROBE_BATCH at a time: the first bursts of a batch are in flight together (see ScanBurst / wave_scan_all)
 // and their marks go straight into the verdict table -- an entry that IS live stops at the first id two instances with different endChars
 // reach, without scanning the rest.  Returns the verdict (1 / 0; -1: undecided by the table).
-#ifndef PROBE_BATCH
 #define PROBE_BATCH 4
-#endif
 // (Recognising separators by their slot here as well -- one character per window instead of three loads -- was measured 0.9 ms SLOWER per
 // stage: the probe is issue-bound, and the bounds of every window cost more instructions than the two 64-byte loads they save.)
 __device__ __forceinline__ int probe_windows(const GraphView &g, BulgeWork &w, VerdictTable &vt, unsigned lane, unsigned id, unsigned tid)
@@ -229,7 +227,7 @@ __device__ __forceinline__ int probe_endchars(const GraphView &g, const BulgeWor
 // element, a window that touches a block which is no longer pristine or carries a write stamp above the prober (the exact order check
 // needs the elements), more instances than the LDS list holds -- flagged PROBE_UNSERVED in live[].
 // Pass 1 takes the endChars alone (see probe_endchars); pass 2 the marks.
-__device__ unsigned long long g_rsv_ticks[8];      // SBL_TEST_FLAGS=32: summed wall-clock ticks of the reservation's phases (set-up, exclusive claims, ordering claims), entries, claims, instances
+__device__ unsigned long long g_rsv_ticks[8];      // test_flags & BT_TF_STATS: summed wall-clock ticks of the reservation's phases (set-up, exclusive claims, ordering claims), entries, claims, instances
 __device__ unsigned g_idx_stats[8];          // SBL_TRACE: probes by outcome of k_probe_idx (known live, < 2 instances, clean, live, table full, not served); reservations: instances served / walked
 __device__ __forceinline__ unsigned long long idx_bits(int lo, int hi)      // bits lo .. hi-1 of a 64-bit word (clamped)
 {
@@ -468,7 +466,7 @@ __global__ void __launch_bounds__(64) k_probe_idx(GraphView g, unsigned nwin, ui
 	// push to a parked id comes from a lower transaction that rewrote what it had read, which is an order violation and ends the attempt).
 	// A parked id still hands its instances to the reservation: it reserves every round until it is through.
 	const bool known_live = !snapshot && g.need[id] == 2;
-	if (known_live && !(instbuf && (bt_parked(g, id) || (g.test_flags & 16384u)))) { if (lane == 0) { live[wi] = 1; if (instbuf) instbuf[(size_t)wi * istride] = BT_NONE; if (g.test_flags & 32u) atomicAdd(&g_idx_stats[0], 1u); } return; }          // found live by an earlier probe and not touched since (a push resets it to 1)
+	if (known_live && !(instbuf && bt_parked(g, id))) { if (lane == 0) { live[wi] = 1; if (instbuf) instbuf[(size_t)wi * istride] = BT_NONE; if (g.test_flags & BT_TF_STATS) atomicAdd(&g_idx_stats[0], 1u); } return; }          // found live by an earlier probe and not touched since (a push resets it to 1)
 	const unsigned n = wave_list_nodes(g, g.head[0][id], g.head[1][id], lane, nullptr, [&](unsigned off, unsigned, unsigned s, unsigned el, unsigned) {
 		if (off < max_inst) { s_sel[off] = el; s_dir[off] = (uint8_t)s; }
 	});
@@ -489,7 +487,7 @@ __global__ void __launch_bounds__(64) k_probe_idx(GraphView g, unsigned nwin, ui
 		if (r < 0) live[wi] = PROBE_UNSERVED;
 		else if (r == 0) { g.need[id] = 0; g.touch[id] = 0; live[wi] = 0; }      // verdict taken now: clean until somebody touches it again
 		else { g.need[id] = 2; live[wi] = 1; }
-		if (g.test_flags & 32u) atomicAdd(&g_idx_stats[n < 2 ? 1 : r == 0 ? 2 : r == 1 ? 3 : r == -1 ? 4 : 5], 1u);
+		if (g.test_flags & BT_TF_STATS) atomicAdd(&g_idx_stats[n < 2 ? 1 : r == 0 ? 2 : r == 1 ? 3 : r == -1 ? 4 : 5], 1u);
 	}
 	if (instbuf) {                                                       // the instances of a live entry for the reservation
 		unsigned *ib = instbuf + (size_t)wi * istride;
@@ -520,7 +518,7 @@ __global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe(GraphView g, unsigne
 	WSYNC();
 	// the windows go straight into the verdict table, a batch at a time (probe_windows)
 	int verdict = 0;
-	if (ok && g.probe_pre && probe_endchars(g, w, lane, id, tid)) ok = 0;      // every instance continues with the same character: clean (verdict stays 0)
+	if (ok && probe_endchars(g, w, lane, id, tid)) ok = 0;      // every instance continues with the same character: clean (verdict stays 0)
 	if (ok) {
 		verdict = probe_windows(g, w, vt, lane, id, tid);
 		if (verdict < 0) {                                                // undecided by the table: every window is needed
@@ -830,7 +828,7 @@ __global__ void __launch_bounds__(64 * RSV_WAVES_MAX) k_reserve(GraphView g, uns
 	const unsigned w = blockIdx.x, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
 	round_stamp(g, 1);
 	if (w >= nwin || !live[w]) return;
-	const bool rprof = (g.test_flags & 32u) != 0u;
+	const bool rprof = (g.test_flags & BT_TF_STATS) != 0u;
 	unsigned long long rt = rprof ? wall_clock64() : 0ull;
 #define RSV_T(i) do { if (rprof && threadIdx.x == 0) { const unsigned long long n_ = wall_clock64(); atomicAdd(&g_rsv_ticks[i], n_ - rt); rt = n_; } } while (0)
 	extern __shared__ unsigned rsv_dyn[];                             // the seen-set (1 << seen_bits words), then one list of list_cap words per wave
@@ -887,7 +885,7 @@ __global__ void __launch_bounds__(64 * RSV_WAVES_MAX) k_reserve(GraphView g, uns
 	// stale, which orders it against them (bt_footprint, bulge_txn.h); instances walking away cannot see or touch it.
 	auto order = [&](unsigned b0, unsigned b1) { wave_claim_order(g, cl, st, id, b0, lane); wave_claim_order(g, cl, st, id, b1, lane); };
 	const unsigned ninst = ninst_s;
-	const bool burst = !(g.test_flags & 4u);                          // (SBL_TEST_FLAGS=4: the step-wise walks everywhere, for A/B runs)
+	const bool burst = !(g.test_flags & BT_TF_STEPWISE_RESERVE);      // (the step-wise walks everywhere: tests)
 	// block index (round 5): groups of four instances, sixteen lanes each (reserve_idx_masks); an instance it cannot serve takes the walks
 	const unsigned NA = (fwd + 1u + 126u) >> 6, NB = (back + 1u + 126u) >> 6;
 	const bool indexed = g.idx_reserve && NA + NB <= 16u && ninst <= RESUME_SLOTS;
@@ -908,7 +906,7 @@ __global__ void __launch_bounds__(64 * RSV_WAVES_MAX) k_reserve(GraphView g, uns
 				reserve_idx_gather(g, L, L.ahead ? L.ord : 0ull, L.s ^ 1u, false, [&](unsigned b) { wave_claim_order(g, cl, st, id, b, lane); });
 				reserve_idx_gather(g, L, L.ahead ? 0ull : L.ord, L.s, true, [&](unsigned b) { wave_claim_order(g, cl, st, id, b, lane); });
 			}
-			if (lane < 4u && i0 + lane < ninst) { served[i0 + lane] = (uint8_t)((((slowm | (slowm >> 4)) >> lane) & 1u) ^ 1u); if (g.test_flags & 32u) atomicAdd(&g_idx_stats[6 + (((slowm | (slowm >> 4)) >> lane) & 1u)], 1u); }
+			if (lane < 4u && i0 + lane < ninst) { served[i0 + lane] = (uint8_t)((((slowm | (slowm >> 4)) >> lane) & 1u) ^ 1u); if (g.test_flags & BT_TF_STATS) atomicAdd(&g_idx_stats[6 + (((slowm | (slowm >> 4)) >> lane) & 1u)], 1u); }
 			if (rprof && threadIdx.x == 0) { const unsigned long long n_ = wall_clock64(); atomicAdd(&g_rsv_ticks[2], n_ - rt); rt = n_; }
 			for (unsigned q = 0; q < 4u && i0 + q < ninst; q++) {
 				const bool wa = (slowm >> q) & 1u, wb = (slowm >> (4u + q)) & 1u;      // which of the instance's two walks the index could not serve

@@ -42,7 +42,7 @@ struct RestartStage {};      // thrown out of an optimistic attempt that would n
 // many strains x genomes of a few kbp x a minBranchSize of a tenth of a genome -- a transaction's neighbourhood IS the genome, the
 // rounds commit one or two transactions each, and a round costs 10 - 30 ms there (tools/stress.py MANY=1: seed 67000 121 s, 67008 17.8 s,
 // 67012 19.8 s against 8.8 / 2.2 / 2.5 s through k_dense_stage, exact either way; the same path is 3 - 100 x SLOWER on every input the
-// rounds parallelise -- measured case by case, tools/gpu_r06_k.sh -- so it is only taken after the rounds have shown what they are)
+// rounds parallelise -- measured case by case, docs/history/r06.md -- so it is only taken after the rounds have shown what they are)
 struct TryDense {};
 #define DENSE_SWITCH_MAX_ELEMS (4u << 20)
 
@@ -59,8 +59,6 @@ struct DeviceBackend {
 	hipEvent_t *ev = nullptr;                                          // SimplifyState::ev
 	unsigned snap_used = 0;                                           // snapshot event pairs recorded in this stage
 	bool timed_commit = false;
-	bool later_stream = getenv("SBL_NO_STREAM_SNAPSHOT") == nullptr && getenv("SBL_NO_LATER_STREAM") == nullptr;
-	bool first_stream = getenv("SBL_NO_STREAM_SNAPSHOT") == nullptr;      // measurement switch: the generic window-walking snapshot for iteration 1 too
 	int prof = 0;
 	// Optimistic attempt: no iteration checkpoints (1.45 GB of device-to-device copies per iteration, 3.6 ms of a 105 ms stage, for a
 	// roll-back the benchmark workloads never take).  An order violation or a pool overflow then abandons the attempt (RestartStage) and
@@ -70,12 +68,11 @@ struct DeviceBackend {
 	// block index of the original slots (GraphView::bidx): read by the probe and the reservation, maintained by the transactions
 	bool use_index = getenv("SBL_NO_BLOCK_INDEX") == nullptr;        // measurement / test switch: every window is walked (round 4)
 	uint32_t idx_nblk = 0;
-	unsigned probe_lds_pad = getenv("SBL_PROBE_LDS_PAD") ? (unsigned)atoi(getenv("SBL_PROBE_LDS_PAD")) : 0u;      // measurement switch: occupancy sensitivity of k_probe_idx
 	// k_probe_idx's LDS by the instances an id has (set with rsv_waves): a handful -- 256-slot verdict table, 64 instances, 64 walked marks = 3.1 KB;
 	// dozens (many strains) -- 1024 slots, 256 instances, 192 marks = 12 KB.  An entry that does not fit goes to the walking probe.
 	unsigned pidx_vbits = 9, pidx_inst = 256, pidx_marks = 192;
 	unsigned istride() const { return std::min(pidx_inst, 128u) + 1u; }      // words per window entry of the instance hand-over (k_probe_idx -> k_reserve)
-	unsigned pidx_lds() const { return ((2u << pidx_vbits) + 2u * pidx_inst + 2u * pidx_marks) * 4u + pidx_inst + probe_lds_pad; }
+	unsigned pidx_lds() const { return ((2u << pidx_vbits) + 2u * pidx_inst + 2u * pidx_marks) * 4u + pidx_inst; }
 	void index_build()
 	{
 		if (!use_index || !idx_nblk) return;
@@ -240,7 +237,7 @@ struct DeviceBackend {
 	// touched (iterations 3, 4: what the few collapses of the previous iteration can see) the window-walking snapshot of just those is cheaper.
 	bool few_touched()
 	{
-		unsigned *cnt = st->ctr.as<unsigned>() + CTR_DETAIL + 8, n = 0;
+		unsigned *cnt = st->ctr.as<unsigned>() + CTR_TOUCHED, n = 0;
 		HIP_TRY(hipMemsetAsync(cnt, 0, 4, c->stream));
 		k_count_touched<<<256, 256, 0, c->stream>>>(st->touch.as<uint8_t>(), nid_, cnt);
 		HIP_TRY(hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, c->stream));
@@ -283,7 +280,7 @@ struct DeviceBackend {
 	uint32_t snap_slice = 0;                                          // entries per launch of the walking probe's arena (= the round buffers' window_max)
 	void snapshot_idx()
 	{
-		unsigned *cnt = st->ctr.as<unsigned>() + CTR_DETAIL + 8, n = 0;
+		unsigned *cnt = st->ctr.as<unsigned>() + CTR_TOUCHED, n = 0;
 		st->snap_list.ensure((size_t)nid_ * 4 + 64); st->snap_live.ensure((size_t)nid_ + 64);
 		HIP_TRY(hipMemsetAsync(cnt, 0, 4, c->stream));
 		k_touched_list<<<(nid_ + 255) / 256, 256, 0, c->stream>>>(st->touch.as<uint8_t>(), nid_, st->snap_list.as<unsigned>(), cnt);
@@ -310,27 +307,28 @@ struct DeviceBackend {
 		uint32_t plo = 0, phi = nid_;
 		const bool split = split_ro();
 		if (split) share(nid_, &plo, &phi);
-		if (!incremental && first_stream) {
+		if (!incremental) {
 			// iteration 1 (also after a replay: the checkpoint restored is the pristine graph): stream over the position-ordered marks
 			MarkStream ms;
 			for (int t = 0; t < 2; t++) { ms.elem[t] = c->d_melem[t].as<unsigned>(); ms.id[t] = c->d_mid[t].as<unsigned>(); ms.aux[t] = st->maux[t].as<unsigned>(); ms.n[t] = c->nmarks[t]; }
 			HIP_TRY(hipMemsetAsync(st->touch.p, 0, (size_t)nid_ + 1, c->stream));
 			k_snapshot_first<<<256 * 32, 64, 0, c->stream>>>(g, ms, st->nmark.as<unsigned>(), st->perm.as<unsigned>(), plo, phi);
-		} else if (incremental && g.idx_probe && !split && getenv("SBL_NO_IDX_SNAPSHOT") == nullptr) {
+		} else if (g.idx_probe && !split) {
 			// iterations 2 ..: the touched ids through the probe of the rounds (k_probe_idx over the block index, the walking probe for what it
 			// cannot serve) -- the same verdict the stream takes, without linearising the marks first (round 5)
 			snapshot_idx();
-		} else if (incremental && later_stream && !few_touched()) {
+		} else if (!few_touched()) {
 			// iterations 2 ..: the same stream over the marks of the current graph in list order
 			st->nmark.ensure((size_t)cap_n * 4);
 			MarkStream ms;
 			linearise_marks(ms);
 			k_snapshot_stream<<<256 * 32, 64, 0, c->stream>>>(g, ms, st->nmark.as<unsigned>(), st->perm.as<unsigned>(), 1, plo, phi);
 		} else {
+			// iterations 2 .. with few ids touched (few_touched): the window-walking snapshot of those
 			// (the walking snapshot's scratch -- up to 16 GB where D is in the thousands -- is only allocated when that kernel runs: a fresh
 			// context that never needs it used to spend seconds mapping it, tools/stress.py LONGK=1)
 			st->snap_arena.ensure((size_t)snap_threads * snap_arena_bytes);
-			k_snapshot<<<snap_threads, 64, 0, c->stream>>>(g, st->snap_arena.as<uint8_t>(), snap_arena_bytes, incremental ? 1 : 0, st->perm.as<unsigned>(), plo, phi);
+			k_snapshot<<<snap_threads, 64, 0, c->stream>>>(g, st->snap_arena.as<uint8_t>(), snap_arena_bytes, 1, st->perm.as<unsigned>(), plo, phi);
 		}
 		HIP_TRY(hipGetLastError());
 		if (split) {
@@ -406,7 +404,6 @@ struct DeviceBackend {
 	}
 	// Per-kernel times of the rounds: start stamps written by the kernels themselves (round_stamp) for probe and reservation, and a
 	// HIP event pair around the dominant kernel, k_commit (what bench.py's roofline is computed from).
-	bool phase_events = getenv("SBL_NO_PHASE_EVENTS") == nullptr;    // measurement switch: what the per-round events themselves cost
 	enum { TS_CAP = 16384 };                                         // rounds with stamps per stage (later ones go untimed)
 	uint32_t ts_round = 0;
 	bool sel_stamped = true;
@@ -489,7 +486,7 @@ struct DeviceBackend {
 	{
 		g.round_bits = (SS_ROUND_MAX - round) << 20;
 		// an event pair around every 4th launch (which ones rotates from stage to stage); the start stamps time all of them
-		const bool sampled = phase_events && ((round + ev_phase) & 3u) == 0;
+		const bool sampled = ((round + ev_phase) & 3u) == 0;
 		if (g.tslot < TS_CAP * 4) ts_kind.back() |= 4;
 		if (sampled) HIP_TRY(hipEventRecord(ev[2], c->stream));
 		if (solo) {
@@ -523,7 +520,7 @@ struct DeviceBackend {
 		// the driver is in chain mode: the rounds have stopped being parallel.  After a second, with less than 40 % of the stage behind it
 		// (the first iteration counted as 80 % of a stage: the later ones see what the few collapses of the one before left), the attempt
 		// is given up for the one-launch path -- which is within 2 x of the rounds on every many-strains case measured and up to 8 x
-		// faster on the slow ones (tools/gpu_r06_k.sh).
+		// faster on the slow ones (docs/history/r06.md).
 		if (may_try_dense && ++chain_rounds >= 32u) {
 			const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_stage).count();
 			const double within = (double)last_lo / (double)(nid_ ? nid_ : 1u);
@@ -628,7 +625,7 @@ static void scan_u32(sbl_ctx *c, SimplifyState *st, unsigned *in, unsigned *out,
 	HIP_TRY(rocprim::exclusive_scan(st->scantmp.p, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
 }
 
-// Inputs up to this many elements take the one-launch path (k_dense_stage) first; SBL_NO_DENSE_PATH=1 / SBL_DENSE_MAX_ELEMS=n: test switches
+// Inputs up to this many elements take the one-launch path (k_dense_stage) first; SBL_NO_DENSE_PATH=1: test switch
 #define DENSE_MAX_ELEMS (1u << 16)
 // The reference's callback sequence (blockfinder.cpp:23-48) is a function of the call index alone -- start, run(min(i, 50)) for i = 1, 2, ...,
 // end -- so an attempt that is abandoned and run again delivers only the calls the caller has not seen yet.
@@ -690,7 +687,6 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 		HIP_TRY(hipHostMalloc((void **)&c->simp->h_ctr, (CTR_COUNT + 16) * 4, hipHostMallocMapped | hipHostMallocCoherent));
 		memset(c->simp->h_ctr, 0, (CTR_COUNT + 16) * 4);
 		if (hipHostGetDevicePointer((void **)&c->simp->d_hctr, c->simp->h_ctr, 0) != hipSuccess) { (void)hipGetLastError(); c->simp->d_hctr = nullptr; }
-		if (getenv("SBL_NO_POST")) c->simp->d_hctr = nullptr;             // measurement switch: copy + synchronise as before
 	}
 	SimplifyState *st = c->simp;
 	DeviceBackend be;
@@ -724,9 +720,7 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 	sbl_compact_marks(c, 1);
 	size_t n0 = c->nmarks[0], n1 = c->nmarks[1], ninst = n0 + n1;
 	c->stats.instances = ninst;
-	size_t dense_max = DENSE_MAX_ELEMS;
-	if (const char *e = getenv("SBL_DENSE_MAX_ELEMS")) dense_max = (size_t)atoll(e);
-	if (force_dense) dense_max = std::max<size_t>(dense_max, DENSE_SWITCH_MAX_ELEMS);
+	const size_t dense_max = force_dense ? DENSE_SWITCH_MAX_ELEMS : DENSE_MAX_ELEMS;
 	const bool dense = allow_dense && E <= dense_max && be.nid_ > 0 && getenv("SBL_NO_DENSE_PATH") == nullptr;
 	// (a job on several GPUs never switches: the decision is timed, and the ranks must stay in step)
 	be.may_try_dense = may_switch && !dense && !c->comm && E <= DENSE_SWITCH_MAX_ELEMS && getenv("SBL_NO_DENSE_PATH") == nullptr && getenv("SBL_NO_DENSE_SWITCH") == nullptr;
@@ -812,8 +806,7 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 		be.snap_threads = (uint32_t)std::max<size_t>(256, std::min<size_t>(256 * 32, (16ull << 30) / be.arena_bytes)) & ~7u;   // a multiple of the 8 XCDs
 		be.big_arena_bytes = (uint32_t)std::min<size_t>(std::max<size_t>(256u << 20, 64 * be.arena_bytes), 0xFFFFFF00u);
 	}
-	uint32_t base_window = 14336;                                        // (swept again at the end of round 3: 86.1 ms against 86.9 ms at 16 384, 62 strains 4.12 against 4.19 s)
-	if (const char *e = getenv("SBL_BASE_WINDOW")) base_window = (uint32_t)std::max(64, atoi(e));      // measurement switch (tools/sweep_window.sh)
+	const uint32_t base_window = 14336;                                  // (swept again at the end of round 3: 86.1 ms against 86.9 ms at 16 384, 62 strains 4.12 against 4.19 s)
 	uint32_t window = c->window ? c->window : std::min<uint32_t>(base_window, std::max<uint32_t>(2048, be.nid_ / 64));
 	window = std::min<uint32_t>(window, (1u << 20) - 1);
 	window = (uint32_t)std::min<size_t>(window, std::max<size_t>(64, (24ull << 30) / be.arena_bytes));
@@ -831,10 +824,10 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 	// by default there; SBL_PARK=4 is what the 2.15 s of profiles/r05_bench_config4.json were measured with.)
 	// Round 6: the serial chain and parking compose (DeviceBackend::chain stops NEW parking, what is parked drains), so the many-instances
 	// regime parks too -- with the cap that was measured best there (4: 2.135 s at 62 strains against 2.36 with 2) -- and so do the
-	// replicated commits of a job on several GPUs (SBL_PARK_COMM=0: debugging switch, the round-5 behaviour).
+	// replicated commits of a job on several GPUs.
 	unsigned park_cap = ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_) ? 4u : 2u;
 	if (const char *e = getenv("SBL_PARK")) park_cap = (unsigned)std::max(0, atoi(e));
-	if (dense || (c->comm && getenv("SBL_PARK_COMM") && atoi(getenv("SBL_PARK_COMM")) == 0)) park_cap = 0;
+	if (dense) park_cap = 0;
 	auto round_buffers = [&](uint32_t w) {
 		st->win.ensure((size_t)w * 4 + 16);
 		st->arena.ensure((size_t)w * be.arena_bytes * (park_cap ? 2u : 1u));      // (second half: the SHADOW slices -- where the entry of a window position works while its own slice holds a parked transaction)
@@ -865,17 +858,13 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 	be.ev = st->ev;
 	be.optimistic = optimistic;
 	be.rsv_waves = ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_) ? 4u : 2u;      // instances per id: a handful, or dozens (many strains)
-	if (const char *e = getenv("SBL_RSV_WAVES")) be.rsv_waves = (unsigned)std::min(4, std::max(1, atoi(e)));      // measurement switch
-	if (getenv("SBL_PROBE_BIG_LDS") == nullptr) {
-		// (the 512-slot table stays: a probe it cannot hold goes to the walking kernel, whose launch then lasts as long as a full probe -- 15 such
-		// entries per round cost more than the 2 KB save; the instance and mark lists follow the input: largest instance count, mark density)
-		be.pidx_inst = (unsigned)std::min<size_t>(256, std::max<size_t>(64, (be_maxn + 15) / 16 * 16));
-		be.pidx_marks = ninst * 8 > E ? 192u : 64u;
-	}
+	// (the 512-slot table stays: a probe it cannot hold goes to the walking kernel, whose launch then lasts as long as a full probe -- 15 such
+	// entries per round cost more than the 2 KB save; the instance and mark lists follow the input: largest instance count, mark density)
+	be.pidx_inst = (unsigned)std::min<size_t>(256, std::max<size_t>(64, (be_maxn + 15) / 16 * 16));
+	be.pidx_marks = ninst * 8 > E ? 192u : 64u;
 	// dozens of instances per id: a 1024-slot table.  With 512 slots 1.7 M of the 17 M probes of the 62-strain stage (2.35 M before the exact
 	// bound in probe_idx) went on to the walking kernel for the table alone; with 1024 none does and the stage takes 2.04 s instead of 2.17 s.
 	if (ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_)) be.pidx_vbits = 10;
-	if (const char *e = getenv("SBL_PIDX_VBITS")) be.pidx_vbits = (unsigned)std::min(11, std::max(8, atoi(e)));      // measurement switch
 	be.ev_phase = c->stage_seq++;
 	be.prof = getenv("SBL_PHASES") ? (atoi(getenv("SBL_PHASES")) > 0 ? atoi(getenv("SBL_PHASES")) : 1) : 0;
 	if (be.prof) sbl_commit_prof_reset();
@@ -898,17 +887,10 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 	}
 	if (((D + k + 2u + 126u) >> 6) > 16u) be.g.idx_probe = 0;           // windows of more than 16 blocks: k_probe_idx could serve nobody (every entry walks, as before round 5)
 	be.g.test_flags = getenv("SBL_TEST_FLAGS") ? (unsigned)atoi(getenv("SBL_TEST_FLAGS")) : 0u;
-	be.g.lazy_rescan = getenv("SBL_EAGER_RESCAN") ? 0u : 1u;            // measurement switch: dirty windows rescanned right after every collapse (round 3)
-	be.g.collapse_g = getenv("SBL_OLD_COLLAPSE") ? 0u : 1u;            // measurement switch: the round-3 collapse (a chain of dependent round trips) instead of the gather-first one
-	be.g.ab_estimate = getenv("SBL_NO_AB_ESTIMATE") ? 0u : 1u;         // measurement switch: AnyBulges of big ids without its counting pass
-	be.g.jscan_rounds = getenv("SBL_NO_JSCAN_ROUNDS") ? 0u : 1u;       // measurement switch
-	be.g.probe_pre = getenv("SBL_NO_PROBE_PRE") ? 0u : 1u;              // measurement switch: the endChar pre-pass of the probe (probe_endchars)
-	be.g.lazy_map = getenv("SBL_EAGER_MAP") ? 0u : 1u;                  // measurement switch: the Boost-ordered map of AnyBulges built eagerly (round 3)
 	be.g.tstamp = nullptr; be.g.tslot = 0;
 	be.g.sep = c->d_sepidx.as<unsigned>(); be.g.nsep = c->nchr + 1; be.g.norig = (uint32_t)E;
-	if (getenv("SBL_SEP_BY_CHAR")) be.g.sep = nullptr;                   // measurement switch: separators recognised by their character everywhere
 	be.index_build();
-	if (!dense && be.phase_events) be.stamps_init();
+	if (!dense) be.stamps_init();
 	HIP_TRY(hipEventRecord(c->ev[3], s));
 
 	// ---- SimplifyGraph
@@ -917,7 +899,7 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 		// tiny input: for iteration, for id, RemoveBulges(id) in one launch (k_dense_stage)
 		be.g.lazy_min = 1;                                            // every id keeps full-size mark lists and takes lazy windows
 		st->big_arena.ensure(be.big_arena_bytes);
-		unsigned *d_out = st->ctr.as<unsigned>() + CTR_DETAIL;        // (the violation-detail words are unused here)
+		unsigned *d_out = st->ctr.as<unsigned>() + CTR_DENSE_ITER;
 		HIP_TRY(hipEventRecord(be.ev[2], s));
 		k_dense_stage<<<1, 64, 0, s>>>(be.g, st->big_arena.as<uint8_t>(), be.big_arena_bytes, max_iter, d_out);
 		HIP_TRY(hipEventRecord(be.ev[3], s));
@@ -930,7 +912,7 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 			if (getenv("SBL_TRACE")) fprintf(stderr, "[sbl] one-launch path: capacity error %u, falling back to the ordered rounds\n", st->h_ctr[CTR_ERR]);
 			return RUN_DENSE_FAILED;
 		}
-		rep.iterations = st->h_ctr[CTR_DETAIL]; rep.bulges = st->h_ctr[CTR_BULGES]; rep.transactions = rep.executed = st->h_ctr[CTR_TXN];
+		rep.iterations = st->h_ctr[CTR_DENSE_ITER]; rep.bulges = st->h_ctr[CTR_BULGES]; rep.transactions = rep.executed = st->h_ctr[CTR_TXN];
 		rep.chain_transactions = rep.transactions;
 		if (progress) {                                               // the reference's callback sequence (blockfinder.cpp:23-48), delivered after the launch
 			progress(0, SBL_PROGRESS_START, user);
@@ -946,12 +928,12 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 		catch (const TryDense &) { HIP_TRY(hipStreamSynchronize(s)); return RUN_TRY_DENSE; }
 	}
 	HIP_TRY(hipEventRecord(c->ev[4], s));
-	if (!dense && be.phase_events) be.stamps_collect();
+	if (!dense) be.stamps_collect();
 	be.snapshots_collect();
-	if (be.g.bidx && (be.g.test_flags & 32u)) sbl_rounds_stats_report();      // SBL_TEST_FLAGS=32: what the block index served
+	if (be.g.bidx && (be.g.test_flags & BT_TF_STATS)) sbl_rounds_stats_report();      // what the block index served
 	if (be.g.bidx && getenv("SBL_CHECK_INDEX")) {                        // test switch: the maintained block index against a rebuild
 		unsigned init[2] = {0u, BT_NONE}, res[2];
-		unsigned *d_out = st->ctr.as<unsigned>() + CTR_DETAIL + 16;
+		unsigned *d_out = st->ctr.as<unsigned>() + CTR_IDXCHECK;
 		HIP_TRY(hipMemcpyAsync(d_out, init, sizeof init, hipMemcpyHostToDevice, s));
 		k_check_blkidx<<<(be.idx_nblk + 3) / 4, 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), st->pv.as<unsigned>(), c->d_bif[0].as<unsigned>(), c->d_bif[1].as<unsigned>(),
 		                                                    st->wmax.as<unsigned>(), be.g.norig, be.idx_nblk, st->bidx.as<unsigned long long>(), d_out);

@@ -92,7 +92,7 @@ __device__ __forceinline__ void wave_stamp(const GraphView &g, unsigned stampv, 
 	if (wm > tid) bad = true;
 	if (bad) {
 		atomicMin(&g.ctr[CTR_VIOL], other < id ? other : id);
-		if (atomicCAS(&g.ctr[CTR_DETAIL], 0u, other != BT_NONE ? 1u : 2u) == 0u) { g.ctr[CTR_DETAIL + 1] = r; g.ctr[CTR_DETAIL + 2] = other != BT_NONE ? other : wm - 1; g.ctr[CTR_DETAIL + 3] = id; g.ctr[CTR_DETAIL + 4] = mode; }
+		if (atomicCAS(&g.ctr[CTR_VDETAIL], 0u, other != BT_NONE ? 1u : 2u) == 0u) { g.ctr[CTR_VDETAIL + 1] = r; g.ctr[CTR_VDETAIL + 2] = other != BT_NONE ? other : wm - 1; g.ctr[CTR_VDETAIL + 3] = id; g.ctr[CTR_VDETAIL + 4] = mode; }
 	}
 }
 
@@ -302,9 +302,7 @@ __device__ __forceinline__ void wave_scan_instance(const GraphView &g, const Bul
 
 // windows first, first + stride, ... of the cache, SCAN_BATCH at a time: the first bursts of a whole batch are issued together and
 // then consumed in order (see ScanBurst: one memory round trip per batch instead of one per window)
-#ifndef SCAN_BATCH
 #define SCAN_BATCH 4
-#endif
 __device__ __forceinline__ void wave_scan_all(const GraphView &g, const BulgeWork &w, unsigned lane, unsigned stampv, unsigned tid, unsigned mode, unsigned id,
                                               unsigned first = 0, unsigned stride = 1)
 {

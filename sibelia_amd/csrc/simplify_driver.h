@@ -45,7 +45,6 @@ SimplifyReport simplify_graph(Backend &be, uint32_t max_iter, uint32_t window, s
 {
 	SimplifyReport rep;
 	const bool trace = getenv("SBL_TRACE") != nullptr;
-	const bool use_chain = getenv("SBL_NO_CHAIN") == nullptr;          // debugging / measurement switch
 	const uint32_t nid = be.nid();
 	const uint64_t per_iter = (uint64_t)nid + 1;                      // ids 0 .. GetMaxId() inclusive
 	const uint64_t threshold = ((uint64_t)nid * max_iter) / 50;       // PROGRESS_STRIDE, blockfinder.cpp:28
@@ -63,9 +62,7 @@ SimplifyReport simplify_graph(Backend &be, uint32_t max_iter, uint32_t window, s
 	if (window > (1u << 20) - 1) window = (1u << 20) - 1;
 	if (window_max < window) window_max = window;
 	if (window_max > (1u << 20) - 1) window_max = (1u << 20) - 1;
-	if (getenv("SBL_FIXED_WINDOW")) window_max = window;              // measurement switch
-	double widen = 0.15;                                              // share of the base window that may stay blocked before the window widens
-	if (const char *e = getenv("SBL_WIDEN")) widen = atof(e);         // measurement switch
+	const double widen = 0.15;                                        // share of the base window that may stay blocked before the window widens
 	do {
 		rep.iterations++;
 		if (nid) {
@@ -114,7 +111,7 @@ SimplifyReport simplify_graph(Backend &be, uint32_t max_iter, uint32_t window, s
 					SimplifyCounters c = be.counters();
 					if (trace) fprintf(stderr, "[sbl] iter %u round %u lo %u limit %u nwin %u solo %u committed %u bulges %u big %u viol %d err %u\n",
 					                   rep.iterations, round, lo, this_limit, nwin, solo, c.v[CTR_COMMITTED], c.v[CTR_BULGES], c.v[CTR_BIG], (int)c.v[CTR_VIOL], c.v[CTR_ERR]);
-					if (trace && c.v[CTR_VIOL] != BT_NONE) fprintf(stderr, "[sbl] violation detail: kind %u resource %u other %u id %u info %u\n", c.v[CTR_DETAIL], c.v[CTR_DETAIL + 1], c.v[CTR_DETAIL + 2], c.v[CTR_DETAIL + 3], c.v[CTR_DETAIL + 4]);
+					if (trace && c.v[CTR_VIOL] != BT_NONE) fprintf(stderr, "[sbl] violation detail: kind %u resource %u other %u id %u info %u\n", c.v[CTR_VDETAIL], c.v[CTR_VDETAIL + 1], c.v[CTR_VDETAIL + 2], c.v[CTR_VDETAIL + 3], c.v[CTR_VDETAIL + 4]);
 					if (c.v[CTR_ERR]) {
 						if (!be.grow(c.v[CTR_ERR])) throw SblError{SBL_ERR_INTERNAL, "bulge removal: unrecoverable capacity error"};
 						replay = true; rep.grow_replays++;
@@ -143,7 +140,7 @@ SimplifyReport simplify_graph(Backend &be, uint32_t max_iter, uint32_t window, s
 					}
 					if (chained) rep.chain_transactions += txn;
 					else if (!solo && blocked >= 8 && txn <= 2) {       // absolute: a handful of slow transactions per round still beat one wave
-						if (++starved >= 2 && use_chain && !chain_mode) {
+						if (++starved >= 2 && !chain_mode) {
 							chain_mode = true;
 							if (trace) fprintf(stderr, "[sbl] iter %u: chain mode from id %u\n", rep.iterations, lo);
 						}

@@ -15,7 +15,7 @@ struct MarkStream { const unsigned *elem[2], *id[2], *aux[2]; unsigned n[2]; };
 // debugging / measurement counters that live beside the kernels that bump them (device globals are per translation unit)
 void sbl_commit_prof_reset();
 void sbl_commit_prof_report(unsigned ts_round);                       // SBL_PHASES=1: prints the phase cycle counters of k_commit
-void sbl_rounds_stats_report();                                      // SBL_TEST_FLAGS=32: what the block index served, reservation phase ticks
+void sbl_rounds_stats_report();                                      // test_flags & BT_TF_STATS: what the block index served, reservation phase ticks
 
 __global__ void __launch_bounds__(256) k_init_links(unsigned *__restrict__ nx, unsigned *__restrict__ pv, unsigned *__restrict__ nodeof0,
                                                     unsigned *__restrict__ nodeof1, uint8_t *__restrict__ ch, size_t E, size_t cap);

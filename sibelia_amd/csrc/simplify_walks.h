@@ -247,7 +247,7 @@ __device__ __forceinline__ void wave_publish_collapse(const GraphView &g, unsign
 	{
 		enum { RC = 4, FC = 3 };
 		const unsigned ub = d ? e + 1 : e - 1;                              // the element before e in its walking direction, if consecutive
-		if (!(g.test_flags & 8u) && nreg <= 64u * RC && reach <= 64u * FC && e != 0 && span_inside(sp, e, d, nreg + reach) && span_inside(sp, ub, d ^ 1u, reach)) {
+		if (!(g.test_flags & BT_TF_STEPWISE_PUBLISH) && nreg <= 64u * RC && reach <= 64u * FC && e != 0 && span_inside(sp, e, d, nreg + reach) && span_inside(sp, ub, d ^ 1u, reach)) {
 			const unsigned *__restrict__ lf = d ? g.pv : g.nx, *__restrict__ lb = d ? g.nx : g.pv;
 			unsigned r0[RC], r1[RC], rl[RC], um[FC], ul[FC], dm[FC], dl[FC];
 			const unsigned l0 = lb[e], dfirst = d ? e - nreg : e + nreg;
@@ -287,7 +287,7 @@ __device__ __forceinline__ void wave_publish_collapse(const GraphView &g, unsign
 							unsigned rm = g.rmax[bt_ridx_elem(c)];
 							if (a > tid || rm > tid) {
 								atomicMin(&g.ctr[CTR_VIOL], id);
-								if (atomicCAS(&g.ctr[CTR_DETAIL], 0u, 4u) == 0u) { g.ctr[CTR_DETAIL + 1] = c; g.ctr[CTR_DETAIL + 2] = (a > rm ? a : rm) - 1; g.ctr[CTR_DETAIL + 3] = id; g.ctr[CTR_DETAIL + 4] = (a > tid ? 1u : 0u) | (rm > tid ? 2u : 0u); }
+								if (atomicCAS(&g.ctr[CTR_VDETAIL], 0u, 4u) == 0u) { g.ctr[CTR_VDETAIL + 1] = c; g.ctr[CTR_VDETAIL + 2] = (a > rm ? a : rm) - 1; g.ctr[CTR_VDETAIL + 3] = id; g.ctr[CTR_VDETAIL + 4] = (a > tid ? 1u : 0u) | (rm > tid ? 2u : 0u); }
 							}
 						}
 					}
@@ -324,7 +324,7 @@ __device__ __forceinline__ void wave_publish_collapse(const GraphView &g, unsign
 				unsigned rm = g.rmax[bt_ridx_elem(c)];
 				if (a > tid || rm > tid) {
 					atomicMin(&g.ctr[CTR_VIOL], id);
-					if (atomicCAS(&g.ctr[CTR_DETAIL], 0u, 4u) == 0u) { g.ctr[CTR_DETAIL + 1] = c; g.ctr[CTR_DETAIL + 2] = (a > rm ? a : rm) - 1; g.ctr[CTR_DETAIL + 3] = id; g.ctr[CTR_DETAIL + 4] = (a > tid ? 1u : 0u) | (rm > tid ? 2u : 0u); }
+					if (atomicCAS(&g.ctr[CTR_VDETAIL], 0u, 4u) == 0u) { g.ctr[CTR_VDETAIL + 1] = c; g.ctr[CTR_VDETAIL + 2] = (a > rm ? a : rm) - 1; g.ctr[CTR_VDETAIL + 3] = id; g.ctr[CTR_VDETAIL + 4] = (a > tid ? 1u : 0u) | (rm > tid ? 2u : 0u); }
 				}
 			}
 		}

@@ -489,7 +489,7 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 		// computed against the occupancy at the start of the chunk and their small-block indices built in ONE launch; a group whose
 		// candidate block comes out the same when its turn comes (it is recomputed: a byte scan) uses that index, any other group
 		// and every further trim iteration takes the one-block path as before.
-		const bool speculate = sy.tiny_out != nullptr && getenv("SBL_NO_TINY_BATCH") == nullptr;
+		const bool speculate = sy.tiny_out != nullptr;
 		const size_t CHUNK = 8192;
 		struct Spec { std::vector<BEdge> now; int slot; };
 		std::vector<Spec> spec;
