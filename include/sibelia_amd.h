@@ -160,6 +160,32 @@ sbl_status sbl_postprocess(sbl_ctx *ctx, int glue, const char *const *names, con
  * Host bookkeeping only: needs neither a context nor a device. */
 sbl_status sbl_glue_stripes(sbl_block *blocks, uint64_t *n, uint32_t nchr);
 
+/* OutputGenerator::ListBlocksSequences (src/outputgenerator.cpp:287-318): the text of blocks_sequences.fasta for a block list
+ * (blocks == NULL: the context's current list, i.e. after sbl_generate_blocks / sbl_postprocess), spelled from the ORIGINAL
+ * records kept on the device.  names as in sbl_postprocess.  Owned by the ctx, valid until the next call.
+ * Per instance, in the reference's order (ONE unstable sort by |id| of a copy of the list): a header line
+ *   >Seq="<description>",Strand='<+|->',Block_id=<|id|>,Start=<from>,End=<to>
+ * (1-based; a reverse instance is reported from its far end, as in blocks_coords.txt), the end - start bases in lines of 80 and a
+ * line feed.  Reverse instances are spelled downwards through the reference's complement table (src/dnasequence.cpp:11-28):
+ * ACGT / acgt swapped, every other character -- ambiguity codes included -- unchanged.  The text is generated by a kernel
+ * (csrc/blockseq.hip) and comes back through a pinned buffer of the context.  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
+ * end < start, end beyond the record, id == 0, no records loaded.
+ * sbl_blocks_sequences_times: device time of the last call's kernel and of its device-to-host copy (event pairs). */
+sbl_status sbl_blocks_sequences(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
+                                const char **text, uint64_t *len);
+sbl_status sbl_blocks_sequences_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
+
+/* OutputGenerator::ListBlocksIndicesGFF (src/outputgenerator.cpp:598-631); blocks / names as above.  Host formatting only:
+ * "##gff-version 2", "##source-version Sibelia 3.0.7", "##Type DNA", then per instance (one unstable sort by |id|) the tab-separated
+ * columns <striped id> Sibelia synteny_block_copy <min(from, to)> <max(from, to)> . <+|-> . <|id|>.  Striped id (src/fasta.h:44-64):
+ * with '|' and '.' read as blanks, a description of exactly five tokens gives its fourth; any other description stands as it is. */
+sbl_status sbl_blocks_gff(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
+                          const char **text, uint64_t *len);
+/* OutputGenerator::ListBlocksIndices (src/outputgenerator.cpp:227-233), the blocks_coords.txt of sbl_postprocess, for any list: under
+ * --allstages the reference's main writes one such file per stage (src/sibelia.cpp:300-308).  blocks / names as above. */
+sbl_status sbl_blocks_coords(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
+                             const char **text, uint64_t *len);
+
 /* Replaces BlockFinder::SerializeGraph (src/serialization.cpp:112-138; defined for records of at least k + 1 characters -- the
  * reference walks off the end of a shorter one): DOT text of the UNcondensed de Bruijn graph of the
  * current state, one line per (k+1)-window, generated on the device (a debugging dump: main only reaches it with -q and never

@@ -106,6 +106,22 @@ namespace SyntenyFinderAMD
 			blocksCoords = t0; permutations = t1; coverageReport = t2;
 		}
 
+		// OutputGenerator::ListBlocksSequences (outputgenerator.cpp:287-318): the text of blocks_sequences.fasta for a block list, spelled on
+		// the device from the original records; OutputGenerator::ListBlocksIndicesGFF (:598-631) / ListBlocksIndices (:227-233): the texts
+		// of blocks_coords.gff / blocks_coords.txt.  descriptions as in PostProcess.
+		std::string ListBlocksSequences(const std::vector<BlockInstance> &block, const std::vector<std::string> &descriptions = std::vector<std::string>())
+		{
+			return BlockReport(&sbl_blocks_sequences, "ListBlocksSequences", block, descriptions);
+		}
+		std::string ListBlocksIndicesGFF(const std::vector<BlockInstance> &block, const std::vector<std::string> &descriptions = std::vector<std::string>())
+		{
+			return BlockReport(&sbl_blocks_gff, "ListBlocksIndicesGFF", block, descriptions);
+		}
+		std::string ListBlocksIndices(const std::vector<BlockInstance> &block, const std::vector<std::string> &descriptions = std::vector<std::string>())
+		{
+			return BlockReport(&sbl_blocks_coords, "ListBlocksIndices", block, descriptions);
+		}
+
 		// Postprocessor::GlueStripes (postprocessor.cpp:37-154) on any block list, e.g. the blocks of an earlier stage (sibelia.cpp:247-253)
 		static void GlueStripes(std::vector<BlockInstance> &block, size_t chrCount)
 		{
@@ -184,6 +200,18 @@ namespace SyntenyFinderAMD
 			}
 			try { Check(sbl_load(ctx_, (uint32_t)ptr.size(), ptr.data(), len.data()), "Init"); }
 			catch (...) { sbl_destroy(ctx_); ctx_ = nullptr; throw; }        // the destructor of a half-built object never runs
+		}
+		typedef sbl_status (*BlockReportFn)(sbl_ctx *, const sbl_block *, uint64_t, const char *const *, const char **, uint64_t *);
+		std::string BlockReport(BlockReportFn fn, const char *what, const std::vector<BlockInstance> &block, const std::vector<std::string> &descriptions)
+		{
+			if (!descriptions.empty() && descriptions.size() != sbl_nchr(ctx_)) throw std::runtime_error(std::string("sibelia_amd: ") + what + ": one description per record expected");
+			std::vector<const char *> nm;
+			for (const std::string &d : descriptions) nm.push_back(d.c_str());
+			std::vector<sbl_block> flat(block.size() + 1);             // (+ 1: an empty list still has an address; NULL selects the context's list)
+			for (size_t i = 0; i < block.size(); i++) { flat[i].id = block[i].id; flat[i].chr = (uint32_t)block[i].chr; flat[i].start = block[i].start; flat[i].end = block[i].end; }
+			const char *t = nullptr; uint64_t n = 0;
+			Check(fn(ctx_, flat.data(), block.size(), nm.empty() ? nullptr : nm.data(), &t, &n), what);
+			return std::string(t, (size_t)n);
 		}
 		struct CallBackBox { ProgressCallBack &f; std::exception_ptr thrown; };
 		static void Trampoline(size_t progress, int state, void *user)

@@ -25,7 +25,8 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_list_edges", "sbl_last_stats", "sbl_last_error", "sbl_strerror", "sbl_set_window",
            "sbl_save_state", "sbl_restore_state", "sbl_load_fasta", "sbl_record_name", "sbl_kmer_hashes", "sbl_generate_blocks", "sbl_postprocess", "sbl_serialize_graph",
            "sbl_set_tempfile_mode", "sbl_rand_advance", "sbl_shard_layout", "sbl_shard_exchange_plan", "sbl_glue_stripes", "sbl_comm_unique_id", "sbl_comm_attach_rccl", "sbl_comm_attach_local", "sbl_comm_detach",
-           "sbl_longk_slices", "sbl_longk_value_bounds", "sbl_longk_owner", "sbl_longk_halo_plan"]
+           "sbl_longk_slices", "sbl_longk_value_bounds", "sbl_longk_owner", "sbl_longk_halo_plan",
+           "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords"]
 
 
 class StageStats(C.Structure):
@@ -87,6 +88,9 @@ def load_library():
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         L.sbl_serialize_graph.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_kmer_hashes.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        for fn in (L.sbl_blocks_sequences, L.sbl_blocks_gff, L.sbl_blocks_coords):
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_blocks_sequences_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -218,6 +222,42 @@ class BlockFinder:
         t = [C.c_char_p() for _ in range(3)]
         self._check(self.L.sbl_postprocess(self.h, int(glue), nm, C.byref(b), C.byref(n), C.byref(t[0]), C.byref(t[1]), C.byref(t[2])), "sbl_postprocess")
         return _view(b.value, n.value, formats.BLOCK_DTYPE), [x.value for x in t]
+
+    def _block_report(self, fn, what, blocks, names) -> bytes:
+        nm = None
+        if names is not None:
+            if len(names) != self.L.sbl_nchr(self.h):      # the C entry points read one name per loaded record
+                raise ValueError("%s: %d names for %d records" % (what, len(names), self.L.sbl_nchr(self.h)))
+            nm = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        b, n = None, 0
+        if blocks is not None:
+            arr = np.ascontiguousarray(blocks, dtype=formats.BLOCK_DTYPE)
+            n = len(arr)
+            # (blocks == NULL selects the context's list: an explicit empty list still needs an address)
+            hold = C.create_string_buffer(formats.BLOCK_DTYPE.itemsize)
+            b = arr.ctypes.data if n else C.addressof(hold)
+        t, ln = C.c_void_p(), C.c_uint64()
+        self._check(fn(self.h, b, n, nm, C.byref(t), C.byref(ln)), what)
+        return C.string_at(t, ln.value) if ln.value else b""
+
+    def blocks_sequences(self, blocks: Optional[np.ndarray] = None, names: Optional[Sequence[str]] = None) -> bytes:
+        """OutputGenerator::ListBlocksSequences (reference src/outputgenerator.cpp:287-318): the text of blocks_sequences.fasta for
+        `blocks` (None: the blocks of the last GenerateSyntenyBlocks / postprocess), generated on the device from the original records."""
+        return self._block_report(self.L.sbl_blocks_sequences, "sbl_blocks_sequences", blocks, names)
+
+    def blocks_sequences_times(self) -> Tuple[float, float]:
+        """(kernel ms, device-to-host copy ms) of the last blocks_sequences call, from event pairs."""
+        k, d = C.c_double(), C.c_double()
+        self._check(self.L.sbl_blocks_sequences_times(self.h, C.byref(k), C.byref(d)), "sbl_blocks_sequences_times")
+        return k.value, d.value
+
+    def blocks_gff(self, blocks: Optional[np.ndarray] = None, names: Optional[Sequence[str]] = None) -> bytes:
+        """OutputGenerator::ListBlocksIndicesGFF (reference src/outputgenerator.cpp:598-631): the text of blocks_coords.gff."""
+        return self._block_report(self.L.sbl_blocks_gff, "sbl_blocks_gff", blocks, names)
+
+    def blocks_coords(self, blocks: Optional[np.ndarray] = None, names: Optional[Sequence[str]] = None) -> bytes:
+        """OutputGenerator::ListBlocksIndices (reference src/outputgenerator.cpp:227-233): the text of blocks_coords.txt for any list."""
+        return self._block_report(self.L.sbl_blocks_coords, "sbl_blocks_coords", blocks, names)
 
     def serialize_graph(self, k: int) -> bytes:
         """BlockFinder::SerializeGraph (reference src/blockfinder.h:41): DOT text of the uncondensed graph."""

@@ -225,7 +225,76 @@ std::string coverage_report(const std::vector<sbl_block> &block, const Records &
 	return t.s;
 }
 
+// FASTARecord::GetStripedId (src/fasta.h:44-64): '|' and '.' count as blanks; a description of exactly five blank-separated tokens
+// (gi|<number>|<db>|<accession>.<version>|) is reported as its fourth one, the accession; any other description as it is
+std::string striped_id(const std::string &description)
+{
+	std::vector<std::string> token;
+	std::string cur;
+	for (char ch : description) {
+		const bool blank = ch == '|' || ch == '.' || ch == ' ' || (ch >= '\t' && ch <= '\r');
+		if (!blank) cur += ch;
+		else if (!cur.empty()) { token.push_back(cur); cur.clear(); }
+	}
+	if (!cur.empty()) token.push_back(cur);
+	return token.size() == 5 ? token[3] : description;
+}
+
+// ListBlocksIndicesGFF (src/outputgenerator.cpp:598-631): three header lines, then one row per instance after ONE unstable sort by |id|
+std::string blocks_gff(const std::vector<sbl_block> &block, const Records &r)
+{
+	Text t;
+	t.s = "##gff-version 2\n##source-version Sibelia 3.0.7\n##Type DNA\n";       // VERSION, src/sibelia.cpp:11
+	std::vector<sbl_block> v = block;
+	sbl_sort_by_id(v);
+	std::vector<std::string> striped;
+	for (const std::string &n : r.name) striped.push_back(striped_id(n));
+	for (const sbl_block &b : v) {
+		const bool fwd = b.id > 0;
+		const unsigned long long from = fwd ? b.start + 1 : b.end, to = fwd ? b.end : b.start + 1;      // conventional start / end
+		t.s += striped[b.chr];
+		t.row("\tSibelia\tsynteny_block_copy\t%llu\t%llu\t.\t%c\t.\t%d\n", std::min(from, to), std::max(from, to), fwd ? '+' : '-', iabs(b.id));
+	}
+	return t.s;
+}
+
+Records records_of(const sbl_ctx *c, const char *const *names)
+{
+	Records r;
+	for (uint32_t i = 0; i < c->nchr; i++) {
+		r.size.push_back(c->orig_sepidx[i + 1] - c->orig_sepidx[i] - 1);
+		r.name.push_back(names ? std::string(names[i]) : i < c->fa_names.size() ? c->fa_names[i] : std::string());
+	}
+	return r;
+}
+
 }  // namespace
+
+// std::sort(..., compareById) / GroupBy(blockList, compareById) of the reference's writers: the same libstdc++ call on the same element order
+void sbl_sort_by_id(std::vector<sbl_block> &v) { (void)group_by(v, ById()); }
+
+extern "C" sbl_status sbl_blocks_gff(sbl_ctx *c, const sbl_block *blocks, uint64_t n, const char *const *names, const char **text, uint64_t *len)
+{
+	return guarded(c, [&] {
+		if (!blocks) { blocks = c->blocks.data(); n = c->blocks.size(); }
+		sbl_check_blocks(c, blocks, n);
+		c->gff_text = blocks_gff(std::vector<sbl_block>(blocks, blocks + n), records_of(c, names));
+		if (text) *text = c->gff_text.data();
+		if (len) *len = c->gff_text.size();
+	});
+}
+
+// blocks_coords.txt of a caller's list: under --allstages the reference's main writes one per stage (src/sibelia.cpp:300-308)
+extern "C" sbl_status sbl_blocks_coords(sbl_ctx *c, const sbl_block *blocks, uint64_t n, const char *const *names, const char **text, uint64_t *len)
+{
+	return guarded(c, [&] {
+		if (!blocks) { blocks = c->blocks.data(); n = c->blocks.size(); }
+		sbl_check_blocks(c, blocks, n);
+		c->coords_text = blocks_coords(std::vector<sbl_block>(blocks, blocks + n), records_of(c, names));
+		if (text) *text = c->coords_text.data();
+		if (len) *len = c->coords_text.size();
+	});
+}
 
 extern "C" sbl_status sbl_postprocess(sbl_ctx *c, int glue, const char *const *names, const sbl_block **blocks, uint64_t *n,
                                       const char **coords, const char **perms, const char **coverage)

@@ -55,6 +55,7 @@ struct sbl_ctx {
 	{
 		host_free(h_ch, h_pinned); host_free(h_opos, h_pinned); host_free(h_old_ch, h_old_pinned); host_free(h_old_opos, h_old_pinned);
 		h_ch = h_old_ch = nullptr; h_opos = h_old_opos = nullptr; h_cap = 0;
+		host_free(h_bs_text, h_bs_pinned); h_bs_text = nullptr; h_bs_cap = 0;
 	}
 
 	// ---- enumeration workspace
@@ -81,6 +82,17 @@ struct sbl_ctx {
 	std::vector<sbl_block> blocks;
 	std::string graph_text;              // sbl_serialize_graph
 	std::string report[3];               // sbl_postprocess: blocks_coords.txt, genomes_permutations.txt, coverage_report.txt
+	std::string gff_text, coords_text;   // sbl_blocks_gff, sbl_blocks_coords
+
+	// sbl_blocks_sequences (blockseq.hip): descriptors, text offsets, header blob and the text on the device; the text comes back
+	// through ONE pinned staging buffer (pageable when the pinned allocation fails: h_bs_pinned), freed with the context
+	DevBuf d_bs_desc, d_bs_off, d_bs_hdr, d_bs_text;
+	std::string bs_headers;
+	char *h_bs_text = nullptr;
+	size_t h_bs_cap = 0;
+	bool h_bs_pinned = true;
+	uint64_t bs_len = 0;
+	double bs_kernel_ms = 0, bs_copy_ms = 0;   // event pairs around the kernel / the device-to-host copy of the last call
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;
@@ -138,6 +150,10 @@ void sbl_longk_free(sbl_ctx *c);
 // implemented in longk_fp.hip
 bool sbl_run_enumeration_longk_fp(sbl_ctx *c, uint32_t k, size_t elem_capacity);   // k > 32: window fingerprints + bucketed table + exact verification; false = a verification failed, run the doubling
 void sbl_longk_fp_free(sbl_ctx *c);
+// implemented in postprocess.hip
+void sbl_sort_by_id(std::vector<sbl_block> &v);   // the one unstable sort by |id| the reference's writers apply to a copy of the list
+// implemented in blockseq.hip
+void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n);   // a caller's block list against the loaded records (throws SBL_ERR_BAD_ARG)
 // implemented in simplify.hip
 void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges);
 void sbl_simplify_free(sbl_ctx *c);

@@ -107,6 +107,12 @@ class LocalShardedFinder:
     def postprocess(self, names=None, glue=True):
         return self.ranks[0].postprocess(names, glue)
 
+    def blocks_sequences(self, blocks=None, names=None):
+        return self.ranks[0].blocks_sequences(blocks, names)
+
+    def blocks_gff(self, blocks=None, names=None):
+        return self.ranks[0].blocks_gff(blocks, names)
+
     def serialize_graph(self, k):
         return self.ranks[0].serialize_graph(k)
 

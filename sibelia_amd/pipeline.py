@@ -1,0 +1,374 @@
+"""The whole pipeline of the reference's program (reference src/sibelia.cpp:186-345) over BlockFinder.
+
+`parse_args` reads the reference's command line, `run` restates its main: the stage cascade with the trimK / lastK rule, the
+per-stage blocks of --allstages / -v (computed BEFORE the stage: they consume the rand() stream), the rand() stream kept in step
+with and without -r, and the choice of which files are written.  `run` returns (return code, {relative file name: bytes}, text for
+standard output); `main` writes the files and prints the text (python -m sibelia_amd).
+
+Not written: circos/ and d3_blocks_diagram.html -- the reference instantiates them from templates embedded in its own sources.
+
+Everything up to `run` (option parsing, stage files, the k rule, the file plan) imports and works without the HIP library.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import re
+import sys
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+INT_MAX = 2 ** 31 - 1
+MAX_INPUT_SIZE = 1 << 30                      # src/common.h:52
+
+# the parameter sets of src/util.cpp:52-87: (vertex size k, minimum branch size) per stage
+PARAMETER_SETS = {
+    "loose": [(30, 150), (100, 1000), (1000, 5000), (5000, 15000)],
+    "fine": [(30, 150), (100, 500), (500, 1500)],
+    "far": [(15, 120), (100, 500), (500, 1500)],
+}
+
+NOT_WRITTEN = ("The Circos files (circos/) and d3_blocks_diagram.html of the reference program are not written: "
+               "they are instantiated from templates embedded in the reference's sources.")
+
+
+class PipelineError(RuntimeError):
+    """What the reference's main reports as `error: <message>` with return code 1."""
+
+
+# ------------------------------------------------------------------------------------------ stage files
+
+def parse_stage_text(text: str) -> List[Tuple[int, int]]:
+    """ReadStageFile (src/util.cpp:11-50) on the file's text: a count, then `count` pairs of integers, all separated by blanks;
+    what follows the last pair is ignored, as a C++ stream extraction leaves it unread."""
+    tokens = text.split()
+    at = 0
+
+    def take() -> Optional[int]:
+        nonlocal at
+        if at >= len(tokens):
+            return None
+        m = re.match(r"[+-]?\d+", tokens[at])       # operator>>(int) reads the longest integer prefix and fails without one
+        if not m:
+            at = len(tokens)                        # a failed extraction leaves the stream failed: every later read fails too
+            return None
+        if m.end() == len(tokens[at]):
+            at += 1
+        else:
+            tokens[at] = tokens[at][m.end():]       # the rest of the token stays in the stream
+        v = int(m.group())
+        if not -2 ** 31 <= v <= INT_MAX:            # out of range for int: the extraction fails
+            at = len(tokens)
+            return None
+        return v
+
+    count = take()
+    if count is None:
+        raise PipelineError("cannot read stage file")
+    if count < 0:
+        raise PipelineError("number of stages must be nonnegative")
+    stages = []
+    for _ in range(count):
+        k = take()
+        d = take() if k is not None else None
+        if k is None or d is None:
+            raise PipelineError("too few records in the stage file")
+        if k < 2:
+            raise PipelineError("vertex size in stage record must be at least 2")
+        if d < 0:
+            raise PipelineError("minimum branch size in stage record must be nonnegative")
+        stages.append((k, d))
+    return stages
+
+
+def read_stage_file(path: str) -> List[Tuple[int, int]]:
+    try:
+        with open(path, "r", errors="replace") as f:
+            text = f.read()
+    except OSError:
+        raise PipelineError("cannot open stage file")
+    return parse_stage_text(text)
+
+
+# ------------------------------------------------------------------------------------------ command line
+
+class _Parser(argparse.ArgumentParser):
+    def error(self, message):                       # TCLAP's ArgException: reported by main, return code 1
+        raise PipelineError(message)
+
+
+def _greater_than(bound: int) -> Callable[[str], int]:
+    def conv(s: str) -> int:
+        v = int(s)
+        if v <= bound:
+            raise argparse.ArgumentTypeError("integer > %d expected" % bound)
+        return v
+    return conv
+
+
+def _unsigned(s: str) -> int:
+    v = int(s)
+    if v < 0 or v > 2 ** 32 - 1:
+        raise argparse.ArgumentTypeError("unsigned integer expected")
+    return v
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = _Parser(prog="python -m sibelia_amd", description="Program for finding synteny blocks in closely related genomes "
+                "(Sibelia 3.0.7's command line over the MI355X library).  " + NOT_WRITTEN)
+    p.add_argument("-s", "--parameters", choices=sorted(PARAMETER_SETS), default=None,
+                   help="Parameters set, used for the simplification. Option \"loose\" produces fewer blocks, but they are larger (\"fine\" is opposite).")
+    p.add_argument("-k", "--stagefile", default=None, metavar="file name", help="File that contains manually chosen simplifications parameters.")
+    p.add_argument("-i", "--maxiterations", type=_greater_than(0), default=4, help="Maximum number of iterations during a stage of simplification, default = 4.")
+    p.add_argument("-m", "--minblocksize", type=_unsigned, default=5000, help="Minimum size of a synteny block, default value = 5000 BP.")
+    p.add_argument("-a", "--sharedonly", action="store_true", help="Output only blocks that occur exactly once in each input sequence.")
+    p.add_argument("-r", "--inram", action="store_true", help="Perform all computations in RAM, don't create temp files.")
+    p.add_argument("-t", "--tempdir", default=None, metavar="dir name", help="Directory where temporary files are stored.")
+    p.add_argument("-o", "--outdir", default=".", metavar="dir name", help="Directory where output files are written")
+    p.add_argument("-g", "--graphfile", action="store_true", help="Output resulting condensed de Bruijn graph (in dot format).")
+    p.add_argument("-q", "--sequencesfile", action="store_true", help="Output sequences of synteny blocks (FASTA format).")
+    p.add_argument("-v", "--visualize", action="store_true", help="Compute the blocks of every stage, as the reference does for its hierarchy diagram (the diagram itself is not written).")
+    p.add_argument("--allstages", action="store_true", help="Output coordinates of synteny blocks from all stages")
+    p.add_argument("--gff", action="store_true", help="Use GFF format for reporting blocks coordinates")
+    p.add_argument("--lastk", type=_greater_than(1), default=None, help="Value of K used for the synteny blocks inferring.")
+    p.add_argument("--nopostprocess", action="store_true", help="Do not perform postprocessing (stripe gluing).")
+    p.add_argument("--noblocks", action="store_true", help="Do not compute synteny blocks")
+    p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
+    p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
+    return p
+
+
+def parse_args(argv: Sequence[str]) -> argparse.Namespace:
+    """The reference's options by letter and name; exactly one of -s / -k (TCLAP xorAdd, src/sibelia.cpp:184)."""
+    opt = build_parser().parse_args(list(argv))
+    if (opt.parameters is None) == (opt.stagefile is None):
+        raise PipelineError("exactly one of -s (--parameters) and -k (--stagefile) is required")
+    return opt
+
+
+def stages_of(opt: argparse.Namespace) -> List[Tuple[int, int]]:
+    return list(PARAMETER_SETS[opt.parameters]) if opt.parameters is not None else read_stage_file(opt.stagefile)
+
+
+# ------------------------------------------------------------------------------------------ the k rule and the file plan
+
+def stage_trim_k(stages: Sequence[Tuple[int, int]], i: int) -> int:
+    """trimK of the per-stage GenerateSyntenyBlocks before stage i: the smallest k so far (src/sibelia.cpp:244)."""
+    return min([INT_MAX] + [k for k, _ in stages[:i + 1]])
+
+
+def final_k(stages: Sequence[Tuple[int, int]], min_block_size: int, lastk: Optional[int] = None) -> Tuple[int, int]:
+    """(lastK, trimK) of the final GenerateSyntenyBlocks (src/sibelia.cpp:271-272)."""
+    mbs = _as_int(min_block_size)
+    trim_k = min([INT_MAX, mbs] + [k for k, _ in stages])
+    last_k = lastk if lastk is not None else min(stages[-1][0] if stages else INT_MAX, mbs)
+    return last_k, trim_k
+
+
+def _as_int(u: int) -> int:
+    """static_cast<int>(unsigned)"""
+    return u - 2 ** 32 if u >= 2 ** 31 else u
+
+
+def tempdir_of(opt: argparse.Namespace) -> str:
+    return opt.tempdir if opt.tempdir is not None else opt.outdir
+
+
+def stage_graph_written(opt: argparse.Namespace, i: int, outdir_exists: bool) -> bool:
+    """de_bruijn_graph<i>.dot of stage i is opened without creating the output directory (src/sibelia.cpp:256-262): it exists only if
+    the directory was there already, or if an earlier index created it as its temp directory -- without -r every index does that first
+    (src/vertexenumeration.cpp:187), and before stage 0's graph the only index is the one of the stage's blocks."""
+    if outdir_exists:
+        return True
+    if opt.inram or os.path.abspath(tempdir_of(opt)) != os.path.abspath(opt.outdir):
+        return False
+    return i > 0 or not opt.noblocks
+
+
+def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = False) -> List[str]:
+    """Names of the files a run with these options writes, relative to the output directory, in the order they are written."""
+    out = []
+    if (opt.visualize or opt.allstages) and opt.graphfile:
+        out += ["de_bruijn_graph%d.dot" % i for i in range(nstages) if stage_graph_written(opt, i, outdir_exists)]
+    if not opt.noblocks:
+        ext = ".gff" if opt.gff else ".txt"
+        out += ["blocks_coords%d%s" % (i, ext) for i in range(nstages + 1)] if opt.allstages else ["blocks_coords" + ext]
+        out += ["genomes_permutations.txt", "coverage_report.txt"]
+        if opt.sequencesfile:
+            out.append("blocks_sequences.fasta")
+    if opt.graphfile:
+        out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
+    return out
+
+
+class ProgressBar:
+    """PutProgressChr (src/util.cpp:89-111): `prev` is a static of the function -- it survives from one bar to the next and is reset
+    only when a bar starts."""
+    START, RUN, END = 0, 1, 2
+
+    def __init__(self, write: Callable[[str], None]):
+        self.prev = 0
+        self.write = write
+
+    def __call__(self, progress: int, state: int) -> None:
+        while self.prev < progress:
+            self.prev += 1
+            self.write(".")
+        if state == self.START:
+            self.prev = 0
+            self.write("[")
+        elif state == self.END:
+            self.write("]\n")
+
+
+# ------------------------------------------------------------------------------------------ input
+
+def _fasta_error(path: str) -> Optional[str]:
+    """The message FASTAReader::GetSequences (src/fasta.cpp:23-104) ends with on this file, None if it parses."""
+    valid = b"ACGTURYKMSWBDHWNX-"
+    header, have_seq, line = b"", False, 1
+    what = None
+    with open(path, "rb") as f:
+        rows = f.read().split(b"\n")
+    if rows and rows[-1] == b"" and len(rows) > 1:
+        rows.pop()                                  # text after the last line feed: none
+    for raw in rows:
+        buf = raw.strip(b" \t\n\v\f\r")
+        if not buf:
+            continue
+        if buf[:1] == b">":
+            if header and not have_seq:
+                what = "empty sequence"
+                break
+            if header:
+                have_seq = False
+            sp = buf.find(b" ")
+            header = buf[1:sp] if sp >= 0 else buf[1:]
+            if not header:
+                what = "empty header"
+                break
+        else:
+            bad = [c for c in buf if bytes([c]).upper() not in valid]
+            if bad:
+                what = "illegal character: " + chr(bad[0])
+                break
+            have_seq = True
+        line += 1
+    if what is None and not have_seq:
+        what = "empty sequence"
+    return None if what is None else "parse error in %s on line %d: %s" % (path, line, what)
+
+
+def load_input(filenames: Sequence[str], device: int = -1):
+    """-> (finder, names).  One file goes through the FASTA loader on the device; several are read on the host and appended to one
+    record list, as the reference does (src/sibelia.cpp:209-225)."""
+    from . import workloads
+    from .api import BlockFinder, SibeliaError
+    for f in filenames:
+        if not os.path.isfile(f) or not os.access(f, os.R_OK):
+            raise PipelineError("Cannot open file " + f)
+    try:
+        if len(filenames) == 1:
+            bf = BlockFinder.from_fasta(filenames[0], device=device)
+            return bf, None
+        names, seqs = [], []
+        for f in filenames:
+            try:
+                n, s = workloads.read_fasta(f)
+            except ValueError as e:
+                raise PipelineError(_fasta_error(f) or "parse error in %s: %s" % (f, e))
+            names += n
+            seqs += s
+        if sum(len(s) for s in seqs) > MAX_INPUT_SIZE:
+            raise PipelineError("Input is larger than 1 GB, can't proceed")
+        bf = BlockFinder(seqs, device=device)
+        return bf, names
+    except SibeliaError as e:
+        text = str(e)
+        m = re.search(r"\((.*)\)\s*$", text, re.S)
+        if "input exceeds" in text and "total input" in text:
+            raise PipelineError("Input is larger than 1 GB, can't proceed")
+        raise PipelineError(m.group(1) if m and m.group(1) else text)
+
+
+# ------------------------------------------------------------------------------------------ main
+
+def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outdir_exists: Optional[bool] = None) -> Tuple[int, Dict[str, bytes], str]:
+    """The reference's main (src/sibelia.cpp:186-345).  `write` receives the standard output as it is produced; `outdir_exists`
+    (default: look) is whether the output directory is there before the run.  Raises PipelineError for what main reports as an error."""
+    from . import formats
+    from .api import glue_stripes
+    opt = parse_args(argv)
+    stages = stages_of(opt)
+    if outdir_exists is None:
+        outdir_exists = os.path.isdir(opt.outdir)
+    printed: List[str] = []
+
+    def say(s: str) -> None:
+        printed.append(s)
+        if write:
+            write(s)
+
+    bar = ProgressBar(say)
+    bf, names = load_input(opt.filenames, opt.device)
+    files: Dict[str, bytes] = {}
+    try:
+        if not opt.inram:
+            bf.set_tempfile_mode(True)            # BlockFinder(chrList, tempDir): temp-file names come out of the same rand() stream
+        nchr = len(names) if names is not None else len(bf.record_names())
+        history = [None] * (len(stages) + 1)
+        every_stage = opt.visualize or opt.allstages
+        for i, (k, branch) in enumerate(stages):
+            if every_stage:
+                if not opt.noblocks:
+                    b = bf.GenerateSyntenyBlocks(k, stage_trim_k(stages, i), k, opt.sharedonly)
+                    history[i] = b if opt.nopostprocess else glue_stripes(b, nchr)
+                if opt.graphfile:
+                    text = formats.dot_text(bf.list_edges(k))      # runs whether the file can be opened or not: it draws from rand()
+                    if stage_graph_written(opt, i, outdir_exists):
+                        files["de_bruijn_graph%d.dot" % i] = text
+            say("Simplification stage %d of %d\n" % (i + 1, len(stages)))
+            say("Enumerating vertices of the graph, then performing bulge removal...\n")
+            bf.PerformGraphSimplifications(k, branch, opt.maxiterations, bar)
+        say("Finding synteny blocks and generating the output...\n")
+        last_k, trim_k = final_k(stages, opt.minblocksize, opt.lastk)
+        if not opt.noblocks:
+            bf.GenerateSyntenyBlocks(last_k, trim_k, opt.minblocksize, opt.sharedonly)
+            blocks, (coords, perms, coverage) = bf.postprocess(names, glue=not opt.nopostprocess)
+            history[-1] = blocks
+            writer, ext = (bf.blocks_gff, ".gff") if opt.gff else (bf.blocks_coords, ".txt")
+            if opt.allstages:
+                for i, h in enumerate(history):
+                    files["blocks_coords%d%s" % (i, ext)] = writer(h, names)
+            else:
+                files["blocks_coords" + ext] = writer(None, names) if opt.gff else coords
+            files["genomes_permutations.txt"] = perms
+            files["coverage_report.txt"] = coverage
+            if opt.sequencesfile:
+                files["blocks_sequences.fasta"] = bf.blocks_sequences(None, names)
+        if opt.graphfile:
+            files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
+    finally:
+        bf.close()
+    assert list(files) == planned_files(opt, len(stages), outdir_exists)
+    return 0, files, "".join(printed)
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+
+    def write(s: str) -> None:
+        sys.stdout.write(s)
+        sys.stdout.flush()
+    try:
+        opt = parse_args(argv)
+        rc, files, _ = run(argv, write=write, outdir_exists=os.path.isdir(opt.outdir))
+        if not opt.inram:                           # the reference's indices create their temp directory (by default the output directory)
+            os.makedirs(tempdir_of(opt), exist_ok=True)
+        os.makedirs(opt.outdir, exist_ok=True)
+        for name, data in files.items():
+            with open(os.path.join(opt.outdir, name), "wb") as f:
+                f.write(data)
+        return rc
+    except PipelineError as e:
+        sys.stderr.write("error: %s\n" % e)
+        return 1
