@@ -21,9 +21,9 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <rocprim/rocprim.hpp>
 
 #include "sbl_ctx.h"
+#include "sbl_prim.h"
 #include "kmer_kernels.h"
 
 static inline unsigned nblocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
@@ -158,14 +158,6 @@ __global__ void __launch_bounds__(256) k_amb_write(const uint8_t *__restrict__ c
 	}
 }
 
-static void scan_u32(sbl_ctx *c, const unsigned *in, unsigned *out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-	c->d_scantmp.ensure(tmp);
-	HIP_TRY(rocprim::exclusive_scan(c->d_scantmp.p, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-}
-
 // d_ch (padded with '$'), d_sepidx and c->sepidx / nchr / nelem are in place: derive op[] and the ambiguity list on the device
 void sbl_finish_load(sbl_ctx *c)
 {
@@ -185,7 +177,7 @@ void sbl_finish_load(sbl_ctx *c)
 		c->d_chunkcnt.ensure((size_t)(nchunks + 1) * 4); c->d_chunkoff.ensure((size_t)(nchunks + 1) * 4);
 		HIP_TRY(hipMemsetAsync(c->d_chunkcnt.p, 0, (size_t)(nchunks + 1) * 4, s));
 		k_amb_flags<<<nchunks, 256, 0, s>>>(c->d_ch.as<uint8_t>(), E, c->d_chunkcnt.as<unsigned>());
-		scan_u32(c, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), nchunks + 1);
+		prim::exclusive_scan(s, c->d_scantmp, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), 0u, nchunks + 1, rocprim::plus<unsigned>());
 		c->d_amb_elem.ensure((size_t)namb * 4); c->d_amb_char.ensure(namb);
 		k_amb_write<<<nblocks(nchunks, 256), 256, 0, s>>>(c->d_ch.as<uint8_t>(), E, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), nchunks,
 		                                                 c->d_amb_elem.as<unsigned>(), c->d_amb_char.as<uint8_t>());
@@ -237,7 +229,7 @@ extern "C" sbl_status sbl_load_fasta(sbl_ctx *c, const char *path)
 		c->d_chunkcnt.ensure((size_t)(nchk + 1) * 4); c->d_chunkoff.ensure((size_t)(nchk + 1) * 4);
 		HIP_TRY(hipMemsetAsync(c->d_chunkcnt.p, 0, (size_t)(nchk + 1) * 4, s));
 		k_fa_count_nl<<<nchk, 256, 0, s>>>(txt.as<uint8_t>(), n, c->d_chunkcnt.as<unsigned>());
-		scan_u32(c, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), nchk + 1);
+		prim::exclusive_scan(s, c->d_scantmp, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), 0u, nchk + 1, rocprim::plus<unsigned>());
 		unsigned nnl = 0;
 		HIP_TRY(hipMemcpyAsync(&nnl, c->d_chunkoff.as<unsigned>() + nchk, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
@@ -254,9 +246,9 @@ extern "C" sbl_status sbl_load_fasta(sbl_ctx *c, const char *path)
 		HIP_TRY(hipMemsetAsync(err, 0xFF, 8, s));
 		k_fa_line_starts<<<nchk, 256, 0, s>>>(txt.as<uint8_t>(), n, c->d_chunkoff.as<unsigned>(), line_start);
 		k_fa_lines<<<nblocks(nlines, 256), 256, 0, s>>>(txt.as<uint8_t>(), n, line_start, nlines, la, lb, nonempty, isheader, seqlen, err);
-		scan_u32(c, nonempty, ne_before, stride);
-		scan_u32(c, isheader, hdr_before, stride);
-		scan_u32(c, seqlen, seq_before, stride);
+		prim::exclusive_scan(s, c->d_scantmp, nonempty, ne_before, 0u, stride, rocprim::plus<unsigned>());
+		prim::exclusive_scan(s, c->d_scantmp, isheader, hdr_before, 0u, stride, rocprim::plus<unsigned>());
+		prim::exclusive_scan(s, c->d_scantmp, seqlen, seq_before, 0u, stride, rocprim::plus<unsigned>());
 		unsigned tot[3];
 		HIP_TRY(hipMemcpyAsync(&tot[0], ne_before + nlines, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipMemcpyAsync(&tot[1], hdr_before + nlines, 4, hipMemcpyDeviceToHost, s));

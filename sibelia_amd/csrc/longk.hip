@@ -10,9 +10,9 @@
 // Every step is a data-parallel kernel, a radix sort, a scan or a segmented OR -- HBM-streaming integer work.
 #include <cstring>
 #include <algorithm>
-#include <rocprim/rocprim.hpp>
 
 #include "sbl_ctx.h"
+#include "sbl_prim.h"
 
 static inline unsigned nblocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
@@ -239,8 +239,8 @@ struct LongKShardHolder;              // workspaces of the sharded variant (belo
 struct LongKScratch {
 	DevBuf rank[2], keys, skeys, idx, sidx, flag, scan, mask, gkeys, gmask, gcount, gbif, gid, tmp, sym, act, aux;
 	LongKShardHolder *shard = nullptr;
+	~LongKScratch();                  // (below, where the holder is complete)
 };
-static void lk_shard_free(LongKShardHolder *h);
 static LongKScratch &lk_of(sbl_ctx *c)      // grow-only scratch owned by the context (contexts may live on different devices / host threads)
 {
 	if (!c->lk) c->lk = new LongKScratch;
@@ -248,58 +248,8 @@ static LongKScratch &lk_of(sbl_ctx *c)      // grow-only scratch owned by the co
 }
 void sbl_longk_free(sbl_ctx *c)
 {
-	if (!c->lk) return;
-	LongKScratch &L = *c->lk;
-	for (DevBuf *b : { &L.rank[0], &L.rank[1], &L.keys, &L.skeys, &L.idx, &L.sidx, &L.flag, &L.scan, &L.mask, &L.gkeys, &L.gmask, &L.gcount, &L.gbif, &L.gid, &L.tmp, &L.sym, &L.act, &L.aux })
-		b->release();
-	lk_shard_free(L.shard);
 	delete c->lk;
 	c->lk = nullptr;
-}
-
-static void lk_sort(sbl_ctx *c, unsigned long long *kin, unsigned long long *kout, unsigned *vin, unsigned *vout, size_t n, unsigned bits = 64)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-	lk_of(c).tmp.ensure(tmp);
-	HIP_TRY(rocprim::radix_sort_pairs(lk_of(c).tmp.p, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-}
-static void lk_sort32(sbl_ctx *c, unsigned *kin, unsigned *kout, unsigned *vin, unsigned *vout, size_t n, unsigned bits)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-	lk_of(c).tmp.ensure(tmp);
-	HIP_TRY(rocprim::radix_sort_pairs(lk_of(c).tmp.p, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-}
-static unsigned lk_bits(unsigned long long v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; return b; }
-static void lk_inclusive_scan(sbl_ctx *c, unsigned *in, unsigned *out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::plus<unsigned>(), c->stream));
-	lk_of(c).tmp.ensure(tmp);
-	HIP_TRY(rocprim::inclusive_scan(lk_of(c).tmp.p, tmp, in, out, n, rocprim::plus<unsigned>(), c->stream));
-}
-static void lk_exclusive_scan(sbl_ctx *c, unsigned *in, unsigned *out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-	lk_of(c).tmp.ensure(tmp);
-	HIP_TRY(rocprim::exclusive_scan(lk_of(c).tmp.p, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-}
-
-static void lk_max_scan(sbl_ctx *c, unsigned *in, unsigned *out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::maximum<unsigned>(), c->stream));
-	lk_of(c).tmp.ensure(tmp);
-	HIP_TRY(rocprim::inclusive_scan(lk_of(c).tmp.p, tmp, in, out, n, rocprim::maximum<unsigned>(), c->stream));
-}
-static void lk_select(sbl_ctx *c, unsigned *in, unsigned *flags, unsigned *out, unsigned *count_out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::select(nullptr, tmp, in, flags, out, count_out, n, c->stream));
-	lk_of(c).tmp.ensure(tmp);
-	HIP_TRY(rocprim::select(lk_of(c).tmp.p, tmp, in, flags, out, count_out, n, c->stream));
 }
 
 struct BitOr { __host__ __device__ unsigned operator()(unsigned a, unsigned b) const { return a | b; } };
@@ -361,26 +311,26 @@ void sbl_run_enumeration_longk(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 		unsigned &na = na_final;
 		na = (unsigned)np;
 		bool first = true;
-		const unsigned rbp = lk_bits(np);                            // ranks are indices into the sorted order from the first round on
+		const unsigned rbp = prim::bits_of(np);                            // ranks are indices into the sorted order from the first round on
 		while (2 * h <= k && na) {
 			// a round over EVERY suffix (sequential key construction, ranks back by a sort) while most of them are still active -- sets of
 			// related genomes stay that way --, over the active ones only (two gathers and a scatter per suffix) once they are the minority
 			const bool full = first || na > np / 2;
-			const unsigned rb = first ? lk_bits(maxrank) : rbp;
+			const unsigned rb = first ? prim::bits_of(maxrank) : rbp;
 			const unsigned m = full ? (unsigned)np : na;
 			const bool from27 = first && first27;                   // the first round: rank_27 straight from the symbols (k_lk_key27), one 63-bit sort
 			if (from27) k_lk_key27<<<nblocks(np, 256), 256, 0, s>>>(L.sym.as<unsigned>(), (unsigned)np, L.keys.as<unsigned long long>(), L.idx.as<unsigned>());
 			else if (full) k_lk_pair_keys<<<nblocks(np, 256), 256, 0, s>>>(rank, (unsigned)np, (unsigned)h, rb, L.keys.as<unsigned long long>(), L.idx.as<unsigned>());
 			else k_lk_active_keys<<<nblocks(na, 256), 256, 0, s>>>(rank, L.act.as<unsigned>(), na, (unsigned)np, (unsigned)h, rb, L.keys.as<unsigned long long>(), L.idx.as<unsigned>());
-			lk_sort(c, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), m, from27 ? 63u : std::min(64u, 2 * rb));
+			prim::sort_pairs(s, L.tmp, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), m, 0, from27 ? 63u : std::min(64u, 2 * rb));
 			k_lk_heads2<<<nblocks(m, 256), 256, 0, s>>>(L.skeys.as<unsigned long long>(), m, rb, L.flag.as<unsigned>(), L.scan.as<unsigned>());
-			lk_max_scan(c, L.flag.as<unsigned>(), L.mask.as<unsigned>(), m);       // gstart
-			lk_max_scan(c, L.scan.as<unsigned>(), L.aux.as<unsigned>(), m);        // sstart
+			prim::inclusive_scan(s, L.tmp, L.flag.as<unsigned>(), L.mask.as<unsigned>(), m, rocprim::maximum<unsigned>());       // gstart
+			prim::inclusive_scan(s, L.tmp, L.scan.as<unsigned>(), L.aux.as<unsigned>(), m, rocprim::maximum<unsigned>());        // sstart
 			const bool pairs = full && by_sort;                      // everybody in the sort: the new ranks go back into position order by a sort
 			k_lk_newrank<<<nblocks(m, 256), 256, 0, s>>>(L.skeys.as<unsigned long long>(), L.sidx.as<unsigned>(), L.mask.as<unsigned>(), L.aux.as<unsigned>(), m, rb, full ? 1 : 0,
 			                                            rank, L.flag.as<unsigned>(), pairs ? L.scan.as<unsigned>() : nullptr);
-			if (pairs) lk_sort32(c, L.sidx.as<unsigned>(), L.idx.as<unsigned>(), L.scan.as<unsigned>(), rank, m, lk_bits(np - 1));
-			lk_select(c, L.sidx.as<unsigned>(), L.flag.as<unsigned>(), L.act.as<unsigned>(), c->d_counters.as<unsigned>() + 8, m);
+			if (pairs) prim::sort_pairs(s, L.tmp, L.sidx.as<unsigned>(), L.idx.as<unsigned>(), L.scan.as<unsigned>(), rank, m, 0, prim::bits_of(np - 1));
+			prim::select(s, L.tmp, L.sidx.as<unsigned>(), L.flag.as<unsigned>(), L.act.as<unsigned>(), c->d_counters.as<unsigned>() + 8, m);
 			HIP_TRY(hipMemcpyAsync(&na, c->d_counters.as<unsigned>() + 8, 4, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
 			const bool was_first = first;
@@ -406,31 +356,31 @@ void sbl_run_enumeration_longk(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 		const unsigned ncand = na + 4u * c->nchr;
 		k_lk_cand_keys<<<nblocks(ncand, 256), 256, 0, s>>>(rank, L.act.as<unsigned>(), na, c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, k, (unsigned)h,
 		                                                  L.keys.as<unsigned long long>(), L.idx.as<unsigned>(), c->d_counters.as<unsigned>());
-		lk_sort(c, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), ncand);
+		prim::sort_pairs(s, L.tmp, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), ncand, 0, 64);
 		HIP_TRY(hipMemcpyAsync(&nv, c->d_counters.p, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 	}
 	if (plain) {
 		while (2 * h <= k) {
-			const unsigned rb = lk_bits(maxrank);
+			const unsigned rb = prim::bits_of(maxrank);
 			k_lk_pair_keys<<<nblocks(np, 256), 256, 0, s>>>(rank, (unsigned)np, (unsigned)h, rb, L.keys.as<unsigned long long>(), L.idx.as<unsigned>());
-			lk_sort(c, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), np, std::min(64u, 2 * rb));
+			prim::sort_pairs(s, L.tmp, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), np, 0, std::min(64u, 2 * rb));
 			k_lk_heads<<<nblocks(np, 256), 256, 0, s>>>(L.skeys.as<unsigned long long>(), (unsigned)np, L.flag.as<unsigned>());
-			lk_inclusive_scan(c, L.flag.as<unsigned>(), L.scan.as<unsigned>(), np);
+			prim::inclusive_scan(s, L.tmp, L.flag.as<unsigned>(), L.scan.as<unsigned>(), np, rocprim::plus<unsigned>());
 			if (by_sort) {
 				// (sidx, scan - 1) sorted by sidx = rank[] in position order; L.flag / L.idx are free at this point
 				k_lk_rank_values<<<nblocks(np, 256), 256, 0, s>>>(L.scan.as<unsigned>(), (unsigned)np, L.flag.as<unsigned>());
-				lk_sort32(c, L.sidx.as<unsigned>(), L.idx.as<unsigned>(), L.flag.as<unsigned>(), rank, np, lk_bits(np - 1));
+				prim::sort_pairs(s, L.tmp, L.sidx.as<unsigned>(), L.idx.as<unsigned>(), L.flag.as<unsigned>(), rank, np, 0, prim::bits_of(np - 1));
 			} else
 				k_lk_scatter_rank<<<nblocks(np, 256), 256, 0, s>>>(L.sidx.as<unsigned>(), L.scan.as<unsigned>(), (unsigned)np, rank);
 			HIP_TRY(hipMemcpyAsync(&maxrank, L.scan.as<unsigned>() + (np - 1), 4, hipMemcpyDeviceToHost, s));      // number of distinct 2h-prefixes
 			HIP_TRY(hipStreamSynchronize(s));
 			h *= 2;
 		}
-		const unsigned rbw = lk_bits((unsigned long long)maxrank + 1);   // (+ 1: the all-ones key of that width stays above every valid key)
+		const unsigned rbw = prim::bits_of((unsigned long long)maxrank + 1);   // (+ 1: the all-ones key of that width stays above every valid key)
 		k_lk_window_keys<<<nblocks(n, 256), 256, 0, s>>>(rank, c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, (unsigned)n, k, (unsigned)h, rbw,
 		                                                L.keys.as<unsigned long long>(), L.idx.as<unsigned>());
-		lk_sort(c, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), n, std::min(64u, 2 * rbw));
+		prim::sort_pairs(s, L.tmp, L.keys.as<unsigned long long>(), L.skeys.as<unsigned long long>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), n, 0, std::min(64u, 2 * rbw));
 		{	// valid windows = the metric's N, at the front of the sorted order (the invalid ones carry the largest key)
 			unsigned long long N = 0;
 			for (uint32_t ch = 0; ch < c->nchr; ch++) { const size_t len = c->sepidx[ch + 1] - c->sepidx[ch] - 1; if (len >= k) N += 2 * (len - k + 1); }
@@ -451,22 +401,18 @@ void sbl_run_enumeration_longk(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 	if (nv) {
 		k_lk_masks<<<nblocks(nv, 256), 256, 0, s>>>(L.skeys.as<unsigned long long>(), L.sidx.as<unsigned>(), nv, L.sym.as<unsigned>(), k,
 		                                           L.mask.as<unsigned>(), L.flag.as<unsigned>());
-		lk_inclusive_scan(c, L.flag.as<unsigned>(), L.scan.as<unsigned>(), nv);
+		prim::inclusive_scan(s, L.tmp, L.flag.as<unsigned>(), L.scan.as<unsigned>(), nv, rocprim::plus<unsigned>());
 		unsigned ngroups = 0;
 		HIP_TRY(hipMemcpyAsync(&ngroups, L.scan.as<unsigned>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		L.gkeys.ensure((size_t)ngroups * 4 + 16); L.gmask.ensure((size_t)ngroups * 4 + 16); L.gcount.ensure(16);
 		L.gbif.ensure((size_t)ngroups * 4 + 16); L.gid.ensure((size_t)ngroups * 4 + 16);
 		{	// segmented OR of the masks: key = group number (the scan), one output per group, in order
-			size_t tmp = 0;
-			HIP_TRY(rocprim::reduce_by_key(nullptr, tmp, L.scan.as<unsigned>(), L.mask.as<unsigned>(), nv, L.gkeys.as<unsigned>(), L.gmask.as<unsigned>(),
-			                               L.gcount.as<unsigned>(), BitOr(), rocprim::equal_to<unsigned>(), s));
-			L.tmp.ensure(tmp);
-			HIP_TRY(rocprim::reduce_by_key(L.tmp.p, tmp, L.scan.as<unsigned>(), L.mask.as<unsigned>(), nv, L.gkeys.as<unsigned>(), L.gmask.as<unsigned>(),
-			                               L.gcount.as<unsigned>(), BitOr(), rocprim::equal_to<unsigned>(), s));
+			prim::reduce_by_key(s, L.tmp, L.scan.as<unsigned>(), L.mask.as<unsigned>(), nv, L.gkeys.as<unsigned>(), L.gmask.as<unsigned>(),
+			                    L.gcount.as<unsigned>(), BitOr(), rocprim::equal_to<unsigned>());
 		}
 		k_lk_group_bif<<<nblocks(ngroups, 256), 256, 0, s>>>(L.gmask.as<unsigned>(), ngroups, L.gbif.as<unsigned>());
-		lk_exclusive_scan(c, L.gbif.as<unsigned>(), L.gid.as<unsigned>(), ngroups);
+		prim::exclusive_scan(s, L.tmp, L.gbif.as<unsigned>(), L.gid.as<unsigned>(), 0u, ngroups, rocprim::plus<unsigned>());
 		unsigned last_id = 0, last_bif = 0;
 		HIP_TRY(hipMemcpyAsync(&last_id, L.gid.as<unsigned>() + (ngroups - 1), 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipMemcpyAsync(&last_bif, L.gbif.as<unsigned>() + (ngroups - 1), 4, hipMemcpyDeviceToHost, s));
@@ -730,6 +676,7 @@ struct LkShardScratch {
 	DevBuf rk, halo, aflag, act, k0, i0, k1, i1, rkeys, ridx, skeys, sidx, f0, f1, s0, s1, ov, oi1, ov1, bi, bv, cnt, bounds, mcode, mid, gcode, gid2;
 };
 struct LongKShardHolder { LkShardScratch s; };
+LongKScratch::~LongKScratch() { delete shard; }
 
 namespace {
 struct LksClock {
@@ -831,14 +778,14 @@ static void run_enumeration_longk_sharded(sbl_ctx *c, uint32_t k, size_t elem_ca
 	// ---- the first three doubling rounds are arithmetic (base-5 number of 8 symbols), on the slice
 	if (len) k_lks_rank8<<<nblocks(len, 256), 256, 0, s>>>(c->d_ch.as<uint8_t>(), c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, (unsigned)n, lo, len, S.rk.as<unsigned>(), S.act.as<unsigned>());
 	size_t h = 8;
-	const unsigned maxrank0 = 390624, rbp = lk_bits(np);
+	const unsigned maxrank0 = 390624, rbp = prim::bits_of(np);
 	SBL_CHECK(sbl_longk_value_bounds(R, maxrank0, V.data()) == SBL_OK, SBL_ERR_INTERNAL, "value bounds");
 	unsigned na = len;                                                    // my active positions
 	unsigned long long na_all = np;
 	bool first = true;
 	unsigned round = 0;
 	while (2 * h <= k && na_all) {
-		const unsigned rb = first ? lk_bits(maxrank0) : rbp;
+		const unsigned rb = first ? prim::bits_of(maxrank0) : rbp;
 		const unsigned long long bytes0 = c->stats.exchange_bytes;
 		lks_fetch_halo(c, S, clk, np, h);
 		S.k0.ensure((size_t)na * 8 + 16); S.i0.ensure((size_t)na * 4 + 16);
@@ -855,10 +802,10 @@ static void run_enumeration_longk_sharded(sbl_ctx *c, uint32_t k, size_t elem_ca
 		}
 		S.skeys.ensure(m * 8 + 16); S.sidx.ensure(m * 4 + 16); S.f0.ensure(m * 4 + 16); S.f1.ensure(m * 4 + 16); S.s0.ensure(m * 4 + 16); S.s1.ensure(m * 4 + 16); S.ov.ensure(m * 4 + 16);
 		if (m) {
-			lk_sort(c, S.rkeys.as<unsigned long long>(), S.skeys.as<unsigned long long>(), S.ridx.as<unsigned>(), S.sidx.as<unsigned>(), m, std::min(64u, 2 * rb));
+			prim::sort_pairs(s, L.tmp, S.rkeys.as<unsigned long long>(), S.skeys.as<unsigned long long>(), S.ridx.as<unsigned>(), S.sidx.as<unsigned>(), m, 0, std::min(64u, 2 * rb));
 			k_lk_heads2<<<nblocks(m, 256), 256, 0, s>>>(S.skeys.as<unsigned long long>(), (unsigned)m, rb, S.f0.as<unsigned>(), S.f1.as<unsigned>());
-			lk_max_scan(c, S.f0.as<unsigned>(), S.s0.as<unsigned>(), m);      // gstart
-			lk_max_scan(c, S.f1.as<unsigned>(), S.s1.as<unsigned>(), m);      // sstart
+			prim::inclusive_scan(s, L.tmp, S.f0.as<unsigned>(), S.s0.as<unsigned>(), m, rocprim::maximum<unsigned>());      // gstart
+			prim::inclusive_scan(s, L.tmp, S.f1.as<unsigned>(), S.s1.as<unsigned>(), m, rocprim::maximum<unsigned>());      // sstart
 			k_lks_newrank<<<nblocks(m, 256), 256, 0, s>>>(S.skeys.as<unsigned long long>(), S.s0.as<unsigned>(), S.s1.as<unsigned>(), (unsigned)m, rb, first ? 1 : 0, (unsigned)G[r], S.ov.as<unsigned>());
 		}
 		// back to the position side
@@ -866,11 +813,8 @@ static void run_enumeration_longk_sharded(sbl_ctx *c, uint32_t k, size_t elem_ca
 		SBL_CHECK(mb == na, SBL_ERR_INTERNAL, "sharded rank doubling: a position did not get its rank back");
 		if (mb) k_lks_apply<<<nblocks(mb, 256), 256, 0, s>>>(S.bi.as<unsigned>(), S.bv.as<unsigned>(), (unsigned)mb, lo, S.rk.as<unsigned>(), S.aflag.as<unsigned>());
 		if (len) {
-			size_t tmp = 0;
 			rocprim::counting_iterator<unsigned> it(lo);
-			HIP_TRY(rocprim::select(nullptr, tmp, it, S.aflag.as<unsigned>(), S.act.as<unsigned>(), c->d_counters.as<unsigned>() + 8, (size_t)len, s));
-			L.tmp.ensure(tmp);
-			HIP_TRY(rocprim::select(L.tmp.p, tmp, it, S.aflag.as<unsigned>(), S.act.as<unsigned>(), c->d_counters.as<unsigned>() + 8, (size_t)len, s));
+			prim::select(s, L.tmp, it, S.aflag.as<unsigned>(), S.act.as<unsigned>(), c->d_counters.as<unsigned>() + 8, (size_t)len);
 			HIP_TRY(hipMemcpyAsync(&na, c->d_counters.as<unsigned>() + 8, 4, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
 		} else na = 0;
@@ -892,13 +836,8 @@ static void run_enumeration_longk_sharded(sbl_ctx *c, uint32_t k, size_t elem_ca
 	                                              c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, k, (unsigned)h, rbp, S.k0.as<unsigned long long>(), S.i0.as<unsigned>(), S.f0.as<unsigned>());
 	unsigned nvl = 0;
 	{
-		size_t tmp = 0;
-		HIP_TRY(rocprim::select(nullptr, tmp, S.k0.as<unsigned long long>(), S.f0.as<unsigned>(), S.k1.as<unsigned long long>(), c->d_counters.as<unsigned>() + 8, (size_t)ncand, s));
-		L.tmp.ensure(tmp);
-		HIP_TRY(rocprim::select(L.tmp.p, tmp, S.k0.as<unsigned long long>(), S.f0.as<unsigned>(), S.k1.as<unsigned long long>(), c->d_counters.as<unsigned>() + 8, (size_t)ncand, s));
-		HIP_TRY(rocprim::select(nullptr, tmp, S.i0.as<unsigned>(), S.f0.as<unsigned>(), S.i1.as<unsigned>(), c->d_counters.as<unsigned>() + 8, (size_t)ncand, s));
-		L.tmp.ensure(tmp);
-		HIP_TRY(rocprim::select(L.tmp.p, tmp, S.i0.as<unsigned>(), S.f0.as<unsigned>(), S.i1.as<unsigned>(), c->d_counters.as<unsigned>() + 8, (size_t)ncand, s));
+		prim::select(s, L.tmp, S.k0.as<unsigned long long>(), S.f0.as<unsigned>(), S.k1.as<unsigned long long>(), c->d_counters.as<unsigned>() + 8, (size_t)ncand);
+		prim::select(s, L.tmp, S.i0.as<unsigned>(), S.f0.as<unsigned>(), S.i1.as<unsigned>(), c->d_counters.as<unsigned>() + 8, (size_t)ncand);
 		HIP_TRY(hipMemcpyAsync(&nvl, c->d_counters.as<unsigned>() + 8, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 	}
@@ -918,24 +857,20 @@ static void run_enumeration_longk_sharded(sbl_ctx *c, uint32_t k, size_t elem_ca
 	S.mcode.ensure(nv * 4 + 16); S.mid.ensure(nv * 4 + 16);
 	unsigned ngroups = 0;
 	if (nv) {
-		lk_sort(c, S.rkeys.as<unsigned long long>(), S.skeys.as<unsigned long long>(), S.ridx.as<unsigned>(), S.sidx.as<unsigned>(), nv, std::min(64u, 2 * rbp));
+		prim::sort_pairs(s, L.tmp, S.rkeys.as<unsigned long long>(), S.skeys.as<unsigned long long>(), S.ridx.as<unsigned>(), S.sidx.as<unsigned>(), nv, 0, std::min(64u, 2 * rbp));
 		k_lks_masks<<<nblocks(nv, 256), 256, 0, s>>>(S.skeys.as<unsigned long long>(), S.sidx.as<unsigned>(), (unsigned)nv, c->d_ch.as<uint8_t>(), c->d_sepidx.as<unsigned>(), c->nchr,
 		                                            (unsigned)E, (unsigned)n, k, S.f1.as<unsigned>(), S.f0.as<unsigned>());
-		lk_inclusive_scan(c, S.f0.as<unsigned>(), S.s0.as<unsigned>(), nv);
+		prim::inclusive_scan(s, L.tmp, S.f0.as<unsigned>(), S.s0.as<unsigned>(), nv, rocprim::plus<unsigned>());
 		HIP_TRY(hipMemcpyAsync(&ngroups, S.s0.as<unsigned>() + (nv - 1), 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		L.gkeys.ensure((size_t)ngroups * 4 + 16); L.gmask.ensure((size_t)ngroups * 4 + 16); L.gcount.ensure(16);
 		L.gbif.ensure((size_t)ngroups * 4 + 16); L.gid.ensure((size_t)ngroups * 4 + 16);
 		{
-			size_t tmp = 0;
-			HIP_TRY(rocprim::reduce_by_key(nullptr, tmp, S.s0.as<unsigned>(), S.f1.as<unsigned>(), nv, L.gkeys.as<unsigned>(), L.gmask.as<unsigned>(),
-			                               L.gcount.as<unsigned>(), BitOr(), rocprim::equal_to<unsigned>(), s));
-			L.tmp.ensure(tmp);
-			HIP_TRY(rocprim::reduce_by_key(L.tmp.p, tmp, S.s0.as<unsigned>(), S.f1.as<unsigned>(), nv, L.gkeys.as<unsigned>(), L.gmask.as<unsigned>(),
-			                               L.gcount.as<unsigned>(), BitOr(), rocprim::equal_to<unsigned>(), s));
+			prim::reduce_by_key(s, L.tmp, S.s0.as<unsigned>(), S.f1.as<unsigned>(), nv, L.gkeys.as<unsigned>(), L.gmask.as<unsigned>(),
+			                    L.gcount.as<unsigned>(), BitOr(), rocprim::equal_to<unsigned>());
 		}
 		k_lk_group_bif<<<nblocks(ngroups, 256), 256, 0, s>>>(L.gmask.as<unsigned>(), ngroups, L.gbif.as<unsigned>());
-		lk_exclusive_scan(c, L.gbif.as<unsigned>(), L.gid.as<unsigned>(), ngroups);
+		prim::exclusive_scan(s, L.tmp, L.gbif.as<unsigned>(), L.gid.as<unsigned>(), 0u, ngroups, rocprim::plus<unsigned>());
 		unsigned last_id = 0, last_bif = 0;
 		HIP_TRY(hipMemcpyAsync(&last_id, L.gid.as<unsigned>() + (ngroups - 1), 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipMemcpyAsync(&last_bif, L.gbif.as<unsigned>() + (ngroups - 1), 4, hipMemcpyDeviceToHost, s));
@@ -974,14 +909,4 @@ static void run_enumeration_longk_sharded(sbl_ctx *c, uint32_t k, size_t elem_ca
 	c->stats.exchange_ms = clk.ms;
 	if (trace) fprintf(stderr, "[sbl] long-k rank %u: %u rounds, %zu candidate windows sorted here, %u bifurcation groups here of %llu, %llu bytes sent in all\n", r, round, nv, nbif_local, nbif,
 	                   (unsigned long long)c->stats.exchange_bytes);
-}
-
-static void lk_shard_free(LongKShardHolder *h)
-{
-	if (!h) return;
-	LkShardScratch &S = h->s;
-	for (DevBuf *b : { &S.rk, &S.halo, &S.aflag, &S.act, &S.k0, &S.i0, &S.k1, &S.i1, &S.rkeys, &S.ridx, &S.skeys, &S.sidx, &S.f0, &S.f1, &S.s0, &S.s1, &S.ov, &S.oi1, &S.ov1, &S.bi, &S.bv,
-	                   &S.cnt, &S.bounds, &S.mcode, &S.mid, &S.gcode, &S.gid2 })
-		b->release();
-	delete h;
 }

@@ -26,9 +26,9 @@
 // Integer work only: no MFMA.
 #include <cstring>
 #include <algorithm>
-#include <rocprim/rocprim.hpp>
 
 #include "sbl_ctx.h"
+#include "sbl_prim.h"
 #include "sbl_comm.h"
 #include "kmer_bucket_kernels.h"
 #include <chrono>
@@ -657,17 +657,11 @@ static LongKFpScratch &fp_of(sbl_ctx *c)
 }
 void sbl_longk_fp_free(sbl_ctx *c)
 {
-	if (!c->lkfp) return;
-	LongKFpScratch &L = c->lkfp->s;
-	for (DevBuf *b : { &L.tiles, &L.PT, &L.ST, &L.pwrun, &L.pwT, &L.ctot, &L.cP, &L.cS, &L.key1, &L.rec, &L.skey1, &L.srec, &L.rkey, &L.rval, &L.gpairs, &L.gel, &L.gid, &L.tmp, &L.boff, &L.ctr, &L.pairs, &L.members, &L.ref, &L.payload, &L.rank,
-	                   &L.keys, &L.skeys, &L.idx, &L.sidx, &L.head, &L.gstart, &L.pairids })
-		b->release();
 	delete c->lkfp;
 	c->lkfp = nullptr;
 }
 
 static Fp fp_pow(Fp b, unsigned long long e) { Fp r{1, 1}; while (e) { if (e & 1) r = fp_mul(r, b); b = fp_mul(b, b); e >>= 1; } return r; }
-static unsigned fp_bits(unsigned long long v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; return b; }
 struct MaxU32 { __host__ __device__ unsigned operator()(unsigned a, unsigned b) const { return a > b ? a : b; } };
 
 // returns false when the verification found two different k-mers under one fingerprint (the caller then runs the exact rank doubling)
@@ -781,10 +775,7 @@ bool sbl_run_enumeration_longk_fp(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 	size_t nown = nmine;
 	auto partition = [&](u64 *kin, u64 *kout, u64 *vin, u64 *vout, size_t m) {
 		if (!m) return;
-		size_t tmp = 0;
-		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, m, 0, bits, s));
-		L.tmp.ensure(tmp);
-		HIP_TRY(rocprim::radix_sort_pairs(L.tmp.p, tmp, kin, kout, vin, vout, m, 0, bits, s));
+		prim::sort_pairs(s, L.tmp, kin, kout, vin, vout, m, 0, bits);
 	};
 	for (int attempt = 0;; attempt++) {
 		SBL_CHECK(attempt < 8, SBL_ERR_INTERNAL, "k-mer bucket classification did not converge");
@@ -893,19 +884,20 @@ bool sbl_run_enumeration_longk_fp(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 		HIP_TRY(hipMemcpyAsync(&nkeys, d_nkeys, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipMemsetAsync(L.rank.p, 0, cap * 4, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		const unsigned rbits = fp_bits(nkeys ? nkeys - 1 : 0), csym = std::min(27u, (64u - rbits) / 2u);
+		const unsigned rbits = prim::bits_of(nkeys ? nkeys - 1 : 0), csym = std::min(27u, (64u - rbits) / 2u);
 		const bool small = nkeys <= FP_RANK_SMALL && getenv("SBL_FP_RANK_ROUNDS") == nullptr;      // (SBL_FP_RANK_ROUNDS=1: test switch, the refinement rounds for every size)
 		if (small) k_fp_rank_small<<<nkeys, 64, 0, s>>>(c->d_pk.as<u64>(), L.ref.as<u64>(), nkeys, k, L.rank.as<unsigned>());
-		size_t tsort = 0, tscan = 0;
-		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tsort, L.keys.as<u64>(), L.skeys.as<u64>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), nkeys, 0, 64, s));
-		HIP_TRY(rocprim::inclusive_scan(nullptr, tscan, L.head.as<unsigned>(), L.gstart.as<unsigned>(), nkeys, MaxU32(), s));
-		L.tmp.ensure(std::max(tsort, tscan));
+		// ONE buffer for the sort and the scan of the rounds, grown before either is launched: below, no ensure() frees it under a kernel in flight
+		const unsigned sortbits = std::min(64u, rbits + 2 * csym);
+		const size_t tsort = std::max(prim::sort_pairs_bytes(s, L.keys.as<u64>(), L.skeys.as<u64>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), nkeys, 0, 64),
+		                              prim::sort_pairs_bytes(s, L.keys.as<u64>(), L.skeys.as<u64>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), nkeys, 0, sortbits));
+		L.tmp.ensure(std::max(tsort, prim::inclusive_scan_bytes(s, L.head.as<unsigned>(), L.gstart.as<unsigned>(), nkeys, MaxU32())));
 		for (unsigned off = 0; off < k && !small; off += csym) {
 			HIP_TRY(hipMemsetAsync(d_nheads, 0, 4, s));
 			k_fp_rank_keys<<<nblocks(nkeys, 256), 256, 0, s>>>(c->d_pk.as<u64>(), L.ref.as<u64>(), L.rank.as<unsigned>(), nkeys, k, off, csym, L.keys.as<u64>(), L.idx.as<unsigned>());
-			HIP_TRY(rocprim::radix_sort_pairs(L.tmp.p, tsort, L.keys.as<u64>(), L.skeys.as<u64>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), nkeys, 0, std::min(64u, rbits + 2 * csym), s));
+			prim::sort_pairs(s, L.tmp, L.keys.as<u64>(), L.skeys.as<u64>(), L.idx.as<unsigned>(), L.sidx.as<unsigned>(), nkeys, 0, sortbits);
 			k_fp_rank_heads<<<nblocks(nkeys, 256), 256, 0, s>>>(L.skeys.as<u64>(), nkeys, L.head.as<unsigned>(), d_nheads);
-			HIP_TRY(rocprim::inclusive_scan(L.tmp.p, tscan, L.head.as<unsigned>(), L.gstart.as<unsigned>(), nkeys, MaxU32(), s));
+			prim::inclusive_scan(s, L.tmp, L.head.as<unsigned>(), L.gstart.as<unsigned>(), nkeys, MaxU32());
 			k_fp_rank_apply<<<nblocks(nkeys, 256), 256, 0, s>>>(L.sidx.as<unsigned>(), L.gstart.as<unsigned>(), nkeys, L.rank.as<unsigned>());
 			unsigned heads = 0;
 			HIP_TRY(hipMemcpyAsync(&heads, d_nheads, 4, hipMemcpyDeviceToHost, s));
@@ -943,10 +935,7 @@ bool sbl_run_enumeration_longk_fp(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 			if (!nmem) continue;
 			L.keys.ensure((size_t)nmem * 4 + 16); L.skeys.ensure((size_t)nmem * 4 + 16);
 			k_fp_mark_pairs<<<nblocks(nmem, 256), 256, 0, s>>>(L.members.as<u64>(), nmem, k, myids, (unsigned)st, L.keys.as<unsigned>(), L.skeys.as<unsigned>());
-			size_t tmp = 0;
-			HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, L.keys.as<unsigned>(), c->d_melem[st].as<unsigned>(), L.skeys.as<unsigned>(), c->d_mid[st].as<unsigned>(), nmem, 0, 32, s));
-			L.tmp.ensure(tmp);
-			HIP_TRY(rocprim::radix_sort_pairs(L.tmp.p, tmp, L.keys.as<unsigned>(), c->d_melem[st].as<unsigned>(), L.skeys.as<unsigned>(), c->d_mid[st].as<unsigned>(), nmem, 0, 32, s));
+			prim::sort_pairs(s, L.tmp, L.keys.as<unsigned>(), c->d_melem[st].as<unsigned>(), L.skeys.as<unsigned>(), c->d_mid[st].as<unsigned>(), nmem, 0, 32);
 		}
 		c->marks_compact_ready = true;
 	}

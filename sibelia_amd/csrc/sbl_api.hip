@@ -4,9 +4,8 @@
 // sort runs in a HIP kernel on the context's device.  There is no host compute path.
 #include <cstring>
 #include <algorithm>
-#include <rocprim/rocprim.hpp>
-
 #include "sbl_ctx.h"
+#include "sbl_prim.h"
 #include "sbl_comm.h"
 #include "kmer_kernels.h"
 #include "kmer_bucket_kernels.h"
@@ -182,30 +181,6 @@ void sbl_pack(sbl_ctx *c)
 	HIP_TRY(hipGetLastError());
 }
 
-static void device_sort_pairs(sbl_ctx *c, unsigned long long *kin, unsigned long long *kout, unsigned *vin, unsigned *vout, size_t n, unsigned bits)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-	c->d_sorttmp.ensure(tmp);
-	HIP_TRY(rocprim::radix_sort_pairs(c->d_sorttmp.p, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-}
-static void device_exclusive_scan(sbl_ctx *c, unsigned *in, unsigned *out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-	c->d_scantmp.ensure(tmp);
-	HIP_TRY(rocprim::exclusive_scan(c->d_scantmp.p, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-}
-
-static void device_sort_records(sbl_ctx *c, unsigned long long *kin, unsigned long long *kout, unsigned long long *vin, unsigned long long *vout,
-                                size_t n, unsigned begin_bit, unsigned end_bit)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, begin_bit, end_bit, c->stream));
-	c->d_sorttmp.ensure(tmp);
-	HIP_TRY(rocprim::radix_sort_pairs(c->d_sorttmp.p, tmp, kin, kout, vin, vout, n, begin_bit, end_bit, c->stream));
-}
-
 // E1 (+ the dense form of E2): pack -> k-mer records -> radix partition by hash prefix -> per-bucket LDS tables (classify)
 // -> rank of the bifurcation codes -> marks of the member positions (kmer_bucket_kernels.h).
 // elem_capacity >= nelem is the allocated length of the mark arrays (simplification appends elements).
@@ -272,7 +247,7 @@ void sbl_run_enumeration(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 				bits = std::min(bits + 2, 28u);                  // grid = 2^bits workgroups, offsets (2^bits + 1) x 4 B: bounded
 				k_kmer_records<<<grid, KM_THREADS, 0, s>>>(c->d_pk.as<unsigned long long>(), c->d_sp.as<unsigned>(), nwords, E, k, (size_t)0, ntiles, k0, v0);
 			}
-			device_sort_records(c, k0, k1, v0, v1, n, 0, bits);
+			prim::sort_pairs(s, c->d_sorttmp, k0, k1, v0, v1, n, 0, bits);
 			c->d_boff.ensure((((size_t)1 << bits) + 1) * 4 + 64);
 			k_bucket_bounds<<<nblocks(((size_t)1 << bits) + 1, 256), 256, 0, s>>>(k1, n, bits, c->d_boff.as<unsigned>());
 		}
@@ -297,8 +272,8 @@ void sbl_run_enumeration(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 	c->d_skeys.ensure((size_t)nkeys * 8 + 16); c->d_spayload.ensure((size_t)nkeys * 4 + 16);
 	c->d_pairids.ensure((size_t)npairs * 8 + 16);
 	if (nkeys) {
-		device_sort_pairs(c, c->d_keys.as<unsigned long long>(), c->d_skeys.as<unsigned long long>(),
-		                  c->d_payload.as<unsigned>(), c->d_spayload.as<unsigned>(), nkeys, 2 * k);
+		prim::sort_pairs(s, c->d_sorttmp, c->d_keys.as<unsigned long long>(), c->d_skeys.as<unsigned long long>(),
+		                 c->d_payload.as<unsigned>(), c->d_spayload.as<unsigned>(), nkeys, 0, 2 * k);
 		k_scatter_ids<<<nblocks(nkeys, 256), 256, 0, s>>>(c->d_skeys.as<unsigned long long>(), c->d_spayload.as<unsigned>(), nkeys, k,
 		                                                 c->d_pairids.as<unsigned>());
 	}
@@ -337,7 +312,7 @@ void sbl_compact_marks(sbl_ctx *c, int strand)
 	c->d_chunkcnt.ensure((size_t)(nchunks + 1) * 4); c->d_chunkoff.ensure((size_t)(nchunks + 1) * 4);
 	HIP_TRY(hipMemsetAsync(c->d_chunkcnt.p, 0, (size_t)(nchunks + 1) * 4, s));
 	k_count_marks<<<nchunks, 256, 0, s>>>(c->d_bif[strand].as<unsigned>(), E, c->d_chunkcnt.as<unsigned>());
-	device_exclusive_scan(c, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), nchunks + 1);
+	prim::exclusive_scan(s, c->d_scantmp, c->d_chunkcnt.as<unsigned>(), c->d_chunkoff.as<unsigned>(), 0u, nchunks + 1, rocprim::plus<unsigned>());
 	unsigned total = 0;
 	HIP_TRY(hipMemcpyAsync(&total, c->d_chunkoff.as<unsigned>() + nchunks, 4, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
@@ -362,8 +337,8 @@ extern "C" sbl_status sbl_create(sbl_ctx **out, int device)
 	sbl_ctx *c = new (std::nothrow) sbl_ctx();
 	if (!c) return SBL_ERR_OOM;
 	c->device = device;
-	if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return SBL_ERR_HIP; }
-	for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) { delete c; return SBL_ERR_HIP; }
+	if (hipStreamCreate(&c->stream) != hipSuccess) { sbl_destroy(c); return SBL_ERR_HIP; }
+	for (auto &e : c->ev) if (hipEventCreate(&e) != hipSuccess) { sbl_destroy(c); return SBL_ERR_HIP; }
 	*out = c;
 	return SBL_OK;
 }
@@ -379,14 +354,13 @@ extern "C" void sbl_destroy(sbl_ctx *c)
 	sbl_comm_release(c);
 	sbl_longk_free(c);
 	sbl_longk_fp_free(c);
-	DevBuf *bufs[] = { &c->d_send, &c->d_recv, &c->d_otable, &c->d_oused, &c->d_allkeys, &c->d_allkeys2, &c->d_gelem[0], &c->d_gelem[1], &c->d_gid[0], &c->d_gid[1], &c->d_stage, &c->d_ch, &c->d_op, &c->d_sepidx, &c->d_amb_elem, &c->d_amb_char, &c->d_pk, &c->d_sp, &c->d_counters,
-	                   &c->d_keys, &c->d_payload, &c->d_skeys, &c->d_spayload, &c->d_pairids, &c->d_sorttmp, &c->d_bif[0], &c->d_bif[1],
-	                   &c->d_chunkcnt, &c->d_chunkoff, &c->d_scantmp, &c->d_save_ch, &c->d_save_op, &c->d_melem[0], &c->d_melem[1], &c->d_mid[0], &c->d_mid[1], &c->d_inst, &c->d_edges, &c->d_valid, &c->d_rec_keys[0], &c->d_rec_keys[1], &c->d_rec_vals[0], &c->d_rec_vals[1], &c->d_boff, &c->d_fa_text, &c->d_fa_lines, &c->d_fa_recs, &c->d_orig_ch,
-	                   &c->d_bs_desc, &c->d_bs_off, &c->d_bs_hdr, &c->d_bs_text };
-	for (DevBuf *b : bufs) b->release();
-	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
+	// the members free themselves with the context; its stream and events go after the buffers that may still be in use on them
+	hipStream_t stream = c->stream;
+	hipEvent_t ev[8];
+	std::copy(c->ev, c->ev + 8, ev);
 	delete c;
+	for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+	if (stream) (void)hipStreamDestroy(stream);
 }
 
 extern "C" sbl_status sbl_load(sbl_ctx *c, uint32_t nchr, const uint8_t *const *seq, const uint64_t *len)
@@ -579,28 +553,22 @@ extern "C" sbl_status sbl_serialize_graph(sbl_ctx *c, uint32_t k, const char **t
 		c->graph_text = head;
 		if (nlines) {
 			SBL_CHECK(nlines < 0xFFFFFFF0ull, SBL_ERR_TOO_LARGE, "too many lines");
-			DevBuf d_off, d_len, d_toff, d_text;                         // freed below (a debugging dump: no workspace kept)
-			try {
-				d_off.ensure((size_t)(c->nchr + 1) * 8); d_len.ensure((size_t)(nlines + 1) * 4); d_toff.ensure((size_t)(nlines + 1) * 8);
-				HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), (size_t)(c->nchr + 1) * 8, hipMemcpyHostToDevice, s));
-				HIP_TRY(hipMemsetAsync(d_len.p, 0, (size_t)(nlines + 1) * 4, s));
-				k_graph_line_len<<<nblocks(nlines, 256), 256, 0, s>>>(d_off.as<unsigned long long>(), c->nchr, k, nlines, d_len.as<unsigned>());
-				size_t tmp = 0;
-				HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, d_len.as<unsigned>(), d_toff.as<unsigned long long>(), 0ull, (size_t)nlines + 1, rocprim::plus<unsigned long long>(), s));
-				c->d_scantmp.ensure(tmp);
-				HIP_TRY(rocprim::exclusive_scan(c->d_scantmp.p, tmp, d_len.as<unsigned>(), d_toff.as<unsigned long long>(), 0ull, (size_t)nlines + 1, rocprim::plus<unsigned long long>(), s));
-				unsigned long long total = 0;
-				HIP_TRY(hipMemcpyAsync(&total, d_toff.as<unsigned long long>() + nlines, 8, hipMemcpyDeviceToHost, s));
-				HIP_TRY(hipStreamSynchronize(s));
-				d_text.ensure(total + 16);
-				k_graph_lines<<<nblocks(nlines, 256), 256, 0, s>>>(c->d_ch.as<uint8_t>(), c->d_sepidx.as<unsigned>(), d_off.as<unsigned long long>(), c->nchr, k, nlines,
-				                                                  d_toff.as<unsigned long long>(), d_text.as<char>());
-				HIP_TRY(hipGetLastError());
-				c->graph_text.resize(head.size() + total);
-				HIP_TRY(hipMemcpyAsync(&c->graph_text[head.size()], d_text.p, total, hipMemcpyDeviceToHost, s));
-				HIP_TRY(hipStreamSynchronize(s));
-			} catch (...) { d_off.release(); d_len.release(); d_toff.release(); d_text.release(); throw; }
-			d_off.release(); d_len.release(); d_toff.release(); d_text.release();
+			DevBuf d_off, d_len, d_toff, d_text;                         // freed on the way out (a debugging dump: no workspace kept)
+			d_off.ensure((size_t)(c->nchr + 1) * 8); d_len.ensure((size_t)(nlines + 1) * 4); d_toff.ensure((size_t)(nlines + 1) * 8);
+			HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), (size_t)(c->nchr + 1) * 8, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemsetAsync(d_len.p, 0, (size_t)(nlines + 1) * 4, s));
+			k_graph_line_len<<<nblocks(nlines, 256), 256, 0, s>>>(d_off.as<unsigned long long>(), c->nchr, k, nlines, d_len.as<unsigned>());
+			prim::exclusive_scan(s, c->d_scantmp, d_len.as<unsigned>(), d_toff.as<unsigned long long>(), 0ull, (size_t)nlines + 1, rocprim::plus<unsigned long long>());
+			unsigned long long total = 0;
+			HIP_TRY(hipMemcpyAsync(&total, d_toff.as<unsigned long long>() + nlines, 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			d_text.ensure(total + 16);
+			k_graph_lines<<<nblocks(nlines, 256), 256, 0, s>>>(c->d_ch.as<uint8_t>(), c->d_sepidx.as<unsigned>(), d_off.as<unsigned long long>(), c->nchr, k, nlines,
+			                                                  d_toff.as<unsigned long long>(), d_text.as<char>());
+			HIP_TRY(hipGetLastError());
+			c->graph_text.resize(head.size() + total);
+			HIP_TRY(hipMemcpyAsync(&c->graph_text[head.size()], d_text.p, total, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
 		}
 		c->graph_text += tail;
 		if (text) *text = c->graph_text.data();

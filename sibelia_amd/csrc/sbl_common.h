@@ -37,10 +37,21 @@ inline void sbl_devbuf_cap_check(size_t old_cap, size_t want)
 	}
 }
 
-// Grow-only device buffer.
+// Grow-only device buffer that owns its memory: freed with the object that holds it.  Move-only (std::swap works; sbl_devbuf_total()
+// counts every allocation exactly once).  Never give one static storage duration: it must not outlive the HIP runtime.
 struct DevBuf {
 	void *p = nullptr;
 	size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept
+	{
+		if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+		return *this;
+	}
+	~DevBuf() { release(); }
 	void ensure(size_t bytes)
 	{
 		if (bytes <= cap) return;

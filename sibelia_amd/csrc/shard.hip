@@ -30,10 +30,10 @@
 #include <link.h>
 #include <pthread.h>
 #include <time.h>
-#include <rocprim/rocprim.hpp>
 #include <rccl/rccl.h>
 
 #include "sbl_ctx.h"
+#include "sbl_prim.h"
 #include "sbl_comm.h"
 #include "kmer_kernels.h"
 #include "kmer_bucket_kernels.h"
@@ -387,12 +387,8 @@ static void run_enumeration_sharded(sbl_ctx *c, uint32_t k, size_t elem_capacity
 		if (nmine) {
 			k_kmer_records<<<(unsigned)std::min<size_t>(t1 - t0, 256 * 16), KM_THREADS, 0, s>>>(c->d_pk.as<unsigned long long>(), c->d_sp.as<unsigned>(), nwords, E, k, t0, t1,
 			                                                                                  c->d_rec_keys[0].as<unsigned long long>(), c->d_rec_vals[0].as<unsigned long long>());
-			size_t tmp = 0;
-			HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, c->d_rec_keys[0].as<unsigned long long>(), c->d_rec_keys[1].as<unsigned long long>(),
-			                                  c->d_rec_vals[0].as<unsigned long long>(), c->d_rec_vals[1].as<unsigned long long>(), nmine, 0, bits, s));
-			c->d_sorttmp.ensure(tmp);
-			HIP_TRY(rocprim::radix_sort_pairs(c->d_sorttmp.p, tmp, c->d_rec_keys[0].as<unsigned long long>(), c->d_rec_keys[1].as<unsigned long long>(),
-			                                  c->d_rec_vals[0].as<unsigned long long>(), c->d_rec_vals[1].as<unsigned long long>(), nmine, 0, bits, s));
+			prim::sort_pairs(s, c->d_sorttmp, c->d_rec_keys[0].as<unsigned long long>(), c->d_rec_keys[1].as<unsigned long long>(),
+			                 c->d_rec_vals[0].as<unsigned long long>(), c->d_rec_vals[1].as<unsigned long long>(), nmine, 0, bits);
 			k_bucket_bounds<<<nblocks(nb + 1, 256), 256, 0, s>>>(c->d_rec_keys[1].as<unsigned long long>(), nmine, bits, c->d_boff.as<unsigned>());
 			HIP_TRY(hipGetLastError());
 			for (uint32_t p = 0; p <= R; p++) HIP_TRY(hipMemcpyAsync(&send_at[p], c->d_boff.as<unsigned>() + fb[p], 4, hipMemcpyDeviceToHost, s));
@@ -420,10 +416,7 @@ static void run_enumeration_sharded(sbl_ctx *c, uint32_t k, size_t elem_capacity
 		for (int i = 0; i < 2; i++) { c->d_otable.ensure(nrecv * 8 + 16); c->d_oused.ensure(nrecv * 8 + 16); }
 		unsigned long long *ok = c->d_otable.as<unsigned long long>(), *ov = c->d_oused.as<unsigned long long>();
 		if (nrecv) {
-			size_t tmp = 0;
-			HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, c->d_recv.as<unsigned long long>(), ok, c->d_send.as<unsigned long long>(), ov, nrecv, 0, bits, s));
-			c->d_sorttmp.ensure(tmp);
-			HIP_TRY(rocprim::radix_sort_pairs(c->d_sorttmp.p, tmp, c->d_recv.as<unsigned long long>(), ok, c->d_send.as<unsigned long long>(), ov, nrecv, 0, bits, s));
+			prim::sort_pairs(s, c->d_sorttmp, c->d_recv.as<unsigned long long>(), ok, c->d_send.as<unsigned long long>(), ov, nrecv, 0, bits);
 		}
 		k_bucket_bounds<<<nblocks(nb + 1, 256), 256, 0, s>>>(ok, nrecv, bits, c->d_boff.as<unsigned>());
 		unsigned long long *members = c->d_recv.as<unsigned long long>();          // the unsorted received keys are dead: their space holds the member list
@@ -461,10 +454,7 @@ static void run_enumeration_sharded(sbl_ctx *c, uint32_t k, size_t elem_capacity
 	c->d_allkeys2.ensure(nkeys * 8 + 16);
 	c->d_pairids.ensure((size_t)npairs * 8 + 16);
 	if (nkeys) {
-		size_t tmp = 0;
-		HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp, c->d_allkeys.as<unsigned long long>(), c->d_allkeys2.as<unsigned long long>(), nkeys, 0, 2 * k, s));
-		c->d_sorttmp.ensure(tmp);
-		HIP_TRY(rocprim::radix_sort_keys(c->d_sorttmp.p, tmp, c->d_allkeys.as<unsigned long long>(), c->d_allkeys2.as<unsigned long long>(), nkeys, 0, 2 * k, s));
+		prim::sort_keys(s, c->d_sorttmp, c->d_allkeys.as<unsigned long long>(), c->d_allkeys2.as<unsigned long long>(), nkeys, 0, 2 * k);
 		if (mykeys)
 			k_rank_own_keys<<<nblocks(mykeys, 256), 256, 0, s>>>(c->d_keys.as<unsigned long long>(), c->d_payload.as<unsigned>(), mykeys,
 			                                                    c->d_allkeys2.as<unsigned long long>(), (unsigned)nkeys, k, c->d_pairids.as<unsigned>());

@@ -4,11 +4,11 @@
 // simplify_kernels.h); the host only sequences launches (simplify_driver.h) and reads a counter block back per round.
 #include <cstring>
 #include <algorithm>
-#include <rocprim/rocprim.hpp>
-
+#include <array>
 #include <chrono>
 
 #include "sbl_ctx.h"
+#include "sbl_prim.h"
 #include "sbl_comm.h"
 #include "kmer_kernels.h"
 #include "simplify_driver.h"
@@ -18,7 +18,27 @@
 static inline unsigned nblocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // ------------------------------------------------------------------------------------------- device backend
-struct SimplifyState {
+// What a SimplifyState holds besides device buffers.  A base class, so that it is destroyed AFTER the buffers: the park stream and the
+// events go after the memory that may still be in use on them.
+struct SimplifyHandles {
+	hipStream_t park_stream = nullptr; hipEvent_t park_ev[2] = {nullptr, nullptr};      // k_resume beside k_commit (GraphView::park_of)
+	unsigned *h_ctr = nullptr;            // pinned, mapped: CTR_COUNT counters + the sequence number of the last post (k_select_write)
+	unsigned *d_hctr = nullptr;           // its device address
+	unsigned post_seq = 0;
+	hipEvent_t ev[8] = {};                // created once per context (DeviceBackend borrows them): commit sampling pair [2, 3]
+	std::vector<hipEvent_t> snap_ev;      // start / stop pairs around the snapshots of a stage, read at its end (no host synchronisation per snapshot)
+	unsigned char *h_init = nullptr;      // pinned staging for the small host-to-device initialisations of a stage (no synchronisation needed before the host moves on)
+	~SimplifyHandles()
+	{
+		if (park_stream) (void)hipStreamDestroy(park_stream);
+		for (auto &e : park_ev) if (e) (void)hipEventDestroy(e);
+		if (h_ctr) (void)hipHostFree(h_ctr);
+		if (h_init) (void)hipHostFree(h_init);
+		for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+		for (auto &e : snap_ev) (void)hipEventDestroy(e);
+	}
+};
+struct SimplifyState : SimplifyHandles {
 	DevBuf ch, op, nx, pv, nodeof[2];
 	DevBuf nslot, nnext, nidst, nclr, ndead, head[2], lsize[2];
 	DevBuf ctr, need, big, touch, ck_touch, own, lock, rmax, wmax, win;
@@ -28,14 +48,53 @@ struct SimplifyState {
 	DevBuf nmark, maux[2], iota, sel, tstamp;
 	DevBuf lin, elin, lmpos[2], lmid[2], cnt1k, off1k;      // linearised marks of the later snapshots
 	DevBuf flag, segidx, seg_head, seg_len, seg_succ_elem, succ[2], dist[2], newidx, ch_out, op_out;
-	hipStream_t park_stream = nullptr; hipEvent_t park_ev[2] = {nullptr, nullptr};      // k_resume beside k_commit (GraphView::park_of)
-	unsigned *h_ctr = nullptr;            // pinned, mapped: CTR_COUNT counters + the sequence number of the last post (k_select_write)
-	unsigned *d_hctr = nullptr;           // its device address
-	unsigned post_seq = 0;
-	hipEvent_t ev[8] = {};                // created once per context (DeviceBackend borrows them): commit sampling pair [2, 3]
-	std::vector<hipEvent_t> snap_ev;      // start / stop pairs around the snapshots of a stage, read at its end (no host synchronisation per snapshot)
-	unsigned char *h_init = nullptr;      // pinned staging for the small host-to-device initialisations of a stage (no synchronisation needed before the host moves on)
 };
+void sbl_simplify_free(sbl_ctx *c)
+{
+	delete c->simp;
+	c->simp = nullptr;
+}
+
+// The environment switches of the stage, read once per sbl_simplify_run (tests set and clear them between calls on one context).
+// Nothing below read_switches() calls getenv.
+struct StageSwitches {
+	struct Value { bool set = false; long long v = 0; };      // a switch that carries a number
+	bool checkpoints;            // SBL_CHECKPOINTS: measurement / test switch, iteration checkpoints from the first attempt on
+	bool trace;                  // SBL_TRACE: the stage narrates its decisions on stderr
+	bool no_block_index;         // SBL_NO_BLOCK_INDEX: measurement / test switch, no block index -- every window is walked
+	bool no_idx_probe;           // SBL_NO_IDX_PROBE: measurement switch, the walking probe for every entry
+	bool no_idx_reserve;         // SBL_NO_IDX_RESERVE: measurement switch, the walking reservation for every entry
+	bool replicated_phases;      // SBL_REPLICATED_PHASES: measurement / test switch, every GPU of a job computes every verdict
+	bool no_dense_path;          // SBL_NO_DENSE_PATH: test switch, small inputs take the ordered rounds too
+	bool no_dense_switch;        // SBL_NO_DENSE_SWITCH: the rounds never give up for the one-launch path (TryDense)
+	bool check_index;            // SBL_CHECK_INDEX: test switch, the maintained block index against a rebuild at the end of the stage
+	bool check_dictionary;       // SBL_CHECK_DICTIONARY: the reference's dictionary invariant on the stage's final graph
+	Value park;                  // SBL_PARK=n: collapses per launch and parked transaction (0: parking off)
+	int phases;                  // SBL_PHASES=n: cycle counters of the decision loops, level n (0: off)
+	unsigned test_flags;         // SBL_TEST_FLAGS: GraphView::test_flags (BT_TF_*)
+	Value test_elem_slack;       // SBL_TEST_ELEM_SLACK: test hook, the element slack -- provokes the grow / restart paths
+	Value test_dense_node_slack; // SBL_TEST_DENSE_NODE_SLACK: test hook, the node slack of the one-launch path -- provokes its fall-back
+	Value test_fail_rank;        // SBL_TEST_FAIL_SIMPLIFY_RANK: test hook, this rank leaves the stage between two collectives
+	Value test_corrupt_mark;     // SBL_TEST_CORRUPT_MARK: test hook, one wrong mark for the dictionary check to find
+};
+static StageSwitches read_switches()
+{
+	auto flag = [](const char *name) { return getenv(name) != nullptr; };
+	auto value = [](const char *name) { StageSwitches::Value r; if (const char *e = getenv(name)) { r.set = true; r.v = atoll(e); } return r; };
+	StageSwitches w;
+	w.checkpoints = flag("SBL_CHECKPOINTS"); w.trace = flag("SBL_TRACE");
+	w.no_block_index = flag("SBL_NO_BLOCK_INDEX"); w.no_idx_probe = flag("SBL_NO_IDX_PROBE"); w.no_idx_reserve = flag("SBL_NO_IDX_RESERVE");
+	w.replicated_phases = flag("SBL_REPLICATED_PHASES");
+	w.no_dense_path = flag("SBL_NO_DENSE_PATH"); w.no_dense_switch = flag("SBL_NO_DENSE_SWITCH");
+	w.check_index = flag("SBL_CHECK_INDEX"); w.check_dictionary = flag("SBL_CHECK_DICTIONARY");
+	w.park = value("SBL_PARK");
+	const StageSwitches::Value ph = value("SBL_PHASES");
+	w.phases = ph.set ? ((int)ph.v > 0 ? (int)ph.v : 1) : 0;
+	w.test_flags = (unsigned)(int)value("SBL_TEST_FLAGS").v;
+	w.test_elem_slack = value("SBL_TEST_ELEM_SLACK"); w.test_dense_node_slack = value("SBL_TEST_DENSE_NODE_SLACK");
+	w.test_fail_rank = value("SBL_TEST_FAIL_SIMPLIFY_RANK"); w.test_corrupt_mark = value("SBL_TEST_CORRUPT_MARK");
+	return w;
+}
 
 struct RestartStage {};      // thrown out of an optimistic attempt that would need a roll-back (DeviceBackend::restore)
 // thrown out of the ordered rounds when they have turned into a slow serial chain and the one-launch path is the better bet (round 6):
@@ -49,6 +108,7 @@ struct TryDense {};
 struct DeviceBackend {
 	sbl_ctx *c;
 	SimplifyState *st;
+	const StageSwitches &sw;
 	GraphView g{};
 	uint32_t cap_e = 0, cap_n = 0, nid_ = 0;
 	size_t ne0_ = 0;                                                  // elements of the stage's input (padded): cap_e - ne0_ is the insertion slack
@@ -66,7 +126,7 @@ struct DeviceBackend {
 	bool optimistic = false;
 	unsigned rsv_waves = 4;                                           // waves of a reservation workgroup (k_reserve)
 	// block index of the original slots (GraphView::bidx): read by the probe and the reservation, maintained by the transactions
-	bool use_index = getenv("SBL_NO_BLOCK_INDEX") == nullptr;        // measurement / test switch: every window is walked (round 4)
+	bool use_index;                                                   // off: every window is walked (StageSwitches::no_block_index; the one-launch path reads no index)
 	uint32_t idx_nblk = 0;
 	// k_probe_idx's LDS by the instances an id has (set with rsv_waves): a handful -- 256-slot verdict table, 64 instances, 64 walked marks = 3.1 KB;
 	// dozens (many strains) -- 1024 slots, 256 instances, 192 marks = 12 KB.  An entry that does not fit goes to the walking probe.
@@ -84,7 +144,7 @@ struct DeviceBackend {
 	double commit_event_ms = 0; uint64_t commit_event_launches = 0;      // the event pairs around every 4th launch of the commit kernel
 	unsigned ev_phase = 0;
 
-	DeviceBackend() = default;
+	DeviceBackend(sbl_ctx *c_, SimplifyState *st_, const StageSwitches &sw_) : c(c_), st(st_), sw(sw_), use_index(!sw_.no_block_index) {}
 	DeviceBackend(const DeviceBackend &) = delete;
 	uint32_t nid() { return nid_; }
 	void bind()
@@ -105,8 +165,8 @@ struct DeviceBackend {
 		st->rmax.ensure(nres * 4); st->wmax.ensure(nres * 4);
 		g.lock = nullptr; g.rmax = st->rmax.as<uint32_t>(); g.wmax = st->wmax.as<uint32_t>();
 		g.bidx = use_index && idx_nblk ? st->bidx.as<unsigned long long>() : nullptr;
-		g.idx_probe = g.bidx && getenv("SBL_NO_IDX_PROBE") == nullptr ? 1u : 0u;        // measurement switches: the walking probe / reservation for every entry
-		g.idx_reserve = g.bidx && getenv("SBL_NO_IDX_RESERVE") == nullptr ? 1u : 0u;
+		g.idx_probe = g.bidx && !sw.no_idx_probe ? 1u : 0u;
+		g.idx_reserve = g.bidx && !sw.no_idx_reserve ? 1u : 0u;
 	}
 	// ---- the switch to the one-launch path (TryDense): allowed for this attempt, chain-mode rounds so far, progress of the stage
 	bool may_try_dense = false;
@@ -131,6 +191,17 @@ struct DeviceBackend {
 		HIP_TRY(hipMemcpyAsync(st->h_ctr, st->ctr.p, CTR_COUNT * 4, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 	}
+	// every mutable array of the graph with its checkpoint copy and the bytes in use (as of the counters checkpoint() read)
+	struct CkEntry { DevBuf *live, *ck; size_t bytes; };
+	std::array<CkEntry, 16> ck_table()
+	{
+		const size_t ne4 = (size_t)ck_ne * 4, nn4 = (size_t)ck_nn * 4, id4 = ((size_t)nid_ + 1) * 4;
+		return {{ {&st->ch, &st->ck_ch, ck_ne}, {&st->op, &st->ck_op, ne4}, {&st->nx, &st->ck_nx, ne4}, {&st->pv, &st->ck_pv, ne4},
+		          {&c->d_bif[0], &st->ck_bif[0], ne4}, {&st->nodeof[0], &st->ck_nodeof[0], ne4}, {&st->head[0], &st->ck_head[0], id4}, {&st->lsize[0], &st->ck_lsize[0], id4},
+		          {&c->d_bif[1], &st->ck_bif[1], ne4}, {&st->nodeof[1], &st->ck_nodeof[1], ne4}, {&st->head[1], &st->ck_head[1], id4}, {&st->lsize[1], &st->ck_lsize[1], id4},
+		          {&st->touch, &st->ck_touch, (size_t)nid_ + 1},
+		          {&st->nslot, &st->ck_nslot, nn4}, {&st->nnext, &st->ck_nnext, nn4}, {&st->ndead, &st->ck_ndead, ck_nn} }};
+	}
 	void copy(DevBuf &dst, const DevBuf &src, size_t bytes)
 	{
 		dst.ensure(bytes);
@@ -142,25 +213,12 @@ struct DeviceBackend {
 		read_ctr();
 		ck_ne = st->h_ctr[CTR_NE]; ck_nn = st->h_ctr[CTR_NN];
 		if (optimistic) return;
-		copy(st->ck_ch, st->ch, ck_ne); copy(st->ck_op, st->op, (size_t)ck_ne * 4); copy(st->ck_nx, st->nx, (size_t)ck_ne * 4); copy(st->ck_pv, st->pv, (size_t)ck_ne * 4);
-		for (int s = 0; s < 2; s++) {
-			copy(st->ck_bif[s], c->d_bif[s], (size_t)ck_ne * 4); copy(st->ck_nodeof[s], st->nodeof[s], (size_t)ck_ne * 4);
-			copy(st->ck_head[s], st->head[s], ((size_t)nid_ + 1) * 4); copy(st->ck_lsize[s], st->lsize[s], ((size_t)nid_ + 1) * 4);
-		}
-		copy(st->ck_touch, st->touch, (size_t)nid_ + 1);
-		copy(st->ck_nslot, st->nslot, (size_t)ck_nn * 4); copy(st->ck_nnext, st->nnext, (size_t)ck_nn * 4); copy(st->ck_ndead, st->ndead, ck_nn);
+		for (const CkEntry &e : ck_table()) copy(*e.ck, *e.live, e.bytes);
 	}
 	void restore()
 	{
 		if (optimistic) throw RestartStage{};
-		auto back = [&](DevBuf &dst, const DevBuf &src, size_t bytes) { if (bytes) HIP_TRY(hipMemcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToDevice, c->stream)); };
-		back(st->ch, st->ck_ch, ck_ne); back(st->op, st->ck_op, (size_t)ck_ne * 4); back(st->nx, st->ck_nx, (size_t)ck_ne * 4); back(st->pv, st->ck_pv, (size_t)ck_ne * 4);
-		for (int s = 0; s < 2; s++) {
-			back(c->d_bif[s], st->ck_bif[s], (size_t)ck_ne * 4); back(st->nodeof[s], st->ck_nodeof[s], (size_t)ck_ne * 4);
-			back(st->head[s], st->ck_head[s], ((size_t)nid_ + 1) * 4); back(st->lsize[s], st->ck_lsize[s], ((size_t)nid_ + 1) * 4);
-		}
-		back(st->touch, st->ck_touch, (size_t)nid_ + 1);
-		back(st->nslot, st->ck_nslot, (size_t)ck_nn * 4); back(st->nnext, st->ck_nnext, (size_t)ck_nn * 4); back(st->ndead, st->ck_ndead, ck_nn);
+		for (const CkEntry &e : ck_table()) copy(*e.live, *e.ck, e.bytes);      // (the live arrays are at least as large: nothing grows)
 		unsigned v[2] = { ck_ne, ck_nn };
 		HIP_TRY(hipMemcpyAsync(st->ctr.as<unsigned>() + CTR_NE, &v[0], 4, hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(hipMemcpyAsync(st->ctr.as<unsigned>() + CTR_NN, &v[1], 4, hipMemcpyHostToDevice, c->stream));
@@ -168,18 +226,13 @@ struct DeviceBackend {
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		parked_known = 0;                                           // (reset_round_state clears the device side before the first round)
 	}
-	// segment ranking of the current list (shared with the copy-back): returns the list length, leaves flag / segidx / seg_head / dist[cur] filled
+	// segment ranking of the current list (the later snapshots and the copy-back): returns the list length, leaves flag / segidx / seg_head / dist[cur] filled
 	unsigned long long rank_segments(unsigned ne, int *cur_out)
 	{
 		hipStream_t s = c->stream;
 		st->flag.ensure((size_t)ne * 4 + 16); st->segidx.ensure((size_t)ne * 4 + 16);
 		k_seg_flags<<<(ne + 255) / 256, 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->flag.as<unsigned>());
-		{
-			size_t tmp = 0;
-			HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, st->flag.as<unsigned>(), st->segidx.as<unsigned>(), 0u, (size_t)ne + 1, rocprim::plus<unsigned>(), s));
-			st->scantmp.ensure(tmp);
-			HIP_TRY(rocprim::exclusive_scan(st->scantmp.p, tmp, st->flag.as<unsigned>(), st->segidx.as<unsigned>(), 0u, (size_t)ne + 1, rocprim::plus<unsigned>(), s));
-		}
+		prim::exclusive_scan(s, st->scantmp, st->flag.as<unsigned>(), st->segidx.as<unsigned>(), 0u, (size_t)ne + 1, rocprim::plus<unsigned>());
 		unsigned nseg = 0;
 		HIP_TRY(hipMemcpyAsync(&nseg, st->segidx.as<unsigned>() + ne, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
@@ -215,10 +268,7 @@ struct DeviceBackend {
 		for (int t = 0; t < 2; t++) {
 			HIP_TRY(hipMemsetAsync(st->cnt1k.p, 0, (size_t)(nchunks + 1) * 4, s));
 			k_count_marks_lin<<<nchunks, 256, 0, s>>>(c->d_bif[t].as<unsigned>(), st->elin.as<unsigned>(), (size_t)total, st->cnt1k.as<unsigned>());
-			size_t tmp = 0;
-			HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, st->cnt1k.as<unsigned>(), st->off1k.as<unsigned>(), 0u, (size_t)nchunks + 1, rocprim::plus<unsigned>(), s));
-			st->scantmp.ensure(tmp);
-			HIP_TRY(rocprim::exclusive_scan(st->scantmp.p, tmp, st->cnt1k.as<unsigned>(), st->off1k.as<unsigned>(), 0u, (size_t)nchunks + 1, rocprim::plus<unsigned>(), s));
+			prim::exclusive_scan(s, st->scantmp, st->cnt1k.as<unsigned>(), st->off1k.as<unsigned>(), 0u, (size_t)nchunks + 1, rocprim::plus<unsigned>());
 			unsigned nm = 0;
 			HIP_TRY(hipMemcpyAsync(&nm, st->off1k.as<unsigned>() + nchunks, 4, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
@@ -249,8 +299,8 @@ struct DeviceBackend {
 	// ---- read-only phases split over the attached GPUs (SURVEY.md 8e, row "Simplification"): the commits are replicated, so the graph is
 	// identical on every GPU before a snapshot and before a probe; each GPU takes the verdicts of ITS share (a slice of the positional
 	// order of the ids / of the window) and the verdict bytes are all-gathered: 1 B per id per snapshot, 1 B per window entry per round.
-	// SBL_REPLICATED_PHASES=1: measurement / test switch, every GPU computes everything (the round-3 behaviour).
-	bool split_ro() const { return c->comm && c->comm->n > 1 && getenv("SBL_REPLICATED_PHASES") == nullptr; }
+	// (StageSwitches::replicated_phases: every GPU computes everything, the round-3 behaviour.)
+	bool split_ro() const { return c->comm && c->comm->n > 1 && !sw.replicated_phases; }
 	double ro_ms = 0;                                                 // host time inside the verdict collectives
 	void share(uint32_t n, uint32_t *lo, uint32_t *hi) const
 	{
@@ -589,43 +639,7 @@ struct DeviceBackend {
 	}
 };
 
-void sbl_simplify_free(sbl_ctx *c)
-{
-	SimplifyState *st = c->simp;
-	if (!st) return;
-	DevBuf *bufs[] = { &st->ch, &st->op, &st->nx, &st->pv, &st->nodeof[0], &st->nodeof[1], &st->nslot, &st->nnext, &st->nidst, &st->nclr, &st->ndead,
-	                   &st->head[0], &st->head[1], &st->lsize[0], &st->lsize[1], &st->ctr, &st->need, &st->big, &st->touch, &st->ck_touch, &st->own, &st->lock, &st->rmax, &st->wmax, &st->win,
-	                   &st->arena, &st->snap_arena, &st->big_arena, &st->claims, &st->live, &st->robuf, &st->bidx, &st->instbuf, &st->snap_list, &st->snap_live, &st->park_of, &st->slice_busy, &st->park_list, &st->ck_ch, &st->ck_op, &st->ck_nx, &st->ck_pv, &st->ck_bif[0], &st->ck_bif[1],
-	                   &st->ck_nodeof[0], &st->ck_nodeof[1], &st->ck_nslot, &st->ck_nnext, &st->ck_ndead, &st->ck_head[0], &st->ck_head[1], &st->ck_lsize[0], &st->ck_lsize[1],
-	                   &st->lin, &st->elin, &st->lmpos[0], &st->lmpos[1], &st->lmid[0], &st->lmid[1], &st->cnt1k, &st->off1k, &st->sel, &st->tstamp, &st->nmark, &st->maux[0], &st->maux[1], &st->iota, &st->keys, &st->skeys, &st->selem, &st->sorttmp, &st->scantmp, &st->perm, &st->permin, &st->flag, &st->segidx, &st->seg_head, &st->seg_len, &st->seg_succ_elem,
-	                   &st->succ[0], &st->succ[1], &st->dist[0], &st->dist[1], &st->newidx, &st->ch_out, &st->op_out };
-	for (DevBuf *b : bufs) b->release();
-	if (st->park_stream) { (void)hipStreamDestroy(st->park_stream); for (auto &e : st->park_ev) if (e) (void)hipEventDestroy(e); }
-	if (st->h_ctr) (void)hipHostFree(st->h_ctr);
-	if (st->h_init) (void)hipHostFree(st->h_init);
-	for (auto &e : st->ev) if (e) (void)hipEventDestroy(e);
-	for (auto &e : st->snap_ev) (void)hipEventDestroy(e);
-	delete st;
-	c->simp = nullptr;
-}
-
-static void sort_pairs64(sbl_ctx *c, SimplifyState *st, unsigned long long *kin, unsigned long long *kout, unsigned *vin, unsigned *vout, size_t n, unsigned bits = 64)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-	st->sorttmp.ensure(tmp);
-	HIP_TRY(rocprim::radix_sort_pairs(st->sorttmp.p, tmp, kin, kout, vin, vout, n, 0, bits, c->stream));
-}
-static unsigned bits_of(unsigned long long v) { unsigned b = 1; while (b < 64 && (v >> b)) b++; return b; }
-static void scan_u32(sbl_ctx *c, SimplifyState *st, unsigned *in, unsigned *out, size_t n)
-{
-	size_t tmp = 0;
-	HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-	st->scantmp.ensure(tmp);
-	HIP_TRY(rocprim::exclusive_scan(st->scantmp.p, tmp, in, out, 0u, n, rocprim::plus<unsigned>(), c->stream));
-}
-
-// Inputs up to this many elements take the one-launch path (k_dense_stage) first; SBL_NO_DENSE_PATH=1: test switch
+// Inputs up to this many elements take the one-launch path (k_dense_stage) first (StageSwitches::no_dense_path: never)
 #define DENSE_MAX_ELEMS (1u << 16)
 // The reference's callback sequence (blockfinder.cpp:23-48) is a function of the call index alone -- start, run(min(i, 50)) for i = 1, 2, ...,
 // end -- so an attempt that is abandoned and run again delivers only the calls the caller has not seen yet.
@@ -641,262 +655,231 @@ struct ProgressFilter {
 		else if (!f->ended) { f->ended = true; f->fn(p, state, f->user); }
 	}
 };
-enum { RUN_DONE = 0, RUN_DENSE_FAILED = 1, RUN_RESTART = 2, RUN_TRY_DENSE = 3 };
-static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges, bool allow_dense, bool optimistic,
-                             bool force_dense = false /* the one-launch path for up to DENSE_SWITCH_MAX_ELEMS elements: the rounds gave up (TryDense) */, bool may_switch = false /* this attempt may give up for it */);
-static void simplify_run_guarded(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges);
-void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges)
-{
-	// With several GPUs on one job every snapshot and every probe of the stage is a collective (allgather_shares): a rank that leaves
-	// the stage with an error anywhere -- an allocation that fails, a HIP error, a check that throws -- must release the peers that
-	// would wait for it there (the deterministic RestartStage is thrown on all ranks alike and never gets here).
-	if (!c->comm) { simplify_run_guarded(c, k, D, max_iter, progress, user, bulges); return; }
-	try { simplify_run_guarded(c, k, D, max_iter, progress, user, bulges); }
-	catch (...) { c->comm->abort_peers(); throw; }
-}
-static void simplify_run_guarded(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges)
-{
-	// the stage's input (d_ch / d_op) is only replaced by the copy-back at the very end, so an attempt that cannot finish -- a one-launch
-	// run out of pool or arena space, an optimistic run that would need a roll-back -- is simply followed by the next one from the same input
-	ProgressFilter pf{progress, user};
-	sbl_progress_fn pfn = progress ? &ProgressFilter::relay : nullptr;
-	// (SBL_CHECKPOINTS: measurement / test switch, checkpoints from the first attempt on; hint_checkpoints: the previous stage of this
-	// context had to be abandoned for an order violation -- inputs that do that once tend to do it again, and an abandoned attempt
-	// costs a whole stage, a checkpoint 2 - 4 %)
-	const bool optimistic = getenv("SBL_CHECKPOINTS") == nullptr && !c->hint_checkpoints;
-	int r = simplify_run_impl(c, k, D, max_iter, pfn, &pf, bulges, true, optimistic, false, true);
-	if (r == RUN_TRY_DENSE) {
-		if (getenv("SBL_TRACE")) fprintf(stderr, "[sbl] the ordered rounds have turned into a slow serial chain: the stage runs again through the one-launch path\n");
-		r = simplify_run_impl(c, k, D, max_iter, pfn, &pf, bulges, true, optimistic, true, false);
-		c->stats.replays++;                                               // the abandoned attempt
-	}
-	if (r == RUN_DENSE_FAILED) r = simplify_run_impl(c, k, D, max_iter, pfn, &pf, bulges, false, optimistic);
-	if (r == RUN_RESTART) {
-		if (getenv("SBL_TRACE")) fprintf(stderr, "[sbl] optimistic attempt abandoned: the stage runs again with iteration checkpoints (element slack hint %zu, node capacity hint %zu)\n", c->hint_elem_slack, c->hint_cap_n);
-		(void)simplify_run_impl(c, k, D, max_iter, pfn, &pf, bulges, false, false);
-		c->stats.replays++;                                               // the abandoned attempt
-		c->hint_checkpoints = c->stats.replays > c->stats.grow_replays + 1;      // order violations (not just a pool that was too small): the next stage starts with checkpoints
-	} else if (!optimistic && r == RUN_DONE && c->stats.replays == c->stats.grow_replays) c->hint_checkpoints = false;      // a checkpointed stage that never rolled back
-}
-static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges, bool allow_dense, bool optimistic,
-                             bool force_dense, bool may_switch)
-{
-	hipStream_t s = c->stream;
-	if (!c->simp) {
-		c->simp = new SimplifyState();
-		HIP_TRY(hipHostMalloc((void **)&c->simp->h_ctr, (CTR_COUNT + 16) * 4, hipHostMallocMapped | hipHostMallocCoherent));
-		memset(c->simp->h_ctr, 0, (CTR_COUNT + 16) * 4);
-		if (hipHostGetDevicePointer((void **)&c->simp->d_hctr, c->simp->h_ctr, 0) != hipSuccess) { (void)hipGetLastError(); c->simp->d_hctr = nullptr; }
-	}
-	SimplifyState *st = c->simp;
+
+// ------------------------------------------------------------------------------------------- one attempt at the stage, phase by phase
+struct StageAttempt {
+	sbl_ctx *c;
+	SimplifyState *st;
+	const StageSwitches &sw;
+	const uint32_t k, D, max_iter;
+	hipStream_t s;
 	DeviceBackend be;
-	be.c = c; be.st = st;
-	c->stats = sbl_stage_stats{};
-	HIP_TRY(hipEventRecord(c->ev[2], s));
+	// what the set-up phases work out for the later ones
+	size_t E = 0, ne0 = 0, n0 = 0, ninst = 0, maxn = 0;               // elements of the input (padded: ne0), marks of strand 0, instances, most instances of one id
+	bool dense = false;                                               // this attempt takes the one-launch path
+	uint32_t window = 0, window_max = 0;
+	unsigned park_cap = 0;
+	unsigned ne = 0; unsigned long long total = 0;                    // copy-back: slots of the final list, its length
 
-	// ---- E1: enumeration into mark arrays with room for inserted elements
-	size_t E = c->nelem, ne0 = (E + 31) / 32 * 32;
-	size_t cap_e = ne0 + E / 8 + (1u << 20);
-	if (const char *e = getenv("SBL_TEST_ELEM_SLACK")) cap_e = ne0 + (size_t)atoll(e);      // test hook: provoke the grow / restart paths
-	cap_e = std::max(cap_e, ne0 + std::min<size_t>(c->hint_elem_slack, 4 * E + (1u << 20)));      // what an abandoned attempt of this context asked for (DeviceBackend::grow), bounded by the current input
-	be.ne0_ = ne0;
-	SBL_CHECK(cap_e < 0xFFFFFFF0ull, SBL_ERR_TOO_LARGE, "element capacity overflow");
-	sbl_run_enumeration(c, k, cap_e);
-	if (c->comm) if (const char *e = getenv("SBL_TEST_FAIL_SIMPLIFY_RANK")) if ((uint32_t)atoi(e) == c->comm->rank)      // test hook: this rank leaves the stage between two collectives
-		throw SblError{SBL_ERR_OOM, "out of memory (SBL_TEST_FAIL_SIMPLIFY_RANK: this rank leaves the simplification stage)"};
-	be.nid_ = c->bif_count;
-	be.cap_e = (uint32_t)cap_e;
+	StageAttempt(sbl_ctx *c_, const StageSwitches &sw_, uint32_t k_, uint32_t D_, uint32_t max_iter_)
+		: c(c_), st(c_->simp), sw(sw_), k(k_), D(D_), max_iter(max_iter_), s(c_->stream), be(c_, c_->simp, sw_) {}
 
-	// ---- graph arrays
-	st->ch.ensure(cap_e); st->op.ensure(cap_e * 4); st->nx.ensure(cap_e * 4); st->pv.ensure(cap_e * 4);
-	st->nodeof[0].ensure(cap_e * 4); st->nodeof[1].ensure(cap_e * 4);
-	HIP_TRY(hipMemcpyAsync(st->ch.p, c->d_ch.p, E, hipMemcpyDeviceToDevice, s));
-	HIP_TRY(hipMemcpyAsync(st->op.p, c->d_op.p, E * 4, hipMemcpyDeviceToDevice, s));
-	k_init_links<<<nblocks(cap_e, 256), 256, 0, s>>>(st->nx.as<unsigned>(), st->pv.as<unsigned>(), st->nodeof[0].as<unsigned>(), st->nodeof[1].as<unsigned>(),
-	                                                st->ch.as<uint8_t>(), E, cap_e);
+	bool many_instances() const { return ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_); }      // instances per id: a handful, or dozens (many strains)
 
-	// ---- E2: instance lists in the reference's initial order
-	sbl_compact_marks(c, 0);
-	sbl_compact_marks(c, 1);
-	size_t n0 = c->nmarks[0], n1 = c->nmarks[1], ninst = n0 + n1;
-	c->stats.instances = ninst;
-	const size_t dense_max = force_dense ? DENSE_SWITCH_MAX_ELEMS : DENSE_MAX_ELEMS;
-	const bool dense = allow_dense && E <= dense_max && be.nid_ > 0 && getenv("SBL_NO_DENSE_PATH") == nullptr;
-	// (a job on several GPUs never switches: the decision is timed, and the ranks must stay in step)
-	be.may_try_dense = may_switch && !dense && !c->comm && E <= DENSE_SWITCH_MAX_ELEMS && getenv("SBL_NO_DENSE_PATH") == nullptr && getenv("SBL_NO_DENSE_SWITCH") == nullptr;
-	be.max_iter_ = max_iter ? max_iter : 1u;
-	// (the one-launch path cannot grow a pool and replay: low-complexity input makes hundreds of nodes per collapse, and 16 M nodes are 270 MB)
-	size_t cap_n = dense ? std::max<size_t>(4 * ninst + (1u << 20), 16u << 20) : 4 * ninst + (1u << 20);
-	if (dense) if (const char *e = getenv("SBL_TEST_DENSE_NODE_SLACK")) cap_n = ninst + (size_t)atoll(e);      // test hook: provoke the fall-back
-	cap_n = std::max(cap_n, c->hint_cap_n);
-	SBL_CHECK(cap_n < 0x7FFFFFF0ull, SBL_ERR_TOO_LARGE, "node capacity overflow");
-	be.cap_n = (uint32_t)cap_n;
-	st->nslot.ensure(cap_n * 4); st->nnext.ensure(cap_n * 4); st->nidst.ensure(cap_n * 4); st->nclr.ensure(cap_n * 4); st->ndead.ensure(cap_n);
-	size_t nidp = (size_t)be.nid_ + 1;
-	for (int t = 0; t < 2; t++) {
-		st->head[t].ensure(nidp * 4); st->lsize[t].ensure(nidp * 4);
-		HIP_TRY(hipMemsetAsync(st->head[t].p, 0xFF, nidp * 4, s));
-		HIP_TRY(hipMemsetAsync(st->lsize[t].p, 0, nidp * 4, s));
-	}
-	size_t nmax = std::max(n0, n1);
-	st->keys.ensure(nmax * 8 + 16); st->skeys.ensure(nmax * 8 + 16); st->selem.ensure(nmax * 4 + 16); st->iota.ensure(nmax * 4 + 16);
-	st->nmark.ensure(cap_n * 4);
-	for (int t = 0; t < 2; t++) st->maux[t].ensure(16);
-	const unsigned ordbits = bits_of(2ull * E), idbits = bits_of(be.nid_);      // sort keys of id_bits + ordbits bits (48 on the benchmark workload: 6 radix passes, not 8)
-	for (int t = 0; t < 2; t++) {
-		unsigned n = c->nmarks[t];
-		if (!n) continue;
-		k_instance_keys<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[t].as<unsigned>(), c->d_mid[t].as<unsigned>(), n, (unsigned)t,
-		                                               c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, ordbits, st->keys.as<unsigned long long>(), st->iota.as<unsigned>());
-		sort_pairs64(c, st, st->keys.as<unsigned long long>(), st->skeys.as<unsigned long long>(), st->iota.as<unsigned>(), st->selem.as<unsigned>(), n, std::min(64u, idbits + ordbits));
-		k_build_lists<<<nblocks(n, 256), 256, 0, s>>>(st->skeys.as<unsigned long long>(), st->selem.as<unsigned>(), c->d_melem[t].as<unsigned>(), n, t ? (unsigned)n0 : 0u, (unsigned)t, ordbits,
-		                                             st->nslot.as<unsigned>(), st->nnext.as<unsigned>(), st->nidst.as<unsigned>(), st->ndead.as<uint8_t>(),
-		                                             st->head[t].as<unsigned>(), st->lsize[t].as<unsigned>(), st->nodeof[t].as<unsigned>(), st->nmark.as<unsigned>());
-		st->maux[t].ensure((size_t)n * 4 + 16);
-		k_mark_aux<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[t].as<unsigned>(), n, (unsigned)t, c->d_sepidx.as<unsigned>(), c->nchr, c->d_ch.as<uint8_t>(), k, st->maux[t].as<unsigned>());
-	}
-	HIP_TRY(hipGetLastError());
-	// positional order of the ids for the snapshot kernel
-	st->perm.ensure(nidp * 4 + 16); st->permin.ensure(nidp * 4 + 16);
-	st->keys.ensure(nidp * 8 + 16); st->skeys.ensure(nidp * 8 + 16);
-	if (be.nid_) {
-		k_id_position_keys<<<nblocks(be.nid_, 256), 256, 0, s>>>(st->head[0].as<unsigned>(), st->head[1].as<unsigned>(), st->nslot.as<unsigned>(), be.nid_,
-		                                                       st->keys.as<unsigned long long>(), st->permin.as<unsigned>());
-		sort_pairs64(c, st, st->keys.as<unsigned long long>(), st->skeys.as<unsigned long long>(), st->permin.as<unsigned>(), st->perm.as<unsigned>(), be.nid_, 32);      // keys are element slots, or 2^32 - 1
-	}
-	HIP_TRY(hipGetLastError());
-
-	size_t be_maxn = 0;                                                // largest number of instances of an id (below)
-	// ---- control state
-	st->ctr.ensure(CTR_COUNT * 4);
-	st->sel.ensure((1024 + 16) * 4);
+	// ---- E1, E2: enumeration into mark arrays with room for inserted elements, graph arrays, instance lists in the reference's initial order
+	void setup_graph(bool allow_dense, bool force_dense, bool may_switch)
 	{
-		// counter block and the header of the selection scratch (k_select_*: header + one count per chunk of ids; the kernels leave the header
-		// reset) from a pinned staging buffer the context keeps: the copies are asynchronous and the host does not wait for them
-		if (!st->h_init) HIP_TRY(hipHostMalloc((void **)&st->h_init, (CTR_COUNT + 4) * 4, hipHostMallocDefault));
-		HIP_TRY(hipStreamSynchronize(s));                                  // (a previous stage's copies from the buffer have long completed; cheap when idle)
-		unsigned *v = reinterpret_cast<unsigned *>(st->h_init);
-		memset(v, 0, CTR_COUNT * 4);
-		v[CTR_NE] = (unsigned)ne0; v[CTR_NN] = (unsigned)ninst; v[CTR_VIOL] = BT_NONE;
-		v[CTR_COUNT] = SBL_NONE; v[CTR_COUNT + 1] = SBL_NONE; v[CTR_COUNT + 2] = 0u; v[CTR_COUNT + 3] = 0u;
-		HIP_TRY(hipMemcpyAsync(st->ctr.p, v, CTR_COUNT * 4, hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(st->sel.p, v + CTR_COUNT, 16, hipMemcpyHostToDevice, s));
+		E = c->nelem; ne0 = (E + 31) / 32 * 32;
+		size_t cap_e = ne0 + E / 8 + (1u << 20);
+		if (sw.test_elem_slack.set) cap_e = ne0 + (size_t)sw.test_elem_slack.v;
+		cap_e = std::max(cap_e, ne0 + std::min<size_t>(c->hint_elem_slack, 4 * E + (1u << 20)));      // what an abandoned attempt of this context asked for (DeviceBackend::grow), bounded by the current input
+		be.ne0_ = ne0;
+		SBL_CHECK(cap_e < 0xFFFFFFF0ull, SBL_ERR_TOO_LARGE, "element capacity overflow");
+		sbl_run_enumeration(c, k, cap_e);
+		if (c->comm && sw.test_fail_rank.set && (uint32_t)(int)sw.test_fail_rank.v == c->comm->rank)
+			throw SblError{SBL_ERR_OOM, "out of memory (SBL_TEST_FAIL_SIMPLIFY_RANK: this rank leaves the simplification stage)"};
+		be.nid_ = c->bif_count;
+		be.cap_e = (uint32_t)cap_e;
+
+		// ---- graph arrays
+		st->ch.ensure(cap_e); st->op.ensure(cap_e * 4); st->nx.ensure(cap_e * 4); st->pv.ensure(cap_e * 4);
+		st->nodeof[0].ensure(cap_e * 4); st->nodeof[1].ensure(cap_e * 4);
+		HIP_TRY(hipMemcpyAsync(st->ch.p, c->d_ch.p, E, hipMemcpyDeviceToDevice, s));
+		HIP_TRY(hipMemcpyAsync(st->op.p, c->d_op.p, E * 4, hipMemcpyDeviceToDevice, s));
+		k_init_links<<<nblocks(cap_e, 256), 256, 0, s>>>(st->nx.as<unsigned>(), st->pv.as<unsigned>(), st->nodeof[0].as<unsigned>(), st->nodeof[1].as<unsigned>(),
+		                                                st->ch.as<uint8_t>(), E, cap_e);
+
+		// ---- E2
+		sbl_compact_marks(c, 0);
+		sbl_compact_marks(c, 1);
+		n0 = c->nmarks[0];
+		const size_t n1 = c->nmarks[1];
+		ninst = n0 + n1;
+		c->stats.instances = ninst;
+		const size_t dense_max = force_dense ? DENSE_SWITCH_MAX_ELEMS : DENSE_MAX_ELEMS;
+		dense = allow_dense && E <= dense_max && be.nid_ > 0 && !sw.no_dense_path;
+		// (a job on several GPUs never switches: the decision is timed, and the ranks must stay in step)
+		be.may_try_dense = may_switch && !dense && !c->comm && E <= DENSE_SWITCH_MAX_ELEMS && !sw.no_dense_path && !sw.no_dense_switch;
+		be.max_iter_ = max_iter ? max_iter : 1u;
+		// (the one-launch path cannot grow a pool and replay: low-complexity input makes hundreds of nodes per collapse, and 16 M nodes are 270 MB)
+		size_t cap_n = dense ? std::max<size_t>(4 * ninst + (1u << 20), 16u << 20) : 4 * ninst + (1u << 20);
+		if (dense && sw.test_dense_node_slack.set) cap_n = ninst + (size_t)sw.test_dense_node_slack.v;
+		cap_n = std::max(cap_n, c->hint_cap_n);
+		SBL_CHECK(cap_n < 0x7FFFFFF0ull, SBL_ERR_TOO_LARGE, "node capacity overflow");
+		be.cap_n = (uint32_t)cap_n;
+		st->nslot.ensure(cap_n * 4); st->nnext.ensure(cap_n * 4); st->nidst.ensure(cap_n * 4); st->nclr.ensure(cap_n * 4); st->ndead.ensure(cap_n);
+		const size_t nidp = (size_t)be.nid_ + 1;
+		for (int t = 0; t < 2; t++) {
+			st->head[t].ensure(nidp * 4); st->lsize[t].ensure(nidp * 4);
+			HIP_TRY(hipMemsetAsync(st->head[t].p, 0xFF, nidp * 4, s));
+			HIP_TRY(hipMemsetAsync(st->lsize[t].p, 0, nidp * 4, s));
+		}
+		const size_t nmax = std::max(n0, n1);
+		st->keys.ensure(nmax * 8 + 16); st->skeys.ensure(nmax * 8 + 16); st->selem.ensure(nmax * 4 + 16); st->iota.ensure(nmax * 4 + 16);
+		st->nmark.ensure(cap_n * 4);
+		for (int t = 0; t < 2; t++) st->maux[t].ensure(16);
+		const unsigned ordbits = prim::bits_of(2ull * E), idbits = prim::bits_of(be.nid_);      // sort keys of id_bits + ordbits bits (48 on the benchmark workload: 6 radix passes, not 8)
+		for (int t = 0; t < 2; t++) {
+			unsigned n = c->nmarks[t];
+			if (!n) continue;
+			k_instance_keys<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[t].as<unsigned>(), c->d_mid[t].as<unsigned>(), n, (unsigned)t,
+			                                               c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, ordbits, st->keys.as<unsigned long long>(), st->iota.as<unsigned>());
+			prim::sort_pairs(s, st->sorttmp, st->keys.as<unsigned long long>(), st->skeys.as<unsigned long long>(), st->iota.as<unsigned>(), st->selem.as<unsigned>(), n, 0, std::min(64u, idbits + ordbits));
+			k_build_lists<<<nblocks(n, 256), 256, 0, s>>>(st->skeys.as<unsigned long long>(), st->selem.as<unsigned>(), c->d_melem[t].as<unsigned>(), n, t ? (unsigned)n0 : 0u, (unsigned)t, ordbits,
+			                                             st->nslot.as<unsigned>(), st->nnext.as<unsigned>(), st->nidst.as<unsigned>(), st->ndead.as<uint8_t>(),
+			                                             st->head[t].as<unsigned>(), st->lsize[t].as<unsigned>(), st->nodeof[t].as<unsigned>(), st->nmark.as<unsigned>());
+			st->maux[t].ensure((size_t)n * 4 + 16);
+			k_mark_aux<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[t].as<unsigned>(), n, (unsigned)t, c->d_sepidx.as<unsigned>(), c->nchr, c->d_ch.as<uint8_t>(), k, st->maux[t].as<unsigned>());
+		}
+		HIP_TRY(hipGetLastError());
+		// positional order of the ids for the snapshot kernel
+		st->perm.ensure(nidp * 4 + 16); st->permin.ensure(nidp * 4 + 16);
+		st->keys.ensure(nidp * 8 + 16); st->skeys.ensure(nidp * 8 + 16);
+		if (be.nid_) {
+			k_id_position_keys<<<nblocks(be.nid_, 256), 256, 0, s>>>(st->head[0].as<unsigned>(), st->head[1].as<unsigned>(), st->nslot.as<unsigned>(), be.nid_,
+			                                                       st->keys.as<unsigned long long>(), st->permin.as<unsigned>());
+			prim::sort_pairs(s, st->sorttmp, st->keys.as<unsigned long long>(), st->skeys.as<unsigned long long>(), st->permin.as<unsigned>(), st->perm.as<unsigned>(), be.nid_, 0, 32);      // keys are element slots, or 2^32 - 1
+		}
+		HIP_TRY(hipGetLastError());
 	}
-	st->need.ensure(nidp); st->big.ensure(nidp); st->touch.ensure(nidp); st->own.ensure(nidp * 4);
-	HIP_TRY(hipMemsetAsync(st->need.p, 0, nidp, s));
-	HIP_TRY(hipMemsetAsync(st->big.p, 0, nidp, s));
-	HIP_TRY(hipMemsetAsync(st->touch.p, 0, nidp, s));
-	// scratch arena per window entry: window caches of ~16 instances (17 B per step, D + k + 2 steps) + FillVisit / Overlap
-	// buffers + the AnyBulges map; ids that need more run alone in the big arena
+
+	// ---- control state; arena, window and round buffers (with the out-of-memory retry ladder); what the kernels' LDS is sized by; the view
+	void size_buffers(bool optimistic)
 	{
-		// instances per id: the arena holds the window caches of an id with up to 1.5x the typical maximum (ids with
-		// more -- repeat families -- run alone in the big arena)
-		unsigned maxn = 0;
-		HIP_TRY(hipMemsetAsync(st->ctr.as<unsigned>() + CTR_BIG, 0, 4, s));
-		if (be.nid_) k_max_instances<<<256, 256, 0, s>>>(st->lsize[0].as<unsigned>(), st->lsize[1].as<unsigned>(), be.nid_, st->ctr.as<unsigned>() + CTR_BIG);
-		HIP_TRY(hipMemcpyAsync(&maxn, st->ctr.as<unsigned>() + CTR_BIG, 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		HIP_TRY(hipMemsetAsync(st->ctr.as<unsigned>() + CTR_BIG, 0, 4, s));
-		be_maxn = maxn;
-		size_t slots = std::min<size_t>(std::max<size_t>(16, maxn + maxn / 2), 2048);
-		size_t ws = (size_t)D + k + 2;
-		size_t need = slots * 17 * ws + 12 * (size_t)D + 8 * (size_t)k + (64u << 10) + slots * 64;
-		be.arena_bytes = (uint32_t)std::min<size_t>(std::max<size_t>(need, 128u << 10), 1u << 30);
-		be.snap_arena_bytes = be.arena_bytes;
-		be.snap_threads = (uint32_t)std::max<size_t>(256, std::min<size_t>(256 * 32, (16ull << 30) / be.arena_bytes)) & ~7u;   // a multiple of the 8 XCDs
-		be.big_arena_bytes = (uint32_t)std::min<size_t>(std::max<size_t>(256u << 20, 64 * be.arena_bytes), 0xFFFFFF00u);
-	}
-	const uint32_t base_window = 14336;                                  // (swept again at the end of round 3: 86.1 ms against 86.9 ms at 16 384, 62 strains 4.12 against 4.19 s)
-	uint32_t window = c->window ? c->window : std::min<uint32_t>(base_window, std::max<uint32_t>(2048, be.nid_ / 64));
-	window = std::min<uint32_t>(window, (1u << 20) - 1);
-	window = (uint32_t)std::min<size_t>(window, std::max<size_t>(64, (24ull << 30) / be.arena_bytes));
-	window = std::max<uint32_t>(1, std::min<uint32_t>(window, be.nid_ ? be.nid_ : 1));
-	be.window = window;
-	// the driver widens the window up to 4x while rounds are capacity-bound (simplify_driver.h); an explicit sbl_set_window pins it
-	uint32_t window_max = c->window ? window : (uint32_t)std::min<size_t>((size_t)window * 4, std::max<size_t>(window, (48ull << 30) / be.arena_bytes));
-	window_max = std::max<uint32_t>(window, std::min<uint32_t>(window_max, be.nid_ ? be.nid_ : 1));
-	// parked transactions (GraphView::park_of): SBL_PARK=n collapses per launch and transaction (0: off)
-	// (8 x 4.6 Mbp: 59.5 ms without, 56.9 with 2, 57.5 with 3, 61 with 1 -- every parked transaction costs its dependants a round; 62 strains,
-	// where an id has dozens of instances and a transaction up to 28 collapses: 2.44 s without, 2.36 with 2, 2.18 with 3, 2.135 with 4, 2.15 with 5.
-	// But ids with dozens of instances are also the regime of the serial chain -- one or two transactions per round, which chain() does not
-	// enter while anything is parked, and something always is when every transaction parks seven times: 57 strains x 8 kbp at D = 369 took
-	// 17 734 rounds, 238 s instead of seconds (tools/stress.py MANY=1, seed 67000; still exact).  Until chain() makes parking stop, it is OFF
-	// by default there; SBL_PARK=4 is what the 2.15 s of profiles/r05_bench_config4.json were measured with.)
-	// Round 6: the serial chain and parking compose (DeviceBackend::chain stops NEW parking, what is parked drains), so the many-instances
-	// regime parks too -- with the cap that was measured best there (4: 2.135 s at 62 strains against 2.36 with 2) -- and so do the
-	// replicated commits of a job on several GPUs.
-	unsigned park_cap = ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_) ? 4u : 2u;
-	if (const char *e = getenv("SBL_PARK")) park_cap = (unsigned)std::max(0, atoi(e));
-	if (dense) park_cap = 0;
-	auto round_buffers = [&](uint32_t w) {
-		st->win.ensure((size_t)w * 4 + 16);
-		st->arena.ensure((size_t)w * be.arena_bytes * (park_cap ? 2u : 1u));      // (second half: the SHADOW slices -- where the entry of a window position works while its own slice holds a parked transaction)
-		st->claims.ensure((size_t)w * (CLAIM_CAP + 1) * 4);
-		st->live.ensure((size_t)w + 64);
-		st->instbuf.ensure((size_t)w * 129 * 4);                          // (DeviceBackend::istride() <= 129)
-		st->slice_busy.ensure(2 * ((size_t)w + 64));                      // (second half: the copy k_reserve takes for k_commit)
-		st->park_list.ensure((size_t)w * 4 + 64);
-	};
-	be.snap_slice = window_max;
-	if (!dense) {
-		// a smaller or partly occupied GPU: first without the shadow slices (parking is a ~5 % optimisation, a 4 x smaller window is not),
-		// then with the pinned window, which always was enough
-		try { round_buffers(window_max); }
-		catch (const SblError &) {
-			(void)hipGetLastError();
-			bool ok = false;
-			if (park_cap) { park_cap = 0; try { round_buffers(window_max); ok = true; } catch (const SblError &) { (void)hipGetLastError(); } }
-			if (!ok) {
-				if (window_max == window) throw;
-				window_max = window;
-				be.snap_slice = window;
-				round_buffers(window);
+		const size_t nidp = (size_t)be.nid_ + 1;
+		st->ctr.ensure(CTR_COUNT * 4);
+		st->sel.ensure((1024 + 16) * 4);
+		{
+			// counter block and the header of the selection scratch (k_select_*: header + one count per chunk of ids; the kernels leave the header
+			// reset) from a pinned staging buffer the context keeps: the copies are asynchronous and the host does not wait for them
+			if (!st->h_init) HIP_TRY(hipHostMalloc((void **)&st->h_init, (CTR_COUNT + 4) * 4, hipHostMallocDefault));
+			HIP_TRY(hipStreamSynchronize(s));                                  // (a previous stage's copies from the buffer have long completed; cheap when idle)
+			unsigned *v = reinterpret_cast<unsigned *>(st->h_init);
+			memset(v, 0, CTR_COUNT * 4);
+			v[CTR_NE] = (unsigned)ne0; v[CTR_NN] = (unsigned)ninst; v[CTR_VIOL] = BT_NONE;
+			v[CTR_COUNT] = SBL_NONE; v[CTR_COUNT + 1] = SBL_NONE; v[CTR_COUNT + 2] = 0u; v[CTR_COUNT + 3] = 0u;
+			HIP_TRY(hipMemcpyAsync(st->ctr.p, v, CTR_COUNT * 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(st->sel.p, v + CTR_COUNT, 16, hipMemcpyHostToDevice, s));
+		}
+		st->need.ensure(nidp); st->big.ensure(nidp); st->touch.ensure(nidp); st->own.ensure(nidp * 4);
+		HIP_TRY(hipMemsetAsync(st->need.p, 0, nidp, s));
+		HIP_TRY(hipMemsetAsync(st->big.p, 0, nidp, s));
+		HIP_TRY(hipMemsetAsync(st->touch.p, 0, nidp, s));
+		// scratch arena per window entry: window caches of ~16 instances (17 B per step, D + k + 2 steps) + FillVisit / Overlap
+		// buffers + the AnyBulges map; ids that need more run alone in the big arena
+		{
+			// instances per id: the arena holds the window caches of an id with up to 1.5x the typical maximum (ids with
+			// more -- repeat families -- run alone in the big arena)
+			unsigned m = 0;
+			HIP_TRY(hipMemsetAsync(st->ctr.as<unsigned>() + CTR_BIG, 0, 4, s));
+			if (be.nid_) k_max_instances<<<256, 256, 0, s>>>(st->lsize[0].as<unsigned>(), st->lsize[1].as<unsigned>(), be.nid_, st->ctr.as<unsigned>() + CTR_BIG);
+			HIP_TRY(hipMemcpyAsync(&m, st->ctr.as<unsigned>() + CTR_BIG, 4, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			HIP_TRY(hipMemsetAsync(st->ctr.as<unsigned>() + CTR_BIG, 0, 4, s));
+			maxn = m;
+			size_t slots = std::min<size_t>(std::max<size_t>(16, maxn + maxn / 2), 2048);
+			size_t ws = (size_t)D + k + 2;
+			size_t need = slots * 17 * ws + 12 * (size_t)D + 8 * (size_t)k + (64u << 10) + slots * 64;
+			be.arena_bytes = (uint32_t)std::min<size_t>(std::max<size_t>(need, 128u << 10), 1u << 30);
+			be.snap_arena_bytes = be.arena_bytes;
+			be.snap_threads = (uint32_t)std::max<size_t>(256, std::min<size_t>(256 * 32, (16ull << 30) / be.arena_bytes)) & ~7u;   // a multiple of the 8 XCDs
+			be.big_arena_bytes = (uint32_t)std::min<size_t>(std::max<size_t>(256u << 20, 64 * be.arena_bytes), 0xFFFFFF00u);
+		}
+		const uint32_t base_window = 14336;                                  // (swept again at the end of round 3: 86.1 ms against 86.9 ms at 16 384, 62 strains 4.12 against 4.19 s)
+		window = c->window ? c->window : std::min<uint32_t>(base_window, std::max<uint32_t>(2048, be.nid_ / 64));
+		window = std::min<uint32_t>(window, (1u << 20) - 1);
+		window = (uint32_t)std::min<size_t>(window, std::max<size_t>(64, (24ull << 30) / be.arena_bytes));
+		window = std::max<uint32_t>(1, std::min<uint32_t>(window, be.nid_ ? be.nid_ : 1));
+		be.window = window;
+		// the driver widens the window up to 4x while rounds are capacity-bound (simplify_driver.h); an explicit sbl_set_window pins it
+		window_max = c->window ? window : (uint32_t)std::min<size_t>((size_t)window * 4, std::max<size_t>(window, (48ull << 30) / be.arena_bytes));
+		window_max = std::max<uint32_t>(window, std::min<uint32_t>(window_max, be.nid_ ? be.nid_ : 1));
+		// parked transactions (GraphView::park_of): SBL_PARK=n collapses per launch and transaction (0: off)
+		// (8 x 4.6 Mbp: 59.5 ms without, 56.9 with 2, 57.5 with 3, 61 with 1 -- every parked transaction costs its dependants a round; 62 strains,
+		// where an id has dozens of instances and a transaction up to 28 collapses: 2.44 s without, 2.36 with 2, 2.18 with 3, 2.135 with 4, 2.15 with 5.
+		// But ids with dozens of instances are also the regime of the serial chain -- one or two transactions per round, which chain() does not
+		// enter while anything is parked, and something always is when every transaction parks seven times: 57 strains x 8 kbp at D = 369 took
+		// 17 734 rounds, 238 s instead of seconds (tools/stress.py MANY=1, seed 67000; still exact).  Until chain() makes parking stop, it is OFF
+		// by default there; SBL_PARK=4 is what the 2.15 s of profiles/r05_bench_config4.json were measured with.)
+		// Round 6: the serial chain and parking compose (DeviceBackend::chain stops NEW parking, what is parked drains), so the many-instances
+		// regime parks too -- with the cap that was measured best there (4: 2.135 s at 62 strains against 2.36 with 2) -- and so do the
+		// replicated commits of a job on several GPUs.
+		park_cap = many_instances() ? 4u : 2u;
+		if (sw.park.set) park_cap = (unsigned)std::max(0, (int)sw.park.v);
+		if (dense) park_cap = 0;
+		auto round_buffers = [&](uint32_t w) {
+			st->win.ensure((size_t)w * 4 + 16);
+			st->arena.ensure((size_t)w * be.arena_bytes * (park_cap ? 2u : 1u));      // (second half: the SHADOW slices -- where the entry of a window position works while its own slice holds a parked transaction)
+			st->claims.ensure((size_t)w * (CLAIM_CAP + 1) * 4);
+			st->live.ensure((size_t)w + 64);
+			st->instbuf.ensure((size_t)w * 129 * 4);                          // (DeviceBackend::istride() <= 129)
+			st->slice_busy.ensure(2 * ((size_t)w + 64));                      // (second half: the copy k_reserve takes for k_commit)
+			st->park_list.ensure((size_t)w * 4 + 64);
+		};
+		be.snap_slice = window_max;
+		if (!dense) {
+			// a smaller or partly occupied GPU: first without the shadow slices (parking is a ~5 % optimisation, a 4 x smaller window is not),
+			// then with the pinned window, which always was enough
+			try { round_buffers(window_max); }
+			catch (const SblError &) {
+				(void)hipGetLastError();
+				bool ok = false;
+				if (park_cap) { park_cap = 0; try { round_buffers(window_max); ok = true; } catch (const SblError &) { (void)hipGetLastError(); } }
+				if (!ok) {
+					if (window_max == window) throw;
+					window_max = window;
+					be.snap_slice = window;
+					round_buffers(window);
+				}
 			}
 		}
+		for (auto &e : st->ev) if (!e) HIP_TRY(hipEventCreate(&e));
+		be.ev = st->ev;
+		be.optimistic = optimistic;
+		be.rsv_waves = many_instances() ? 4u : 2u;
+		// (the 512-slot table stays: a probe it cannot hold goes to the walking kernel, whose launch then lasts as long as a full probe -- 15 such
+		// entries per round cost more than the 2 KB save; the instance and mark lists follow the input: largest instance count, mark density)
+		be.pidx_inst = (unsigned)std::min<size_t>(256, std::max<size_t>(64, (maxn + 15) / 16 * 16));
+		be.pidx_marks = ninst * 8 > E ? 192u : 64u;
+		// dozens of instances per id: a 1024-slot table.  With 512 slots 1.7 M of the 17 M probes of the 62-strain stage (2.35 M before the exact
+		// bound in probe_idx) went on to the walking kernel for the table alone; with 1024 none does and the stage takes 2.04 s instead of 2.17 s.
+		if (many_instances()) be.pidx_vbits = 10;
+		be.ev_phase = c->stage_seq++;
+		be.prof = sw.phases;
+		if (be.prof) sbl_commit_prof_reset();
+		if (dense) be.use_index = false;                                   // (the one-launch path reads no index: nothing to maintain)
+		be.idx_nblk = be.use_index ? (uint32_t)((E + 63) / 64) : 0u;
+		if (be.idx_nblk) st->bidx.ensure((size_t)be.idx_nblk * BT_IDX_WORDS * 8);
+		be.bind();
+		be.g.k = k; be.g.D = D;
 	}
-	for (auto &e : st->ev) if (!e) HIP_TRY(hipEventCreate(&e));
-	be.ev = st->ev;
-	be.optimistic = optimistic;
-	be.rsv_waves = ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_) ? 4u : 2u;      // instances per id: a handful, or dozens (many strains)
-	// (the 512-slot table stays: a probe it cannot hold goes to the walking kernel, whose launch then lasts as long as a full probe -- 15 such
-	// entries per round cost more than the 2 KB save; the instance and mark lists follow the input: largest instance count, mark density)
-	be.pidx_inst = (unsigned)std::min<size_t>(256, std::max<size_t>(64, (be_maxn + 15) / 16 * 16));
-	be.pidx_marks = ninst * 8 > E ? 192u : 64u;
-	// dozens of instances per id: a 1024-slot table.  With 512 slots 1.7 M of the 17 M probes of the 62-strain stage (2.35 M before the exact
-	// bound in probe_idx) went on to the walking kernel for the table alone; with 1024 none does and the stage takes 2.04 s instead of 2.17 s.
-	if (ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_)) be.pidx_vbits = 10;
-	be.ev_phase = c->stage_seq++;
-	be.prof = getenv("SBL_PHASES") ? (atoi(getenv("SBL_PHASES")) > 0 ? atoi(getenv("SBL_PHASES")) : 1) : 0;
-	if (be.prof) sbl_commit_prof_reset();
-	if (dense) be.use_index = false;                                   // (the one-launch path reads no index: nothing to maintain)
-	be.idx_nblk = be.use_index ? (uint32_t)((E + 63) / 64) : 0u;
-	if (be.idx_nblk) st->bidx.ensure((size_t)be.idx_nblk * BT_IDX_WORDS * 8);
-	be.bind();
-	be.g.k = k; be.g.D = D;
-	{
-		const unsigned cap = park_cap;
-		be.g.park_cap = cap; be.g.park_of = nullptr; be.g.slice_busy = nullptr; be.g.shadow_base = 0; be.park_slices = 0;
-		be.g.park_hold = 0; be.g.any_parked = 0; be.g.park_list = nullptr;
-		if (cap) {
-			if (!st->park_stream) { HIP_TRY(hipStreamCreateWithFlags(&st->park_stream, hipStreamNonBlocking)); for (auto &e : st->park_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-			st->park_of.ensure(((size_t)be.nid_ + 1) * 4);
-			be.park_slices = (size_t)window_max + 64;
-			be.g.park_of = st->park_of.as<unsigned>(); be.g.slice_busy = st->slice_busy.as<uint8_t>(); be.g.shadow_base = window_max;
-			be.g.park_list = st->park_list.as<unsigned>();
-		}
-	}
-	if (((D + k + 2u + 126u) >> 6) > 16u) be.g.idx_probe = 0;           // windows of more than 16 blocks: k_probe_idx could serve nobody (every entry walks, as before round 5)
-	be.g.test_flags = getenv("SBL_TEST_FLAGS") ? (unsigned)atoi(getenv("SBL_TEST_FLAGS")) : 0u;
-	be.g.tstamp = nullptr; be.g.tslot = 0;
-	be.g.sep = c->d_sepidx.as<unsigned>(); be.g.nsep = c->nchr + 1; be.g.norig = (uint32_t)E;
-	be.index_build();
-	if (!dense) be.stamps_init();
-	HIP_TRY(hipEventRecord(c->ev[3], s));
 
-	// ---- SimplifyGraph
-	SimplifyReport rep;
-	if (dense) {
-		// tiny input: for iteration, for id, RemoveBulges(id) in one launch (k_dense_stage)
+	// ---- parked transactions: their stream and events (made once per context), park_of and the view's fields
+	void setup_park()
+	{
+		be.g.park_cap = park_cap; be.g.park_of = nullptr; be.g.slice_busy = nullptr; be.g.shadow_base = 0; be.park_slices = 0;
+		be.g.park_hold = 0; be.g.any_parked = 0; be.g.park_list = nullptr;
+		if (!park_cap) return;
+		if (!st->park_stream) { HIP_TRY(hipStreamCreateWithFlags(&st->park_stream, hipStreamNonBlocking)); for (auto &e : st->park_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+		st->park_of.ensure(((size_t)be.nid_ + 1) * 4);
+		be.park_slices = (size_t)window_max + 64;
+		be.g.park_of = st->park_of.as<unsigned>(); be.g.slice_busy = st->slice_busy.as<uint8_t>(); be.g.shadow_base = window_max;
+		be.g.park_list = st->park_list.as<unsigned>();
+	}
+
+	// ---- tiny input: for iteration, for id, RemoveBulges(id) in one launch (k_dense_stage); false: out of pool or arena space
+	bool run_dense(SimplifyReport &rep, sbl_progress_fn progress, void *user)
+	{
 		be.g.lazy_min = 1;                                            // every id keeps full-size mark lists and takes lazy windows
 		st->big_arena.ensure(be.big_arena_bytes);
 		unsigned *d_out = st->ctr.as<unsigned>() + CTR_DENSE_ITER;
@@ -909,8 +892,8 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 		HIP_TRY(hipEventElapsedTime(&ms, be.ev[2], be.ev[3]));
 		be.commit_ms = ms;
 		if (st->h_ctr[CTR_ERR]) {
-			if (getenv("SBL_TRACE")) fprintf(stderr, "[sbl] one-launch path: capacity error %u, falling back to the ordered rounds\n", st->h_ctr[CTR_ERR]);
-			return RUN_DENSE_FAILED;
+			if (sw.trace) fprintf(stderr, "[sbl] one-launch path: capacity error %u, falling back to the ordered rounds\n", st->h_ctr[CTR_ERR]);
+			return false;
 		}
 		rep.iterations = st->h_ctr[CTR_DENSE_ITER]; rep.bulges = st->h_ctr[CTR_BULGES]; rep.transactions = rep.executed = st->h_ctr[CTR_TXN];
 		rep.chain_transactions = rep.transactions;
@@ -922,16 +905,12 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 			for (uint64_t i = 0; i < due; i++) { tp = std::min<uint64_t>(tp + 1, 50); progress((size_t)tp, SBL_PROGRESS_RUN, user); }
 			progress(50, SBL_PROGRESS_END, user);
 		}
-	} else {
-		try { rep = simplify_graph(be, max_iter, window, progress, user, window_max); }
-		catch (const RestartStage &) { HIP_TRY(hipStreamSynchronize(s)); return RUN_RESTART; }
-		catch (const TryDense &) { HIP_TRY(hipStreamSynchronize(s)); return RUN_TRY_DENSE; }
+		return true;
 	}
-	HIP_TRY(hipEventRecord(c->ev[4], s));
-	if (!dense) be.stamps_collect();
-	be.snapshots_collect();
-	if (be.g.bidx && (be.g.test_flags & BT_TF_STATS)) sbl_rounds_stats_report();      // what the block index served
-	if (be.g.bidx && getenv("SBL_CHECK_INDEX")) {                        // test switch: the maintained block index against a rebuild
+
+	// ---- test switch: the maintained block index against a rebuild
+	void check_index()
+	{
 		unsigned init[2] = {0u, BT_NONE}, res[2];
 		unsigned *d_out = st->ctr.as<unsigned>() + CTR_IDXCHECK;
 		HIP_TRY(hipMemcpyAsync(d_out, init, sizeof init, hipMemcpyHostToDevice, s));
@@ -939,86 +918,162 @@ static int simplify_run_impl(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_it
 		                                                    st->wmax.as<unsigned>(), be.g.norig, be.idx_nblk, st->bidx.as<unsigned long long>(), d_out);
 		HIP_TRY(hipMemcpyAsync(res, d_out, sizeof res, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		if (getenv("SBL_TRACE")) fprintf(stderr, "[sbl] block index check: %u of %u blocks differ from a rebuild\n", res[0], be.idx_nblk);
+		if (sw.trace) fprintf(stderr, "[sbl] block index check: %u of %u blocks differ from a rebuild\n", res[0], be.idx_nblk);
 		if (res[0]) { char b[160]; snprintf(b, sizeof b, "block index out of date: %u of %u blocks differ from a rebuild (first: block %u)", res[0], be.idx_nblk, res[1]); throw SblError{SBL_ERR_INTERNAL, b}; }
 	}
 
-	// ---- T3: copy-back (reference src/blockfinder.cpp:85-95): linearise the list into the dense state arrays
-	be.read_ctr();
-	unsigned ne = st->h_ctr[CTR_NE];
-	st->flag.ensure((size_t)ne * 4 + 16); st->segidx.ensure((size_t)ne * 4 + 16); st->newidx.ensure((size_t)ne * 4 + 16);
-	k_seg_flags<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->flag.as<unsigned>());
-	scan_u32(c, st, st->flag.as<unsigned>(), st->segidx.as<unsigned>(), (size_t)ne + 1);
-	unsigned nseg = 0;
-	HIP_TRY(hipMemcpyAsync(&nseg, st->segidx.as<unsigned>() + ne, 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	SBL_CHECK(nseg >= 1, SBL_ERR_INTERNAL, "copy-back: empty list");
-	st->seg_head.ensure((size_t)nseg * 4); st->seg_len.ensure((size_t)nseg * 4); st->seg_succ_elem.ensure((size_t)nseg * 4);
-	for (int t = 0; t < 2; t++) { st->succ[t].ensure((size_t)nseg * 4); st->dist[t].ensure((size_t)nseg * 8); }
-	k_seg_tails<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->flag.as<unsigned>(), st->segidx.as<unsigned>(),
-	                                            st->seg_head.as<unsigned>(), st->seg_len.as<unsigned>(), st->seg_succ_elem.as<unsigned>());
-	k_seg_finish<<<nblocks(nseg, 256), 256, 0, s>>>(nseg, st->seg_head.as<unsigned>(), st->seg_len.as<unsigned>(), st->seg_succ_elem.as<unsigned>(),
-	                                               st->flag.as<unsigned>(), st->segidx.as<unsigned>(), st->succ[0].as<unsigned>(), st->dist[0].as<unsigned long long>());
-	int cur = 0;
-	for (unsigned span = 1; span < nseg; span <<= 1, cur ^= 1)
-		k_seg_jump<<<nblocks(nseg, 256), 256, 0, s>>>(nseg, st->succ[cur].as<unsigned>(), st->dist[cur].as<unsigned long long>(),
-		                                             st->succ[cur ^ 1].as<unsigned>(), st->dist[cur ^ 1].as<unsigned long long>());
-	// segment 0 starts with element 0 (the first '$'), the head of the whole list: dist[0] = new total length
-	unsigned long long total = 0;
-	HIP_TRY(hipMemcpyAsync(&total, st->dist[cur].p, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	size_t Enew = (size_t)total, Epad = (Enew + 31) / 32 * 32 + 64;
-	st->ch_out.ensure(Epad); st->op_out.ensure(Enew * 4 + 16);
-	k_scatter_linear<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), st->op.as<unsigned>(), ne, st->flag.as<unsigned>(), st->segidx.as<unsigned>(),
-	                                                 st->seg_head.as<unsigned>(), st->dist[cur].as<unsigned long long>(), total,
-	                                                 st->ch_out.as<uint8_t>(), st->op_out.as<unsigned>(), st->newidx.as<unsigned>());
-	k_fill_bytes<<<nblocks(Epad - Enew, 256), 256, 0, s>>>(st->ch_out.as<uint8_t>(), (uint8_t)'$', Enew, Epad);
-	k_remap_seps<<<nblocks(c->nchr + 1, 64), 64, 0, s>>>(st->newidx.as<unsigned>(), c->d_sepidx.as<unsigned>(), c->nchr + 1);
-	k_sep_positions<<<nblocks(c->nchr, 64), 64, 0, s>>>(c->d_sepidx.as<unsigned>(), c->nchr, st->op_out.as<unsigned>());
-	HIP_TRY(hipGetLastError());
-	c->stats.dict_checked = 0; c->stats.dict_mismatches = 0;
-	if (getenv("SBL_CHECK_DICTIONARY") && c->dict_keys && k <= 32) {
-		// the reference's own invariant (IndexedSequence::Test) on the stage's final graph, see k_dict_check
+	// ---- T3: copy-back (reference src/blockfinder.cpp:85-95): linearise the list into the dense state arrays ch_out / op_out
+	void copy_back()
+	{
+		be.read_ctr();
+		ne = st->h_ctr[CTR_NE];
+		int cur = 0;
+		total = be.rank_segments(ne, &cur);                             // segment 0 starts with element 0 (the first '$'): the new total length
+		const size_t Enew = (size_t)total, Epad = (Enew + 31) / 32 * 32 + 64;
+		st->newidx.ensure((size_t)ne * 4 + 16);
+		st->ch_out.ensure(Epad); st->op_out.ensure(Enew * 4 + 16);
+		k_scatter_linear<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), st->op.as<unsigned>(), ne, st->flag.as<unsigned>(), st->segidx.as<unsigned>(),
+		                                                 st->seg_head.as<unsigned>(), st->dist[cur].as<unsigned long long>(), total,
+		                                                 st->ch_out.as<uint8_t>(), st->op_out.as<unsigned>(), st->newidx.as<unsigned>());
+		k_fill_bytes<<<nblocks(Epad - Enew, 256), 256, 0, s>>>(st->ch_out.as<uint8_t>(), (uint8_t)'$', Enew, Epad);
+		k_remap_seps<<<nblocks(c->nchr + 1, 64), 64, 0, s>>>(st->newidx.as<unsigned>(), c->d_sepidx.as<unsigned>(), c->nchr + 1);
+		k_sep_positions<<<nblocks(c->nchr, 64), 64, 0, s>>>(c->d_sepidx.as<unsigned>(), c->nchr, st->op_out.as<unsigned>());
+		HIP_TRY(hipGetLastError());
+	}
+
+	// ---- the reference's own invariant (IndexedSequence::Test) on the stage's final graph, see k_dict_check
+	void check_dictionary()
+	{
 		st->scantmp.ensure(64);
 		unsigned long long init[6] = {0, 0, ~0ull, 0, 0, 0}, res[6];
 		HIP_TRY(hipMemcpyAsync(st->scantmp.p, init, sizeof init, hipMemcpyHostToDevice, s));
-		if (getenv("SBL_TEST_CORRUPT_MARK")) {                              // test hook: the check must notice ONE wrong mark among hundreds of millions
+		if (sw.test_corrupt_mark.set) {                                     // test hook: the check must notice ONE wrong mark among hundreds of millions
 			const unsigned wrong = 0;
-			HIP_TRY(hipMemcpyAsync(c->d_bif[0].as<unsigned>() + (c->sepidx[0] + 1 + (size_t)atoll(getenv("SBL_TEST_CORRUPT_MARK"))), &wrong, 4, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(c->d_bif[0].as<unsigned>() + (c->sepidx[0] + 1 + (size_t)sw.test_corrupt_mark.v), &wrong, 4, hipMemcpyHostToDevice, s));
 		}
 		k_dict_check<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), ne, st->newidx.as<unsigned>(), st->ch_out.as<uint8_t>(), total, c->d_bif[0].as<unsigned>(), c->d_bif[1].as<unsigned>(),
 		                                             c->dict_keys, be.nid_, k, st->scantmp.as<unsigned long long>());
 		HIP_TRY(hipMemcpyAsync(res, st->scantmp.p, sizeof res, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		c->stats.dict_checked = res[0]; c->stats.dict_mismatches = res[1];
-		if (getenv("SBL_TRACE")) fprintf(stderr, "[sbl] dictionary invariant (IndexedSequence::Test): %llu windows checked, %llu mismatches\n", res[0], res[1]);
-		if (res[1] && !getenv("SBL_TEST_CORRUPT_MARK")) {
+		if (sw.trace) fprintf(stderr, "[sbl] dictionary invariant (IndexedSequence::Test): %llu windows checked, %llu mismatches\n", res[0], res[1]);
+		if (res[1] && !sw.test_corrupt_mark.set) {
 			char b[256];
 			snprintf(b, sizeof b, "dictionary invariant violated (IndexedSequence::Test): %llu of %llu windows; first at slot %llu strand %llu: stored id %llu, the dictionary says %llu",
 			         res[1], res[0], res[2], res[3], res[4], res[5]);
 			throw SblError{SBL_ERR_INTERNAL, b};
 		}
 	}
-	std::swap(c->d_ch, st->ch_out);
-	std::swap(c->d_op, st->op_out);
-	HIP_TRY(hipMemcpyAsync(c->sepidx.data(), c->d_sepidx.p, (size_t)(c->nchr + 1) * 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipEventRecord(c->ev[5], s));
-	HIP_TRY(hipStreamSynchronize(s));
-	c->nelem = Enew;
 
-	float ms_enum = 0, ms_simp = 0, ms_copy = 0;
-	HIP_TRY(hipEventElapsedTime(&ms_enum, c->ev[2], c->ev[3]));
-	HIP_TRY(hipEventElapsedTime(&ms_simp, c->ev[3], c->ev[4]));
-	HIP_TRY(hipEventElapsedTime(&ms_copy, c->ev[4], c->ev[5]));
-	c->stats.enumerate_ms = ms_enum; c->stats.simplify_ms = ms_simp; c->stats.copyback_ms = ms_copy;
-	c->stats.total_ms = ms_enum + ms_simp + ms_copy;
-	c->stats.bulges = rep.bulges; c->stats.iterations = rep.iterations; c->stats.rounds = rep.rounds; c->stats.replays = rep.replays; c->stats.grow_replays = rep.grow_replays;
-	c->stats.snapshot_ms = be.snapshot_ms; c->stats.reserve_ms = be.reserve_ms; c->stats.commit_ms = be.commit_ms; c->stats.probe_ms = be.probe_ms;
-	c->stats.commit_event_ms = be.commit_event_ms; c->stats.commit_event_launches = be.commit_event_launches;
-	c->stats.verdict_ms = be.ro_ms; c->stats.ro_ranks = be.split_ro() ? c->comm->n : 1;
-	c->stats.executed = rep.executed; c->stats.transactions = rep.transactions; c->stats.chain_transactions = rep.chain_transactions;
-	c->stats.device_bytes = sbl_devbuf_total().load();
+	// ---- the linearised arrays become the state of the context
+	void adopt_state()
+	{
+		std::swap(c->d_ch, st->ch_out);
+		std::swap(c->d_op, st->op_out);
+		HIP_TRY(hipMemcpyAsync(c->sepidx.data(), c->d_sepidx.p, (size_t)(c->nchr + 1) * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipEventRecord(c->ev[5], s));
+		HIP_TRY(hipStreamSynchronize(s));
+		c->nelem = (size_t)total;
+	}
+
+	void fill_stats(const SimplifyReport &rep)
+	{
+		float ms_enum = 0, ms_simp = 0, ms_copy = 0;
+		HIP_TRY(hipEventElapsedTime(&ms_enum, c->ev[2], c->ev[3]));
+		HIP_TRY(hipEventElapsedTime(&ms_simp, c->ev[3], c->ev[4]));
+		HIP_TRY(hipEventElapsedTime(&ms_copy, c->ev[4], c->ev[5]));
+		c->stats.enumerate_ms = ms_enum; c->stats.simplify_ms = ms_simp; c->stats.copyback_ms = ms_copy;
+		c->stats.total_ms = ms_enum + ms_simp + ms_copy;
+		c->stats.bulges = rep.bulges; c->stats.iterations = rep.iterations; c->stats.rounds = rep.rounds; c->stats.replays = rep.replays; c->stats.grow_replays = rep.grow_replays;
+		c->stats.snapshot_ms = be.snapshot_ms; c->stats.reserve_ms = be.reserve_ms; c->stats.commit_ms = be.commit_ms; c->stats.probe_ms = be.probe_ms;
+		c->stats.commit_event_ms = be.commit_event_ms; c->stats.commit_event_launches = be.commit_event_launches;
+		c->stats.verdict_ms = be.ro_ms; c->stats.ro_ranks = be.split_ro() ? c->comm->n : 1;
+		c->stats.executed = rep.executed; c->stats.transactions = rep.transactions; c->stats.chain_transactions = rep.chain_transactions;
+		c->stats.device_bytes = sbl_devbuf_total().load();
+	}
+};
+
+enum { RUN_DONE = 0, RUN_DENSE_FAILED = 1, RUN_RESTART = 2, RUN_TRY_DENSE = 3 };
+static int simplify_run_impl(sbl_ctx *c, const StageSwitches &sw, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges, bool allow_dense, bool optimistic,
+                             bool force_dense = false /* the one-launch path for up to DENSE_SWITCH_MAX_ELEMS elements: the rounds gave up (TryDense) */, bool may_switch = false /* this attempt may give up for it */)
+{
+	hipStream_t s = c->stream;
+	if (!c->simp) {
+		c->simp = new SimplifyState();
+		HIP_TRY(hipHostMalloc((void **)&c->simp->h_ctr, (CTR_COUNT + 16) * 4, hipHostMallocMapped | hipHostMallocCoherent));
+		memset(c->simp->h_ctr, 0, (CTR_COUNT + 16) * 4);
+		if (hipHostGetDevicePointer((void **)&c->simp->d_hctr, c->simp->h_ctr, 0) != hipSuccess) { (void)hipGetLastError(); c->simp->d_hctr = nullptr; }
+	}
+	StageAttempt a(c, sw, k, D, max_iter);
+	DeviceBackend &be = a.be;
+	c->stats = sbl_stage_stats{};
+	HIP_TRY(hipEventRecord(c->ev[2], s));
+	a.setup_graph(allow_dense, force_dense, may_switch);
+	a.size_buffers(optimistic);
+	a.setup_park();
+	if (((D + k + 2u + 126u) >> 6) > 16u) be.g.idx_probe = 0;           // windows of more than 16 blocks: k_probe_idx could serve nobody (every entry walks, as before round 5)
+	be.g.test_flags = sw.test_flags;
+	be.g.tstamp = nullptr; be.g.tslot = 0;
+	be.g.sep = c->d_sepidx.as<unsigned>(); be.g.nsep = c->nchr + 1; be.g.norig = (uint32_t)a.E;
+	be.index_build();
+	if (!a.dense) be.stamps_init();
+	HIP_TRY(hipEventRecord(c->ev[3], s));
+
+	// ---- SimplifyGraph
+	SimplifyReport rep;
+	if (a.dense) {
+		if (!a.run_dense(rep, progress, user)) return RUN_DENSE_FAILED;
+	} else {
+		try { rep = simplify_graph(be, max_iter, a.window, progress, user, a.window_max); }
+		catch (const RestartStage &) { HIP_TRY(hipStreamSynchronize(s)); return RUN_RESTART; }
+		catch (const TryDense &) { HIP_TRY(hipStreamSynchronize(s)); return RUN_TRY_DENSE; }
+	}
+	HIP_TRY(hipEventRecord(c->ev[4], s));
+	if (!a.dense) be.stamps_collect();
+	be.snapshots_collect();
+	if (be.g.bidx && (be.g.test_flags & BT_TF_STATS)) sbl_rounds_stats_report();      // what the block index served
+	if (be.g.bidx && sw.check_index) a.check_index();
+
+	a.copy_back();
+	c->stats.dict_checked = 0; c->stats.dict_mismatches = 0;
+	if (sw.check_dictionary && c->dict_keys && k <= 32) a.check_dictionary();
+	a.adopt_state();
+	a.fill_stats(rep);
 	if (be.prof) sbl_commit_prof_report(be.ts_round);
 	*bulges = rep.bulges;
 	return RUN_DONE;
+}
+
+static void simplify_run_guarded(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges)
+{
+	// the stage's input (d_ch / d_op) is only replaced by the copy-back at the very end, so an attempt that cannot finish -- a one-launch
+	// run out of pool or arena space, an optimistic run that would need a roll-back -- is simply followed by the next one from the same input
+	const StageSwitches sw = read_switches();
+	ProgressFilter pf{progress, user};
+	sbl_progress_fn pfn = progress ? &ProgressFilter::relay : nullptr;
+	// (hint_checkpoints: the previous stage of this context had to be abandoned for an order violation -- inputs that do that once tend to
+	// do it again, and an abandoned attempt costs a whole stage, a checkpoint 2 - 4 %)
+	const bool optimistic = !sw.checkpoints && !c->hint_checkpoints;
+	int r = simplify_run_impl(c, sw, k, D, max_iter, pfn, &pf, bulges, true, optimistic, false, true);
+	if (r == RUN_TRY_DENSE) {
+		if (sw.trace) fprintf(stderr, "[sbl] the ordered rounds have turned into a slow serial chain: the stage runs again through the one-launch path\n");
+		r = simplify_run_impl(c, sw, k, D, max_iter, pfn, &pf, bulges, true, optimistic, true, false);
+		c->stats.replays++;                                               // the abandoned attempt
+	}
+	if (r == RUN_DENSE_FAILED) r = simplify_run_impl(c, sw, k, D, max_iter, pfn, &pf, bulges, false, optimistic);
+	if (r == RUN_RESTART) {
+		if (sw.trace) fprintf(stderr, "[sbl] optimistic attempt abandoned: the stage runs again with iteration checkpoints (element slack hint %zu, node capacity hint %zu)\n", c->hint_elem_slack, c->hint_cap_n);
+		(void)simplify_run_impl(c, sw, k, D, max_iter, pfn, &pf, bulges, false, false);
+		c->stats.replays++;                                               // the abandoned attempt
+		c->hint_checkpoints = c->stats.replays > c->stats.grow_replays + 1;      // order violations (not just a pool that was too small): the next stage starts with checkpoints
+	} else if (!optimistic && r == RUN_DONE && c->stats.replays == c->stats.grow_replays) c->hint_checkpoints = false;      // a checkpointed stage that never rolled back
+}
+void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges)
+{
+	// With several GPUs on one job every snapshot and every probe of the stage is a collective (allgather_shares): a rank that leaves
+	// the stage with an error anywhere -- an allocation that fails, a HIP error, a check that throws -- must release the peers that
+	// would wait for it there (the deterministic RestartStage is thrown on all ranks alike and never gets here).
+	if (!c->comm) { simplify_run_guarded(c, k, D, max_iter, progress, user, bulges); return; }
+	try { simplify_run_guarded(c, k, D, max_iter, progress, user, bulges); }
+	catch (...) { c->comm->abort_peers(); throw; }
 }

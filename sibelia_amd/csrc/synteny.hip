@@ -295,8 +295,6 @@ struct Synteny {
 		HIP_TRY(hipMemcpyAsync(bpool.data(), d_bpool.p, words * 4, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 	}
-	void batch_release() { d_bdesc.release(); d_bheads.release(); d_bpool.release(); }
-	~Synteny() { batch_release(); }
 	// the negative list is reported per sequence in descending element order (sbl_enumerate: each chromosome's run reversed)
 	void tiny_result(const unsigned *head, const unsigned *inst0, const unsigned *inst1, uint32_t *bif_count, const sbl_inst **inst, uint64_t *ninst)
 	{
@@ -535,7 +533,6 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 				blockCount++;
 			}
 		}
-		sy.batch_release();
 		std::sort(c->blocks.begin(), c->blocks.end(), [](const sbl_block &a, const sbl_block &b) { return std::make_pair(a.chr, a.start) < std::make_pair(b.chr, b.start); });
 		if (blocks) *blocks = c->blocks.data();
 		if (n) *n = c->blocks.size();

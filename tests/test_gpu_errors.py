@@ -142,3 +142,48 @@ def test_a_failing_virtual_rank_releases_its_peers(monkeypatch):
         monkeypatch.delenv("SBL_TEST_FAIL_RANK")
     finally:
         f.close()
+
+
+def test_a_destroyed_context_gives_back_every_device_byte(monkeypatch):
+    """device_bytes of the stage statistics is the process-wide total of device buffer bytes.  Context A (ordered rounds, park stream,
+    arenas) runs its stage twice from a saved state, so that its grow-only buffers have reached their size; context B then lives and
+    dies beside it -- a k <= 32 stage on the rounds, a k = 40 stage through the fingerprints and through the rank doubling, block
+    generation, blocks_sequences -- and A's third run must report exactly the total of its second: whatever B held is back."""
+    from sibelia_amd import BlockFinder, workloads as W
+    a = BlockFinder(W.gen_strains(L0=20_000, n=4, seed=17, inv_min=1000, inv_max=3000), device=0)      # 80 kbp: above the one-launch limit
+    b = None
+    try:
+        a.save_state()
+        want = a.simplify_stage(25, 150, 4)
+        assert a.stats()["rounds"] > 0, "context A was expected to take the ordered rounds"
+        a.restore_state()
+        assert a.simplify_stage(25, 150, 4) == want
+        held = int(a.stats()["device_bytes"])
+        assert held > 0
+
+        b = BlockFinder(W.gen_strains(L0=8_000, n=3, seed=23, inv_min=400, inv_max=2000) + W.random_dna(2_000, 1, seed=24), device=0)
+        b.save_state()
+        monkeypatch.setenv("SBL_NO_DENSE_PATH", "1")
+        b.simplify_stage(25, 150, 4)
+        monkeypatch.delenv("SBL_NO_DENSE_PATH")
+        assert b.stats()["rounds"] > 0
+        assert int(b.stats()["device_bytes"]) > held
+        b.restore_state()
+        b.simplify_stage(40, 150, 4)
+        assert int(b.stats()["longk_path"]) == 1
+        b.restore_state()
+        monkeypatch.setenv("SBL_LONGK_DOUBLING", "1")
+        b.simplify_stage(40, 150, 4)
+        monkeypatch.delenv("SBL_LONGK_DOUBLING")
+        assert int(b.stats()["longk_path"]) == 2
+        assert len(b.generate_blocks(25, 25, 500)) > 0
+        assert len(b.blocks_sequences()) > 0
+        b.close()
+
+        a.restore_state()
+        assert a.simplify_stage(25, 150, 4) == want
+        assert int(a.stats()["device_bytes"]) == held, "device bytes held after context B was destroyed: %d, before it was created: %d" % (int(a.stats()["device_bytes"]), held)
+    finally:
+        if b is not None:
+            b.close()
+        a.close()

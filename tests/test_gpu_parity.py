@@ -629,3 +629,40 @@ def test_long_k_stage_on_random_records_takes_the_active_set_path():
         assert bf.simplify_stage(k, D, 4) == orc.simplify_stage(k, D, 4)
         (sa, pa), (sb, pb) = bf.state(), orc.state()
         assert sa == sb and all(np.array_equal(x, y) for x, y in zip(pa, pb))
+
+
+def _copy_back_inputs():
+    """Two records of 300 random bases that differ by nothing / one insertion / a substitution, an insertion, a deletion and another
+    insertion 60 - 70 bases apart: the stage (15, 50) removes 0 / 1 / 4 bulges (asserted below), so the list the copy-back linearises
+    is one segment of consecutive slots (no pointer-jumping pass) / the two or three segments one collapse leaves / at least four."""
+    from sibelia_amd import workloads as W
+    base = W.random_dna(300, 1, seed=91)[0]
+    sub = base[:40] + (b"A" if base[40:41] != b"A" else b"C") + base[41:]
+    return {"none": ([base, base], 0),
+            "one": ([base, base[:150] + b"ACG" + base[150:]], 1),
+            "several": ([base, sub[:100] + b"TTGA" + base[100:170] + base[176:240] + b"G" + base[240:]], 4)}
+
+
+@pytest.mark.parametrize("rounds", [False, True], ids=["one_launch", "ordered_rounds"])
+@pytest.mark.parametrize("shape", ["none", "one", "several"])
+def test_copy_back_after_zero_one_and_several_collapses(shape, rounds, monkeypatch):
+    """sequences and original positions after the stage against the oracle, through the one-launch path and (SBL_NO_DENSE_PATH=1)
+    through the ordered rounds: both end in the same copy-back (segment ranking by pointer jumping, then the scatter)"""
+    from oracle.oracle import Oracle
+    seqs, bulges = _copy_back_inputs()[shape]
+    if rounds:
+        monkeypatch.setenv("SBL_NO_DENSE_PATH", "1")
+    bf, orc = _bf(seqs), Oracle(seqs)
+    try:
+        assert orc.simplify_stage(15, 50, 4) == bulges
+        assert bf.simplify_stage(15, 50, 4) == bulges
+        # which path ran: the one-launch path counts no rounds; the ordered rounds count one per window, and a window needs a pending id
+        # (with no bulge anywhere the first snapshot leaves none pending: no round, but the same copy-back)
+        if not rounds:
+            assert bf.stats()["rounds"] == 0
+        elif bulges:
+            assert bf.stats()["rounds"] > 0
+        (sa, pa), (sb, pb) = bf.state(), orc.state()
+        assert sa == sb and all(np.array_equal(x, y) for x, y in zip(pa, pb))
+    finally:
+        bf.close()
