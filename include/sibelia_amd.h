@@ -186,6 +186,43 @@ sbl_status sbl_blocks_gff(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, con
 sbl_status sbl_blocks_coords(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
                              const char **text, uint64_t *len);
 
+/* Postprocessor::ImproveBlockBoundaries (src/postprocessor.cpp:156-348), what the reference's main runs under --correctboundaries after
+ * GlueStripes (src/sibelia.cpp:198-225, :295-298), on the context's CURRENT block list (after sbl_postprocess); chromosomes
+ * 0 .. n_reference_chr - 1 are the reference set (the records of the first input file).  R = min(min_block_size, 1024)
+ * (MAX_CORRECTION_RANGE, src/postprocessor.cpp:15).  The list is sorted by |id| with the reference's unstable sort (the same libstdc++
+ * call on the same element order) and REPLACED: for every id with exactly one instance inside the reference set and one outside it the
+ * reference instance comes first, both change sign if it lay on the negative strand, and both are re-cut (UpdateBlockBoundaries,
+ * :279-293) by two local alignments -- start windows and end windows (DetermineLeft / RightProbableBoundaries :199-238,
+ * GetBoundariesSequence :240-255), taken from the ORIGINAL records on the device -- run in batches by csrc/boundary_align.hip.
+ * Groups are corrected in the reference's order wherever the order can matter (DESIGN.md "Boundary correction").  The three texts of
+ * sbl_postprocess are rendered again; sbl_blocks_sequences / _gff / _coords with blocks == NULL then see the corrected list.
+ * Where the reference is undefined: a block with start < R that has a previous block (start - R wraps as size_t, :209) is given the
+ * signed result here (the window starts behind the previous block); R == 0 is SBL_ERR_BAD_ARG, as are a missing list or records and
+ * n_reference_chr == 0 or >= sbl_nchr(ctx).  Windows are cut to their record.  A list is missing until sbl_generate_blocks has run; an
+ * EMPTY list is a list: nothing is corrected and the texts are rendered, as the reference's loop runs over nothing (:317-348). */
+sbl_status sbl_correct_boundaries(sbl_ctx *ctx, uint32_t min_block_size, uint32_t n_reference_chr, const char *const *names,
+                                  const sbl_block **blocks, uint64_t *n,
+                                  const char **blocks_coords, const char **genomes_permutations, const char **coverage_report);
+
+/* The bare batched alignment behind it: Postprocessor::LocalAlignment (src/postprocessor.cpp:257-277) = SeqAn 1.3.1's
+ * localAlignment(align, Score<int>(25, -75, -75)) (src/include/seqan/align/align_local_dynprog.h:229-336, :545-648, :718-751) for ndesc
+ * pairs of byte strings of at most SBL_ALIGN_MAX_LEN characters each (bytes are compared as they are: N == N).
+ * out_coords: 4 values per pair -- clipped begin and end position of a, then of b.  An empty string or a best score of 0: (0, na, 0, nb). */
+#define SBL_ALIGN_MAX_LEN 2047
+typedef struct { const uint8_t *a; const uint8_t *b; uint32_t na, nb; } sbl_align_desc;
+sbl_status sbl_align_windows(sbl_ctx *ctx, uint64_t ndesc, const sbl_align_desc *descriptors, uint32_t *out_coords);
+
+/* Counters of the last sbl_correct_boundaries (or sbl_align_windows: groups = levels = 0). */
+typedef struct {
+	uint64_t groups;                 /* id groups that were corrected */
+	uint64_t alignments;             /* local alignments run (2 per group) */
+	uint64_t levels;                 /* dependency levels: batches in which the groups were aligned */
+	uint64_t launches;               /* kernel launches (a level whose trace codes exceed the cap takes several) */
+	uint64_t cells;                  /* matrix cells filled */
+	double kernel_ms;                /* device time of the launches (event pairs) */
+} sbl_correct_stats_t;
+sbl_status sbl_correct_stats(const sbl_ctx *ctx, sbl_correct_stats_t *out);
+
 /* Replaces BlockFinder::SerializeGraph (src/serialization.cpp:112-138; defined for records of at least k + 1 characters -- the
  * reference walks off the end of a shorter one): DOT text of the UNcondensed de Bruijn graph of the
  * current state, one line per (k+1)-window, generated on the device (a debugging dump: main only reaches it with -q and never

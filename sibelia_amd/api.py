@@ -26,7 +26,10 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_save_state", "sbl_restore_state", "sbl_load_fasta", "sbl_record_name", "sbl_kmer_hashes", "sbl_generate_blocks", "sbl_postprocess", "sbl_serialize_graph",
            "sbl_set_tempfile_mode", "sbl_rand_advance", "sbl_shard_layout", "sbl_shard_exchange_plan", "sbl_glue_stripes", "sbl_comm_unique_id", "sbl_comm_attach_rccl", "sbl_comm_attach_local", "sbl_comm_detach",
            "sbl_longk_slices", "sbl_longk_value_bounds", "sbl_longk_owner", "sbl_longk_halo_plan",
-           "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords"]
+           "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords",
+           "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats"]
+
+ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
 
 class StageStats(C.Structure):
@@ -44,6 +47,15 @@ class StageStats(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class CorrectStats(C.Structure):
+    _fields_ = [("groups", C.c_uint64), ("alignments", C.c_uint64), ("levels", C.c_uint64), ("launches", C.c_uint64), ("cells", C.c_uint64),
+                ("kernel_ms", C.c_double)]
+
+
+class AlignDesc(C.Structure):
+    _fields_ = [("a", C.c_char_p), ("b", C.c_char_p), ("na", C.c_uint32), ("nb", C.c_uint32)]
 
 
 class SibeliaError(RuntimeError):
@@ -91,6 +103,10 @@ def load_library():
         for fn in (L.sbl_blocks_sequences, L.sbl_blocks_gff, L.sbl_blocks_coords):
             fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_blocks_sequences_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_correct_boundaries.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
+        L.sbl_align_windows.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(AlignDesc), C.c_void_p]
+        L.sbl_correct_stats.argtypes = [C.c_void_p, C.POINTER(CorrectStats)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -222,6 +238,38 @@ class BlockFinder:
         t = [C.c_char_p() for _ in range(3)]
         self._check(self.L.sbl_postprocess(self.h, int(glue), nm, C.byref(b), C.byref(n), C.byref(t[0]), C.byref(t[1]), C.byref(t[2])), "sbl_postprocess")
         return _view(b.value, n.value, formats.BLOCK_DTYPE), [x.value for x in t]
+
+    def correct_boundaries(self, min_block_size: int, n_reference_chr: int, names: Optional[Sequence[str]] = None):
+        """Postprocessor::ImproveBlockBoundaries (reference src/postprocessor.cpp:156-348; --correctboundaries) on the blocks of the last
+        postprocess: records 0 .. n_reference_chr - 1 are the reference set.  Replaces the context's list; returns it and the three
+        texts of postprocess rendered again.  The alignments run in batches on the device (csrc/boundary_align.hip)."""
+        nm = None
+        if names is not None:
+            if len(names) != self.L.sbl_nchr(self.h):
+                raise ValueError("correct_boundaries: %d names for %d records" % (len(names), self.L.sbl_nchr(self.h)))
+            nm = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        b, n = C.c_void_p(), C.c_uint64()
+        t = [C.c_char_p() for _ in range(3)]
+        self._check(self.L.sbl_correct_boundaries(self.h, min_block_size, n_reference_chr, nm, C.byref(b), C.byref(n),
+                                                  C.byref(t[0]), C.byref(t[1]), C.byref(t[2])), "sbl_correct_boundaries")
+        return _view(b.value, n.value, formats.BLOCK_DTYPE), [x.value for x in t]
+
+    def align_windows(self, pairs: Sequence[Tuple[bytes, bytes]]) -> np.ndarray:
+        """The batched local alignment behind correct_boundaries (Postprocessor::LocalAlignment, reference src/postprocessor.cpp:257-277)
+        for pairs of byte strings of at most ALIGN_MAX_LEN characters: one row (a begin, a end, b begin, b end) per pair."""
+        pairs = [(bytes(a), bytes(b)) for a, b in pairs]
+        desc = (AlignDesc * max(1, len(pairs)))()
+        for d, (a, b) in zip(desc, pairs):
+            d.a, d.b, d.na, d.nb = a, b, len(a), len(b)
+        out = np.zeros((len(pairs), 4), dtype=np.uint32)
+        self._check(self.L.sbl_align_windows(self.h, len(pairs), desc, out.ctypes.data), "sbl_align_windows")
+        return out
+
+    def correct_stats(self) -> dict:
+        """Counters of the last correct_boundaries / align_windows: groups, alignments, levels, launches, cells, kernel_ms."""
+        s = CorrectStats()
+        self._check(self.L.sbl_correct_stats(self.h, C.byref(s)), "sbl_correct_stats")
+        return {f: getattr(s, f) for f, _ in s._fields_}
 
     def _block_report(self, fn, what, blocks, names) -> bytes:
         nm = None

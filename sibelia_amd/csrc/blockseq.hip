@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "sbl_ctx.h"
+#include "sbl_dna.h"
 
 namespace {
 
@@ -52,11 +53,6 @@ __device__ inline u64 complement8(u64 x)
 	const u64 at = (zero8(f ^ 0x4141414141414141ull) | zero8(f ^ 0x5454545454545454ull)) >> 7;
 	const u64 cg = (zero8(f ^ 0x4343434343434343ull) | zero8(f ^ 0x4747474747474747ull)) >> 7;
 	return x ^ (at * 0x15) ^ (cg * 0x04);                               // 'A' ^ 'T' = 0x15, 'C' ^ 'G' = 0x04
-}
-__device__ inline unsigned char complement1(unsigned char c)
-{
-	const unsigned char f = c & 0xDF;
-	return f == 'A' || f == 'T' ? c ^ 0x15 : f == 'C' || f == 'G' ? c ^ 0x04 : c;
 }
 
 struct B16 { u64 lo, hi; };

@@ -273,6 +273,14 @@ Records records_of(const sbl_ctx *c, const char *const *names)
 // std::sort(..., compareById) / GroupBy(blockList, compareById) of the reference's writers: the same libstdc++ call on the same element order
 void sbl_sort_by_id(std::vector<sbl_block> &v) { (void)group_by(v, ById()); }
 
+void sbl_render_reports(sbl_ctx *c, const char *const *names)
+{
+	const Records r = records_of(c, names);
+	c->report[0] = blocks_coords(c->blocks, r);
+	c->report[1] = permutations(c->blocks, r);
+	c->report[2] = coverage_report(c->blocks, r);
+}
+
 extern "C" sbl_status sbl_blocks_gff(sbl_ctx *c, const sbl_block *blocks, uint64_t n, const char *const *names, const char **text, uint64_t *len)
 {
 	return guarded(c, [&] {
@@ -301,15 +309,8 @@ extern "C" sbl_status sbl_postprocess(sbl_ctx *c, int glue, const char *const *n
 {
 	return guarded(c, [&] {
 		SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1, SBL_ERR_BAD_ARG, "no records loaded");
-		Records r;
-		for (uint32_t i = 0; i < c->nchr; i++) {
-			r.size.push_back(c->orig_sepidx[i + 1] - c->orig_sepidx[i] - 1);
-			r.name.push_back(names ? std::string(names[i]) : i < c->fa_names.size() ? c->fa_names[i] : std::string());
-		}
 		if (glue) glue_stripes(c->blocks, c->nchr);
-		c->report[0] = blocks_coords(c->blocks, r);
-		c->report[1] = permutations(c->blocks, r);
-		c->report[2] = coverage_report(c->blocks, r);
+		sbl_render_reports(c, names);
 		if (blocks) *blocks = c->blocks.data();
 		if (n) *n = c->blocks.size();
 		if (coords) *coords = c->report[0].c_str();

@@ -80,6 +80,7 @@ struct sbl_ctx {
 	std::vector<sbl_edge> edges;
 	std::vector<uint64_t> h_hashes;
 	std::vector<sbl_block> blocks;
+	bool have_blocks = false;            // sbl_generate_blocks has run: an EMPTY list is a list too
 	std::string graph_text;              // sbl_serialize_graph
 	std::string report[3];               // sbl_postprocess: blocks_coords.txt, genomes_permutations.txt, coverage_report.txt
 	std::string gff_text, coords_text;   // sbl_blocks_gff, sbl_blocks_coords
@@ -93,6 +94,10 @@ struct sbl_ctx {
 	bool h_bs_pinned = true;
 	uint64_t bs_len = 0;
 	double bs_kernel_ms = 0, bs_copy_ms = 0;   // event pairs around the kernel / the device-to-host copy of the last call
+
+	// sbl_correct_boundaries / sbl_align_windows (boundary_align.hip): descriptors, trace codes, results, caller-supplied strings
+	DevBuf d_ba_desc, d_ba_codes, d_ba_out, d_ba_seq;
+	sbl_correct_stats_t correct_stats{};
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;
@@ -151,6 +156,7 @@ void sbl_longk_free(sbl_ctx *c);
 bool sbl_run_enumeration_longk_fp(sbl_ctx *c, uint32_t k, size_t elem_capacity);   // k > 32: window fingerprints + bucketed table + exact verification; false = a verification failed, run the doubling
 void sbl_longk_fp_free(sbl_ctx *c);
 // implemented in postprocess.hip
+void sbl_render_reports(sbl_ctx *c, const char *const *names);   // report[0..2] of c->blocks (blocks_coords.txt, genomes_permutations.txt, coverage_report.txt)
 void sbl_sort_by_id(std::vector<sbl_block> &v);   // the one unstable sort by |id| the reference's writers apply to a copy of the list
 // implemented in blockseq.hip
 void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n);   // a caller's block list against the loaded records (throws SBL_ERR_BAD_ARG)

@@ -479,6 +479,7 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 		}
 		std::sort(group.begin(), group.end(), [](const std::pair<size_t, size_t> &a, const std::pair<size_t, size_t> &b) { return a.second - a.first > b.second - b.first; });
 		c->blocks.clear();
+		c->have_blocks = true;
 		int blockCount = 1;
 		std::vector<BEdge> now;
 		std::vector<uint32_t> occur(c->nchr);

@@ -132,6 +132,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lastk", type=_greater_than(1), default=None, help="Value of K used for the synteny blocks inferring.")
     p.add_argument("--nopostprocess", action="store_true", help="Do not perform postprocessing (stripe gluing).")
     p.add_argument("--noblocks", action="store_true", help="Do not compute synteny blocks")
+    p.add_argument("--correctboundaries", action="store_true", help="Correct boundaries of unique synteny blocks.")
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
     return p
@@ -142,6 +143,8 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
     opt = build_parser().parse_args(list(argv))
     if (opt.parameters is None) == (opt.stagefile is None):
         raise PipelineError("exactly one of -s (--parameters) and -k (--stagefile) is required")
+    if opt.correctboundaries and len(opt.filenames) != 2:      # src/sibelia.cpp:203-206, before any file is read
+        raise PipelineError("In correction mode only two FASTA files are acceptable")
     return opt
 
 
@@ -259,7 +262,7 @@ def _fasta_error(path: str) -> Optional[str]:
 
 
 def load_input(filenames: Sequence[str], device: int = -1):
-    """-> (finder, names).  One file goes through the FASTA loader on the device; several are read on the host and appended to one
+    """-> (finder, names, records in the first file (None for a single file)).  One file goes through the FASTA loader on the device; several are read on the host and appended to one
     record list, as the reference does (src/sibelia.cpp:209-225)."""
     from . import workloads
     from .api import BlockFinder, SibeliaError
@@ -269,8 +272,8 @@ def load_input(filenames: Sequence[str], device: int = -1):
     try:
         if len(filenames) == 1:
             bf = BlockFinder.from_fasta(filenames[0], device=device)
-            return bf, None
-        names, seqs = [], []
+            return bf, None, None
+        names, seqs, nfirst = [], [], None
         for f in filenames:
             try:
                 n, s = workloads.read_fasta(f)
@@ -278,10 +281,12 @@ def load_input(filenames: Sequence[str], device: int = -1):
                 raise PipelineError(_fasta_error(f) or "parse error in %s: %s" % (f, e))
             names += n
             seqs += s
+            if nfirst is None:
+                nfirst = len(n)                 # referenceChrId: the records of the first file (src/sibelia.cpp:218-224)
         if sum(len(s) for s in seqs) > MAX_INPUT_SIZE:
             raise PipelineError("Input is larger than 1 GB, can't proceed")
         bf = BlockFinder(seqs, device=device)
-        return bf, names
+        return bf, names, nfirst
     except SibeliaError as e:
         text = str(e)
         m = re.search(r"\((.*)\)\s*$", text, re.S)
@@ -296,7 +301,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
     """The reference's main (src/sibelia.cpp:186-345).  `write` receives the standard output as it is produced; `outdir_exists`
     (default: look) is whether the output directory is there before the run.  Raises PipelineError for what main reports as an error."""
     from . import formats
-    from .api import glue_stripes
+    from .api import SibeliaError, glue_stripes
     opt = parse_args(argv)
     stages = stages_of(opt)
     if outdir_exists is None:
@@ -309,7 +314,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
             write(s)
 
     bar = ProgressBar(say)
-    bf, names = load_input(opt.filenames, opt.device)
+    bf, names, nfirst = load_input(opt.filenames, opt.device)
     files: Dict[str, bytes] = {}
     try:
         if not opt.inram:
@@ -334,6 +339,11 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
         if not opt.noblocks:
             bf.GenerateSyntenyBlocks(last_k, trim_k, opt.minblocksize, opt.sharedonly)
             blocks, (coords, perms, coverage) = bf.postprocess(names, glue=not opt.nopostprocess)
+            if opt.correctboundaries:           # Postprocessor::ImproveBlockBoundaries (src/sibelia.cpp:295-298), before any writer
+                try:
+                    blocks, (coords, perms, coverage) = bf.correct_boundaries(opt.minblocksize, nfirst, names)
+                except SibeliaError as e:
+                    raise PipelineError(str(e))
             history[-1] = blocks
             writer, ext = (bf.blocks_gff, ".gff") if opt.gff else (bf.blocks_coords, ".txt")
             if opt.allstages:
