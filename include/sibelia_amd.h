@@ -130,6 +130,8 @@ sbl_status sbl_simplify_stage(sbl_ctx *ctx, uint32_t k, uint32_t min_branch_size
  * Borrowed pointers, valid until the next mutating call. */
 sbl_status sbl_get_state(sbl_ctx *ctx, uint32_t chr, const uint8_t **seq, const uint32_t **orig_pos, uint64_t *len);
 uint32_t sbl_nchr(const sbl_ctx *ctx);
+/* Length of record chr as loaded (sbl_load or sbl_load_fasta; simplification does not change it); 0 for a record that does not exist. */
+uint64_t sbl_record_size(const sbl_ctx *ctx, uint32_t chr);
 
 /* Replaces BlockFinder::ListEdges on a fresh index at k (src/serialization.cpp:56-86), the
  * observation channel behind SerializeCondensedGraph (src/serialization.cpp:88-110). */
@@ -168,7 +170,8 @@ sbl_status sbl_glue_stripes(sbl_block *blocks, uint64_t *n, uint32_t nchr);
  * (1-based; a reverse instance is reported from its far end, as in blocks_coords.txt), the end - start bases in lines of 80 and a
  * line feed.  Reverse instances are spelled downwards through the reference's complement table (src/dnasequence.cpp:11-28):
  * ACGT / acgt swapped, every other character -- ambiguity codes included -- unchanged.  The text is generated by a kernel
- * (csrc/blockseq.hip) and comes back through a pinned buffer of the context.  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
+ * (csrc/blockseq.hip) and comes back through a pinned buffer of the context, valid until the next sbl_blocks_sequences,
+ * sbl_align_pairs or sbl_align_unique_blocks (they share the buffer).  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
  * end < start, end beyond the record, id == 0, no records loaded.
  * sbl_blocks_sequences_times: device time of the last call's kernel and of its device-to-host copy (event pairs). */
 sbl_status sbl_blocks_sequences(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
@@ -222,6 +225,58 @@ typedef struct {
 	double kernel_ms;                /* device time of the launches (event pairs) */
 } sbl_correct_stats_t;
 sbl_status sbl_correct_stats(const sbl_ctx *ctx, sbl_correct_stats_t *out);
+
+/* Base-by-base alignment of block instances (csrc/block_align.hip): what the reference's comparison tool C-Sibelia.py does with the
+ * blocks of a two-genome run by handing each one to an external LAGAN process (src/csibelia/C-Sibelia.py:274-309).  LAGAN is an anchored
+ * heuristic; the alignment here is defined by this project: the GLOBAL alignment of a (n bytes) and b (m bytes) with
+ * match +25, mismatch -75, gap column -75 in 32-bit arithmetic, bytes compared as they are, filled from the ends
+ *   S[n][m] = 0, S[i][m] = -75 (n - i), S[n][j] = -75 (m - j), S[i][j] = max(S[i+1][j+1] + (a[i] == b[j] ? 25 : -75), S[i+1][j] - 75, S[i][j+1] - 75)
+ * and traced forward from (0, 0): the diagonal step if it attains the maximum, else the i step (a[i] over '-'), else the j step.
+ * Only a band lo - w <= j - i <= hi + w (lo = min(0, m - n), hi = max(0, m - n)) is filled; a banded score strictly greater than
+ * U(w) = 25 (min(n, m) - (w + 1)) - 75 (|m - n| + 2 (w + 1)) proves that score and trace equal the unbanded ones, otherwise w is doubled
+ * and the pair runs again, until the band covers the matrix.  The first w is 64 (SBL_TEST_GALIGN_W0: test switch; results do not
+ * depend on it, band_w and passes do).
+ * A pair is SKIPPED -- status SBL_GALIGN_SKIPPED, no score, no runs, no rows; never an error, never a partial result -- when the trace
+ * codes (2 bits per band cell) at the w it has reached exceed the per-alignment cap (8 GiB; SBL_TEST_GALIGN_CAP_KB: test switch), when
+ * the band's score diagonal no longer fits the LDS (more than 12288 band offsets) or when 75 (n + m) does not fit the 32-bit scores
+ * (n + m >= 2^23).  A batch is split so that the codes of one launch stay below 32 GiB
+ * (SBL_TEST_GALIGN_TOTAL_KB: test switch).
+ *
+ * sbl_pair_desc: two half-open ranges of the ORIGINAL records on the device; rev: read downwards through the complement table.
+ * sbl_align_run: `len` columns of one kind -- '=' equal, 'X' unequal, 'I' a[i] over '-', 'D' '-' over b[j].
+ * sbl_pair_result: runs[first_run, first_run + nruns); the gapped row of a is rows[row_off, row_off + row_len), the row of b follows it
+ * directly (the same length).  The rows are spelled on the device from the runs and the records and come back through the context's
+ * pinned buffer.  n == 0 or m == 0 is legal: all gaps.  Everything returned is owned by the ctx and valid until the next call.
+ * That pinned buffer is the ONE sbl_blocks_sequences hands its text out of: `rows` is overwritten by the next sbl_blocks_sequences as
+ * well as by the next sbl_align_* call, and the text of an earlier sbl_blocks_sequences does not survive an sbl_align_* call.  A caller
+ * that needs both copies the first before it asks for the second.
+ * SBL_ERR_BAD_ARG: a range outside its record, end < start, a record that does not exist, no records loaded. */
+#define SBL_GALIGN_OK 0
+#define SBL_GALIGN_SKIPPED 1
+typedef struct { uint32_t chr_a; uint64_t start_a, end_a; uint32_t rev_a; uint32_t chr_b; uint64_t start_b, end_b; uint32_t rev_b; } sbl_pair_desc;
+typedef struct { uint32_t op, len; } sbl_align_run;
+typedef struct { uint32_t status; int32_t score; uint32_t band_w, passes; uint64_t first_run, nruns, row_off, row_len; } sbl_pair_result;
+sbl_status sbl_align_pairs(sbl_ctx *ctx, uint64_t npairs, const sbl_pair_desc *desc, const sbl_pair_result **res,
+                           const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len);
+
+/* The pairs C-Sibelia.py aligns (determine_unique_block, src/csibelia/C-Sibelia.py:314-323) out of the context's CURRENT block list
+ * (after sbl_postprocess / sbl_correct_boundaries): the ids with exactly two instances, one on records 0 .. n_reference_chr - 1 and
+ * one outside them, both at least min_block_size long.  The reference instance is a; both are read on the strand the list reports.
+ * Results in ascending block id, together with the ids and the descriptors that were aligned.  An empty list is a list (n = 0); a
+ * missing list or records and n_reference_chr == 0 or >= sbl_nchr(ctx) are SBL_ERR_BAD_ARG. */
+sbl_status sbl_align_unique_blocks(sbl_ctx *ctx, uint32_t min_block_size, uint32_t n_reference_chr, const int32_t **ids,
+                                   const sbl_pair_desc **desc, uint64_t *n, const sbl_pair_result **res,
+                                   const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len);
+
+/* Counters of the last sbl_align_pairs / sbl_align_unique_blocks. */
+typedef struct {
+	uint64_t pairs, skipped;         /* pairs given; ... of which skipped */
+	uint64_t passes;                 /* alignments run, band doublings included */
+	uint64_t launches;               /* launches of the alignment kernel (one per band class and memory chunk of a pass) */
+	uint64_t cells;                  /* band slots swept: (n + m + 1) * ceil(band offsets / 2) per pass of a pair */
+	double kernel_ms, spell_ms;      /* device time of the alignment launches / of the kernel that spells the rows (event pairs) */
+} sbl_align_stats_t;
+sbl_status sbl_align_stats(const sbl_ctx *ctx, sbl_align_stats_t *out);
 
 /* Replaces BlockFinder::SerializeGraph (src/serialization.cpp:112-138; defined for records of at least k + 1 characters -- the
  * reference walks off the end of a shorter one): DOT text of the UNcondensed de Bruijn graph of the

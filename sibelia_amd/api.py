@@ -27,7 +27,8 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_set_tempfile_mode", "sbl_rand_advance", "sbl_shard_layout", "sbl_shard_exchange_plan", "sbl_glue_stripes", "sbl_comm_unique_id", "sbl_comm_attach_rccl", "sbl_comm_attach_local", "sbl_comm_detach",
            "sbl_longk_slices", "sbl_longk_value_bounds", "sbl_longk_owner", "sbl_longk_halo_plan",
            "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords",
-           "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats"]
+           "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
+           "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -56,6 +57,40 @@ class CorrectStats(C.Structure):
 
 class AlignDesc(C.Structure):
     _fields_ = [("a", C.c_char_p), ("b", C.c_char_p), ("na", C.c_uint32), ("nb", C.c_uint32)]
+
+
+GALIGN_OK, GALIGN_SKIPPED = 0, 1                   # SBL_GALIGN_OK, SBL_GALIGN_SKIPPED
+
+
+class PairDesc(C.Structure):
+    _fields_ = [("chr_a", C.c_uint32), ("start_a", C.c_uint64), ("end_a", C.c_uint64), ("rev_a", C.c_uint32),
+                ("chr_b", C.c_uint32), ("start_b", C.c_uint64), ("end_b", C.c_uint64), ("rev_b", C.c_uint32)]
+
+
+PAIR_RESULT_DTYPE = np.dtype([("status", "<u4"), ("score", "<i4"), ("band_w", "<u4"), ("passes", "<u4"),
+                              ("first_run", "<u8"), ("nruns", "<u8"), ("row_off", "<u8"), ("row_len", "<u8")])
+ALIGN_RUN_DTYPE = np.dtype([("op", "<u4"), ("len", "<u4")])
+
+
+class AlignStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("skipped", C.c_uint64), ("passes", C.c_uint64), ("launches", C.c_uint64), ("cells", C.c_uint64),
+                ("kernel_ms", C.c_double), ("spell_ms", C.c_double)]
+
+
+class PairAlignment:
+    """One sbl_pair_result: status (GALIGN_OK / GALIGN_SKIPPED), score, band_w, passes, runs [(op, length)] with op in '=XID', and the
+    two gapped rows.  A skipped pair has score None, no runs and no rows."""
+    __slots__ = ("status", "score", "band_w", "passes", "runs", "row_a", "row_b")
+
+    def __init__(self, r, runs, rows):
+        self.status, self.band_w, self.passes = int(r["status"]), int(r["band_w"]), int(r["passes"])
+        if self.status == GALIGN_OK:
+            at, n, off, ln = int(r["first_run"]), int(r["nruns"]), int(r["row_off"]), int(r["row_len"])
+            self.score = int(r["score"])
+            self.runs = [(chr(int(o)), int(l)) for o, l in runs[at:at + n]]
+            self.row_a, self.row_b = rows[off:off + ln], rows[off + ln:off + 2 * ln]
+        else:
+            self.score, self.runs, self.row_a, self.row_b = None, [], b"", b""
 
 
 class SibeliaError(RuntimeError):
@@ -95,6 +130,8 @@ def load_library():
         L.sbl_load_fasta.argtypes = [C.c_void_p, C.c_char_p]
         L.sbl_record_name.argtypes = [C.c_void_p, C.c_uint32]
         L.sbl_record_name.restype = C.c_char_p
+        L.sbl_record_size.argtypes = [C.c_void_p, C.c_uint32]
+        L.sbl_record_size.restype = C.c_uint64
         L.sbl_generate_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_postprocess.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
@@ -107,6 +144,10 @@ def load_library():
                                              C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         L.sbl_align_windows.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(AlignDesc), C.c_void_p]
         L.sbl_correct_stats.argtypes = [C.c_void_p, C.POINTER(CorrectStats)]
+        tail = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_align_pairs.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PairDesc)] + tail
+        L.sbl_align_unique_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + tail
+        L.sbl_align_stats.argtypes = [C.c_void_p, C.POINTER(AlignStats)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -151,6 +192,10 @@ class BlockFinder:
 
     def record_names(self) -> List[str]:
         return [self.L.sbl_record_name(self.h, i).decode() for i in range(self.L.sbl_nchr(self.h))]
+
+    def record_sizes(self) -> List[int]:
+        """Lengths of the records as loaded, from the library: the same after either loader."""
+        return [int(self.L.sbl_record_size(self.h, i)) for i in range(self.L.sbl_nchr(self.h))]
 
     def _check(self, rc, what):
         if rc:
@@ -269,6 +314,41 @@ class BlockFinder:
         """Counters of the last correct_boundaries / align_windows: groups, alignments, levels, launches, cells, kernel_ms."""
         s = CorrectStats()
         self._check(self.L.sbl_correct_stats(self.h, C.byref(s)), "sbl_correct_stats")
+        return {f: getattr(s, f) for f, _ in s._fields_}
+
+    def _pair_alignments(self, n, res, runs, nruns, rows, rows_len) -> List[PairAlignment]:
+        r = _view(res.value, n, PAIR_RESULT_DTYPE)
+        u = _view(runs.value, nruns.value, ALIGN_RUN_DTYPE)
+        text = C.string_at(rows.value, rows_len.value) if rows_len.value else b""
+        return [PairAlignment(x, u, text) for x in r]
+
+    def align_pairs(self, pairs: Sequence[Tuple[int, int, int, bool, int, int, int, bool]]) -> List[PairAlignment]:
+        """Banded global alignment (csrc/block_align.hip; defined in include/sibelia_amd.h) of pairs of ranges of the original records:
+        (chr_a, start_a, end_a, rev_a, chr_b, start_b, end_b, rev_b), half-open; rev: read downwards through the complement table."""
+        desc = (PairDesc * max(1, len(pairs)))()
+        for d, p in zip(desc, pairs):
+            d.chr_a, d.start_a, d.end_a, d.rev_a, d.chr_b, d.start_b, d.end_b, d.rev_b = [int(x) for x in p]
+        res, runs, rows = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nruns, rows_len = C.c_uint64(), C.c_uint64()
+        self._check(self.L.sbl_align_pairs(self.h, len(pairs), desc, C.byref(res), C.byref(runs), C.byref(nruns), C.byref(rows), C.byref(rows_len)), "sbl_align_pairs")
+        return self._pair_alignments(len(pairs), res, runs, nruns, rows, rows_len)
+
+    def align_unique_blocks(self, min_block_size: int, n_reference_chr: int):
+        """The alignments C-Sibelia.py makes of a two-genome run (reference src/csibelia/C-Sibelia.py:314-323), on the current block list:
+        every id with one instance on records 0 .. n_reference_chr - 1 and one outside them, both at least min_block_size long, the
+        reference instance first.  -> (ids ascending, descriptors as in align_pairs, [PairAlignment])."""
+        ids, desc, res, runs, rows = (C.c_void_p() for _ in range(5))
+        n, nruns, rows_len = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sbl_align_unique_blocks(self.h, min_block_size, n_reference_chr, C.byref(ids), C.byref(desc), C.byref(n), C.byref(res),
+                                                   C.byref(runs), C.byref(nruns), C.byref(rows), C.byref(rows_len)), "sbl_align_unique_blocks")
+        d = C.cast(desc, C.POINTER(PairDesc))
+        descs = [(d[i].chr_a, d[i].start_a, d[i].end_a, bool(d[i].rev_a), d[i].chr_b, d[i].start_b, d[i].end_b, bool(d[i].rev_b)) for i in range(n.value)]
+        return [int(x) for x in _view(ids.value, n.value, np.dtype("<i4"))], descs, self._pair_alignments(n.value, res, runs, nruns, rows, rows_len)
+
+    def align_stats(self) -> dict:
+        """Counters of the last align_pairs / align_unique_blocks: pairs, skipped, passes, launches, cells, kernel_ms, spell_ms."""
+        s = AlignStats()
+        self._check(self.L.sbl_align_stats(self.h, C.byref(s)), "sbl_align_stats")
         return {f: getattr(s, f) for f, _ in s._fields_}
 
     def _block_report(self, fn, what, blocks, names) -> bytes:

@@ -1,0 +1,507 @@
+// block_align.hip -- base-by-base alignment of the two instances of every unique block: the step the reference's comparison tool
+// C-Sibelia.py (reference src/csibelia/C-Sibelia.py:274-309) leaves to one external LAGAN process per block.  The alignment is defined by
+// this project (include/sibelia_amd.h): a banded GLOBAL alignment with the scores of boundary_align.hip (+25 / -75 / -75,
+// 32 bit), filled from the ends so that the trace runs forward, with a certificate that the band lost nothing.
+//
+//   band      offsets k = j - i - lo + w, 0 <= k < W = |m - n| + 2 w + 1.  On the anti-diagonal d = i + j only the offsets of one
+//             parity hold a cell; the three neighbours of a cell are offset k two diagonals back (i + 1, j + 1) and offsets k - 1,
+//             k + 1 one diagonal back ((i + 1, j), (i, j + 1)).  So ONE score array indexed by k serves all three diagonals: a diagonal
+//             writes its own parity and reads the other one.  Offsets outside [0, W) read as minus infinity; the matrix borders
+//             (i == n or j == m) are cells of the sweep with the closed form -75 ((n - i) + (m - j)).
+//   kernel    one workgroup per pair, diagonals from n + m down to 0.  A lane owns the 8 consecutive offsets 8 q .. 8 q + 7: the 4
+//             cells of a diagonal among them give one byte of trace codes (2 bits: 0 diagonal / equal, 1 diagonal / unequal, 2 i step,
+//             3 j step -- decided at fill time), stored BY DIAGONAL, so a wave writes consecutive bytes and the offset of a diagonal
+//             is d * B.  W <= 512: one wave, the scores live in registers, the two neighbours beyond a lane's offsets come by one
+//             cross-lane move per diagonal, no barrier.  Wider bands: the score array lives in LDS, 256 or 1024 lanes, one barrier per
+//             diagonal.  The bases never fit the LDS as a whole: per 64 diagonals the stretch of a and of b those diagonals touch is
+//             staged from the original records (a reverse instance downwards through complement1).
+//   trace     one wave: lane t fetches the code t steps ahead along the direction of the current step, one ballot consumes the run.
+//             It emits runs (op, length); the certificate is checked first -- a pair that fails it is not traced.
+//   spelling  k_spell_rows, output-stationary like blockseq.hip: a lane owns 16 bytes of the two gapped rows, finds its pair and its
+//             run by binary search over offsets the host made from the runs, and writes them with one vector store.
+//   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
+//             grouped by band class (register / LDS 256 / LDS 1024) and chunked under the total cap on the trace codes.
+#include <algorithm>
+#include <cstring>
+
+#include "sbl_ctx.h"
+#include "sbl_dna.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int GA_MATCH = 25, GA_PENALTY = 75, GA_NEG = -(1 << 30);
+constexpr int GA_CHUNK = 64;                           // diagonals per staged stretch of bases
+constexpr unsigned GA_REG_W = 512, GA_MID_W = 4096, GA_MAX_W = 12288;      // band offsets: one wave in registers / 256 lanes / 1024 lanes (LDS: 4 (W + 2) + 2 (W / 2 + 40) <= 64 KiB)
+constexpr u64 GA_MAX_DIAG = 1ull << 23;                // 75 (n + m) stays clear of GA_NEG
+constexpr unsigned GA_W0 = 64;
+constexpr size_t GA_PAIR_CAP = (size_t)8 << 30, GA_TOTAL_CAP = (size_t)32 << 30;
+constexpr unsigned GA_ALIGN = 256;
+
+struct GaJob {
+	u64 src_a, src_b;                // first byte of the range in the sequence buffer
+	u64 code_off, run_off;           // first byte of its trace codes; first run
+	unsigned n, m, rev_a, rev_b;
+	unsigned w, W, B, full;          // band; offsets; code bytes per diagonal; the band covers the matrix
+};
+struct GaOut { int score; unsigned nruns, ok, pad_; };
+
+__host__ __device__ inline int ga_bound(int n, int m, int w)
+{
+	const int mn = n < m ? n : m, diff = n < m ? m - n : n - m;
+	return GA_MATCH * (mn - (w + 1)) - GA_PENALTY * (diff + 2 * (w + 1));
+}
+
+__device__ inline unsigned ga_seg(unsigned W) { return (W + GA_CHUNK) / 2 + 8; }      // bytes of a staged stretch
+
+// one cell: the neighbours' scores in, score and trace code out
+__device__ inline int ga_cell(int g, int up, int lf, bool eq, unsigned &code)
+{
+	const int dg = g + (eq ? GA_MATCH : -GA_PENALTY), u = up - GA_PENALTY, l = lf - GA_PENALTY;
+	int val = dg > u ? dg : u;
+	val = l > val ? l : val;
+	code = dg == val ? (eq ? 0u : 1u) : u == val ? 2u : 3u;
+	return val;
+}
+
+struct GaView {                                         // what a cell needs to find itself
+	int n, m, lo, w, W, imin, jmin;
+	const uint8_t *sa, *sb;
+};
+
+// the 4 cells of diagonal d among offsets 8 q + P + 2 c; s: the lane's 8 scores (REG) -- prev / next: s[7] of lane q - 1, s[0] of lane q + 1
+template <int P> __device__ inline unsigned ga_quad_reg(const GaView &V, int d, int q, int (&s)[8], int prev, int next, int &score)
+{
+	unsigned byte = 0;
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		const int k = 8 * q + 2 * c + P;
+		if (k >= V.W) continue;
+		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
+		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
+		int val;
+		unsigned code = 0;
+		if (i == V.n || j == V.m) val = -GA_PENALTY * ((V.n - i) + (V.m - j));
+		else {
+			const int up = P == 0 && c == 0 ? prev : s[2 * c + P - 1 < 0 ? 0 : 2 * c + P - 1];
+			const int lf = P == 1 && c == 3 ? next : s[2 * c + P + 1 > 7 ? 7 : 2 * c + P + 1];
+			val = ga_cell(s[2 * c + P], up, lf, V.sa[i - V.imin] == V.sb[j - V.jmin], code);
+		}
+		s[2 * c + P] = val;
+		if (d == 0) score = val;
+		byte |= code << (2 * c);
+	}
+	return byte;
+}
+
+// the same over the score array S in LDS (S[k + 1] = offset k; S[0] and S[W + 1] are minus infinity)
+__device__ inline unsigned ga_quad_lds(const GaView &V, int d, int q, int p, int *S, int &score)
+{
+	unsigned byte = 0;
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		const int k = 8 * q + 2 * c + p;
+		if (k >= V.W) break;
+		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
+		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
+		int val;
+		unsigned code = 0;
+		if (i == V.n || j == V.m) val = -GA_PENALTY * ((V.n - i) + (V.m - j));
+		else val = ga_cell(S[k + 1], S[k], S[k + 2], V.sa[i - V.imin] == V.sb[j - V.jmin], code);
+		S[k + 1] = val;
+		if (d == 0) score = val;
+		byte |= code << (2 * c);
+	}
+	return byte;
+}
+
+// code of cell (ci, cj); 4: beyond the matrix or the band
+__device__ inline unsigned ga_fetch(const uint8_t *codes, const GaJob &J, int lo, int ci, int cj)
+{
+	if (ci >= (int)J.n || cj >= (int)J.m) return 4;
+	const int k = cj - ci - lo + (int)J.w;
+	if (k < 0 || k >= (int)J.W) return 4;
+	return (codes[(u64)(unsigned)(ci + cj) * J.B + (unsigned)(k >> 3)] >> (2 * ((k >> 1) & 3))) & 3;
+}
+
+template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_align(const uint8_t *__restrict__ seq, const GaJob *__restrict__ jobs,
+                                                                                     uint8_t *codes_all, sbl_align_run *runs_all, GaOut *__restrict__ out)
+{
+	extern __shared__ int ga_lds[];
+	__shared__ int s_score;
+	const GaJob J = jobs[blockIdx.x];
+	const int n = (int)J.n, m = (int)J.m, w = (int)J.w, W = (int)J.W, B = (int)J.B;
+	const int lo = m - n < 0 ? m - n : 0, omin = lo - w, omax = omin + W - 1;
+	const int tid = (int)threadIdx.x, T = (int)blockDim.x;
+	int *const S = ga_lds;                                                  // LDS kernel only: W + 2 scores
+	uint8_t *const sa = reinterpret_cast<uint8_t *>(ga_lds + (REG ? 0 : W + 2));
+	uint8_t *const sb = sa + ga_seg((unsigned)W);
+	uint8_t *const mycodes = codes_all + J.code_off;
+	GaView V{n, m, lo, w, W, 0, 0, sa, sb};
+	int s[8];
+	int score = 0;
+	if (REG) { for (int c = 0; c < 8; c++) s[c] = GA_NEG; }
+	else { for (int k = tid; k < W + 2; k += T) S[k] = GA_NEG; }
+	if (tid == 0) s_score = 0;
+
+	for (int dtop = n + m; dtop >= 0; dtop -= GA_CHUNK) {
+		const int dbot = dtop - (GA_CHUNK - 1) > 0 ? dtop - (GA_CHUNK - 1) : 0;
+		// the stretch of a and b the cells of diagonals dbot .. dtop read: i = (d - o) / 2, j = (d + o) / 2 over the band's offsets o
+		int imin = (dbot - omax) >> 1, imax = (dtop - omin) >> 1, jmin = (dbot + omin) >> 1, jmax = (dtop + omax) >> 1;
+		imin = imin < 0 ? 0 : imin; imax = imax > n - 1 ? n - 1 : imax;
+		jmin = jmin < 0 ? 0 : jmin; jmax = jmax > m - 1 ? m - 1 : jmax;
+		__syncthreads();                                                    // the previous stretch is no longer read
+		for (int t = tid; t <= imax - imin; t += T) {
+			const unsigned i = (unsigned)(imin + t);
+			sa[t] = J.rev_a ? complement1(seq[J.src_a + ((unsigned)n - 1 - i)]) : seq[J.src_a + i];
+		}
+		for (int t = tid; t <= jmax - jmin; t += T) {
+			const unsigned j = (unsigned)(jmin + t);
+			sb[t] = J.rev_b ? complement1(seq[J.src_b + ((unsigned)m - 1 - j)]) : seq[J.src_b + j];
+		}
+		V.imin = imin; V.jmin = jmin;
+		__syncthreads();
+		for (int d = dtop; d >= dbot; d--) {
+			const int p = (d - lo + w) & 1;                                  // the parity of the offsets that hold a cell on this diagonal
+			if (REG) {
+				const int prev = __shfl_up(s[7], 1), next = __shfl_down(s[0], 1);
+				const unsigned byte = p ? ga_quad_reg<1>(V, d, tid, s, tid == 0 ? GA_NEG : prev, tid == 63 ? GA_NEG : next, score)
+				                        : ga_quad_reg<0>(V, d, tid, s, tid == 0 ? GA_NEG : prev, tid == 63 ? GA_NEG : next, score);
+				if (tid < B) mycodes[(u64)(unsigned)d * (unsigned)B + (unsigned)tid] = (uint8_t)byte;
+			} else {
+				for (int q = tid; q < B; q += T) mycodes[(u64)(unsigned)d * (unsigned)B + (unsigned)q] = (uint8_t)ga_quad_lds(V, d, q, p, S, score);
+				__syncthreads();
+			}
+		}
+	}
+	// exactly one lane filled (0, 0)
+	{
+		const int k0 = w - lo, q0 = k0 >> 3;
+		if ((REG ? tid : q0 % T) == (REG ? q0 : tid)) s_score = score;
+	}
+	__threadfence_block();
+	__syncthreads();
+	if (tid >= 64) return;
+	score = s_score;
+	if (!J.full && !(score > ga_bound(n, m, w))) {                           // the band may have cut an optimal path: run again, wider
+		if (tid == 0) out[blockIdx.x] = GaOut{score, 0, 0, 0};
+		return;
+	}
+
+	sbl_align_run *const runs = runs_all + J.run_off;
+	unsigned nruns = 0, cur_op = 0, cur_len = 0;
+	auto emit = [&](unsigned op, unsigned len) {
+		if (op == cur_op) { cur_len += len; return; }
+		if (cur_len) { if (tid == 0) runs[nruns] = sbl_align_run{cur_op, cur_len}; nruns++; }
+		cur_op = op; cur_len = len;
+	};
+	int i = 0, j = 0;
+	while (i < n && j < m) {
+		unsigned c = ga_fetch(mycodes, J, lo, i + tid, j + tid);
+		const unsigned c0 = (unsigned)__shfl((int)c, 0);
+		if (c0 >= 2) c = c0 == 2 ? ga_fetch(mycodes, J, lo, i + tid, j) : ga_fetch(mycodes, J, lo, i, j + tid);
+		const u64 other = __ballot(c != c0);
+		const int f = other ? __ffsll((long long)other) - 1 : 64;
+		if (c0 < 2) { emit(c0 == 0 ? '=' : 'X', (unsigned)f); i += f; j += f; }
+		else if (c0 == 2) { emit('I', (unsigned)f); i += f; }
+		else { emit('D', (unsigned)f); j += f; }
+	}
+	if (i < n) emit('I', (unsigned)(n - i));
+	if (j < m) emit('D', (unsigned)(m - j));
+	emit(0, 0);
+	if (tid == 0) out[blockIdx.x] = GaOut{score, nruns, 1, 0};
+}
+
+// ---- spelling
+
+struct GaSpan { u64 col; unsigned ai, bj, op, len; };                       // a run: first column in its pair's row, first base of a / b
+struct GaPair { u64 src_a, src_b, toff, first_span; unsigned n, m, rev_a, rev_b, nspans, pad_; u64 L; };      // toff: the pair's text (2 L bytes)
+
+constexpr unsigned GS_THREADS = 256;
+
+template <class F> __device__ inline u64 ga_find(u64 lo, u64 hi, F le)   // largest x in [lo, hi) with le(x) (le(lo) holds)
+{
+	while (hi - lo > 1) {
+		const u64 mid = lo + (hi - lo) / 2;
+		if (le(mid)) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+__global__ __launch_bounds__(GS_THREADS) void k_spell_rows(const uint8_t *__restrict__ seq, const GaPair *__restrict__ pairs, u64 npairs,
+                                                           const GaSpan *__restrict__ spans, u64 total, uint4 *__restrict__ out)
+{
+	const u64 t0 = ((u64)blockIdx.x * GS_THREADS + threadIdx.x) * 16;
+	if (t0 >= total) return;
+	u64 pi = ga_find(0, npairs, [&](u64 x) { return pairs[x].toff <= t0; });
+	GaPair P = pairs[pi];
+	u64 off = t0 - P.toff;                                                    // inside the pair's text: row a, then row b
+	unsigned row = 0;
+	u64 col = 0, si = 0;
+	GaSpan R{};
+	auto seek = [&]() {                                                       // (pair, off) -> row, column and run; false: the pair's text is exhausted
+		while (off >= 2 * P.L) {
+			off -= 2 * P.L;
+			if (++pi >= npairs) return false;
+			P = pairs[pi];
+		}
+		row = off >= P.L;
+		col = off - (row ? P.L : 0);
+		si = ga_find(P.first_span, P.first_span + P.nspans, [&](u64 x) { return spans[x].col <= col; });
+		R = spans[si];
+		return true;
+	};
+	u64 wlo = 0, whi = 0;
+	bool live = seek();
+	for (unsigned b = 0; b < 16 && live && t0 + b < total; b++) {
+		if (col == P.L) { live = seek(); if (!live) break; }
+		else if (col >= R.col + R.len) R = spans[++si];
+		const u64 in = col - R.col;
+		unsigned char ch;
+		if (row == 0) ch = R.op == 'D' ? '-' : P.rev_a ? complement1(seq[P.src_a + (P.n - 1 - (R.ai + in))]) : seq[P.src_a + R.ai + in];
+		else ch = R.op == 'I' ? '-' : P.rev_b ? complement1(seq[P.src_b + (P.m - 1 - (R.bj + in))]) : seq[P.src_b + R.bj + in];
+		if (b < 8) wlo |= (u64)ch << (8 * b); else whi |= (u64)ch << (8 * (b - 8));
+		col++; off++;
+	}
+	out[t0 / 16] = make_uint4((unsigned)wlo, (unsigned)(wlo >> 32), (unsigned)whi, (unsigned)(whi >> 32));
+}
+
+// ---- host
+
+unsigned ga_env(const char *name, unsigned fallback)
+{
+	if (const char *e = getenv(name)) { const long long v = atoll(e); if (v > 0) return (unsigned)std::min<long long>(v, 1 << 30); }
+	return fallback;
+}
+
+struct Pending { size_t at; unsigned w; };
+
+// one pass: the pending pairs of one band class at their current w, chunked under the total cap.  Fills res (score, status) and appends
+// the runs of the pairs that pass the certificate; returns those that have to run again.
+void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<size_t> &which, int cls, std::vector<uint8_t> &passed)
+{
+	const size_t total_cap = getenv("SBL_TEST_GALIGN_TOTAL_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_TOTAL_KB", 1) << 10 : GA_TOTAL_CAP;
+	hipStream_t s = c->stream;
+	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : 1024;
+	std::vector<GaJob> chunk;
+	std::vector<GaOut> got;
+	for (size_t at = 0; at < which.size();) {
+		chunk.clear();
+		u64 bytes = 0, nrun = 0;
+		size_t lds = 0;
+		const size_t first = at;
+		for (; at < which.size(); at++) {
+			GaJob j = jobs[which[at]];
+			const u64 need = ((u64)(j.n + j.m + 1) * j.B + GA_ALIGN - 1) / GA_ALIGN * GA_ALIGN;
+			if (!chunk.empty() && bytes + need > total_cap) break;
+			j.code_off = bytes; j.run_off = nrun;
+			bytes += need; nrun += (u64)j.n + j.m + 1;
+			lds = std::max(lds, (cls ? (size_t)(j.W + 2) * 4 : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
+			chunk.push_back(j);
+			c->align_stats.cells += (u64)(j.n + j.m + 1) * ((j.W + 1) / 2);
+		}
+		c->d_ga_job.ensure(chunk.size() * sizeof(GaJob)); c->d_ga_codes.ensure((size_t)bytes); c->d_ga_out.ensure(chunk.size() * sizeof(GaOut));
+		c->d_ga_runs.ensure((size_t)nrun * sizeof(sbl_align_run));
+		got.resize(chunk.size());
+		HIP_TRY(hipMemcpyAsync(c->d_ga_job.p, chunk.data(), chunk.size() * sizeof(GaJob), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipEventRecord(c->ev[0], s));
+		if (cls == 0) k_block_align<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+		else k_block_align<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(c->ev[1], s));
+		HIP_TRY(hipMemcpyAsync(got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+		c->align_stats.kernel_ms += ms;
+		c->align_stats.launches++;
+		c->align_stats.passes += chunk.size();
+		u64 more = 0;
+		for (const GaOut &o : got) more += o.ok ? o.nruns : 0;
+		size_t fill = c->ga_runs.size();
+		c->ga_runs.resize(fill + (size_t)more);
+		for (size_t k = 0; k < chunk.size(); k++) {
+			sbl_pair_result &r = c->ga_res[which[first + k]];
+			r.passes++;
+			r.band_w = chunk[k].w;
+			if (!got[k].ok) continue;
+			passed[which[first + k]] = 1;
+			r.status = SBL_GALIGN_OK; r.score = got[k].score; r.first_run = fill; r.nruns = got[k].nruns;
+			if (got[k].nruns) HIP_TRY(hipMemcpyAsync(&c->ga_runs[fill], c->d_ga_runs.as<sbl_align_run>() + chunk[k].run_off, (size_t)got[k].nruns * sizeof(sbl_align_run), hipMemcpyDeviceToHost, s));
+			fill += got[k].nruns;
+		}
+		HIP_TRY(hipStreamSynchronize(s));
+	}
+}
+
+// aligns c->ga_desc (checked) into c->ga_res / ga_runs and spells the rows into h_bs_text
+void ga_run(sbl_ctx *c, u64 *rows_len)
+{
+	const std::vector<sbl_pair_desc> &desc = c->ga_desc;
+	const size_t N = desc.size();
+	const size_t pair_cap = getenv("SBL_TEST_GALIGN_CAP_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_CAP_KB", 1) << 10 : GA_PAIR_CAP;
+	const unsigned w0 = ga_env("SBL_TEST_GALIGN_W0", GA_W0);
+	c->align_stats = sbl_align_stats_t{};
+	c->align_stats.pairs = N;
+	c->ga_res.assign(N, sbl_pair_result{});
+	c->ga_runs.clear();
+	std::vector<GaJob> jobs(N);
+	std::vector<Pending> pending;
+	for (size_t i = 0; i < N; i++) {
+		const sbl_pair_desc &d = desc[i];
+		GaJob &j = jobs[i];
+		j = GaJob{};
+		j.src_a = (u64)c->orig_sepidx[d.chr_a] + 1 + d.start_a; j.src_b = (u64)c->orig_sepidx[d.chr_b] + 1 + d.start_b;
+		const u64 n = d.end_a - d.start_a, m = d.end_b - d.start_b;
+		sbl_pair_result &r = c->ga_res[i];
+		if (n + m >= GA_MAX_DIAG) { r.status = SBL_GALIGN_SKIPPED; continue; }
+		j.n = (unsigned)n; j.m = (unsigned)m; j.rev_a = d.rev_a != 0; j.rev_b = d.rev_b != 0;
+		if (n == 0 || m == 0) {                                               // all gaps: nothing to fill
+			r.score = -GA_PENALTY * (int)(n + m);
+			r.first_run = c->ga_runs.size();
+			if (n + m) { c->ga_runs.push_back(sbl_align_run{n ? (uint32_t)'I' : (uint32_t)'D', (uint32_t)(n + m)}); r.nruns = 1; }
+			continue;
+		}
+		pending.push_back(Pending{i, w0});
+	}
+	std::vector<uint8_t> passed(N, 0);
+	std::vector<size_t> cls[3];
+	while (!pending.empty()) {
+		for (auto &v : cls) v.clear();
+		for (Pending &p : pending) {
+			GaJob &j = jobs[p.at];
+			const unsigned mn = std::min(j.n, j.m), diff = std::max(j.n, j.m) - mn;
+			j.w = std::min(p.w, mn);                                          // w = min(n, m): the band covers the matrix
+			j.full = j.w >= mn;
+			j.W = diff + 2 * j.w + 1;
+			j.B = ((j.W + 1) / 2 + 3) / 4;
+			if (j.W > GA_MAX_W || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
+			cls[j.W <= GA_REG_W ? 0 : j.W <= GA_MID_W ? 1 : 2].push_back(p.at);
+		}
+		for (int k = 0; k < 3; k++) if (!cls[k].empty()) ga_launch(c, jobs, cls[k], k, passed);
+		std::vector<Pending> again;
+		for (const Pending &p : pending) if (!passed[p.at]) again.push_back(Pending{p.at, jobs[p.at].w * 2});
+		pending.swap(again);
+	}
+	c->stats.device_bytes = sbl_devbuf_total().load();
+
+	// ---- rows: per aligned pair 2 L bytes, spelled from the runs
+	std::vector<GaPair> pairs;
+	std::vector<GaSpan> spans;
+	u64 total = 0;
+	for (size_t i = 0; i < N; i++) {
+		sbl_pair_result &r = c->ga_res[i];
+		if (r.status != SBL_GALIGN_OK) { r = sbl_pair_result{SBL_GALIGN_SKIPPED, 0, r.band_w, r.passes, 0, 0, 0, 0}; c->align_stats.skipped++; continue; }
+		GaPair P{jobs[i].src_a, jobs[i].src_b, total, spans.size(), jobs[i].n, jobs[i].m, jobs[i].rev_a, jobs[i].rev_b, (unsigned)r.nruns, 0, 0};
+		unsigned ai = 0, bj = 0;
+		for (u64 k = 0; k < r.nruns; k++) {
+			const sbl_align_run &run = c->ga_runs[r.first_run + k];
+			spans.push_back(GaSpan{P.L, ai, bj, run.op, run.len});
+			P.L += run.len;
+			if (run.op != 'D') ai += run.len;
+			if (run.op != 'I') bj += run.len;
+		}
+		SBL_CHECK(ai == P.n && bj == P.m, SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
+		r.row_off = total; r.row_len = P.L;
+		total += 2 * P.L;
+		if (P.L) pairs.push_back(P);
+	}
+	if (total) {
+		hipStream_t s = c->stream;
+		const size_t padded = (size_t)((total + 15) / 16 * 16);
+		const u64 groups = (padded / 16 + GS_THREADS - 1) / GS_THREADS;
+		SBL_CHECK(groups < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
+		c->d_ga_pair.ensure(pairs.size() * sizeof(GaPair)); c->d_ga_span.ensure(spans.size() * sizeof(GaSpan)); c->d_ga_text.ensure(padded);
+		sbl_text_staging(c, padded);
+		HIP_TRY(hipMemcpyAsync(c->d_ga_pair.p, pairs.data(), pairs.size() * sizeof(GaPair), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(c->d_ga_span.p, spans.data(), spans.size() * sizeof(GaSpan), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipEventRecord(c->ev[0], s));
+		k_spell_rows<<<(unsigned)groups, GS_THREADS, 0, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_pair.as<GaPair>(), pairs.size(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(c->ev[1], s));
+		HIP_TRY(hipMemcpyAsync(c->h_bs_text, c->d_ga_text.p, padded, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+		c->align_stats.spell_ms = ms;
+		c->stats.device_bytes = sbl_devbuf_total().load();
+	}
+	*rows_len = total;
+}
+
+void ga_check(const sbl_ctx *c, const sbl_pair_desc *d, u64 n)
+{
+	SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+	SBL_CHECK(n == 0 || d, SBL_ERR_BAD_ARG, "null pair descriptors");
+	for (u64 i = 0; i < n; i++) {
+		SBL_CHECK(d[i].chr_a < c->nchr && d[i].chr_b < c->nchr, SBL_ERR_BAD_ARG, "a pair on a record that does not exist");
+		SBL_CHECK(d[i].end_a >= d[i].start_a && d[i].end_b >= d[i].start_b, SBL_ERR_BAD_ARG, "a range ends before it starts");
+		SBL_CHECK(d[i].end_a <= (u64)(c->orig_sepidx[d[i].chr_a + 1] - c->orig_sepidx[d[i].chr_a] - 1) &&
+		          d[i].end_b <= (u64)(c->orig_sepidx[d[i].chr_b + 1] - c->orig_sepidx[d[i].chr_b] - 1), SBL_ERR_BAD_ARG, "a range runs beyond its record");
+	}
+}
+
+void ga_hand_out(sbl_ctx *c, u64 rows_len, const sbl_pair_result **res, const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rl)
+{
+	if (res) *res = c->ga_res.data();
+	if (runs) *runs = c->ga_runs.data();
+	if (nruns) *nruns = c->ga_runs.size();
+	if (rows) *rows = rows_len ? c->h_bs_text : "";
+	if (rl) *rl = rows_len;
+}
+
+}  // namespace
+
+extern "C" sbl_status sbl_align_stats(const sbl_ctx *c, sbl_align_stats_t *out)
+{
+	if (!c || !out) return SBL_ERR_BAD_ARG;
+	*out = c->align_stats;
+	return SBL_OK;
+}
+
+extern "C" sbl_status sbl_align_pairs(sbl_ctx *c, uint64_t npairs, const sbl_pair_desc *desc, const sbl_pair_result **res,
+                                      const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len)
+{
+	return guarded(c, [&] {
+		ga_check(c, desc, npairs);
+		c->ga_ids.clear();
+		c->ga_desc.assign(desc, desc + npairs);
+		u64 total = 0;
+		ga_run(c, &total);
+		ga_hand_out(c, total, res, runs, nruns, rows, rows_len);
+	});
+}
+
+extern "C" sbl_status sbl_align_unique_blocks(sbl_ctx *c, uint32_t min_block_size, uint32_t n_reference_chr, const int32_t **ids,
+                                              const sbl_pair_desc **desc, uint64_t *n, const sbl_pair_result **res,
+                                              const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+		SBL_CHECK(c->have_blocks, SBL_ERR_BAD_ARG, "no block list: run sbl_generate_blocks / sbl_postprocess first");
+		SBL_CHECK(n_reference_chr > 0 && n_reference_chr < c->nchr, SBL_ERR_BAD_ARG, "the reference set must hold at least one record and leave at least one outside it");
+		sbl_check_blocks(c, c->blocks.data(), c->blocks.size());
+		std::vector<sbl_block> v = c->blocks;
+		std::stable_sort(v.begin(), v.end(), [](const sbl_block &x, const sbl_block &y) { return std::abs(x.id) < std::abs(y.id); });
+		c->ga_ids.clear(); c->ga_desc.clear();
+		for (size_t i = 0; i < v.size();) {
+			size_t j = i;
+			while (j < v.size() && std::abs(v[j].id) == std::abs(v[i].id)) j++;
+			if (j - i == 2 && (v[i].chr < n_reference_chr) != (v[i + 1].chr < n_reference_chr)) {      // determine_unique_block (C-Sibelia.py:314-323)
+				const sbl_block &a = v[i].chr < n_reference_chr ? v[i] : v[i + 1], &b = v[i].chr < n_reference_chr ? v[i + 1] : v[i];
+				if (a.end - a.start >= min_block_size && b.end - b.start >= min_block_size) {
+					c->ga_ids.push_back(std::abs(a.id));
+					c->ga_desc.push_back(sbl_pair_desc{a.chr, a.start, a.end, a.id < 0, b.chr, b.start, b.end, b.id < 0});
+				}
+			}
+			i = j;
+		}
+		u64 total = 0;
+		ga_run(c, &total);
+		if (ids) *ids = c->ga_ids.data();
+		if (desc) *desc = c->ga_desc.data();
+		if (n) *n = c->ga_desc.size();
+		ga_hand_out(c, total, res, runs, nruns, rows, rows_len);
+	});
+}

@@ -176,6 +176,22 @@ void sbl_blockseq_launch(sbl_ctx *c, const void *d_desc, const void *d_toff, uin
 	HIP_TRY(hipGetLastError());
 }
 
+// the context's pinned staging buffer for device-made text, at least `bytes` large (pageable when pinning fails)
+void sbl_text_staging(sbl_ctx *c, size_t bytes)
+{
+	if (bytes <= c->h_bs_cap) return;
+	c->host_free(c->h_bs_text, c->h_bs_pinned);
+	c->h_bs_text = nullptr; c->h_bs_cap = 0;
+	const size_t cap = bytes + bytes / 16 + 4096;
+	c->h_bs_pinned = hipHostMalloc((void **)&c->h_bs_text, cap) == hipSuccess;
+	if (!c->h_bs_pinned) {                                             // a host that cannot pin that much still gets its text
+		(void)hipGetLastError();
+		c->h_bs_text = (char *)malloc(cap);
+		if (!c->h_bs_text) throw SblError{SBL_ERR_OOM, "host staging buffer for device-made text"};
+	}
+	c->h_bs_cap = cap;
+}
+
 // checks shared by the two reports that take a caller's list
 void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n)
 {
@@ -225,18 +241,7 @@ extern "C" sbl_status sbl_blocks_sequences(sbl_ctx *c, const sbl_block *blocks, 
 			hipStream_t s = c->stream;
 			const size_t padded = (size_t)((total + 15) / 16 * 16);
 			c->d_bs_desc.ensure(n * sizeof(BsDesc)); c->d_bs_off.ensure((n + 1) * 8); c->d_bs_hdr.ensure(hdr.size()); c->d_bs_text.ensure(padded);
-			if (padded > c->h_bs_cap) {
-				c->host_free(c->h_bs_text, c->h_bs_pinned);
-				c->h_bs_text = nullptr; c->h_bs_cap = 0;
-				const size_t cap = padded + padded / 16 + 4096;
-				c->h_bs_pinned = hipHostMalloc((void **)&c->h_bs_text, cap) == hipSuccess;
-				if (!c->h_bs_pinned) {                                     // a host that cannot pin that much still gets its text
-					(void)hipGetLastError();
-					c->h_bs_text = (char *)malloc(cap);
-					if (!c->h_bs_text) throw SblError{SBL_ERR_OOM, "host staging buffer for the block sequences"};
-				}
-				c->h_bs_cap = cap;
-			}
+			sbl_text_staging(c, padded);
 			HIP_TRY(hipMemcpyAsync(c->d_bs_desc.p, desc.data(), n * sizeof(BsDesc), hipMemcpyHostToDevice, s));
 			HIP_TRY(hipMemcpyAsync(c->d_bs_off.p, toff.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
 			HIP_TRY(hipMemcpyAsync(c->d_bs_hdr.p, hdr.data(), hdr.size(), hipMemcpyHostToDevice, s));

@@ -398,6 +398,11 @@ extern "C" sbl_status sbl_load(sbl_ctx *c, uint32_t nchr, const uint8_t *const *
 
 extern "C" uint32_t sbl_nchr(const sbl_ctx *c) { return c ? c->nchr : 0; }
 
+extern "C" uint64_t sbl_record_size(const sbl_ctx *c, uint32_t chr)
+{
+	return c && (size_t)chr + 1 < c->orig_sepidx.size() ? (uint64_t)(c->orig_sepidx[chr + 1] - c->orig_sepidx[chr] - 1) : 0;
+}
+
 extern "C" sbl_status sbl_enumerate(sbl_ctx *c, uint32_t k, uint32_t *bif_count,
                                     const sbl_inst **pos, uint64_t *npos, const sbl_inst **neg, uint64_t *nneg)
 {

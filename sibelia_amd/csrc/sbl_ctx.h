@@ -99,6 +99,15 @@ struct sbl_ctx {
 	DevBuf d_ba_desc, d_ba_codes, d_ba_out, d_ba_seq;
 	sbl_correct_stats_t correct_stats{};
 
+	// sbl_align_pairs / sbl_align_unique_blocks (block_align.hip): jobs, trace codes, per-job results, runs; spans, offsets and rows of the
+	// spelling kernel (the rows come back through h_bs_text); what the calls hand out
+	DevBuf d_ga_job, d_ga_codes, d_ga_out, d_ga_runs, d_ga_span, d_ga_pair, d_ga_text;
+	std::vector<sbl_pair_result> ga_res;
+	std::vector<sbl_align_run> ga_runs;
+	std::vector<sbl_pair_desc> ga_desc;
+	std::vector<int32_t> ga_ids;
+	sbl_align_stats_t align_stats{};
+
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;
 	DevBuf d_send, d_recv, d_otable, d_oused, d_allkeys, d_allkeys2, d_gelem[2], d_gid[2], d_stage;
@@ -160,6 +169,7 @@ void sbl_render_reports(sbl_ctx *c, const char *const *names);   // report[0..2]
 void sbl_sort_by_id(std::vector<sbl_block> &v);   // the one unstable sort by |id| the reference's writers apply to a copy of the list
 // implemented in blockseq.hip
 void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n);   // a caller's block list against the loaded records (throws SBL_ERR_BAD_ARG)
+void sbl_text_staging(sbl_ctx *c, size_t bytes);   // h_bs_text, the pinned staging buffer of device-made text, grown to `bytes`
 // implemented in simplify.hip
 void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges);
 void sbl_simplify_free(sbl_ctx *c);

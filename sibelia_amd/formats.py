@@ -79,3 +79,98 @@ def dot_text(edges: np.ndarray) -> bytes:
 
 def sha256(b: bytes) -> str:
     return hashlib.sha256(b).hexdigest()
+
+
+# ------------------------------------------------------------------------------------------ alignments of unique blocks (--maf, --variants)
+
+MINIMUM_CONTEXT_SIZE = 30                         # src/csibelia/C-Sibelia.py:20
+# reverse_complementary (C-Sibelia.py:84-90) maps upper-case ACGT; both loaders upper-case the records, so that is all a run ever sees.
+# The table also maps acgt, as the device's complement table (csrc/sbl_dna.h) does: rows of a '-' instance and alleles never disagree.
+_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def strip_chr_id(chr_id: str) -> str:
+    """strip_chr_id (C-Sibelia.py:92-96): gi|...|ref|NC_000000.1| -> NC_000000."""
+    part = chr_id.split("|")
+    return part[-2].split(".")[0] if len(part) == 5 else chr_id
+
+
+def maf_line(name: str, start: int, end: int, reverse: bool, record_size: int, row: bytes) -> bytes:
+    """One `s` line of write_alignments_maf (C-Sibelia.py:473-484) for the instance [start, end) (0-based, half-open) of a record:
+    s <description> <start> <size> <strand> <record size> <row>; start is 0-based and counted from the record's end for '-'."""
+    at = record_size - end if reverse else start
+    return b"s %s %d %d %s %d %s" % (name.encode(), at, end - start, b"-" if reverse else b"+", record_size, row)
+
+
+def maf_text(groups) -> bytes:
+    """write_alignments_maf: `##maf version=1`, an empty line, then per group `a`, its `s` lines (maf_line) and an empty line."""
+    out = [b"##maf version=1\n"]
+    for lines in groups:
+        out.append(b"a")
+        out += list(lines)
+        out.append(b"")
+    return b"\n".join(out) + b"\n"
+
+
+def variants_from_runs(runs, row_a: bytes, row_b: bytes, start: int, end: int, reverse: bool):
+    """parse_alignment (C-Sibelia.py:206-252) from the runs of an alignment -- (op, length) with op in '=XID', '=' the only kind whose
+    columns are equal -- instead of a scan of the rows.  [start, end): the reference-side instance, 0-based half-open; reverse: it is
+    read on '-'.  -> [(POS, REF, ALT)].
+      * maximal stretches of equal / unequal columns become segments;
+      * an equal segment shorter than 30 columns that is not the first is merged into the unequal segments around it;
+      * each unequal segment is one variant;
+      * POS comes from the reference-side map of columns to 1-based positions -- start + 1 upwards, or `end` downwards for a '-'
+        instance, advancing on every column whose reference row is no gap;
+      * the base before the segment is included (shift = 1: POS - 1, one more column) unless the segment starts the alignment or is a
+        single substitution;
+      * alleles are the rows' columns without gaps, reverse-complemented when the reference instance is on '-' (an empty one stays
+        empty here; vcf_text writes '.')."""
+    stretches = []                                  # [first column, one past the last, equal?, reference bases before it]
+    col = used = 0
+    for op, length in runs:
+        op = chr(op) if isinstance(op, int) else op
+        if not length:
+            continue
+        if stretches and stretches[-1][2] == (op == "="):
+            stretches[-1][1] += length
+        else:
+            stretches.append([col, col + length, op == "=", used])
+        col += length
+        used += length if op != "D" else 0
+    if not stretches:
+        return []
+    before = {s[0]: s[3] for s in stretches}
+    segment, at = [], 0
+    for prev, now in zip(stretches, stretches[1:]):
+        if not prev[2] or now[0] - at >= MINIMUM_CONTEXT_SIZE or at == 0:
+            segment.append([at, now[0], prev[2]])
+            at = now[0]
+        elif segment:
+            at = segment.pop()[0]
+    segment.append([at, col, stretches[-1][2]])
+    first, step = (end, -1) if reverse else (start + 1, 1)
+    out = []
+    for s, e, equal in segment:
+        if equal:
+            continue
+        snp = e - s == 1 and row_a[s:e] != b"-" and row_b[s:e] != b"-"
+        shift = 0 if s == 0 or snp else 1
+        ref, alt = row_a[s - shift:e].replace(b"-", b""), row_b[s - shift:e].replace(b"-", b"")
+        if reverse:
+            ref, alt = ref.translate(_COMPLEMENT)[::-1], alt.translate(_COMPLEMENT)[::-1]
+        out.append((first + step * before[s] - shift, ref, alt))
+    return out
+
+
+def vcf_text(reference_name: str, records) -> bytes:
+    """write_vcf_header (C-Sibelia.py:433-440) with ##source=sibelia_amd, then Variant.get_vcf_record (:177-180) per record
+    (reference record description, POS, REF, ALT), sorted by (description, POS) as variant_key does (:502-503): eight tab-separated
+    columns, '.' for an empty allele."""
+    out = ["##fileformat=VCFv4.1", "##source=sibelia_amd", "##reference=" + strip_chr_id(reference_name),
+           '##INFO=<ID=SVTYPE,Number=1,Type=String,Description="Type of structural variant">',
+           '##INFO=<ID=IMPRECISE,Number=0,Type=Flag,Description="Imprecise structural variation">',
+           '##INFO=<ID=CIPOS,Number=2,Type=Integer,Description="Confidence interval around POS for imprecise variants">',
+           "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"])]
+    for name, pos, ref, alt in sorted(records, key=lambda r: (r[0], r[1])):
+        out.append("\t".join([strip_chr_id(name), str(pos), ".", ref.decode("latin1") or ".", alt.decode("latin1") or ".", ".", ".", "."]))
+    return ("\n".join(out) + "\n").encode("latin1")

@@ -5,6 +5,9 @@ per-stage blocks of --allstages / -v (computed BEFORE the stage: they consume th
 with and without -r, and the choice of which files are written.  `run` returns (return code, {relative file name: bytes}, text for
 standard output); `main` writes the files and prints the text (python -m sibelia_amd).
 
+--maf / --variants (two input files) add what the reference's comparison tool C-Sibelia.py makes of such a run: the alignments of the
+unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).
+
 Not written: circos/ and d3_blocks_diagram.html -- the reference instantiates them from templates embedded in its own sources.
 
 Everything up to `run` (option parsing, stage files, the k rule, the file plan) imports and works without the HIP library.
@@ -26,6 +29,9 @@ PARAMETER_SETS = {
     "fine": [(30, 150), (100, 500), (500, 1500)],
     "far": [(15, 120), (100, 500), (500, 1500)],
 }
+
+ALIGN_HELP = ("Blocks that are not unique -- more or fewer than two instances, or not one in each input file -- are not aligned: "
+              "the reference's comparison tool hands them to mlagan, which is out of scope.")
 
 NOT_WRITTEN = ("The Circos files (circos/) and d3_blocks_diagram.html of the reference program are not written: "
                "they are instantiated from templates embedded in the reference's sources.")
@@ -133,6 +139,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--nopostprocess", action="store_true", help="Do not perform postprocessing (stripe gluing).")
     p.add_argument("--noblocks", action="store_true", help="Do not compute synteny blocks")
     p.add_argument("--correctboundaries", action="store_true", help="Correct boundaries of unique synteny blocks.")
+    p.add_argument("--maf", default=None, metavar="FILE", help="Two input files: align the two instances of every unique synteny block base by base "
+                   "on the device and write the alignments in MAF format.  " + ALIGN_HELP)
+    p.add_argument("--variants", default=None, metavar="FILE", help="Two input files: write the SNVs and indels read off those alignments in VCF format "
+                   "(positions on the records of the first file).")
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
     return p
@@ -145,7 +155,30 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         raise PipelineError("exactly one of -s (--parameters) and -k (--stagefile) is required")
     if opt.correctboundaries and len(opt.filenames) != 2:      # src/sibelia.cpp:203-206, before any file is read
         raise PipelineError("In correction mode only two FASTA files are acceptable")
+    if opt.maf is not None or opt.variants is not None:
+        if len(opt.filenames) != 2:                            # before any file is read
+            raise PipelineError("In alignment mode only two FASTA files are acceptable")
+        if opt.noblocks:
+            raise PipelineError("--maf and --variants need the synteny blocks: they cannot be combined with --noblocks")
+        _check_alignment_files(opt)
     return opt
+
+
+def _check_alignment_files(opt: argparse.Namespace) -> None:
+    """--maf / --variants name files of their own: not each other and not a file the run writes anyway."""
+    where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
+    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants)) if f is not None]
+    for o, f in given:
+        if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
+            raise PipelineError("%s needs a file name, not '%s'" % (o, f))
+    if len(given) == 2 and where(opt.maf) == where(opt.variants):
+        raise PipelineError("--maf and --variants name the same file: " + opt.maf)
+    fixed = ["blocks_coords.txt", "blocks_coords.gff", "genomes_permutations.txt", "coverage_report.txt", "blocks_sequences.fasta"]
+    taken = re.compile(r"(blocks_coords\d+\.(txt|gff)|de_bruijn_graph\d*\.dot)$")
+    outdir = os.path.abspath(opt.outdir)
+    for o, f in given:
+        if os.path.dirname(where(f)) == outdir and (os.path.basename(where(f)) in fixed or taken.match(os.path.basename(where(f)))):
+            raise PipelineError("%s names a file the program writes itself: %s" % (o, f))
 
 
 def stages_of(opt: argparse.Namespace) -> List[Tuple[int, int]]:
@@ -198,6 +231,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
+        out += [f for f in (opt.maf, opt.variants) if f is not None]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -295,6 +329,36 @@ def load_input(filenames: Sequence[str], device: int = -1):
         raise PipelineError(m.group(1) if m and m.group(1) else text)
 
 
+# ------------------------------------------------------------------------------------------ alignments of unique blocks
+
+def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: int, complain: Callable[[str], None]) -> Dict[str, bytes]:
+    """--maf / --variants: what C-Sibelia.py does after the reference program has run (src/csibelia/C-Sibelia.py:343-368, :473-484,
+    :433-444), with the alignments made on the device (BlockFinder.align_unique_blocks) instead of by one LAGAN process per block.
+    Skipped blocks are named through `complain`, one line each, and are absent from both files."""
+    from . import formats
+    from .api import GALIGN_OK, SibeliaError
+    try:
+        ids, descs, aligned = bf.align_unique_blocks(opt.minblocksize, nfirst)
+    except SibeliaError as e:
+        raise PipelineError(str(e))
+    size = bf.record_sizes()
+    groups, records = [], []
+    for block, (ca, sa, ea, ra, cb, sb, eb, rb), al in zip(ids, descs, aligned):
+        if al.status != GALIGN_OK:
+            complain("block %d not aligned: %s:%d-%d against %s:%d-%d is beyond the limits of one alignment "
+                     "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, names[ca], sa + 1, ea, names[cb], sb + 1, eb))
+            continue
+        groups.append([formats.maf_line(names[ca], sa, ea, ra, size[ca], al.row_a), formats.maf_line(names[cb], sb, eb, rb, size[cb], al.row_b)])
+        if opt.variants is not None:
+            records += [(names[ca],) + v for v in formats.variants_from_runs(al.runs, al.row_a, al.row_b, sa, ea, ra)]
+    out = {}
+    if opt.maf is not None:
+        out[opt.maf] = formats.maf_text(groups)
+    if opt.variants is not None:
+        out[opt.variants] = formats.vcf_text(names[0], records)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ main
 
 def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outdir_exists: Optional[bool] = None) -> Tuple[int, Dict[str, bytes], str]:
@@ -355,12 +419,24 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
             files["coverage_report.txt"] = coverage
             if opt.sequencesfile:
                 files["blocks_sequences.fasta"] = bf.blocks_sequences(None, names)
+            if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
+                files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
     finally:
         bf.close()
     assert list(files) == planned_files(opt, len(stages), outdir_exists)
     return 0, files, "".join(printed)
+
+
+def write_files(outdir: str, files: Dict[str, bytes]) -> None:
+    """Writes what `run` returned under the output directory; a name with a directory part (--maf sub/a.maf) gets that directory."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, data in files.items():
+        path = os.path.join(outdir, name)
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -374,10 +450,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         rc, files, _ = run(argv, write=write, outdir_exists=os.path.isdir(opt.outdir))
         if not opt.inram:                           # the reference's indices create their temp directory (by default the output directory)
             os.makedirs(tempdir_of(opt), exist_ok=True)
-        os.makedirs(opt.outdir, exist_ok=True)
-        for name, data in files.items():
-            with open(os.path.join(opt.outdir, name), "wb") as f:
-                f.write(data)
+        write_files(opt.outdir, files)
         return rc
     except PipelineError as e:
         sys.stderr.write("error: %s\n" % e)
