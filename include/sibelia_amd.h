@@ -170,8 +170,8 @@ sbl_status sbl_glue_stripes(sbl_block *blocks, uint64_t *n, uint32_t nchr);
  * (1-based; a reverse instance is reported from its far end, as in blocks_coords.txt), the end - start bases in lines of 80 and a
  * line feed.  Reverse instances are spelled downwards through the reference's complement table (src/dnasequence.cpp:11-28):
  * ACGT / acgt swapped, every other character -- ambiguity codes included -- unchanged.  The text is generated by a kernel
- * (csrc/blockseq.hip) and comes back through a pinned buffer of the context, valid until the next sbl_blocks_sequences,
- * sbl_align_pairs or sbl_align_unique_blocks (they share the buffer).  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
+ * (csrc/blockseq.hip) and comes back through a pinned buffer of the context, valid until the next sbl_blocks_sequences
+ * or sbl_align_pairs / _unique_blocks / _groups / _block_groups call (they share the buffer).  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
  * end < start, end beyond the record, id == 0, no records loaded.
  * sbl_blocks_sequences_times: device time of the last call's kernel and of its device-to-host copy (event pairs). */
 sbl_status sbl_blocks_sequences(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
@@ -268,7 +268,44 @@ sbl_status sbl_align_unique_blocks(sbl_ctx *ctx, uint32_t min_block_size, uint32
                                    const sbl_pair_desc **desc, uint64_t *n, const sbl_pair_result **res,
                                    const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len);
 
-/* Counters of the last sbl_align_pairs / sbl_align_unique_blocks. */
+/* Multiple alignment of groups of instances: centre-star on the FIRST instance of every group, defined by this
+ * project -- the reference's comparison tool hands such blocks to mlagan.  A group is an ordered list of r >= 1 instances (half-open
+ * ranges of the ORIGINAL records; rev: read downwards through the complement table); instance 0 is the centre c (n bases), the others
+ * are members.  Every member is aligned to the centre by the banded global alignment above (a = c, b = the member; scores, tie rules,
+ * band doubling, certificate and skip limits unchanged).  A 'D' run that starts at centre index p sits in SLOT p (0 <= p <= n; a pair
+ * has at most one run per slot); G[p] is the longest such run over the members.  The alignment has L = n + sum G[p] columns: for
+ * p = 0 .. n the G[p] columns of slot p, then (p < n) the column of centre base p.  The centre row holds '-' in slot columns; a member
+ * row holds in slot p its inserted bases first and then '-' (left-justified), and in the column of centre base p its aligned base or
+ * '-'.  No column is all gaps; the rows of centre and member k without the columns where both hold '-' are the two rows of
+ * sbl_align_pairs for that pair.  r = 1 gives one row (L = n); n = 0 gives L = the longest member and a centre row of gaps.
+ * If ANY member of a group is SKIPPED by the limits above the whole group is: status SBL_GALIGN_SKIPPED, L = 0, no rows -- never an
+ * error, never a partial group, and the other groups of the call are unaffected.
+ *
+ * sbl_align_groups: group g is inst[group_first[g], group_first[g + 1]) (group_first: ngroups + 1 ascending offsets, the first one 0).
+ * sbl_group_result: row i of the group is rows[row_off + i * L, row_off + (i + 1) * L), centre first, members in the order given.
+ * sbl_member_result: one per INSTANCE, in the order of inst; a member's entry holds its pair's score, band_w and passes (score 0 in a
+ * skipped group), a centre's entry is zero.  The pair passes and the gap slots are merged on the host from the runs; the rows are
+ * spelled on the device (k_spell_groups) and come back through the context's pinned text buffer, under the ownership rule stated above
+ * for sbl_align_pairs: everything returned is owned by the ctx, and `rows` is overwritten by the next sbl_align_* or
+ * sbl_blocks_sequences call.  All offsets are 64 bit.
+ * SBL_ERR_BAD_ARG: an empty group, a range outside its record, end < start, a record that does not exist, no records loaded. */
+typedef struct { uint32_t chr; uint64_t start, end; uint32_t rev; } sbl_group_inst;
+typedef struct { uint32_t status, ninst; uint64_t L, row_off; } sbl_group_result;
+typedef struct { int32_t score; uint32_t band_w, passes; } sbl_member_result;
+sbl_status sbl_align_groups(sbl_ctx *ctx, uint64_t ngroups, const uint64_t *group_first, const sbl_group_inst *inst,
+                            const sbl_group_result **res, const sbl_member_result **members, const char **rows, uint64_t *rows_len);
+
+/* The groups of the context's CURRENT block list (after sbl_postprocess / sbl_correct_boundaries): every id with at least two
+ * instances of at least min_block_size bases, all of them, ordered by ascending (chr, start, end, rev) -- the first is the centre, so
+ * nothing depends on an unstable sort -- and read on the strand the list reports.  Results in ascending block id, together with the
+ * ids, the offsets and the descriptors that were aligned (as for sbl_align_groups).  An empty list is a list (ngroups = 0); a missing
+ * list or records are SBL_ERR_BAD_ARG. */
+sbl_status sbl_align_block_groups(sbl_ctx *ctx, uint32_t min_block_size, const int32_t **ids, const uint64_t **group_first,
+                                  const sbl_group_inst **inst, uint64_t *ngroups, const sbl_group_result **res,
+                                  const sbl_member_result **members, const char **rows, uint64_t *rows_len);
+
+/* Counters of the last sbl_align_pairs / sbl_align_unique_blocks / sbl_align_groups / sbl_align_block_groups (there: the pairs are the
+ * members, `skipped` counts skipped PAIRS, spell_ms is the time of k_spell_groups). */
 typedef struct {
 	uint64_t pairs, skipped;         /* pairs given; ... of which skipped */
 	uint64_t passes;                 /* alignments run, band doublings included */

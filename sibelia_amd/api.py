@@ -28,7 +28,8 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_longk_slices", "sbl_longk_value_bounds", "sbl_longk_owner", "sbl_longk_halo_plan",
            "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords",
            "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
-           "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size"]
+           "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
+           "sbl_align_groups", "sbl_align_block_groups"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -93,6 +94,26 @@ class PairAlignment:
             self.score, self.runs, self.row_a, self.row_b = None, [], b"", b""
 
 
+class GroupInst(C.Structure):
+    _fields_ = [("chr", C.c_uint32), ("start", C.c_uint64), ("end", C.c_uint64), ("rev", C.c_uint32)]
+
+
+GROUP_RESULT_DTYPE = np.dtype([("status", "<u4"), ("ninst", "<u4"), ("L", "<u8"), ("row_off", "<u8")])
+MEMBER_RESULT_DTYPE = np.dtype([("score", "<i4"), ("band_w", "<u4"), ("passes", "<u4")])
+
+
+class GroupAlignment:
+    """One sbl_group_result: status (GALIGN_OK / GALIGN_SKIPPED), L, row_off, the rows (centre first, members in the order given) and
+    per member (score, band_w, passes).  A skipped group has L = 0, no rows and member scores None."""
+    __slots__ = ("status", "L", "row_off", "rows", "members")
+
+    def __init__(self, r, members, text):
+        self.status, self.L, self.row_off = int(r["status"]), int(r["L"]), int(r["row_off"])
+        ok = self.status == GALIGN_OK
+        self.rows = [text[self.row_off + i * self.L:self.row_off + (i + 1) * self.L] for i in range(int(r["ninst"]))] if ok else []
+        self.members = [(int(m["score"]) if ok else None, int(m["band_w"]), int(m["passes"])) for m in members[1:]]
+
+
 class SibeliaError(RuntimeError):
     pass
 
@@ -148,6 +169,9 @@ def load_library():
         L.sbl_align_pairs.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PairDesc)] + tail
         L.sbl_align_unique_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + tail
         L.sbl_align_stats.argtypes = [C.c_void_p, C.POINTER(AlignStats)]
+        gtail = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_align_groups.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(GroupInst)] + gtail
+        L.sbl_align_block_groups.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + gtail
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -345,8 +369,44 @@ class BlockFinder:
         descs = [(d[i].chr_a, d[i].start_a, d[i].end_a, bool(d[i].rev_a), d[i].chr_b, d[i].start_b, d[i].end_b, bool(d[i].rev_b)) for i in range(n.value)]
         return [int(x) for x in _view(ids.value, n.value, np.dtype("<i4"))], descs, self._pair_alignments(n.value, res, runs, nruns, rows, rows_len)
 
+    def _group_alignments(self, first, res, members, rows, rows_len) -> List[GroupAlignment]:
+        r = _view(res.value, len(first) - 1, GROUP_RESULT_DTYPE)
+        m = _view(members.value, int(first[-1]), MEMBER_RESULT_DTYPE)
+        text = C.string_at(rows.value, rows_len.value) if rows_len.value else b""
+        return [GroupAlignment(x, m[int(first[g]):int(first[g + 1])], text) for g, x in enumerate(r)]
+
+    def align_groups(self, groups: Sequence[Sequence[Tuple[int, int, int, bool]]]) -> List[GroupAlignment]:
+        """Centre-star multiple alignment (csrc/block_align.hip; defined in include/sibelia_amd.h) of groups of ranges of
+        the original records: per group a list of (chr, start, end, rev), half-open, the first one the centre."""
+        first = [0]
+        for g in groups:
+            first.append(first[-1] + len(g))
+        flat = [i for g in groups for i in g]
+        inst = (GroupInst * max(1, len(flat)))()
+        for d, i in zip(inst, flat):
+            d.chr, d.start, d.end, d.rev = [int(x) for x in i]
+        res, members, rows = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rows_len = C.c_uint64()
+        self._check(self.L.sbl_align_groups(self.h, len(groups), (C.c_uint64 * len(first))(*first), inst, C.byref(res), C.byref(members),
+                                            C.byref(rows), C.byref(rows_len)), "sbl_align_groups")
+        return self._group_alignments(first, res, members, rows, rows_len)
+
+    def align_block_groups(self, min_block_size: int):
+        """The multiple alignments of the current block list: every id with at least two instances of at least min_block_size bases, all
+        of them by ascending (chr, start, end, rev), the first one the centre.
+        -> (ids ascending, per id its [(chr, start, end, rev)], [GroupAlignment])."""
+        ids, first, inst, res, members, rows = (C.c_void_p() for _ in range(6))
+        n, rows_len = C.c_uint64(), C.c_uint64()
+        self._check(self.L.sbl_align_block_groups(self.h, min_block_size, C.byref(ids), C.byref(first), C.byref(inst), C.byref(n), C.byref(res),
+                                                  C.byref(members), C.byref(rows), C.byref(rows_len)), "sbl_align_block_groups")
+        f = [int(x) for x in _view(first.value, n.value + 1, np.dtype("<u8"))]
+        d = C.cast(inst, C.POINTER(GroupInst))
+        insts = [[(d[i].chr, d[i].start, d[i].end, bool(d[i].rev)) for i in range(f[g], f[g + 1])] for g in range(n.value)]
+        return [int(x) for x in _view(ids.value, n.value, np.dtype("<i4"))], insts, self._group_alignments(f, res, members, rows, rows_len)
+
     def align_stats(self) -> dict:
-        """Counters of the last align_pairs / align_unique_blocks: pairs, skipped, passes, launches, cells, kernel_ms, spell_ms."""
+        """Counters of the last align_pairs / align_unique_blocks / align_groups / align_block_groups: pairs, skipped, passes, launches,
+        cells, kernel_ms, spell_ms."""
         s = AlignStats()
         self._check(self.L.sbl_align_stats(self.h, C.byref(s)), "sbl_align_stats")
         return {f: getattr(s, f) for f, _ in s._fields_}

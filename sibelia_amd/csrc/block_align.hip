@@ -21,6 +21,9 @@
 //             run by binary search over offsets the host made from the runs, and writes them with one vector store.
 //   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
 //             grouped by band class (register / LDS 256 / LDS 1024) and chunked under the total cap on the trace codes.
+//   groups    sbl_align_groups / sbl_align_block_groups: a centre-star multiple alignment per group of instances.  Every
+//             member against the group's first instance through the same passes (ga_passes); the gap slots of a group merged on the
+//             host from the runs; k_spell_groups spells the rows, output-stationary like k_spell_rows.
 #include <algorithm>
 #include <cstring>
 
@@ -267,6 +270,76 @@ __global__ __launch_bounds__(GS_THREADS) void k_spell_rows(const uint8_t *__rest
 	out[t0 / 16] = make_uint4((unsigned)wlo, (unsigned)(wlo >> 32), (unsigned)whi, (unsigned)(whi >> 32));
 }
 
+// ---- spelling of groups: the rows of a centre-star multiple alignment
+
+struct GmInst { u64 src, first_span; unsigned len, rev, nspans, pad_; };       // a row: its range; a member's spans (of the pair centre / member)
+struct GmSlot { u64 col; unsigned p, G; };                                    // gap slot p: G columns from column col = p + the G of the slots before it
+struct GmGroup { u64 toff, L, first_inst, first_slot; unsigned ninst, nslots; };      // toff: the group's text (ninst L bytes); slot 0 always listed
+
+// Output-stationary like k_spell_rows: a lane owns 16 bytes of the text.  Group by binary search over text offsets, then row and column;
+// the column's slot by binary search over the group's merged slots, a member's run by binary search over its spans by centre index.
+// From there the lane steps byte by byte: slot, span, row and group advance as the column does.
+__global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__restrict__ seq, const GmGroup *__restrict__ groups, u64 ngroups,
+                                                             const GmInst *__restrict__ insts, const GmSlot *__restrict__ slots,
+                                                             const GaSpan *__restrict__ spans, u64 total, uint4 *__restrict__ out)
+{
+	const u64 t0 = ((u64)blockIdx.x * GS_THREADS + threadIdx.x) * 16;
+	if (t0 >= total) return;
+	u64 gi = ga_find(0, ngroups, [&](u64 x) { return groups[x].toff <= t0; });
+	GmGroup Q = groups[gi];
+	u64 off = t0 - Q.toff, row = 0, col = 0, si = 0, xi = 0;
+	GmInst I{};
+	GmSlot S{};
+	u64 next_col = 0;                                                         // where the next slot starts (L: none)
+	auto set_slot = [&]() {
+		S = slots[Q.first_slot + si];
+		next_col = si + 1 < Q.nslots ? slots[Q.first_slot + si + 1].col : Q.L;
+	};
+	auto seek = [&]() {                                                       // (group, off) -> row, column, slot and span; false: the text is exhausted
+		while (off >= (u64)Q.ninst * Q.L) {
+			off -= (u64)Q.ninst * Q.L;
+			if (++gi >= ngroups) return false;
+			Q = groups[gi];
+		}
+		row = off / Q.L;
+		col = off - row * Q.L;
+		I = insts[Q.first_inst + row];
+		si = ga_find(0, Q.nslots, [&](u64 x) { return slots[Q.first_slot + x].col <= col; });
+		set_slot();
+		if (row && I.nspans) {
+			const u64 o = col - S.col;
+			const unsigned q = o < S.G ? S.p : S.p + (unsigned)(o - S.G);      // the centre index this column belongs to
+			xi = ga_find(I.first_span, I.first_span + I.nspans, [&](u64 x) { return spans[x].ai <= q; });
+		}
+		return true;
+	};
+	u64 wlo = 0, whi = 0;
+	bool live = seek();
+	for (unsigned b = 0; b < 16 && live && t0 + b < total; b++) {
+		if (col == Q.L) { live = seek(); if (!live) break; }
+		else if (col == next_col) { si++; set_slot(); }
+		const u64 o = col - S.col;
+		const bool in_slot = o < S.G;
+		const unsigned q = in_slot ? S.p : S.p + (unsigned)(o - S.G);
+		unsigned char ch = '-';
+		if (row == 0) {
+			if (!in_slot) ch = I.rev ? complement1(seq[I.src + (I.len - 1 - q)]) : seq[I.src + q];
+		} else if (I.nspans) {
+			while (xi + 1 < I.first_span + I.nspans && spans[xi + 1].ai <= q) xi++;      // the last span that starts at or before centre index q
+			GaSpan R = spans[xi];
+			long long bj = -1;                                                // the member's base in this column
+			if (in_slot) {                                                    // its 'D' run in slot p: R itself (the last run), or the run before R
+				if (R.op != 'D' && R.ai == q && xi > I.first_span) R = spans[xi - 1];
+				if (R.op == 'D' && R.ai == q && o < R.len) bj = (long long)R.bj + (long long)o;
+			} else if (R.op != 'I' && R.op != 'D') bj = (long long)R.bj + (q - R.ai);
+			if (bj >= 0) ch = I.rev ? complement1(seq[I.src + (I.len - 1 - (u64)bj)]) : seq[I.src + (u64)bj];
+		}
+		if (b < 8) wlo |= (u64)ch << (8 * b); else whi |= (u64)ch << (8 * (b - 8));
+		col++; off++;
+	}
+	out[t0 / 16] = make_uint4((unsigned)wlo, (unsigned)(wlo >> 32), (unsigned)whi, (unsigned)(whi >> 32));
+}
+
 // ---- host
 
 unsigned ga_env(const char *name, unsigned fallback)
@@ -335,8 +408,8 @@ void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<siz
 	}
 }
 
-// aligns c->ga_desc (checked) into c->ga_res / ga_runs and spells the rows into h_bs_text
-void ga_run(sbl_ctx *c, u64 *rows_len)
+// the pair passes every sbl_align_* call shares: aligns c->ga_desc (checked) into c->ga_res / ga_runs; jobs: where each pair's bases lie
+void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 {
 	const std::vector<sbl_pair_desc> &desc = c->ga_desc;
 	const size_t N = desc.size();
@@ -346,7 +419,7 @@ void ga_run(sbl_ctx *c, u64 *rows_len)
 	c->align_stats.pairs = N;
 	c->ga_res.assign(N, sbl_pair_result{});
 	c->ga_runs.clear();
-	std::vector<GaJob> jobs(N);
+	jobs.assign(N, GaJob{});
 	std::vector<Pending> pending;
 	for (size_t i = 0; i < N; i++) {
 		const sbl_pair_desc &d = desc[i];
@@ -385,6 +458,53 @@ void ga_run(sbl_ctx *c, u64 *rows_len)
 		pending.swap(again);
 	}
 	c->stats.device_bytes = sbl_devbuf_total().load();
+}
+
+// the runs of pair i as spans, appended; false: they do not spell its two ranges
+bool ga_spans_of(const sbl_ctx *c, size_t i, const GaJob &j, std::vector<GaSpan> &spans, u64 *L)
+{
+	const sbl_pair_result &r = c->ga_res[i];
+	unsigned ai = 0, bj = 0;
+	u64 col = 0;
+	for (u64 k = 0; k < r.nruns; k++) {
+		const sbl_align_run &run = c->ga_runs[r.first_run + k];
+		spans.push_back(GaSpan{col, ai, bj, run.op, run.len});
+		col += run.len;
+		if (run.op != 'D') ai += run.len;
+		if (run.op != 'I') bj += run.len;
+	}
+	*L = col;
+	return ai == j.n && bj == j.m;
+}
+
+// text made on the device: uploads nothing itself, runs `launch` between the events of spell_ms and brings `total` bytes of d_ga_text
+// back through h_bs_text
+template <class F> void ga_fetch_text(sbl_ctx *c, u64 total, F launch)
+{
+	hipStream_t s = c->stream;
+	const size_t padded = (size_t)((total + 15) / 16 * 16);
+	const u64 groups = (padded / 16 + GS_THREADS - 1) / GS_THREADS;
+	SBL_CHECK(groups < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
+	c->d_ga_text.ensure(padded);
+	sbl_text_staging(c, padded);
+	HIP_TRY(hipEventRecord(c->ev[0], s));
+	launch((unsigned)groups, s);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(c->ev[1], s));
+	HIP_TRY(hipMemcpyAsync(c->h_bs_text, c->d_ga_text.p, padded, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	float ms = 0;
+	(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+	c->align_stats.spell_ms = ms;
+	c->stats.device_bytes = sbl_devbuf_total().load();
+}
+
+// aligns c->ga_desc (checked) into c->ga_res / ga_runs and spells the rows into h_bs_text
+void ga_run(sbl_ctx *c, u64 *rows_len)
+{
+	std::vector<GaJob> jobs;
+	ga_passes(c, jobs);
+	const size_t N = jobs.size();
 
 	// ---- rows: per aligned pair 2 L bytes, spelled from the runs
 	std::vector<GaPair> pairs;
@@ -394,40 +514,125 @@ void ga_run(sbl_ctx *c, u64 *rows_len)
 		sbl_pair_result &r = c->ga_res[i];
 		if (r.status != SBL_GALIGN_OK) { r = sbl_pair_result{SBL_GALIGN_SKIPPED, 0, r.band_w, r.passes, 0, 0, 0, 0}; c->align_stats.skipped++; continue; }
 		GaPair P{jobs[i].src_a, jobs[i].src_b, total, spans.size(), jobs[i].n, jobs[i].m, jobs[i].rev_a, jobs[i].rev_b, (unsigned)r.nruns, 0, 0};
-		unsigned ai = 0, bj = 0;
-		for (u64 k = 0; k < r.nruns; k++) {
-			const sbl_align_run &run = c->ga_runs[r.first_run + k];
-			spans.push_back(GaSpan{P.L, ai, bj, run.op, run.len});
-			P.L += run.len;
-			if (run.op != 'D') ai += run.len;
-			if (run.op != 'I') bj += run.len;
-		}
-		SBL_CHECK(ai == P.n && bj == P.m, SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
+		SBL_CHECK(ga_spans_of(c, i, jobs[i], spans, &P.L), SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
 		r.row_off = total; r.row_len = P.L;
 		total += 2 * P.L;
 		if (P.L) pairs.push_back(P);
 	}
 	if (total) {
-		hipStream_t s = c->stream;
-		const size_t padded = (size_t)((total + 15) / 16 * 16);
-		const u64 groups = (padded / 16 + GS_THREADS - 1) / GS_THREADS;
-		SBL_CHECK(groups < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
-		c->d_ga_pair.ensure(pairs.size() * sizeof(GaPair)); c->d_ga_span.ensure(spans.size() * sizeof(GaSpan)); c->d_ga_text.ensure(padded);
-		sbl_text_staging(c, padded);
-		HIP_TRY(hipMemcpyAsync(c->d_ga_pair.p, pairs.data(), pairs.size() * sizeof(GaPair), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(c->d_ga_span.p, spans.data(), spans.size() * sizeof(GaSpan), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipEventRecord(c->ev[0], s));
-		k_spell_rows<<<(unsigned)groups, GS_THREADS, 0, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_pair.as<GaPair>(), pairs.size(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(c->ev[1], s));
-		HIP_TRY(hipMemcpyAsync(c->h_bs_text, c->d_ga_text.p, padded, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-		c->align_stats.spell_ms = ms;
-		c->stats.device_bytes = sbl_devbuf_total().load();
+		c->d_ga_pair.ensure(pairs.size() * sizeof(GaPair)); c->d_ga_span.ensure(spans.size() * sizeof(GaSpan));
+		HIP_TRY(hipMemcpyAsync(c->d_ga_pair.p, pairs.data(), pairs.size() * sizeof(GaPair), hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(c->d_ga_span.p, spans.data(), spans.size() * sizeof(GaSpan), hipMemcpyHostToDevice, c->stream));
+		ga_fetch_text(c, total, [&](unsigned groups, hipStream_t s) {
+			k_spell_rows<<<groups, GS_THREADS, 0, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_pair.as<GaPair>(), pairs.size(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
+		});
 	}
 	*rows_len = total;
+}
+
+// aligns the groups c->gm_first / gm_inst (checked) into c->gm_res / gm_members and spells their rows into h_bs_text: every member against
+// its centre through the pair passes, then per group the merge of the gap slots -- on the host, from the runs: they are here already and
+// their number follows the edits, not the bases -- and one launch of k_spell_groups for the text
+void gm_run(sbl_ctx *c, u64 *rows_len)
+{
+	const std::vector<uint64_t> &first = c->gm_first;
+	const std::vector<sbl_group_inst> &inst = c->gm_inst;
+	const size_t NG = first.size() - 1;
+	c->ga_ids.clear(); c->ga_desc.clear();
+	for (size_t g = 0; g < NG; g++) {
+		const sbl_group_inst &ctr = inst[first[g]];
+		for (u64 k = first[g] + 1; k < first[g + 1]; k++)
+			c->ga_desc.push_back(sbl_pair_desc{ctr.chr, ctr.start, ctr.end, ctr.rev, inst[k].chr, inst[k].start, inst[k].end, inst[k].rev});
+	}
+	std::vector<GaJob> jobs;
+	ga_passes(c, jobs);
+
+	c->gm_res.assign(NG, sbl_group_result{});
+	c->gm_members.assign(inst.size(), sbl_member_result{});
+	std::vector<GmGroup> groups;
+	std::vector<GmInst> rows;
+	std::vector<GmSlot> slots;
+	std::vector<GaSpan> spans;
+	std::vector<std::pair<unsigned, unsigned>> runs_d;                          // (slot, length) of the 'D' runs of a group's members
+	u64 total = 0;
+	size_t pair = 0;
+	for (size_t g = 0; g < NG; g++) {
+		const size_t r = (size_t)(first[g + 1] - first[g]), pair0 = pair;
+		sbl_group_result &res = c->gm_res[g];
+		res.ninst = (uint32_t)r;
+		bool ok = true;
+		for (size_t k = 1; k < r; k++, pair++) {
+			const sbl_pair_result &pr = c->ga_res[pair];
+			if (pr.status != SBL_GALIGN_OK) { ok = false; c->align_stats.skipped++; }
+			c->gm_members[first[g] + k] = sbl_member_result{pr.status == SBL_GALIGN_OK ? pr.score : 0, pr.band_w, pr.passes};
+		}
+		const sbl_group_inst &ctr = inst[first[g]];
+		if (!ok) {
+			res.status = SBL_GALIGN_SKIPPED;
+			for (size_t k = 1; k < r; k++) c->gm_members[first[g] + k].score = 0;
+			continue;
+		}
+		const unsigned n = (unsigned)(ctr.end - ctr.start);
+		GmGroup Q{total, 0, rows.size(), slots.size(), (unsigned)r, 0};
+		rows.push_back(GmInst{(u64)c->orig_sepidx[ctr.chr] + 1 + ctr.start, 0, n, ctr.rev != 0, 0, 0});
+		runs_d.clear();
+		for (size_t k = 1; k < r; k++) {
+			const size_t i = pair0 + k - 1;
+			const size_t at = spans.size();
+			u64 L2 = 0;
+			SBL_CHECK(ga_spans_of(c, i, jobs[i], spans, &L2), SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
+			rows.push_back(GmInst{jobs[i].src_b, at, jobs[i].m, jobs[i].rev_b, (unsigned)(spans.size() - at), 0});
+			for (size_t x = at; x < spans.size(); x++) if (spans[x].op == 'D') runs_d.push_back({spans[x].ai, spans[x].len});
+		}
+		std::sort(runs_d.begin(), runs_d.end());                                // by slot, the longest run of a slot last
+		u64 shift = 0;
+		if (runs_d.empty() || runs_d[0].first != 0) slots.push_back(GmSlot{0, 0, 0});
+		for (size_t x = 0; x < runs_d.size(); x++) {
+			if (x + 1 < runs_d.size() && runs_d[x + 1].first == runs_d[x].first) continue;
+			slots.push_back(GmSlot{runs_d[x].first + shift, runs_d[x].first, runs_d[x].second});
+			shift += runs_d[x].second;
+		}
+		Q.nslots = (unsigned)(slots.size() - Q.first_slot);
+		Q.L = (u64)n + shift;
+		res.L = Q.L; res.row_off = total;
+		total += (u64)r * Q.L;
+		if (Q.L) groups.push_back(Q);
+	}
+	if (total) {
+		hipStream_t s = c->stream;
+		c->d_gm_group.ensure(groups.size() * sizeof(GmGroup)); c->d_gm_inst.ensure(rows.size() * sizeof(GmInst));
+		c->d_gm_slot.ensure(slots.size() * sizeof(GmSlot)); c->d_ga_span.ensure(std::max<size_t>(1, spans.size()) * sizeof(GaSpan));
+		HIP_TRY(hipMemcpyAsync(c->d_gm_group.p, groups.data(), groups.size() * sizeof(GmGroup), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(c->d_gm_inst.p, rows.data(), rows.size() * sizeof(GmInst), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemcpyAsync(c->d_gm_slot.p, slots.data(), slots.size() * sizeof(GmSlot), hipMemcpyHostToDevice, s));
+		if (!spans.empty()) HIP_TRY(hipMemcpyAsync(c->d_ga_span.p, spans.data(), spans.size() * sizeof(GaSpan), hipMemcpyHostToDevice, s));
+		ga_fetch_text(c, total, [&](unsigned blocks, hipStream_t st) {
+			k_spell_groups<<<blocks, GS_THREADS, 0, st>>>(c->d_orig_ch.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), groups.size(), c->d_gm_inst.as<GmInst>(),
+			                                               c->d_gm_slot.as<GmSlot>(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
+		});
+	}
+	*rows_len = total;
+}
+
+void gm_check(const sbl_ctx *c, u64 ngroups, const uint64_t *first, const sbl_group_inst *inst)
+{
+	SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+	SBL_CHECK(ngroups == 0 || (first && inst), SBL_ERR_BAD_ARG, "null group descriptors");
+	SBL_CHECK(ngroups == 0 || first[0] == 0, SBL_ERR_BAD_ARG, "the first group does not start at instance 0");
+	for (u64 g = 0; g < ngroups; g++) SBL_CHECK(first[g + 1] > first[g], SBL_ERR_BAD_ARG, "an empty group");
+	for (u64 i = 0; ngroups && i < first[ngroups]; i++) {
+		SBL_CHECK(inst[i].chr < c->nchr, SBL_ERR_BAD_ARG, "an instance on a record that does not exist");
+		SBL_CHECK(inst[i].end >= inst[i].start, SBL_ERR_BAD_ARG, "a range ends before it starts");
+		SBL_CHECK(inst[i].end <= (u64)(c->orig_sepidx[inst[i].chr + 1] - c->orig_sepidx[inst[i].chr] - 1), SBL_ERR_BAD_ARG, "a range runs beyond its record");
+	}
+}
+
+void gm_hand_out(sbl_ctx *c, u64 rows_len, const sbl_group_result **res, const sbl_member_result **members, const char **rows, uint64_t *rl)
+{
+	if (res) *res = c->gm_res.data();
+	if (members) *members = c->gm_members.data();
+	if (rows) *rows = rows_len ? c->h_bs_text : "";
+	if (rl) *rl = rows_len;
 }
 
 void ga_check(const sbl_ctx *c, const sbl_pair_desc *d, u64 n)
@@ -503,5 +708,59 @@ extern "C" sbl_status sbl_align_unique_blocks(sbl_ctx *c, uint32_t min_block_siz
 		if (desc) *desc = c->ga_desc.data();
 		if (n) *n = c->ga_desc.size();
 		ga_hand_out(c, total, res, runs, nruns, rows, rows_len);
+	});
+}
+
+extern "C" sbl_status sbl_align_groups(sbl_ctx *c, uint64_t ngroups, const uint64_t *group_first, const sbl_group_inst *inst,
+                                       const sbl_group_result **res, const sbl_member_result **members, const char **rows, uint64_t *rows_len)
+{
+	return guarded(c, [&] {
+		gm_check(c, ngroups, group_first, inst);
+		if (ngroups) { c->gm_first.assign(group_first, group_first + ngroups + 1); c->gm_inst.assign(inst, inst + group_first[ngroups]); }
+		else { c->gm_first.assign(1, 0); c->gm_inst.clear(); }
+		u64 total = 0;
+		gm_run(c, &total);
+		gm_hand_out(c, total, res, members, rows, rows_len);
+	});
+}
+
+extern "C" sbl_status sbl_align_block_groups(sbl_ctx *c, uint32_t min_block_size, const int32_t **ids, const uint64_t **group_first,
+                                             const sbl_group_inst **inst, uint64_t *ngroups, const sbl_group_result **res,
+                                             const sbl_member_result **members, const char **rows, uint64_t *rows_len)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+		SBL_CHECK(c->have_blocks, SBL_ERR_BAD_ARG, "no block list: run sbl_generate_blocks / sbl_postprocess first");
+		sbl_check_blocks(c, c->blocks.data(), c->blocks.size());
+		std::vector<sbl_block> v;
+		for (const sbl_block &b : c->blocks) if (b.end - b.start >= min_block_size) v.push_back(b);
+		// by id, then (chr, start, end, rev): a total order up to identical instances, so the centre does not depend on the sort
+		std::sort(v.begin(), v.end(), [](const sbl_block &x, const sbl_block &y) {
+			if (std::abs(x.id) != std::abs(y.id)) return std::abs(x.id) < std::abs(y.id);
+			if (x.chr != y.chr) return x.chr < y.chr;
+			if (x.start != y.start) return x.start < y.start;
+			if (x.end != y.end) return x.end < y.end;
+			return (x.id < 0) < (y.id < 0);
+		});
+		std::vector<int32_t> group_ids;
+		c->gm_first.assign(1, 0); c->gm_inst.clear();
+		for (size_t i = 0; i < v.size();) {
+			size_t j = i;
+			while (j < v.size() && std::abs(v[j].id) == std::abs(v[i].id)) j++;
+			if (j - i >= 2) {
+				group_ids.push_back(std::abs(v[i].id));
+				for (size_t k = i; k < j; k++) c->gm_inst.push_back(sbl_group_inst{v[k].chr, v[k].start, v[k].end, v[k].id < 0});
+				c->gm_first.push_back(c->gm_inst.size());
+			}
+			i = j;
+		}
+		u64 total = 0;
+		gm_run(c, &total);                                                      // (clears ga_ids)
+		c->ga_ids = group_ids;
+		if (ids) *ids = c->ga_ids.data();
+		if (group_first) *group_first = c->gm_first.data();
+		if (inst) *inst = c->gm_inst.data();
+		if (ngroups) *ngroups = c->gm_first.size() - 1;
+		gm_hand_out(c, total, res, members, rows, rows_len);
 	});
 }

@@ -107,6 +107,13 @@ struct sbl_ctx {
 	std::vector<sbl_pair_desc> ga_desc;
 	std::vector<int32_t> ga_ids;
 	sbl_align_stats_t align_stats{};
+	// sbl_align_groups / sbl_align_block_groups: the same pair passes (ga_desc: centre against member); instances, merged gap slots and
+	// groups of k_spell_groups; what the calls hand out
+	DevBuf d_gm_inst, d_gm_slot, d_gm_group;
+	std::vector<uint64_t> gm_first;
+	std::vector<sbl_group_inst> gm_inst;
+	std::vector<sbl_group_result> gm_res;
+	std::vector<sbl_member_result> gm_members;
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;

@@ -6,7 +6,8 @@ with and without -r, and the choice of which files are written.  `run` returns (
 standard output); `main` writes the files and prints the text (python -m sibelia_amd).
 
 --maf / --variants (two input files) add what the reference's comparison tool C-Sibelia.py makes of such a run: the alignments of the
-unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).
+unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).  --multimaf (any number of input files) writes a
+multiple alignment of every block with at least two instances (`align_block_groups`).
 
 Not written: circos/ and d3_blocks_diagram.html -- the reference instantiates them from templates embedded in its own sources.
 
@@ -30,8 +31,13 @@ PARAMETER_SETS = {
     "far": [(15, 120), (100, 500), (500, 1500)],
 }
 
-ALIGN_HELP = ("Blocks that are not unique -- more or fewer than two instances, or not one in each input file -- are not aligned: "
-              "the reference's comparison tool hands them to mlagan, which is out of scope.")
+ALIGN_HELP = ("Blocks that are not unique -- more or fewer than two instances, or not one in each input file -- are not aligned here: "
+              "the reference's comparison tool hands them to mlagan.  See --multimaf.")
+
+MULTI_HELP = ("Any number of input files: align every synteny block with at least two instances, all of its instances, base by base on the "
+              "device and write one MAF paragraph per block.  The alignment is centre-star on the block's first instance (by record, start, "
+              "end, strand): every other instance is aligned to it as under --maf and the gaps are merged.  It is this program's own "
+              "definition, not mlagan's, which the reference's comparison tool runs on such blocks.")
 
 NOT_WRITTEN = ("The Circos files (circos/) and d3_blocks_diagram.html of the reference program are not written: "
                "they are instantiated from templates embedded in the reference's sources.")
@@ -143,6 +149,7 @@ def build_parser() -> argparse.ArgumentParser:
                    "on the device and write the alignments in MAF format.  " + ALIGN_HELP)
     p.add_argument("--variants", default=None, metavar="FILE", help="Two input files: write the SNVs and indels read off those alignments in VCF format "
                    "(positions on the records of the first file).")
+    p.add_argument("--multimaf", default=None, metavar="FILE", help=MULTI_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
     return p
@@ -160,19 +167,24 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
             raise PipelineError("In alignment mode only two FASTA files are acceptable")
         if opt.noblocks:
             raise PipelineError("--maf and --variants need the synteny blocks: they cannot be combined with --noblocks")
+    if opt.multimaf is not None and opt.noblocks:
+        raise PipelineError("--multimaf needs the synteny blocks: it cannot be combined with --noblocks")
+    if opt.maf is not None or opt.variants is not None or opt.multimaf is not None:
         _check_alignment_files(opt)
     return opt
 
 
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --multimaf name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
-    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants)) if f is not None]
+    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--multimaf", opt.multimaf)) if f is not None]
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
-    if len(given) == 2 and where(opt.maf) == where(opt.variants):
-        raise PipelineError("--maf and --variants name the same file: " + opt.maf)
+    for i, (o, f) in enumerate(given):
+        for o2, f2 in given[i + 1:]:
+            if where(f) == where(f2):
+                raise PipelineError("%s and %s name the same file: %s" % (o, o2, f))
     fixed = ["blocks_coords.txt", "blocks_coords.gff", "genomes_permutations.txt", "coverage_report.txt", "blocks_sequences.fasta"]
     taken = re.compile(r"(blocks_coords\d+\.(txt|gff)|de_bruijn_graph\d*\.dot)$")
     outdir = os.path.abspath(opt.outdir)
@@ -231,7 +243,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for f in (opt.maf, opt.variants) if f is not None]      # relative names: under the output directory
+        out += [f for f in (opt.maf, opt.variants, opt.multimaf) if f is not None]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -359,6 +371,26 @@ def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirs
     return out
 
 
+def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], complain: Callable[[str], None]) -> Dict[str, bytes]:
+    """--multimaf: one MAF paragraph per block with at least two instances, in ascending id, its `s` lines in the order of the alignment
+    (centre first: BlockFinder.align_block_groups).  A skipped block is named through `complain` in one line and is absent."""
+    from . import formats
+    from .api import GALIGN_OK, SibeliaError
+    try:
+        ids, insts, aligned = bf.align_block_groups(opt.minblocksize)
+    except SibeliaError as e:
+        raise PipelineError(str(e))
+    size = bf.record_sizes()
+    groups = []
+    for block, inst, al in zip(ids, insts, aligned):
+        if al.status != GALIGN_OK:
+            complain("block %d not aligned: one of its %d instances against %s:%d-%d is beyond the limits of one alignment "
+                     "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2]))
+            continue
+        groups.append([formats.maf_line(names[c], s, e, rev, size[c], row) for (c, s, e, rev), row in zip(inst, al.rows)])
+    return {opt.multimaf: formats.maf_text(groups)}
+
+
 # ------------------------------------------------------------------------------------------ main
 
 def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outdir_exists: Optional[bool] = None) -> Tuple[int, Dict[str, bytes], str]:
@@ -421,6 +453,8 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 files["blocks_sequences.fasta"] = bf.blocks_sequences(None, names)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write))
+            if opt.multimaf is not None:          # likewise on the final list
+                files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
     finally:
