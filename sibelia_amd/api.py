@@ -295,14 +295,19 @@ class BlockFinder:
 
     generate_blocks = GenerateSyntenyBlocks
 
+    def _names_array(self, what: str, names: Optional[Sequence[str]]):
+        """`names` as the `const char *const *` of the C entry points, which read one name per loaded record (include/sibelia_amd.h);
+        None stays NULL: the names of the loaded records."""
+        if names is None:
+            return None
+        if len(names) != self.L.sbl_nchr(self.h):
+            raise ValueError("%s: %d names for %d records" % (what, len(names), self.L.sbl_nchr(self.h)))
+        return (C.c_char_p * len(names))(*[x.encode() for x in names])
+
     def postprocess(self, names: Optional[Sequence[str]] = None, glue: bool = True):
         """GlueStripes (reference src/postprocessor.cpp:37-154) on the blocks of the last GenerateSyntenyBlocks + the texts of
         blocks_coords.txt, genomes_permutations.txt, coverage_report.txt (src/outputgenerator.cpp:162-233)."""
-        nm = None
-        if names is not None:
-            if len(names) != self.L.sbl_nchr(self.h):      # the C entry point reads one name per loaded record (include/sibelia_amd.h)
-                raise ValueError("postprocess: %d names for %d records" % (len(names), self.L.sbl_nchr(self.h)))
-            nm = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        nm = self._names_array("postprocess", names)
         b, n = C.c_void_p(), C.c_uint64()
         t = [C.c_char_p() for _ in range(3)]
         self._check(self.L.sbl_postprocess(self.h, int(glue), nm, C.byref(b), C.byref(n), C.byref(t[0]), C.byref(t[1]), C.byref(t[2])), "sbl_postprocess")
@@ -312,11 +317,7 @@ class BlockFinder:
         """Postprocessor::ImproveBlockBoundaries (reference src/postprocessor.cpp:156-348; --correctboundaries) on the blocks of the last
         postprocess: records 0 .. n_reference_chr - 1 are the reference set.  Replaces the context's list; returns it and the three
         texts of postprocess rendered again.  The alignments run in batches on the device (csrc/boundary_align.hip)."""
-        nm = None
-        if names is not None:
-            if len(names) != self.L.sbl_nchr(self.h):
-                raise ValueError("correct_boundaries: %d names for %d records" % (len(names), self.L.sbl_nchr(self.h)))
-            nm = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        nm = self._names_array("correct_boundaries", names)
         b, n = C.c_void_p(), C.c_uint64()
         t = [C.c_char_p() for _ in range(3)]
         self._check(self.L.sbl_correct_boundaries(self.h, min_block_size, n_reference_chr, nm, C.byref(b), C.byref(n),
@@ -412,11 +413,7 @@ class BlockFinder:
         return {f: getattr(s, f) for f, _ in s._fields_}
 
     def _block_report(self, fn, what, blocks, names) -> bytes:
-        nm = None
-        if names is not None:
-            if len(names) != self.L.sbl_nchr(self.h):      # the C entry points read one name per loaded record
-                raise ValueError("%s: %d names for %d records" % (what, len(names), self.L.sbl_nchr(self.h)))
-            nm = (C.c_char_p * len(names))(*[x.encode() for x in names])
+        nm = self._names_array(what, names)
         b, n = None, 0
         if blocks is not None:
             arr = np.ascontiguousarray(blocks, dtype=formats.BLOCK_DTYPE)

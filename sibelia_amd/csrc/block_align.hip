@@ -1,6 +1,6 @@
 // block_align.hip -- base-by-base alignment of the two instances of every unique block: the step the reference's comparison tool
 // C-Sibelia.py (reference src/csibelia/C-Sibelia.py:274-309) leaves to one external LAGAN process per block.  The alignment is defined by
-// this project (include/sibelia_amd.h): a banded GLOBAL alignment with the scores of boundary_align.hip (+25 / -75 / -75,
+// this project (include/sibelia_amd.h): a banded GLOBAL alignment with the scores of sbl_align.h (+25 / -75 / -75,
 // 32 bit), filled from the ends so that the trace runs forward, with a certificate that the band lost nothing.
 //
 //   band      offsets k = j - i - lo + w, 0 <= k < W = |m - n| + 2 w + 1.  On the anti-diagonal d = i + j only the offsets of one
@@ -17,24 +17,22 @@
 //             staged from the original records (a reverse instance downwards through complement1).
 //   trace     one wave: lane t fetches the code t steps ahead along the direction of the current step, one ballot consumes the run.
 //             It emits runs (op, length); the certificate is checked first -- a pair that fails it is not traced.
-//   spelling  k_spell_rows, output-stationary like blockseq.hip: a lane owns 16 bytes of the two gapped rows, finds its pair and its
-//             run by binary search over offsets the host made from the runs, and writes them with one vector store.
+//   spelling  k_spell_groups, output-stationary like blockseq.hip: a lane owns 16 bytes of the rows, finds its group, its row and its
+//             run by binary search over tables the host made from the runs, and writes them with one vector store.  The two gapped
+//             rows of a pair are the rows of a group of one member (gm_spell).
 //   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
 //             grouped by band class (register / LDS 256 / LDS 1024) and chunked under the total cap on the trace codes.
 //   groups    sbl_align_groups / sbl_align_block_groups: a centre-star multiple alignment per group of instances.  Every
 //             member against the group's first instance through the same passes (ga_passes); the gap slots of a group merged on the
-//             host from the runs; k_spell_groups spells the rows, output-stationary like k_spell_rows.
+//             host from the runs; k_spell_groups spells the rows.
 #include <algorithm>
 #include <cstring>
 
-#include "sbl_ctx.h"
-#include "sbl_dna.h"
+#include "sbl_align.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int GA_MATCH = 25, GA_PENALTY = 75, GA_NEG = -(1 << 30);
+constexpr int GA_NEG = -(1 << 30);
 constexpr int GA_CHUNK = 64;                           // diagonals per staged stretch of bases
 constexpr unsigned GA_REG_W = 512, GA_MID_W = 4096, GA_MAX_W = 12288;      // band offsets: one wave in registers / 256 lanes / 1024 lanes (LDS: 4 (W + 2) + 2 (W / 2 + 40) <= 64 KiB)
 constexpr u64 GA_MAX_DIAG = 1ull << 23;                // 75 (n + m) stays clear of GA_NEG
@@ -53,7 +51,7 @@ struct GaOut { int score; unsigned nruns, ok, pad_; };
 __host__ __device__ inline int ga_bound(int n, int m, int w)
 {
 	const int mn = n < m ? n : m, diff = n < m ? m - n : n - m;
-	return GA_MATCH * (mn - (w + 1)) - GA_PENALTY * (diff + 2 * (w + 1));
+	return AL_MATCH * (mn - (w + 1)) - AL_PENALTY * (diff + 2 * (w + 1));
 }
 
 __device__ inline unsigned ga_seg(unsigned W) { return (W + GA_CHUNK) / 2 + 8; }      // bytes of a staged stretch
@@ -61,7 +59,7 @@ __device__ inline unsigned ga_seg(unsigned W) { return (W + GA_CHUNK) / 2 + 8; }
 // one cell: the neighbours' scores in, score and trace code out
 __device__ inline int ga_cell(int g, int up, int lf, bool eq, unsigned &code)
 {
-	const int dg = g + (eq ? GA_MATCH : -GA_PENALTY), u = up - GA_PENALTY, l = lf - GA_PENALTY;
+	const int dg = g + (eq ? AL_MATCH : -AL_PENALTY), u = up - AL_PENALTY, l = lf - AL_PENALTY;
 	int val = dg > u ? dg : u;
 	val = l > val ? l : val;
 	code = dg == val ? (eq ? 0u : 1u) : u == val ? 2u : 3u;
@@ -85,7 +83,7 @@ template <int P> __device__ inline unsigned ga_quad_reg(const GaView &V, int d, 
 		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
 		int val;
 		unsigned code = 0;
-		if (i == V.n || j == V.m) val = -GA_PENALTY * ((V.n - i) + (V.m - j));
+		if (i == V.n || j == V.m) val = -AL_PENALTY * ((V.n - i) + (V.m - j));
 		else {
 			const int up = P == 0 && c == 0 ? prev : s[2 * c + P - 1 < 0 ? 0 : 2 * c + P - 1];
 			const int lf = P == 1 && c == 3 ? next : s[2 * c + P + 1 > 7 ? 7 : 2 * c + P + 1];
@@ -110,7 +108,7 @@ __device__ inline unsigned ga_quad_lds(const GaView &V, int d, int q, int p, int
 		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
 		int val;
 		unsigned code = 0;
-		if (i == V.n || j == V.m) val = -GA_PENALTY * ((V.n - i) + (V.m - j));
+		if (i == V.n || j == V.m) val = -AL_PENALTY * ((V.n - i) + (V.m - j));
 		else val = ga_cell(S[k + 1], S[k], S[k + 2], V.sa[i - V.imin] == V.sb[j - V.jmin], code);
 		S[k + 1] = val;
 		if (d == 0) score = val;
@@ -155,14 +153,8 @@ template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_a
 		imin = imin < 0 ? 0 : imin; imax = imax > n - 1 ? n - 1 : imax;
 		jmin = jmin < 0 ? 0 : jmin; jmax = jmax > m - 1 ? m - 1 : jmax;
 		__syncthreads();                                                    // the previous stretch is no longer read
-		for (int t = tid; t <= imax - imin; t += T) {
-			const unsigned i = (unsigned)(imin + t);
-			sa[t] = J.rev_a ? complement1(seq[J.src_a + ((unsigned)n - 1 - i)]) : seq[J.src_a + i];
-		}
-		for (int t = tid; t <= jmax - jmin; t += T) {
-			const unsigned j = (unsigned)(jmin + t);
-			sb[t] = J.rev_b ? complement1(seq[J.src_b + ((unsigned)m - 1 - j)]) : seq[J.src_b + j];
-		}
+		for (int t = tid; t <= imax - imin; t += T) sa[t] = strand_base(seq, J.src_a, J.n, (unsigned)(imin + t), J.rev_a);
+		for (int t = tid; t <= jmax - jmin; t += T) sb[t] = strand_base(seq, J.src_b, J.m, (unsigned)(jmin + t), J.rev_b);
 		V.imin = imin; V.jmin = jmin;
 		__syncthreads();
 		for (int d = dtop; d >= dbot; d--) {
@@ -216,10 +208,7 @@ template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_a
 	if (tid == 0) out[blockIdx.x] = GaOut{score, nruns, 1, 0};
 }
 
-// ---- spelling
-
-struct GaSpan { u64 col; unsigned ai, bj, op, len; };                       // a run: first column in its pair's row, first base of a / b
-struct GaPair { u64 src_a, src_b, toff, first_span; unsigned n, m, rev_a, rev_b, nspans, pad_; u64 L; };      // toff: the pair's text (2 L bytes)
+// ---- spelling: the rows of a centre-star multiple alignment; the two rows of a pair are those of a group of one member
 
 constexpr unsigned GS_THREADS = 256;
 
@@ -232,52 +221,14 @@ template <class F> __device__ inline u64 ga_find(u64 lo, u64 hi, F le)   // larg
 	return lo;
 }
 
-__global__ __launch_bounds__(GS_THREADS) void k_spell_rows(const uint8_t *__restrict__ seq, const GaPair *__restrict__ pairs, u64 npairs,
-                                                           const GaSpan *__restrict__ spans, u64 total, uint4 *__restrict__ out)
-{
-	const u64 t0 = ((u64)blockIdx.x * GS_THREADS + threadIdx.x) * 16;
-	if (t0 >= total) return;
-	u64 pi = ga_find(0, npairs, [&](u64 x) { return pairs[x].toff <= t0; });
-	GaPair P = pairs[pi];
-	u64 off = t0 - P.toff;                                                    // inside the pair's text: row a, then row b
-	unsigned row = 0;
-	u64 col = 0, si = 0;
-	GaSpan R{};
-	auto seek = [&]() {                                                       // (pair, off) -> row, column and run; false: the pair's text is exhausted
-		while (off >= 2 * P.L) {
-			off -= 2 * P.L;
-			if (++pi >= npairs) return false;
-			P = pairs[pi];
-		}
-		row = off >= P.L;
-		col = off - (row ? P.L : 0);
-		si = ga_find(P.first_span, P.first_span + P.nspans, [&](u64 x) { return spans[x].col <= col; });
-		R = spans[si];
-		return true;
-	};
-	u64 wlo = 0, whi = 0;
-	bool live = seek();
-	for (unsigned b = 0; b < 16 && live && t0 + b < total; b++) {
-		if (col == P.L) { live = seek(); if (!live) break; }
-		else if (col >= R.col + R.len) R = spans[++si];
-		const u64 in = col - R.col;
-		unsigned char ch;
-		if (row == 0) ch = R.op == 'D' ? '-' : P.rev_a ? complement1(seq[P.src_a + (P.n - 1 - (R.ai + in))]) : seq[P.src_a + R.ai + in];
-		else ch = R.op == 'I' ? '-' : P.rev_b ? complement1(seq[P.src_b + (P.m - 1 - (R.bj + in))]) : seq[P.src_b + R.bj + in];
-		if (b < 8) wlo |= (u64)ch << (8 * b); else whi |= (u64)ch << (8 * (b - 8));
-		col++; off++;
-	}
-	out[t0 / 16] = make_uint4((unsigned)wlo, (unsigned)(wlo >> 32), (unsigned)whi, (unsigned)(whi >> 32));
-}
-
-// ---- spelling of groups: the rows of a centre-star multiple alignment
-
+struct GaSpan { u64 col; unsigned ai, bj, op, len; };                       // a run: first column in its pair's two rows, first base of a / b
 struct GmInst { u64 src, first_span; unsigned len, rev, nspans, pad_; };       // a row: its range; a member's spans (of the pair centre / member)
 struct GmSlot { u64 col; unsigned p, G; };                                    // gap slot p: G columns from column col = p + the G of the slots before it
 struct GmGroup { u64 toff, L, first_inst, first_slot; unsigned ninst, nslots; };      // toff: the group's text (ninst L bytes); slot 0 always listed
 
-// Output-stationary like k_spell_rows: a lane owns 16 bytes of the text.  Group by binary search over text offsets, then row and column;
-// the column's slot by binary search over the group's merged slots, a member's run by binary search over its spans by centre index.
+// Output-stationary like blockseq.hip: a lane owns 16 bytes of the text and writes them with one vector store.  Group by binary search
+// over text offsets, then row and column; the column's slot by binary search over the group's merged slots, a member's run by binary
+// search over its spans by centre index.
 // From there the lane steps byte by byte: slot, span, row and group advance as the column does.
 __global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__restrict__ seq, const GmGroup *__restrict__ groups, u64 ngroups,
                                                              const GmInst *__restrict__ insts, const GmSlot *__restrict__ slots,
@@ -323,7 +274,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__re
 		const unsigned q = in_slot ? S.p : S.p + (unsigned)(o - S.G);
 		unsigned char ch = '-';
 		if (row == 0) {
-			if (!in_slot) ch = I.rev ? complement1(seq[I.src + (I.len - 1 - q)]) : seq[I.src + q];
+			if (!in_slot) ch = strand_base(seq, I.src, I.len, q, I.rev);
 		} else if (I.nspans) {
 			while (xi + 1 < I.first_span + I.nspans && spans[xi + 1].ai <= q) xi++;      // the last span that starts at or before centre index q
 			GaSpan R = spans[xi];
@@ -332,7 +283,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__re
 				if (R.op != 'D' && R.ai == q && xi > I.first_span) R = spans[xi - 1];
 				if (R.op == 'D' && R.ai == q && o < R.len) bj = (long long)R.bj + (long long)o;
 			} else if (R.op != 'I' && R.op != 'D') bj = (long long)R.bj + (q - R.ai);
-			if (bj >= 0) ch = I.rev ? complement1(seq[I.src + (I.len - 1 - (u64)bj)]) : seq[I.src + (u64)bj];
+			if (bj >= 0) ch = strand_base(seq, I.src, I.len, (unsigned)bj, I.rev);
 		}
 		if (b < 8) wlo |= (u64)ch << (8 * b); else whi |= (u64)ch << (8 * (b - 8));
 		col++; off++;
@@ -374,20 +325,13 @@ void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<siz
 			chunk.push_back(j);
 			c->align_stats.cells += (u64)(j.n + j.m + 1) * ((j.W + 1) / 2);
 		}
-		c->d_ga_job.ensure(chunk.size() * sizeof(GaJob)); c->d_ga_codes.ensure((size_t)bytes); c->d_ga_out.ensure(chunk.size() * sizeof(GaOut));
+		al_upload(c, c->d_ga_job, chunk); c->d_ga_codes.ensure((size_t)bytes); c->d_ga_out.ensure(chunk.size() * sizeof(GaOut));
 		c->d_ga_runs.ensure((size_t)nrun * sizeof(sbl_align_run));
 		got.resize(chunk.size());
-		HIP_TRY(hipMemcpyAsync(c->d_ga_job.p, chunk.data(), chunk.size() * sizeof(GaJob), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipEventRecord(c->ev[0], s));
-		if (cls == 0) k_block_align<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
-		else k_block_align<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(c->ev[1], s));
-		HIP_TRY(hipMemcpyAsync(got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-		c->align_stats.kernel_ms += ms;
+		c->align_stats.kernel_ms += al_timed_launch(c, [&] {
+			if (cls == 0) k_block_align<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+			else k_block_align<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+		}, got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut));
 		c->align_stats.launches++;
 		c->align_stats.passes += chunk.size();
 		u64 more = 0;
@@ -431,7 +375,7 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 		if (n + m >= GA_MAX_DIAG) { r.status = SBL_GALIGN_SKIPPED; continue; }
 		j.n = (unsigned)n; j.m = (unsigned)m; j.rev_a = d.rev_a != 0; j.rev_b = d.rev_b != 0;
 		if (n == 0 || m == 0) {                                               // all gaps: nothing to fill
-			r.score = -GA_PENALTY * (int)(n + m);
+			r.score = -AL_PENALTY * (int)(n + m);
 			r.first_run = c->ga_runs.size();
 			if (n + m) { c->ga_runs.push_back(sbl_align_run{n ? (uint32_t)'I' : (uint32_t)'D', (uint32_t)(n + m)}); r.nruns = 1; }
 			continue;
@@ -461,7 +405,7 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 }
 
 // the runs of pair i as spans, appended; false: they do not spell its two ranges
-bool ga_spans_of(const sbl_ctx *c, size_t i, const GaJob &j, std::vector<GaSpan> &spans, u64 *L)
+bool ga_spans_of(const sbl_ctx *c, size_t i, const GaJob &j, std::vector<GaSpan> &spans)
 {
 	const sbl_pair_result &r = c->ga_res[i];
 	unsigned ai = 0, bj = 0;
@@ -473,114 +417,35 @@ bool ga_spans_of(const sbl_ctx *c, size_t i, const GaJob &j, std::vector<GaSpan>
 		if (run.op != 'D') ai += run.len;
 		if (run.op != 'I') bj += run.len;
 	}
-	*L = col;
 	return ai == j.n && bj == j.m;
 }
 
-// text made on the device: uploads nothing itself, runs `launch` between the events of spell_ms and brings `total` bytes of d_ga_text
-// back through h_bs_text
-template <class F> void ga_fetch_text(sbl_ctx *c, u64 total, F launch)
+struct GmWant { u64 src; unsigned n, rev; size_t pair0, npairs; };          // a group to spell: its centre; its members' pairs, consecutive in c->ga_res
+struct GmText { bool ok; u64 L, row_off; };                                 // ok: every pair of the group is aligned -- a group that is not ok has no text
+
+// spells the rows of the groups `want` into h_bs_text and returns the length of the text: per group the merge of the gap slots -- on the
+// host, from the runs: they are here already and their number follows the edits, not the bases -- and one launch of k_spell_groups for
+// the text of all.  Counts the pairs that are not aligned in align_stats.skipped.
+u64 gm_spell(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<GmWant> &want, std::vector<GmText> &text)
 {
-	hipStream_t s = c->stream;
-	const size_t padded = (size_t)((total + 15) / 16 * 16);
-	const u64 groups = (padded / 16 + GS_THREADS - 1) / GS_THREADS;
-	SBL_CHECK(groups < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
-	c->d_ga_text.ensure(padded);
-	sbl_text_staging(c, padded);
-	HIP_TRY(hipEventRecord(c->ev[0], s));
-	launch((unsigned)groups, s);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(c->ev[1], s));
-	HIP_TRY(hipMemcpyAsync(c->h_bs_text, c->d_ga_text.p, padded, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	float ms = 0;
-	(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-	c->align_stats.spell_ms = ms;
-	c->stats.device_bytes = sbl_devbuf_total().load();
-}
-
-// aligns c->ga_desc (checked) into c->ga_res / ga_runs and spells the rows into h_bs_text
-void ga_run(sbl_ctx *c, u64 *rows_len)
-{
-	std::vector<GaJob> jobs;
-	ga_passes(c, jobs);
-	const size_t N = jobs.size();
-
-	// ---- rows: per aligned pair 2 L bytes, spelled from the runs
-	std::vector<GaPair> pairs;
-	std::vector<GaSpan> spans;
-	u64 total = 0;
-	for (size_t i = 0; i < N; i++) {
-		sbl_pair_result &r = c->ga_res[i];
-		if (r.status != SBL_GALIGN_OK) { r = sbl_pair_result{SBL_GALIGN_SKIPPED, 0, r.band_w, r.passes, 0, 0, 0, 0}; c->align_stats.skipped++; continue; }
-		GaPair P{jobs[i].src_a, jobs[i].src_b, total, spans.size(), jobs[i].n, jobs[i].m, jobs[i].rev_a, jobs[i].rev_b, (unsigned)r.nruns, 0, 0};
-		SBL_CHECK(ga_spans_of(c, i, jobs[i], spans, &P.L), SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
-		r.row_off = total; r.row_len = P.L;
-		total += 2 * P.L;
-		if (P.L) pairs.push_back(P);
-	}
-	if (total) {
-		c->d_ga_pair.ensure(pairs.size() * sizeof(GaPair)); c->d_ga_span.ensure(spans.size() * sizeof(GaSpan));
-		HIP_TRY(hipMemcpyAsync(c->d_ga_pair.p, pairs.data(), pairs.size() * sizeof(GaPair), hipMemcpyHostToDevice, c->stream));
-		HIP_TRY(hipMemcpyAsync(c->d_ga_span.p, spans.data(), spans.size() * sizeof(GaSpan), hipMemcpyHostToDevice, c->stream));
-		ga_fetch_text(c, total, [&](unsigned groups, hipStream_t s) {
-			k_spell_rows<<<groups, GS_THREADS, 0, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_pair.as<GaPair>(), pairs.size(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
-		});
-	}
-	*rows_len = total;
-}
-
-// aligns the groups c->gm_first / gm_inst (checked) into c->gm_res / gm_members and spells their rows into h_bs_text: every member against
-// its centre through the pair passes, then per group the merge of the gap slots -- on the host, from the runs: they are here already and
-// their number follows the edits, not the bases -- and one launch of k_spell_groups for the text
-void gm_run(sbl_ctx *c, u64 *rows_len)
-{
-	const std::vector<uint64_t> &first = c->gm_first;
-	const std::vector<sbl_group_inst> &inst = c->gm_inst;
-	const size_t NG = first.size() - 1;
-	c->ga_ids.clear(); c->ga_desc.clear();
-	for (size_t g = 0; g < NG; g++) {
-		const sbl_group_inst &ctr = inst[first[g]];
-		for (u64 k = first[g] + 1; k < first[g + 1]; k++)
-			c->ga_desc.push_back(sbl_pair_desc{ctr.chr, ctr.start, ctr.end, ctr.rev, inst[k].chr, inst[k].start, inst[k].end, inst[k].rev});
-	}
-	std::vector<GaJob> jobs;
-	ga_passes(c, jobs);
-
-	c->gm_res.assign(NG, sbl_group_result{});
-	c->gm_members.assign(inst.size(), sbl_member_result{});
 	std::vector<GmGroup> groups;
 	std::vector<GmInst> rows;
 	std::vector<GmSlot> slots;
 	std::vector<GaSpan> spans;
 	std::vector<std::pair<unsigned, unsigned>> runs_d;                          // (slot, length) of the 'D' runs of a group's members
 	u64 total = 0;
-	size_t pair = 0;
-	for (size_t g = 0; g < NG; g++) {
-		const size_t r = (size_t)(first[g + 1] - first[g]), pair0 = pair;
-		sbl_group_result &res = c->gm_res[g];
-		res.ninst = (uint32_t)r;
+	text.assign(want.size(), GmText{});
+	for (size_t g = 0; g < want.size(); g++) {
+		const GmWant &w = want[g];
 		bool ok = true;
-		for (size_t k = 1; k < r; k++, pair++) {
-			const sbl_pair_result &pr = c->ga_res[pair];
-			if (pr.status != SBL_GALIGN_OK) { ok = false; c->align_stats.skipped++; }
-			c->gm_members[first[g] + k] = sbl_member_result{pr.status == SBL_GALIGN_OK ? pr.score : 0, pr.band_w, pr.passes};
-		}
-		const sbl_group_inst &ctr = inst[first[g]];
-		if (!ok) {
-			res.status = SBL_GALIGN_SKIPPED;
-			for (size_t k = 1; k < r; k++) c->gm_members[first[g] + k].score = 0;
-			continue;
-		}
-		const unsigned n = (unsigned)(ctr.end - ctr.start);
-		GmGroup Q{total, 0, rows.size(), slots.size(), (unsigned)r, 0};
-		rows.push_back(GmInst{(u64)c->orig_sepidx[ctr.chr] + 1 + ctr.start, 0, n, ctr.rev != 0, 0, 0});
+		for (size_t i = w.pair0; i < w.pair0 + w.npairs; i++) if (c->ga_res[i].status != SBL_GALIGN_OK) { ok = false; c->align_stats.skipped++; }
+		if (!ok) continue;
+		GmGroup Q{total, 0, rows.size(), slots.size(), (unsigned)w.npairs + 1, 0};
+		rows.push_back(GmInst{w.src, 0, w.n, w.rev, 0, 0});
 		runs_d.clear();
-		for (size_t k = 1; k < r; k++) {
-			const size_t i = pair0 + k - 1;
+		for (size_t i = w.pair0; i < w.pair0 + w.npairs; i++) {
 			const size_t at = spans.size();
-			u64 L2 = 0;
-			SBL_CHECK(ga_spans_of(c, i, jobs[i], spans, &L2), SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
+			SBL_CHECK(ga_spans_of(c, i, jobs[i], spans), SBL_ERR_INTERNAL, "the runs of an alignment do not spell its two ranges");
 			rows.push_back(GmInst{jobs[i].src_b, at, jobs[i].m, jobs[i].rev_b, (unsigned)(spans.size() - at), 0});
 			for (size_t x = at; x < spans.size(); x++) if (spans[x].op == 'D') runs_d.push_back({spans[x].ai, spans[x].len});
 		}
@@ -593,38 +458,84 @@ void gm_run(sbl_ctx *c, u64 *rows_len)
 			shift += runs_d[x].second;
 		}
 		Q.nslots = (unsigned)(slots.size() - Q.first_slot);
-		Q.L = (u64)n + shift;
-		res.L = Q.L; res.row_off = total;
-		total += (u64)r * Q.L;
+		Q.L = (u64)w.n + shift;
+		text[g] = GmText{true, Q.L, total};
+		total += (u64)Q.ninst * Q.L;
 		if (Q.L) groups.push_back(Q);
 	}
 	if (total) {
-		hipStream_t s = c->stream;
-		c->d_gm_group.ensure(groups.size() * sizeof(GmGroup)); c->d_gm_inst.ensure(rows.size() * sizeof(GmInst));
-		c->d_gm_slot.ensure(slots.size() * sizeof(GmSlot)); c->d_ga_span.ensure(std::max<size_t>(1, spans.size()) * sizeof(GaSpan));
-		HIP_TRY(hipMemcpyAsync(c->d_gm_group.p, groups.data(), groups.size() * sizeof(GmGroup), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(c->d_gm_inst.p, rows.data(), rows.size() * sizeof(GmInst), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipMemcpyAsync(c->d_gm_slot.p, slots.data(), slots.size() * sizeof(GmSlot), hipMemcpyHostToDevice, s));
-		if (!spans.empty()) HIP_TRY(hipMemcpyAsync(c->d_ga_span.p, spans.data(), spans.size() * sizeof(GaSpan), hipMemcpyHostToDevice, s));
-		ga_fetch_text(c, total, [&](unsigned blocks, hipStream_t st) {
-			k_spell_groups<<<blocks, GS_THREADS, 0, st>>>(c->d_orig_ch.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), groups.size(), c->d_gm_inst.as<GmInst>(),
-			                                               c->d_gm_slot.as<GmSlot>(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
-		});
+		const size_t padded = (size_t)((total + 15) / 16 * 16);
+		const u64 blocks = (padded / 16 + GS_THREADS - 1) / GS_THREADS;
+		SBL_CHECK(blocks < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
+		al_upload(c, c->d_gm_group, groups); al_upload(c, c->d_gm_inst, rows); al_upload(c, c->d_gm_slot, slots); al_upload(c, c->d_ga_span, spans);
+		c->d_ga_text.ensure(padded);
+		sbl_text_staging(c, padded);
+		c->align_stats.spell_ms = al_timed_launch(c, [&] {
+			k_spell_groups<<<(unsigned)blocks, GS_THREADS, 0, c->stream>>>(c->d_orig_ch.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), groups.size(), c->d_gm_inst.as<GmInst>(),
+			                                                                 c->d_gm_slot.as<GmSlot>(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
+		}, c->h_bs_text, c->d_ga_text.p, padded);
+		c->stats.device_bytes = sbl_devbuf_total().load();
 	}
-	*rows_len = total;
+	return total;
+}
+
+// aligns c->ga_desc (checked) into c->ga_res / ga_runs and spells the two rows of every pair, a group of one member, into h_bs_text
+void ga_run(sbl_ctx *c, u64 *rows_len)
+{
+	std::vector<GaJob> jobs;
+	ga_passes(c, jobs);
+	std::vector<GmWant> want;
+	std::vector<GmText> text;
+	for (size_t i = 0; i < jobs.size(); i++) want.push_back(GmWant{jobs[i].src_a, jobs[i].n, jobs[i].rev_a, i, 1});
+	*rows_len = gm_spell(c, jobs, want, text);
+	for (size_t i = 0; i < jobs.size(); i++) {
+		sbl_pair_result &r = c->ga_res[i];
+		if (text[i].ok) { r.row_off = text[i].row_off; r.row_len = text[i].L; }
+		else r = sbl_pair_result{SBL_GALIGN_SKIPPED, 0, r.band_w, r.passes, 0, 0, 0, 0};
+	}
+}
+
+// aligns the groups c->gm_first / gm_inst (checked) into c->gm_res / gm_members and spells their rows into h_bs_text: every member against
+// its centre through the pair passes, then the rows of the groups whose members are all aligned
+void gm_run(sbl_ctx *c, u64 *rows_len)
+{
+	const std::vector<uint64_t> &first = c->gm_first;
+	const std::vector<sbl_group_inst> &inst = c->gm_inst;
+	const size_t NG = first.size() - 1;
+	std::vector<GmWant> want;
+	std::vector<GmText> text;
+	c->ga_desc.clear();
+	for (size_t g = 0; g < NG; g++) {
+		const sbl_group_inst &ctr = inst[first[g]];
+		want.push_back(GmWant{(u64)c->orig_sepidx[ctr.chr] + 1 + ctr.start, (unsigned)(ctr.end - ctr.start), ctr.rev != 0, c->ga_desc.size(), (size_t)(first[g + 1] - first[g] - 1)});
+		for (u64 k = first[g] + 1; k < first[g + 1]; k++)
+			c->ga_desc.push_back(sbl_pair_desc{ctr.chr, ctr.start, ctr.end, ctr.rev, inst[k].chr, inst[k].start, inst[k].end, inst[k].rev});
+	}
+	std::vector<GaJob> jobs;
+	ga_passes(c, jobs);
+	*rows_len = gm_spell(c, jobs, want, text);
+
+	c->gm_res.assign(NG, sbl_group_result{});
+	c->gm_members.assign(inst.size(), sbl_member_result{});
+	for (size_t g = 0; g < NG; g++) {
+		sbl_group_result &res = c->gm_res[g];
+		res.ninst = (uint32_t)(first[g + 1] - first[g]);
+		if (text[g].ok) { res.L = text[g].L; res.row_off = text[g].row_off; }
+		else res.status = SBL_GALIGN_SKIPPED;
+		for (size_t k = 0; k < want[g].npairs; k++) {
+			const sbl_pair_result &pr = c->ga_res[want[g].pair0 + k];
+			c->gm_members[first[g] + 1 + k] = sbl_member_result{text[g].ok ? pr.score : 0, pr.band_w, pr.passes};
+		}
+	}
 }
 
 void gm_check(const sbl_ctx *c, u64 ngroups, const uint64_t *first, const sbl_group_inst *inst)
 {
-	SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+	require_records(c);
 	SBL_CHECK(ngroups == 0 || (first && inst), SBL_ERR_BAD_ARG, "null group descriptors");
 	SBL_CHECK(ngroups == 0 || first[0] == 0, SBL_ERR_BAD_ARG, "the first group does not start at instance 0");
 	for (u64 g = 0; g < ngroups; g++) SBL_CHECK(first[g + 1] > first[g], SBL_ERR_BAD_ARG, "an empty group");
-	for (u64 i = 0; ngroups && i < first[ngroups]; i++) {
-		SBL_CHECK(inst[i].chr < c->nchr, SBL_ERR_BAD_ARG, "an instance on a record that does not exist");
-		SBL_CHECK(inst[i].end >= inst[i].start, SBL_ERR_BAD_ARG, "a range ends before it starts");
-		SBL_CHECK(inst[i].end <= (u64)(c->orig_sepidx[inst[i].chr + 1] - c->orig_sepidx[inst[i].chr] - 1), SBL_ERR_BAD_ARG, "a range runs beyond its record");
-	}
+	for (u64 i = 0; ngroups && i < first[ngroups]; i++) check_range(c, inst[i].chr, inst[i].start, inst[i].end, "an instance on a record that does not exist");
 }
 
 void gm_hand_out(sbl_ctx *c, u64 rows_len, const sbl_group_result **res, const sbl_member_result **members, const char **rows, uint64_t *rl)
@@ -637,13 +548,11 @@ void gm_hand_out(sbl_ctx *c, u64 rows_len, const sbl_group_result **res, const s
 
 void ga_check(const sbl_ctx *c, const sbl_pair_desc *d, u64 n)
 {
-	SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+	require_records(c);
 	SBL_CHECK(n == 0 || d, SBL_ERR_BAD_ARG, "null pair descriptors");
 	for (u64 i = 0; i < n; i++) {
-		SBL_CHECK(d[i].chr_a < c->nchr && d[i].chr_b < c->nchr, SBL_ERR_BAD_ARG, "a pair on a record that does not exist");
-		SBL_CHECK(d[i].end_a >= d[i].start_a && d[i].end_b >= d[i].start_b, SBL_ERR_BAD_ARG, "a range ends before it starts");
-		SBL_CHECK(d[i].end_a <= (u64)(c->orig_sepidx[d[i].chr_a + 1] - c->orig_sepidx[d[i].chr_a] - 1) &&
-		          d[i].end_b <= (u64)(c->orig_sepidx[d[i].chr_b + 1] - c->orig_sepidx[d[i].chr_b] - 1), SBL_ERR_BAD_ARG, "a range runs beyond its record");
+		check_range(c, d[i].chr_a, d[i].start_a, d[i].end_a, "a pair on a record that does not exist");
+		check_range(c, d[i].chr_b, d[i].start_b, d[i].end_b, "a pair on a record that does not exist");
 	}
 }
 
@@ -683,25 +592,20 @@ extern "C" sbl_status sbl_align_unique_blocks(sbl_ctx *c, uint32_t min_block_siz
                                               const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len)
 {
 	return guarded(c, [&] {
-		SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
-		SBL_CHECK(c->have_blocks, SBL_ERR_BAD_ARG, "no block list: run sbl_generate_blocks / sbl_postprocess first");
-		SBL_CHECK(n_reference_chr > 0 && n_reference_chr < c->nchr, SBL_ERR_BAD_ARG, "the reference set must hold at least one record and leave at least one outside it");
+		require_records(c);
+		require_blocks(c);
+		require_reference_split(c, n_reference_chr);
 		sbl_check_blocks(c, c->blocks.data(), c->blocks.size());
 		std::vector<sbl_block> v = c->blocks;
 		std::stable_sort(v.begin(), v.end(), [](const sbl_block &x, const sbl_block &y) { return std::abs(x.id) < std::abs(y.id); });
 		c->ga_ids.clear(); c->ga_desc.clear();
-		for (size_t i = 0; i < v.size();) {
-			size_t j = i;
-			while (j < v.size() && std::abs(v[j].id) == std::abs(v[i].id)) j++;
-			if (j - i == 2 && (v[i].chr < n_reference_chr) != (v[i + 1].chr < n_reference_chr)) {      // determine_unique_block (C-Sibelia.py:314-323)
-				const sbl_block &a = v[i].chr < n_reference_chr ? v[i] : v[i + 1], &b = v[i].chr < n_reference_chr ? v[i + 1] : v[i];
-				if (a.end - a.start >= min_block_size && b.end - b.start >= min_block_size) {
-					c->ga_ids.push_back(std::abs(a.id));
-					c->ga_desc.push_back(sbl_pair_desc{a.chr, a.start, a.end, a.id < 0, b.chr, b.start, b.end, b.id < 0});
-				}
-			}
-			i = j;
-		}
+		for_each_id_run(v, [&](size_t i, size_t j) {
+			if (j - i != 2 || (v[i].chr < n_reference_chr) == (v[i + 1].chr < n_reference_chr)) return;      // determine_unique_block (C-Sibelia.py:314-323)
+			const sbl_block &a = v[i].chr < n_reference_chr ? v[i] : v[i + 1], &b = v[i].chr < n_reference_chr ? v[i + 1] : v[i];
+			if (a.end - a.start < min_block_size || b.end - b.start < min_block_size) return;
+			c->ga_ids.push_back(std::abs(a.id));
+			c->ga_desc.push_back(sbl_pair_desc{a.chr, a.start, a.end, a.id < 0, b.chr, b.start, b.end, b.id < 0});
+		});
 		u64 total = 0;
 		ga_run(c, &total);
 		if (ids) *ids = c->ga_ids.data();
@@ -716,6 +620,7 @@ extern "C" sbl_status sbl_align_groups(sbl_ctx *c, uint64_t ngroups, const uint6
 {
 	return guarded(c, [&] {
 		gm_check(c, ngroups, group_first, inst);
+		c->ga_ids.clear();
 		if (ngroups) { c->gm_first.assign(group_first, group_first + ngroups + 1); c->gm_inst.assign(inst, inst + group_first[ngroups]); }
 		else { c->gm_first.assign(1, 0); c->gm_inst.clear(); }
 		u64 total = 0;
@@ -729,8 +634,8 @@ extern "C" sbl_status sbl_align_block_groups(sbl_ctx *c, uint32_t min_block_size
                                              const sbl_member_result **members, const char **rows, uint64_t *rows_len)
 {
 	return guarded(c, [&] {
-		SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
-		SBL_CHECK(c->have_blocks, SBL_ERR_BAD_ARG, "no block list: run sbl_generate_blocks / sbl_postprocess first");
+		require_records(c);
+		require_blocks(c);
 		sbl_check_blocks(c, c->blocks.data(), c->blocks.size());
 		std::vector<sbl_block> v;
 		for (const sbl_block &b : c->blocks) if (b.end - b.start >= min_block_size) v.push_back(b);
@@ -742,21 +647,15 @@ extern "C" sbl_status sbl_align_block_groups(sbl_ctx *c, uint32_t min_block_size
 			if (x.end != y.end) return x.end < y.end;
 			return (x.id < 0) < (y.id < 0);
 		});
-		std::vector<int32_t> group_ids;
-		c->gm_first.assign(1, 0); c->gm_inst.clear();
-		for (size_t i = 0; i < v.size();) {
-			size_t j = i;
-			while (j < v.size() && std::abs(v[j].id) == std::abs(v[i].id)) j++;
-			if (j - i >= 2) {
-				group_ids.push_back(std::abs(v[i].id));
-				for (size_t k = i; k < j; k++) c->gm_inst.push_back(sbl_group_inst{v[k].chr, v[k].start, v[k].end, v[k].id < 0});
-				c->gm_first.push_back(c->gm_inst.size());
-			}
-			i = j;
-		}
+		c->ga_ids.clear(); c->gm_first.assign(1, 0); c->gm_inst.clear();
+		for_each_id_run(v, [&](size_t i, size_t j) {
+			if (j - i < 2) return;
+			c->ga_ids.push_back(std::abs(v[i].id));
+			for (size_t k = i; k < j; k++) c->gm_inst.push_back(sbl_group_inst{v[k].chr, v[k].start, v[k].end, v[k].id < 0});
+			c->gm_first.push_back(c->gm_inst.size());
+		});
 		u64 total = 0;
-		gm_run(c, &total);                                                      // (clears ga_ids)
-		c->ga_ids = group_ids;
+		gm_run(c, &total);
 		if (ids) *ids = c->ga_ids.data();
 		if (group_first) *group_first = c->gm_first.data();
 		if (inst) *inst = c->gm_inst.data();

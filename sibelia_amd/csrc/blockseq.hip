@@ -195,7 +195,7 @@ void sbl_text_staging(sbl_ctx *c, size_t bytes)
 // checks shared by the two reports that take a caller's list
 void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n)
 {
-	SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+	require_records(c);
 	SBL_CHECK(n == 0 || b, SBL_ERR_BAD_ARG, "null block list");
 	for (uint64_t i = 0; i < n; i++) {
 		SBL_CHECK(b[i].id != 0, SBL_ERR_BAD_ARG, "block id 0");

@@ -37,15 +37,11 @@
 #include <cstring>
 #include <set>
 
-#include "sbl_ctx.h"
-#include "sbl_dna.h"
+#include "sbl_align.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr unsigned BA_THREADS = 512, BA_CELLS = 4, BA_MAXLEN = SBL_ALIGN_MAX_LEN, BA_ALIGN = 256;
-constexpr int BA_MATCH = 25, BA_PENALTY = 75;
 constexpr size_t BA_DEFAULT_CAP = (size_t)256 << 20;
 
 struct BaJob {
@@ -78,8 +74,8 @@ __global__ __launch_bounds__(BA_THREADS) void k_boundary_align(const uint8_t *__
 	const BaJob J = jobs[blockIdx.x];
 	const int n = (int)J.na, m = (int)J.nb;
 	const unsigned tid = threadIdx.x;
-	for (int t = tid; t < n; t += BA_THREADS) s_a[t] = J.rev_a ? complement1(seq[J.src_a + (unsigned)(n - 1 - t)]) : seq[J.src_a + (unsigned)t];
-	for (int t = tid; t < m; t += BA_THREADS) s_b[t] = J.rev_b ? complement1(seq[J.src_b + (unsigned)(m - 1 - t)]) : seq[J.src_b + (unsigned)t];
+	for (int t = tid; t < n; t += BA_THREADS) s_a[t] = strand_base(seq, J.src_a, J.na, (unsigned)t, J.rev_a);
+	for (int t = tid; t < m; t += BA_THREADS) s_b[t] = strand_base(seq, J.src_b, J.nb, (unsigned)t, J.rev_b);
 	for (unsigned t = tid; t < 3 * (BA_MAXLEN + 1 + BA_CELLS + 4); t += BA_THREADS) (&s_m[0][0])[t] = 0;
 	__syncthreads();
 
@@ -104,9 +100,9 @@ __global__ __launch_bounds__(BA_THREADS) void k_boundary_align(const uint8_t *__
 				const int v = m1[i + 1], h = m1[i], g = m2[i + 1];          // M[i+1][j], M[i][j+1], M[i+1][j+1]
 				int val;
 				unsigned step;
-				if (s_a[i] == s_b[j]) { val = g + BA_MATCH; step = 1; }
+				if (s_a[i] == s_b[j]) { val = g + AL_MATCH; step = 1; }
 				else {
-					const int vv = v - BA_PENALTY, hh = h - BA_PENALTY, gg = g - BA_PENALTY;
+					const int vv = v - AL_PENALTY, hh = h - AL_PENALTY, gg = g - AL_PENALTY;
 					val = vv > hh ? vv : hh;
 					val = gg > val ? gg : val;
 					if (val <= 0) { val = 0; step = 0; }
@@ -171,7 +167,6 @@ size_t ba_cap()
 void ba_run(sbl_ctx *c, const uint8_t *d_seq, std::vector<BaJob> &jobs, uint32_t *out)
 {
 	const size_t cap = ba_cap();
-	hipStream_t s = c->stream;
 	std::vector<BaJob> chunk;
 	std::vector<size_t> which;
 	std::vector<uint32_t> res;
@@ -193,26 +188,17 @@ void ba_run(sbl_ctx *c, const uint8_t *d_seq, std::vector<BaJob> &jobs, uint32_t
 			c->correct_stats.cells += (u64)j.na * j.nb;
 		}
 		if (chunk.empty()) continue;
-		c->d_ba_desc.ensure(chunk.size() * sizeof(BaJob)); c->d_ba_codes.ensure((size_t)bytes); c->d_ba_out.ensure(chunk.size() * 16);
+		al_upload(c, c->d_ba_desc, chunk); c->d_ba_codes.ensure((size_t)bytes); c->d_ba_out.ensure(chunk.size() * 16);
 		res.resize(chunk.size() * 4);
-		HIP_TRY(hipMemcpyAsync(c->d_ba_desc.p, chunk.data(), chunk.size() * sizeof(BaJob), hipMemcpyHostToDevice, s));
-		HIP_TRY(hipEventRecord(c->ev[0], s));
-		k_boundary_align<<<(unsigned)chunk.size(), BA_THREADS, 0, s>>>(d_seq, c->d_ba_desc.as<BaJob>(), c->d_ba_codes.as<uint8_t>(), c->d_ba_out.as<uint4>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(c->ev[1], s));
-		HIP_TRY(hipMemcpyAsync(res.data(), c->d_ba_out.p, chunk.size() * 16, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-		c->correct_stats.kernel_ms += ms;
+		c->correct_stats.kernel_ms += al_timed_launch(c, [&] {
+			k_boundary_align<<<(unsigned)chunk.size(), BA_THREADS, 0, c->stream>>>(d_seq, c->d_ba_desc.as<BaJob>(), c->d_ba_codes.as<uint8_t>(), c->d_ba_out.as<uint4>());
+		}, res.data(), c->d_ba_out.p, chunk.size() * 16);
 		c->correct_stats.launches++;
 		c->correct_stats.alignments += chunk.size();
 		for (size_t k = 0; k < chunk.size(); k++) memcpy(out + 4 * which[k], &res[4 * k], 16);
 	}
 	c->stats.device_bytes = sbl_devbuf_total().load();
 }
-
-inline int iabs(int x) { return x > 0 ? x : -x; }
 
 struct Window { int64_t lo, hi; };
 
@@ -283,9 +269,9 @@ extern "C" sbl_status sbl_correct_boundaries(sbl_ctx *c, uint32_t min_block_size
                                              const sbl_block **blocks, uint64_t *n, const char **coords, const char **perms, const char **coverage)
 {
 	return guarded(c, [&] {
-		SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
-		SBL_CHECK(c->have_blocks, SBL_ERR_BAD_ARG, "no block list: run sbl_generate_blocks / sbl_postprocess first");      // an empty list is one: nothing is corrected
-		SBL_CHECK(n_reference_chr > 0 && n_reference_chr < c->nchr, SBL_ERR_BAD_ARG, "the reference set must hold at least one record and leave at least one outside it");
+		require_records(c);
+		require_blocks(c);                                                  // an empty list is one: nothing is corrected
+		require_reference_split(c, n_reference_chr);
 		const int64_t R = std::min<int64_t>(min_block_size, 1 << 10);          // MAX_CORRECTION_RANGE, src/postprocessor.cpp:15
 		SBL_CHECK(R > 0, SBL_ERR_BAD_ARG, "correction range 0 (minimum block size 0): undefined in the reference");
 		sbl_check_blocks(c, c->blocks.data(), c->blocks.size());
@@ -295,18 +281,14 @@ extern "C" sbl_status sbl_correct_boundaries(sbl_ctx *c, uint32_t min_block_size
 		std::vector<sbl_block> v = c->blocks;
 		sbl_sort_by_id(v);
 		std::vector<uint32_t> first;                                       // eligible groups: index of the reference instance (the other one follows)
-		for (size_t i = 0; i < v.size();) {
-			size_t j = i;
-			while (j < v.size() && iabs(v[j].id) == iabs(v[i].id)) j++;
+		for_each_id_run(v, [&](size_t i, size_t j) {
 			size_t in_ref = 0;
 			for (size_t k = i; k < j; k++) in_ref += v[k].chr < n_reference_chr;
-			if (in_ref == 1 && j - i == 2) {
-				if (v[i].chr >= n_reference_chr) std::swap(v[i], v[i + 1]);
-				if (v[i].id < 0) { v[i].id = -v[i].id; v[i + 1].id = -v[i + 1].id; }
-				first.push_back((uint32_t)i);
-			}
-			i = j;
-		}
+			if (in_ref != 1 || j - i != 2) return;
+			if (v[i].chr >= n_reference_chr) std::swap(v[i], v[i + 1]);
+			if (v[i].id < 0) { v[i].id = -v[i].id; v[i + 1].id = -v[i + 1].id; }
+			first.push_back((uint32_t)i);
+		});
 		const size_t G = first.size();
 		std::vector<RecordEdges> same(c->nchr);                             // instances per record
 		for (const sbl_block &b : v) same[b.chr].add(b);

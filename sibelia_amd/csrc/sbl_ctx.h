@@ -99,16 +99,16 @@ struct sbl_ctx {
 	DevBuf d_ba_desc, d_ba_codes, d_ba_out, d_ba_seq;
 	sbl_correct_stats_t correct_stats{};
 
-	// sbl_align_pairs / sbl_align_unique_blocks (block_align.hip): jobs, trace codes, per-job results, runs; spans, offsets and rows of the
-	// spelling kernel (the rows come back through h_bs_text); what the calls hand out
-	DevBuf d_ga_job, d_ga_codes, d_ga_out, d_ga_runs, d_ga_span, d_ga_pair, d_ga_text;
+	// sbl_align_pairs / sbl_align_unique_blocks (block_align.hip): jobs, trace codes, per-job results, runs; the spans and the rows of
+	// k_spell_groups (the rows come back through h_bs_text); what the calls hand out
+	DevBuf d_ga_job, d_ga_codes, d_ga_out, d_ga_runs, d_ga_span, d_ga_text;
 	std::vector<sbl_pair_result> ga_res;
 	std::vector<sbl_align_run> ga_runs;
 	std::vector<sbl_pair_desc> ga_desc;
 	std::vector<int32_t> ga_ids;
 	sbl_align_stats_t align_stats{};
-	// sbl_align_groups / sbl_align_block_groups: the same pair passes (ga_desc: centre against member); instances, merged gap slots and
-	// groups of k_spell_groups; what the calls hand out
+	// sbl_align_groups / sbl_align_block_groups: the same pair passes (ga_desc: centre against member); what the calls hand out.  Instances,
+	// merged gap slots and groups of k_spell_groups: every sbl_align_* call spells through them, a pair as a group of one member
 	DevBuf d_gm_inst, d_gm_slot, d_gm_group;
 	std::vector<uint64_t> gm_first;
 	std::vector<sbl_group_inst> gm_inst;
@@ -153,6 +153,16 @@ static sbl_status guarded(sbl_ctx *c, F f)
 		c->err = "unexpected exception";
 		return SBL_ERR_INTERNAL;
 	}
+}
+
+// what the entry points that read the original records / the context's block list ask for first
+inline void require_records(const sbl_ctx *c)
+{
+	SBL_CHECK(c->orig_sepidx.size() == (size_t)c->nchr + 1 && c->d_orig_ch.p, SBL_ERR_BAD_ARG, "no records loaded");
+}
+inline void require_blocks(const sbl_ctx *c)      // an empty list is one
+{
+	SBL_CHECK(c->have_blocks, SBL_ERR_BAD_ARG, "no block list: run sbl_generate_blocks / sbl_postprocess first");
 }
 
 // implemented in sbl_api.hip

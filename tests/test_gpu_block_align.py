@@ -82,7 +82,7 @@ class Batch:
             assert (g.row_a, g.row_b) == rows, (k, len(a), len(b))
 
 
-def test_edge_shapes():
+def edge_pairs():
     rng = np.random.default_rng(21)
     x = rand(rng, 1000)
     pairs = [(b"", b""), (b"", b"ACGT"), (b"ACGT", b""), (b"A", b""), (b"A", b"A"), (b"A", b"C"), (b"A", b"ACGT"), (b"ACGT", b"T")]
@@ -90,6 +90,11 @@ def test_edge_shapes():
     for at in (0, 500, 999):                                   # one substitution: first, middle, last position
         pairs.append((x, x[:at] + (b"A" if x[at:at + 1] != b"A" else b"C") + x[at + 1:]))
     pairs += [(x, x[3:]), (x[3:], x), (x, x[:-5]), (x[:-5], x), (x[:300], b"GG" + x[:300] + b"TTT")]      # an indel at either end
+    return pairs
+
+
+def test_edge_shapes():
+    pairs = edge_pairs()
     b = Batch(pairs)
     got, st = b.run()
     b.check(got)
@@ -125,16 +130,20 @@ def test_reverse_ranges_and_bytes_outside_acgt():
     assert got[0].runs == got[1].runs == got[2].runs == got[3].runs
 
 
-@pytest.fixture(scope="module")
-def random_batch():
-    rng = np.random.default_rng(24)
+def random_pairs(seed=24, count=200):
+    rng = np.random.default_rng(seed)
     pairs = []
-    for _ in range(200):
+    for _ in range(count):
         a = rand(rng, int(rng.integers(1, 401)))
         u = rng.random()
         b = (mutated(rng, a, 0.06, 30) or b"A")[:400] if u < 0.85 else rand(rng, int(rng.integers(1, 401)))
         pairs.append((a, b))
-    return Batch(pairs)
+    return pairs
+
+
+@pytest.fixture(scope="module")
+def random_batch():
+    return Batch(random_pairs())
 
 
 def test_a_batch_of_random_pairs(random_batch):
@@ -151,6 +160,43 @@ def test_results_do_not_depend_on_the_first_band(random_batch, monkeypatch):
         random_batch.check(got)
         passes[w0] = st["passes"]
     assert passes[1] > passes[8] > passes[64] >= 200, passes      # doubling ran
+
+
+def tiny_pairs():
+    """300 pairs of 0 .. 12 bases and their strands: empty and one-sided-empty pairs scattered through the batch, all four strand
+    combinations, and stretches of at least three pairs in a row whose two rows together are shorter than 16 bytes -- among them pairs
+    without any text -- so that the 16 bytes of one lane cross several groups and several empty ones; the text ends off a 16-byte boundary"""
+    rng = np.random.default_rng(27)
+    pairs, revs = [], []
+    for k in range(300):
+        n, m = int(rng.integers(0, 13)), int(rng.integers(0, 13))
+        if k % 20 < 5:                                          # five in a row of at most 3 + 3 bases: at most 12 bytes of text each
+            n, m = int(rng.integers(0, 4)), int(rng.integers(0, 4))
+        a = rand(rng, n)
+        b = rand(rng, m) if rng.random() < 0.4 else (mutated(rng, a, 0.2, 3)[:12] if n else b"")
+        pairs.append((a, b))
+        revs.append((bool(k & 1), bool(k & 2)))
+    x = rand(rng, 7)
+    for k, p in ((0, (b"", b"")), (21, (b"", b"")), (22, (x[:2], b"")), (23, (b"", b"")), (24, (b"", x[:3])), (77, (x, b"")), (150, (b"", x)), (151, (b"", b"")),
+                 (299, (x[:5], x[:3] + x[4:5]))):
+        pairs[k] = p
+    return pairs, revs
+
+
+def test_a_batch_of_tiny_pairs():
+    pairs, revs = tiny_pairs()
+    bt = Batch(pairs, revs)
+    want = bt.want()
+    lens = [2 * len(rows[0]) for _, _, rows in want]
+    assert len(pairs) == 300 and max(max(len(a), len(b)) for a, b in pairs) <= 12
+    assert {(b"", b""), } <= set(pairs) and any(a and not b for a, b in pairs) and any(b and not a for a, b in pairs)
+    assert set(revs) == {(False, False), (True, False), (False, True), (True, True)}
+    assert lens[21] == lens[23] == 0 and sum(lens[20:25]) < 16               # one lane's 16 bytes: five groups, two of them without text
+    assert any(all(0 < x < 16 for x in lens[k:k + 3]) for k in range(298))
+    assert sum(lens) % 16 != 0 and lens[-1] > 0                               # the last pair ends off a 16-byte boundary
+    got, st = bt.run()
+    bt.check(got)
+    assert st["pairs"] == 300 and st["skipped"] == 0
 
 
 def test_wide_bands():

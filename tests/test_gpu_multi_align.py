@@ -134,6 +134,39 @@ def test_pair_projection_against_align_pairs(random_groups):
         bf.close()
 
 
+def test_calls_on_one_context_carry_nothing_over():
+    """align_groups, align_pairs and align_groups again on ONE context -- every call spells through the same device tables -- give what
+    each gives on a fresh context"""
+    from sibelia_amd import BlockFinder
+    rng = np.random.default_rng(47)
+    c = MC.rand(rng, 90)
+    five = [c] + [MC.mutated(rng, c, 0.05, 6) for _ in range(4)]
+    b = Groups([five, [b"ACGTT", b"ACTT"], [MC.rand(rng, 40)], [b"GGA", b"GA", b"GGGA"], five[::-1], [b"", b"AC"]],
+               [[False, True, False, True, False], [False, False], [True], [False] * 3, [True, False, False, True, True], [False, False]])
+    first, second = b.desc[:3], b.desc[3:]
+    pairs = [first[0][0] + m for m in first[0][1:]] + [(0, 0, 0, False, 1, 0, 0, False), second[0][0] + second[0][2]]
+    calls = [lambda bf: bf.align_groups(first), lambda bf: bf.align_pairs(pairs), lambda bf: bf.align_groups(second)]
+
+    def flat(results):
+        return [(r.status, r.L, r.row_off, r.rows, r.members) if hasattr(r, "rows") else (r.status, r.score, r.band_w, r.passes, r.runs, r.row_a, r.row_b)
+                for r in results]
+    want = []
+    for call in calls:                                                          # each on a context of its own
+        bf = BlockFinder(b.records, device=0)
+        try:
+            want.append(flat(call(bf)))
+        finally:
+            bf.close()
+    bf = BlockFinder(b.records, device=0)
+    try:
+        got = [flat(call(bf)) for call in calls]
+    finally:
+        bf.close()
+    assert got == want
+    assert [g[3] for g in got[0] + got[2]] == [rows for rows, _ in b.want()] and len(got[0][0][3]) == 5      # ... and what the model gives
+    assert [p[0] for p in got[1]] == [0] * 6 and (got[1][0][5], got[1][0][6]) == MM.project(got[0][0][3][0], got[0][0][3][1]) and got[1][4][5:] == (b"", b"")
+
+
 def test_one_member_beyond_the_cap_skips_its_group_only(monkeypatch):
     rng = np.random.default_rng(45)
     groups = MC.random_groups(seed=46, count=9, rmin=2, rmax=4, max_len=55, max_indel=5)      # at most 111 diagonals of at most 14 bytes: below 4 KiB

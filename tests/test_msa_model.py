@@ -61,6 +61,18 @@ def test_seeded_random_groups():
     assert shared >= 10                                                         # slots that members fill to different lengths
 
 
+def test_a_group_of_one_member_is_the_pair():
+    """What lets one kernel spell both: the rows of msa([a, b]) are the two rows of the pair alignment of a and b, for the edge shapes of
+    tests/test_gpu_block_align.py (empty and one-sided-empty pairs among them) and for 200 pairs of its random generator."""
+    import test_gpu_block_align as BA
+    pairs = BA.edge_pairs() + BA.random_pairs()
+    assert len(pairs) == 221 and (b"", b"") in pairs and (b"", b"ACGT") in pairs and (b"ACGT", b"") in pairs
+    for a, b in pairs:
+        score, steps = GM.align(a, b)
+        rows, scores = MM.msa([a, b])
+        assert tuple(rows) == GM.rows(a, b, steps) and scores == [score], (a, b)
+
+
 def test_the_banded_pair_equals_the_full_matrix():
     groups = MC.random_groups(seed=32, count=25, rmin=2, rmax=3, max_len=300, max_indel=20)
     groups.append([b"A" * 150, b"C" * 150])                                     # nothing matches: the band has to double up to the matrix
