@@ -171,7 +171,7 @@ sbl_status sbl_glue_stripes(sbl_block *blocks, uint64_t *n, uint32_t nchr);
  * line feed.  Reverse instances are spelled downwards through the reference's complement table (src/dnasequence.cpp:11-28):
  * ACGT / acgt swapped, every other character -- ambiguity codes included -- unchanged.  The text is generated by a kernel
  * (csrc/blockseq.hip) and comes back through a pinned buffer of the context, valid until the next sbl_blocks_sequences
- * or sbl_align_pairs / _unique_blocks / _groups / _block_groups call (they share the buffer).  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
+ * or sbl_align_pairs / _unique_blocks / _groups / _block_groups or sbl_spell_text call (they share the buffer).  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
  * end < start, end beyond the record, id == 0, no records loaded.
  * sbl_blocks_sequences_times: device time of the last call's kernel and of its device-to-host copy (event pairs). */
 sbl_status sbl_blocks_sequences(sbl_ctx *ctx, const sbl_block *blocks, uint64_t n, const char *const *names,
@@ -314,6 +314,45 @@ typedef struct {
 	double kernel_ms, spell_ms;      /* device time of the alignment launches / of the kernel that spells the rows (event pairs) */
 } sbl_align_stats_t;
 sbl_status sbl_align_stats(const sbl_ctx *ctx, sbl_align_stats_t *out);
+
+/* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
+ * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
+ * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST
+ * one the final list; records 0 .. n_reference_chr - 1 are the reference set.  Ranges are 0-based and half-open.
+ * A block is MIXED in a list if it has an instance on a reference record and one off them.  A base is COVERED if an instance of a
+ * mixed block of ANY list holds it.  main(x) is the largest |id| among the mixed blocks of the FINAL list with an instance that holds
+ * base x, 0 if there is none.  For every maximal uncovered run [start, end) of a record with end - start > min_block_size, in record
+ * order and ascending start, one call:
+ *   SBL_CALL_DELETION   the run lies on a reference record: ref_chr = chr, pos = start
+ *   SBL_CALL_INSERTION  the run lies on another record, start > 0, block b = main(start - 1) != 0 has exactly two instances in the final
+ *                       list, one in each set, both at least min_block_size long (the rule of sbl_align_unique_blocks), and
+ *                       pos = (both on the same strand ? end : start) of its reference instance is > 0: ref_chr = that instance's record
+ *   SBL_CALL_UNMAPPED   any other run off the reference records: ref_chr = 0, pos = 0
+ * Owned by the ctx, valid until the next sbl_uncovered_calls.  SBL_ERR_BAD_ARG: no records loaded, nlists == 0, offsets that do not
+ * start at 0 or descend, n_reference_chr == 0 or >= sbl_nchr(ctx), and what sbl_blocks_sequences refuses in a list. */
+#define SBL_CALL_DELETION 0
+#define SBL_CALL_INSERTION 1
+#define SBL_CALL_UNMAPPED 2
+typedef struct { uint32_t kind, chr; uint64_t start, end; uint32_t ref_chr, pad_; uint64_t pos; } sbl_uncovered_call;
+sbl_status sbl_uncovered_calls(sbl_ctx *ctx, uint64_t nlists, const uint64_t *list_first, const sbl_block *blocks, uint32_t min_block_size,
+                               uint32_t n_reference_chr, const sbl_uncovered_call **calls, uint64_t *ncalls);
+
+/* Text put together on the device from the ORIGINAL records (csrc/uncovered.hip, k_spell_text): the concatenation of npieces pieces in
+ * the order given.  A piece is
+ *   SBL_PIECE_LITERAL  bytes [start, end) of `literals` (literal_len bytes), as they are; chr ignored, width 0
+ *   SBL_PIECE_RECORD   bases [start, end) of record chr, forward, upper-cased ('a' .. 'z' only); width > 0: in lines -- a line feed
+ *                      after every `width` bases and one after the last base (none for an empty range)
+ * All offsets are 64 bit.  The text comes back through the context's pinned text buffer under the ownership rule stated for
+ * sbl_align_pairs: it is overwritten by the next sbl_spell_text, sbl_blocks_sequences or sbl_align_* call.  npieces == 0: empty text.
+ * Every argument is checked on the host before anything is launched.  SBL_ERR_BAD_ARG: no records loaded, an unknown kind, a record
+ * that does not exist, end < start, a range beyond its record or beyond the literal text, a wrapped literal.
+ * sbl_spell_text_times: device time of the last call's kernel and of its device-to-host copy (event pairs). */
+#define SBL_PIECE_LITERAL 0
+#define SBL_PIECE_RECORD 1
+typedef struct { uint32_t kind, chr; uint64_t start, end; uint32_t width, pad_; } sbl_text_piece;
+sbl_status sbl_spell_text(sbl_ctx *ctx, uint64_t npieces, const sbl_text_piece *pieces, const char *literals, uint64_t literal_len,
+                          const char **text, uint64_t *text_len);
+sbl_status sbl_spell_text_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 
 /* Replaces BlockFinder::SerializeGraph (src/serialization.cpp:112-138; defined for records of at least k + 1 characters -- the
  * reference walks off the end of a shorter one): DOT text of the UNcondensed de Bruijn graph of the

@@ -29,7 +29,8 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords",
            "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
-           "sbl_align_groups", "sbl_align_block_groups"]
+           "sbl_align_groups", "sbl_align_block_groups",
+           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -114,6 +115,11 @@ class GroupAlignment:
         self.members = [(int(m["score"]) if ok else None, int(m["band_w"]), int(m["passes"])) for m in members[1:]]
 
 
+from .formats import CALL_DELETION, CALL_INSERTION, CALL_UNMAPPED, PIECE_LITERAL, PIECE_RECORD      # noqa: E402,F401  SBL_CALL_*, SBL_PIECE_*
+CALL_DTYPE = np.dtype([("kind", "<u4"), ("chr", "<u4"), ("start", "<u8"), ("end", "<u8"), ("ref_chr", "<u4"), ("pad_", "<u4"), ("pos", "<u8")])
+PIECE_DTYPE = formats.PIECE_DTYPE
+
+
 class SibeliaError(RuntimeError):
     pass
 
@@ -172,6 +178,9 @@ def load_library():
         gtail = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_align_groups.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(GroupInst)] + gtail
         L.sbl_align_block_groups.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + gtail
+        L.sbl_uncovered_calls.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_spell_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_spell_text_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -411,6 +420,36 @@ class BlockFinder:
         s = AlignStats()
         self._check(self.L.sbl_align_stats(self.h, C.byref(s)), "sbl_align_stats")
         return {f: getattr(s, f) for f, _ in s._fields_}
+
+    def uncovered_calls(self, lists: Sequence[np.ndarray], min_block_size: int, n_reference_chr: int) -> np.ndarray:
+        """What C-Sibelia.py calls from the regions no block covers (reference src/csibelia/C-Sibelia.py:373-427):
+        `lists` are the block lists of the stages in order, the last one the final list; records 0 .. n_reference_chr - 1 are the
+        reference set.  -> CALL_DTYPE records (kind CALL_DELETION / CALL_INSERTION / CALL_UNMAPPED, chr, start, end, ref_chr, pos),
+        0-based half-open, in record order and ascending start.  Interval bookkeeping on the host (csrc/uncovered.hip)."""
+        arrs = [np.ascontiguousarray(b, dtype=formats.BLOCK_DTYPE) for b in lists]
+        first = np.cumsum([0] + [len(a) for a in arrs], dtype=np.uint64)
+        flat = np.concatenate(arrs + [np.zeros(1, dtype=formats.BLOCK_DTYPE)])      # never empty: the library wants an address
+        calls, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.sbl_uncovered_calls(self.h, len(arrs), first.ctypes.data_as(C.POINTER(C.c_uint64)), flat.ctypes.data, min_block_size,
+                                               n_reference_chr, C.byref(calls), C.byref(n)), "sbl_uncovered_calls")
+        return _view(calls.value, n.value, CALL_DTYPE)
+
+    def spell_text(self, pieces: np.ndarray, literals: bytes = b"") -> bytes:
+        """The concatenation of `pieces` (PIECE_DTYPE, e.g. formats.TextPieces.pieces()): ranges of `literals` as they are, forward ranges
+        of the original records upper-cased, wrapped into lines of `width` bases where width > 0.  Spelled by k_spell_text
+        (csrc/uncovered.hip) from the records on the device."""
+        arr = np.ascontiguousarray(pieces, dtype=PIECE_DTYPE)
+        hold = C.create_string_buffer(PIECE_DTYPE.itemsize)
+        t, ln = C.c_void_p(), C.c_uint64()
+        self._check(self.L.sbl_spell_text(self.h, len(arr), arr.ctypes.data if len(arr) else C.addressof(hold), bytes(literals), len(literals),
+                                          C.byref(t), C.byref(ln)), "sbl_spell_text")
+        return C.string_at(t, ln.value) if ln.value else b""
+
+    def spell_text_times(self) -> Tuple[float, float]:
+        """(kernel ms, device-to-host copy ms) of the last spell_text call, from event pairs."""
+        k, d = C.c_double(), C.c_double()
+        self._check(self.L.sbl_spell_text_times(self.h, C.byref(k), C.byref(d)), "sbl_spell_text_times")
+        return k.value, d.value
 
     def _block_report(self, fn, what, blocks, names) -> bytes:
         nm = self._names_array(what, names)

@@ -20,6 +20,7 @@
 
 #include "sbl_ctx.h"
 #include "sbl_dna.h"
+#include "sbl_text.h"
 
 namespace {
 
@@ -31,58 +32,13 @@ struct BsDesc {
 	unsigned L, hlen, rev, pad_;
 };
 
-typedef unsigned long long u64;
-
-// largest i in [0, n) with off[i] <= x (off[0] = 0 <= x)
-template <class P> __device__ inline unsigned bs_find(P off, unsigned long long n, u64 x)
-{
-	unsigned long long lo = 0, hi = n;
-	while (hi - lo > 1) {
-		const unsigned long long mid = lo + (hi - lo) / 2;
-		if (off[mid] <= x) lo = mid; else hi = mid;
-	}
-	return (unsigned)lo;
-}
-
 // DNASequence::Translate (src/dnasequence.cpp:11-28) on 8 bytes at once: A <-> T and C <-> G in either case, every other byte unchanged.
-// zero8: 0x80 in every byte of v that is zero (exact: no carries cross bytes)
-__device__ inline u64 zero8(u64 v) { return ~(((v & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | v) & 0x8080808080808080ull; }
 __device__ inline u64 complement8(u64 x)
 {
 	const u64 f = x & 0xDFDFDFDFDFDFDFDFull;                            // case folded: 0x41 only for 'A' / 'a', ...
 	const u64 at = (zero8(f ^ 0x4141414141414141ull) | zero8(f ^ 0x5454545454545454ull)) >> 7;
 	const u64 cg = (zero8(f ^ 0x4343434343434343ull) | zero8(f ^ 0x4747474747474747ull)) >> 7;
 	return x ^ (at * 0x15) ^ (cg * 0x04);                               // 'A' ^ 'T' = 0x15, 'C' ^ 'G' = 0x04
-}
-
-struct B16 { u64 lo, hi; };
-// bytes [sh, sh + 16) of the 32 bytes (a, b), sh in [0, 16)
-__device__ inline B16 window16(uint4 a, uint4 b, unsigned sh)
-{
-	u64 w0 = (u64)a.x | ((u64)a.y << 32), w1 = (u64)a.z | ((u64)a.w << 32), w2 = (u64)b.x | ((u64)b.y << 32), w3 = (u64)b.z | ((u64)b.w << 32);
-	if (sh >= 8) { w0 = w1; w1 = w2; w2 = w3; sh -= 8; }
-	if (!sh) return {w0, w1};
-	const unsigned r = sh * 8;
-	return {(w0 >> r) | (w1 << (64 - r)), (w1 >> r) | (w2 << (64 - r))};
-}
-// 16 bytes with '\n' inserted before byte p (p in [0, 16)); the last byte falls off
-__device__ inline B16 insert_newline(B16 w, unsigned p)
-{
-	B16 o;
-	if (p < 8) {
-		const unsigned r = p * 8;
-		const u64 keep = r ? w.lo & (~0ull >> (64 - r)) : 0;
-		const u64 up = r ? (w.lo >> r) << r : w.lo;                       // bytes p.. of lo
-		o.lo = keep | ((u64)'\n' << r) | (up << 8);
-		o.hi = (w.hi << 8) | (w.lo >> 56);
-	} else {
-		const unsigned r = (p - 8) * 8;
-		const u64 keep = r ? w.hi & (~0ull >> (64 - r)) : 0;
-		const u64 up = r ? (w.hi >> r) << r : w.hi;
-		o.lo = w.lo;
-		o.hi = keep | ((u64)'\n' << r) | (up << 8);
-	}
-	return o;
 }
 
 __global__ __launch_bounds__(BS_THREADS) void k_block_sequences(const uint8_t *__restrict__ orig, const BsDesc *__restrict__ desc,

@@ -95,6 +95,10 @@ struct sbl_ctx {
 	uint64_t bs_len = 0;
 	double bs_kernel_ms = 0, bs_copy_ms = 0;   // event pairs around the kernel / the device-to-host copy of the last call
 
+	// sbl_uncovered_calls / sbl_spell_text (uncovered.hip): what the first hands out; the second spells through d_bs_* and h_bs_text
+	std::vector<sbl_uncovered_call> unc_calls;
+	double st_kernel_ms = 0, st_copy_ms = 0;   // event pairs around k_spell_text / the device-to-host copy of the last call
+
 	// sbl_correct_boundaries / sbl_align_windows (boundary_align.hip): descriptors, trace codes, results, caller-supplied strings
 	DevBuf d_ba_desc, d_ba_codes, d_ba_out, d_ba_seq;
 	sbl_correct_stats_t correct_stats{};

@@ -1,0 +1,51 @@
+// sbl_text.h -- what the output-stationary text kernels share (blockseq.hip: k_block_sequences, uncovered.hip: k_spell_text): the search
+// of a text offset in the offsets of the pieces, and 16 bytes of text held in two registers -- cut out of two aligned source words,
+// opened for a line feed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+typedef unsigned long long u64;
+
+// largest i in [0, n) with off[i] <= x (off[0] = 0 <= x)
+template <class P> __device__ inline unsigned bs_find(P off, unsigned long long n, u64 x)
+{
+	unsigned long long lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const unsigned long long mid = lo + (hi - lo) / 2;
+		if (off[mid] <= x) lo = mid; else hi = mid;
+	}
+	return (unsigned)lo;
+}
+
+// zero8: 0x80 in every byte of v that is zero (exact: no carries cross bytes)
+__device__ inline u64 zero8(u64 v) { return ~(((v & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | v) & 0x8080808080808080ull; }
+
+struct B16 { u64 lo, hi; };
+// bytes [sh, sh + 16) of the 32 bytes (a, b), sh in [0, 16)
+__device__ inline B16 window16(uint4 a, uint4 b, unsigned sh)
+{
+	u64 w0 = (u64)a.x | ((u64)a.y << 32), w1 = (u64)a.z | ((u64)a.w << 32), w2 = (u64)b.x | ((u64)b.y << 32), w3 = (u64)b.z | ((u64)b.w << 32);
+	if (sh >= 8) { w0 = w1; w1 = w2; w2 = w3; sh -= 8; }
+	if (!sh) return {w0, w1};
+	const unsigned r = sh * 8;
+	return {(w0 >> r) | (w1 << (64 - r)), (w1 >> r) | (w2 << (64 - r))};
+}
+// 16 bytes with '\n' inserted before byte p (p in [0, 16)); the last byte falls off
+__device__ inline B16 insert_newline(B16 w, unsigned p)
+{
+	B16 o;
+	if (p < 8) {
+		const unsigned r = p * 8;
+		const u64 keep = r ? w.lo & (~0ull >> (64 - r)) : 0;
+		const u64 up = r ? (w.lo >> r) << r : w.lo;                       // bytes p.. of lo
+		o.lo = keep | ((u64)'\n' << r) | (up << 8);
+		o.hi = (w.hi << 8) | (w.lo >> 56);
+	} else {
+		const unsigned r = (p - 8) * 8;
+		const u64 keep = r ? w.hi & (~0ull >> (64 - r)) : 0;
+		const u64 up = r ? (w.hi >> r) << r : w.hi;
+		o.lo = w.lo;
+		o.hi = keep | ((u64)'\n' << r) | (up << 8);
+	}
+	return o;
+}

@@ -166,11 +166,97 @@ def vcf_text(reference_name: str, records) -> bytes:
     """write_vcf_header (C-Sibelia.py:433-440) with ##source=sibelia_amd, then Variant.get_vcf_record (:177-180) per record
     (reference record description, POS, REF, ALT), sorted by (description, POS) as variant_key does (:502-503): eight tab-separated
     columns, '.' for an empty allele."""
-    out = ["##fileformat=VCFv4.1", "##source=sibelia_amd", "##reference=" + strip_chr_id(reference_name),
-           '##INFO=<ID=SVTYPE,Number=1,Type=String,Description="Type of structural variant">',
-           '##INFO=<ID=IMPRECISE,Number=0,Type=Flag,Description="Imprecise structural variation">',
-           '##INFO=<ID=CIPOS,Number=2,Type=Integer,Description="Confidence interval around POS for imprecise variants">',
-           "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"])]
+    out = vcf_header_lines(reference_name)
     for name, pos, ref, alt in sorted(records, key=lambda r: (r[0], r[1])):
         out.append("\t".join([strip_chr_id(name), str(pos), ".", ref.decode("latin1") or ".", alt.decode("latin1") or ".", ".", ".", "."]))
     return ("\n".join(out) + "\n").encode("latin1")
+
+
+def vcf_header_lines(reference_name: str):
+    return ["##fileformat=VCFv4.1", "##source=sibelia_amd", "##reference=" + strip_chr_id(reference_name),
+            '##INFO=<ID=SVTYPE,Number=1,Type=String,Description="Type of structural variant">',
+            '##INFO=<ID=IMPRECISE,Number=0,Type=Flag,Description="Imprecise structural variation">',
+            '##INFO=<ID=CIPOS,Number=2,Type=Integer,Description="Confidence interval around POS for imprecise variants">',
+            "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"])]
+
+
+# ------------------------------------------------------------------------------------------ calls from uncovered regions (--uncovered, --unmapped)
+
+CALL_DELETION, CALL_INSERTION, CALL_UNMAPPED = 0, 1, 2      # SBL_CALL_* (include/sibelia_amd.h)
+PIECE_LITERAL, PIECE_RECORD = 0, 1                          # SBL_PIECE_*
+PIECE_DTYPE = np.dtype([("kind", "<u4"), ("chr", "<u4"), ("start", "<u8"), ("end", "<u8"), ("width", "<u4"), ("pad_", "<u4")])      # sbl_text_piece
+LINE_LENGTH = 60                                  # src/csibelia/C-Sibelia.py:19
+
+
+class TextPieces:
+    """The ordered piece list of BlockFinder.spell_text: literal text (kept in one blob; neighbouring literals become one piece) and
+    ranges of the original records, which the device spells -- the host never holds an allele."""
+
+    def __init__(self):
+        self.literals = bytearray()
+        self._pieces = []
+
+    def lit(self, text: bytes) -> None:
+        if not text:
+            return
+        at = len(self.literals)
+        self.literals += text
+        if self._pieces and self._pieces[-1][0] == PIECE_LITERAL and self._pieces[-1][3] == at:
+            self._pieces[-1] = (PIECE_LITERAL, 0, self._pieces[-1][2], at + len(text), 0, 0)
+        else:
+            self._pieces.append((PIECE_LITERAL, 0, at, at + len(text), 0, 0))
+
+    def rec(self, chr_: int, start: int, end: int, width: int = 0) -> None:
+        self._pieces.append((PIECE_RECORD, int(chr_), int(start), int(end), int(width), 0))
+
+    def pieces(self) -> np.ndarray:
+        return np.array(self._pieces, dtype=PIECE_DTYPE) if self._pieces else np.zeros(0, dtype=PIECE_DTYPE)
+
+
+def vcf_pieces(names: Sequence[str], first_size: int, first_base: bytes, records, calls, breakends: bool) -> TextPieces:
+    """The VCF of --variants --uncovered as pieces (C-Sibelia.py:433-463, :575-585): the header; with `breakends` two records
+    bnd_<2i> / bnd_<2i + 1> per unmapped insertion i (write_insertions_vcf: on the first reference record at POS 1, REF = `first_base`,
+    that record's first base as its file spells it, CIPOS = 0,<first_size>); then all variant records sorted stably by (description,
+    POS) -- `records` (those of vcf_text: description, POS, REF, ALT) first in the unsorted list, then the deletions and anchored
+    insertions of `calls` (CALL_DTYPE, in record order and ascending start), whose alleles are ranges of the records:
+      deletion [s, e) of record c     POS s, REF c[s - 1, e), ALT c[s - 1, s)   (s = 0: REF c[0, e), ALT '.')
+      insertion [s, e) at p of r      POS p, REF r[p - 1, p), ALT r[p - 1, p) c[s, e)"""
+    t = TextPieces()
+    t.lit(("\n".join(vcf_header_lines(names[0])) + "\n").encode("latin1"))
+    if breakends:
+        chrom, ref = strip_chr_id(names[0]), first_base.decode("latin1")
+        info = "IMPRECISE;SVTYPE=BND;CIPOS=0,%d" % first_size
+        unmapped = [u for u in calls if u["kind"] == CALL_UNMAPPED]
+        for i, u in enumerate(unmapped):
+            contig = names[int(u["chr"])]
+            for j, alt in enumerate(("%s[%s:%d[" % (ref, contig, int(u["start"]) + 1), "]%s:%d]%s" % (contig, int(u["end"]) + 1, ref))):
+                t.lit(("\t".join([chrom, "1", "bnd_%d" % (2 * i + j), ref, alt, ".", ".", info]) + "\n").encode("latin1"))
+    rows = [(name, pos, ref or b".", alt or b".") for name, pos, ref, alt in records]
+    for u in calls:
+        c, s, e, r, p = int(u["chr"]), int(u["start"]), int(u["end"]), int(u["ref_chr"]), int(u["pos"])
+        if u["kind"] == CALL_DELETION:
+            rows.append((names[c], s, (c, s - 1 if s else 0, e), (c, s - 1, s) if s else b"."))
+        elif u["kind"] == CALL_INSERTION:
+            rows.append((names[r], p, (r, p - 1, p), (r, p - 1, p, c, s, e)))
+    for name, pos, ref, alt in sorted(rows, key=lambda x: (x[0], x[1])):
+        t.lit(("%s\t%d\t.\t" % (strip_chr_id(name), pos)).encode("latin1"))
+        for allele, after in ((ref, b"\t"), (alt, b"\t.\t.\t.\n")):
+            if isinstance(allele, bytes):
+                t.lit(allele)
+            else:
+                for k in range(0, len(allele), 3):
+                    t.rec(*allele[k:k + 3])
+            t.lit(after)
+    return t
+
+
+def unmapped_fasta_pieces(names: Sequence[str], calls) -> TextPieces:
+    """write_insertions_fasta (C-Sibelia.py:493-500) as pieces: per unmapped insertion [s, e) of record c the description
+    Seq="<description of c>",Start=<s + 1>",End=<e> -- the quote after Start's value is the reference's -- and the bases in lines of 60."""
+    t = TextPieces()
+    for u in calls:
+        if u["kind"] == CALL_UNMAPPED:
+            c, s, e = int(u["chr"]), int(u["start"]), int(u["end"])
+            t.lit(('>Seq="%s",Start=%d",End=%d\n' % (names[c], s + 1, e)).encode("latin1"))
+            t.rec(c, s, e, LINE_LENGTH)
+    return t

@@ -7,7 +7,9 @@ standard output); `main` writes the files and prints the text (python -m sibelia
 
 --maf / --variants (two input files) add what the reference's comparison tool C-Sibelia.py makes of such a run: the alignments of the
 unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).  --multimaf (any number of input files) writes a
-multiple alignment of every block with at least two instances (`align_block_groups`).
+multiple alignment of every block with at least two instances (`align_block_groups`).  --uncovered adds the rest of C-Sibelia's VCF to
+the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
+that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
 Not written: circos/ and d3_blocks_diagram.html -- the reference instantiates them from templates embedded in its own sources.
 
@@ -38,6 +40,11 @@ MULTI_HELP = ("Any number of input files: align every synteny block with at leas
               "device and write one MAF paragraph per block.  The alignment is centre-star on the block's first instance (by record, start, "
               "end, strand): every other instance is aligned to it as under --maf and the gaps are merged.  It is this program's own "
               "definition, not mlagan's, which the reference's comparison tool runs on such blocks.")
+
+UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
+                  "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
+                  "a deletion, such a region of the second file as an insertion behind the unique block that ends before it, and "
+                  "where there is no such block as two breakend records (bnd_<n>).")
 
 NOT_WRITTEN = ("The Circos files (circos/) and d3_blocks_diagram.html of the reference program are not written: "
                "they are instantiated from templates embedded in the reference's sources.")
@@ -149,6 +156,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "on the device and write the alignments in MAF format.  " + ALIGN_HELP)
     p.add_argument("--variants", default=None, metavar="FILE", help="Two input files: write the SNVs and indels read off those alignments in VCF format "
                    "(positions on the records of the first file).")
+    p.add_argument("--uncovered", action="store_true", help=UNCOVERED_HELP)
+    p.add_argument("--unmapped", default=None, metavar="FILE", help="With --uncovered: write the insertions that cannot be placed to FILE in FASTA format "
+                   "instead of as breakend records.")
     p.add_argument("--multimaf", default=None, metavar="FILE", help=MULTI_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
@@ -169,15 +179,21 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
             raise PipelineError("--maf and --variants need the synteny blocks: they cannot be combined with --noblocks")
     if opt.multimaf is not None and opt.noblocks:
         raise PipelineError("--multimaf needs the synteny blocks: it cannot be combined with --noblocks")
+    if opt.uncovered and opt.variants is None:
+        raise PipelineError("--uncovered adds its records to the file of --variants: it needs --variants")
+    if opt.uncovered and not opt.allstages:
+        raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
+    if opt.unmapped is not None and not opt.uncovered:
+        raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
     if opt.maf is not None or opt.variants is not None or opt.multimaf is not None:
         _check_alignment_files(opt)
     return opt
 
 
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants / --multimaf name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --unmapped / --multimaf name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
-    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--multimaf", opt.multimaf)) if f is not None]
+    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--unmapped", opt.unmapped), ("--multimaf", opt.multimaf)) if f is not None]
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -243,7 +259,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for f in (opt.maf, opt.variants, opt.multimaf) if f is not None]      # relative names: under the output directory
+        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf) if f is not None]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -341,12 +357,39 @@ def load_input(filenames: Sequence[str], device: int = -1):
         raise PipelineError(m.group(1) if m and m.group(1) else text)
 
 
+def check_duplicate_ids(names: Sequence[str]) -> None:
+    """C-Sibelia.py:566-570: the record ids of both files, sorted; the first one that stands twice is an error."""
+    ids = sorted(names)
+    for a, b in zip(ids, ids[1:]):
+        if a == b:
+            raise PipelineError('Found duplicated sequence id "%s"' % a)
+
+
+def first_base(path: str) -> bytes:
+    """The first base of the first record of a FASTA file as the file spells it: C-Sibelia.py reads its files itself and does not change
+    the case (parse_fasta_file :98-116), and the breakend records quote this base (:451)."""
+    import gzip
+    with (gzip.open if path.endswith(".gz") else open)(path, "rb") as f:
+        seen = False
+        for raw in f:
+            line = raw.strip()
+            if line[:1] == b">":
+                if seen:
+                    break
+                seen = True
+            elif line and seen:
+                return line[:1]
+    return b""
+
+
 # ------------------------------------------------------------------------------------------ alignments of unique blocks
 
-def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: int, complain: Callable[[str], None]) -> Dict[str, bytes]:
+def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: int, complain: Callable[[str], None],
+                        history: Optional[Sequence] = None) -> Dict[str, bytes]:
     """--maf / --variants: what C-Sibelia.py does after the reference program has run (src/csibelia/C-Sibelia.py:343-368, :473-484,
     :433-444), with the alignments made on the device (BlockFinder.align_unique_blocks) instead of by one LAGAN process per block.
-    Skipped blocks are named through `complain`, one line each, and are absent from both files."""
+    Skipped blocks are named through `complain`, one line each, and are absent from both files.  `history`: the block lists of the
+    stages and the final one, for --uncovered."""
     from . import formats
     from .api import GALIGN_OK, SibeliaError
     try:
@@ -366,8 +409,29 @@ def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirs
     out = {}
     if opt.maf is not None:
         out[opt.maf] = formats.maf_text(groups)
-    if opt.variants is not None:
+    if opt.variants is not None and opt.uncovered:
+        out.update(uncovered_files(bf, opt, names, nfirst, records, history))
+    elif opt.variants is not None:
         out[opt.variants] = formats.vcf_text(names[0], records)
+    return out
+
+
+def uncovered_files(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: int, records, history: Sequence) -> Dict[str, bytes]:
+    """--uncovered / --unmapped: C-Sibelia.py's calls from the regions no mixed block of any stage covers (:373-427) next
+    to the alignment `records` in the VCF (:575-585), and the insertions it cannot place as breakend records or, with --unmapped, as
+    FASTA (:493-500).  The runs come from interval bookkeeping in the library (BlockFinder.uncovered_calls); each file is one piece
+    list whose record ranges -- the alleles -- are spelled on the device (BlockFinder.spell_text)."""
+    from . import formats
+    from .api import SibeliaError
+    try:
+        calls = bf.uncovered_calls(history, opt.minblocksize, nfirst)
+        vcf = formats.vcf_pieces(names, bf.record_sizes()[0], first_base(opt.filenames[0]), records, calls, opt.unmapped is None)
+        out = {opt.variants: bf.spell_text(vcf.pieces(), vcf.literals)}
+        if opt.unmapped is not None:
+            fa = formats.unmapped_fasta_pieces(names, calls)
+            out[opt.unmapped] = bf.spell_text(fa.pieces(), fa.literals)
+    except SibeliaError as e:
+        raise PipelineError(str(e))
     return out
 
 
@@ -413,6 +477,8 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
     bf, names, nfirst = load_input(opt.filenames, opt.device)
     files: Dict[str, bytes] = {}
     try:
+        if opt.uncovered:
+            check_duplicate_ids(names)
         if not opt.inram:
             bf.set_tempfile_mode(True)            # BlockFinder(chrList, tempDir): temp-file names come out of the same rand() stream
         nchr = len(names) if names is not None else len(bf.record_names())
@@ -452,7 +518,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
             if opt.sequencesfile:
                 files["blocks_sequences.fasta"] = bf.blocks_sequences(None, names)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
-                files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write))
+                files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
             if opt.multimaf is not None:          # likewise on the final list
                 files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write))
         if opt.graphfile:
