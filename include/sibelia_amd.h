@@ -259,6 +259,27 @@ typedef struct { uint32_t status; int32_t score; uint32_t band_w, passes; uint64
 sbl_status sbl_align_pairs(sbl_ctx *ctx, uint64_t npairs, const sbl_pair_desc *desc, const sbl_pair_result **res,
                            const sbl_align_run **runs, uint64_t *nruns, const char **rows, uint64_t *rows_len);
 
+/* Affine gap costs for the alignment above.  `open` = o, 0 <= o <= 100000, is the cost of OPENING a gap run: a run of
+ * L gap columns costs o + 75 L; match +25, mismatch -75 and the 75 per gap column stay.  An 'I' run directly followed by a 'D' run is
+ * two runs.  Three matrices, filled from the ends (absent terms are minus infinity):
+ *   H[n][m] = 0
+ *   E[i][j] = max(E[i+1][j] - 75, H[i+1][j] - o - 75)      i < n   (a[i] over '-')
+ *   F[i][j] = max(F[i][j+1] - 75, H[i][j+1] - o - 75)      j < m   ('-' over b[j])
+ *   H[i][j] = max(H[i+1][j+1] + (a[i] == b[j] ? 25 : -75) [i < n, j < m], E[i][j] [i < n], F[i][j] [j < m])
+ * so H[n][j] = F[n][j] = -o - 75 (m - j) and H[i][m] = E[i][m] = -o - 75 (n - i).  The trace runs from (0, 0) in state H: the diagonal
+ * step if it attains H, else state E if E[i][j] attains it, else state F.  State E at (i, j) emits 'I' and then CLOSES -- back to state
+ * H at (i + 1, j) -- if H[i+1][j] - o - 75 == E[i][j], otherwise it stays in E; state F likewise with 'D' along j.  The result is the
+ * score H[0][0] and runs over = X I D as above; n == 0 or m == 0 scores -(o + 75 (n + m)), two empty strings 0.
+ * o == 0 is the alignment above EXACTLY, ties included (E <= H everywhere, so every gap column closes), and runs the same kernel.
+ * Band, certificate (the same U(w): o >= 0 only lowers a path that leaves the band) and doubling are unchanged.  With o > 0 the trace
+ * codes take 4 bits per band cell -- the two caps apply to the doubled size -- and three score arrays share the 64 KiB of LDS: a pair is
+ * SKIPPED beyond 4992 band offsets (12288 with o == 0), so doubling from 64 stops at w = 2048.
+ * sbl_align_set_gap_open: holds for every later sbl_align_pairs / _unique_blocks / _groups / _block_groups call of the context (default 0);
+ * SBL_ERR_BAD_ARG above 100000, the value stays as it was.  Not used by sbl_correct_boundaries, whose alignment is the reference's.
+ * SBL_TEST_GALIGN_AFFINE=1: test switch, sends o == 0 through the three-state kernel. */
+sbl_status sbl_align_set_gap_open(sbl_ctx *ctx, uint32_t open);
+sbl_status sbl_align_get_gap_open(const sbl_ctx *ctx, uint32_t *open);
+
 /* The pairs C-Sibelia.py aligns (determine_unique_block, src/csibelia/C-Sibelia.py:314-323) out of the context's CURRENT block list
  * (after sbl_postprocess / sbl_correct_boundaries): the ids with exactly two instances, one on records 0 .. n_reference_chr - 1 and
  * one outside them, both at least min_block_size long.  The reference instance is a; both are read on the strand the list reports.

@@ -29,7 +29,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords",
            "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
-           "sbl_align_groups", "sbl_align_block_groups",
+           "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -178,6 +178,8 @@ def load_library():
         gtail = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_align_groups.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(GroupInst)] + gtail
         L.sbl_align_block_groups.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + gtail
+        L.sbl_align_set_gap_open.argtypes = [C.c_void_p, C.c_uint32]
+        L.sbl_align_get_gap_open.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sbl_uncovered_calls.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_spell_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_spell_text_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -420,6 +422,19 @@ class BlockFinder:
         s = AlignStats()
         self._check(self.L.sbl_align_stats(self.h, C.byref(s)), "sbl_align_stats")
         return {f: getattr(s, f) for f, _ in s._fields_}
+
+    def set_gap_open(self, n: int) -> None:
+        """The cost of opening a gap run in every later align_* call of this finder (include/sibelia_amd.h): a run of L gap
+        columns costs n + 75 L.  0 (the default) is the linear gap cost; above 100000 is refused and the value stays as it was."""
+        if not 0 <= int(n) <= 2 ** 32 - 1:
+            raise SibeliaError("sbl_align_set_gap_open: bad argument (a gap opening cost outside 0 .. 100000)")
+        self._check(self.L.sbl_align_set_gap_open(self.h, int(n)), "sbl_align_set_gap_open")
+
+    @property
+    def gap_open(self) -> int:
+        v = C.c_uint32()
+        self._check(self.L.sbl_align_get_gap_open(self.h, C.byref(v)), "sbl_align_get_gap_open")
+        return v.value
 
     def uncovered_calls(self, lists: Sequence[np.ndarray], min_block_size: int, n_reference_chr: int) -> np.ndarray:
         """What C-Sibelia.py calls from the regions no block covers (reference src/csibelia/C-Sibelia.py:373-427):

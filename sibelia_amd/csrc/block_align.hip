@@ -20,8 +20,12 @@
 //   spelling  k_spell_groups, output-stationary like blockseq.hip: a lane owns 16 bytes of the rows, finds its group, its row and its
 //             run by binary search over tables the host made from the runs, and writes them with one vector store.  The two gapped
 //             rows of a pair are the rows of a group of one member (gm_spell).
+//   affine    a gap opening cost o > 0 (sbl_align_set_gap_open) runs k_block_align3 instead: the same sweep over three
+//             score states H / E / F, each one array by offset parity, 4 bits of codes per cell (H's choice, "E / F came by
+//             extension"), a trace walk with a state.  o == 0 runs k_block_align as before.
 //   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
-//             grouped by band class (register / LDS 256 / LDS 1024) and chunked under the total cap on the trace codes.
+//             grouped by band class (register / LDS 256 / LDS 1024; with an opening cost register / LDS 256 / LDS 640) and chunked under
+//             the total cap on the trace codes.
 //   groups    sbl_align_groups / sbl_align_block_groups: a centre-star multiple alignment per group of instances.  Every
 //             member against the group's first instance through the same passes (ga_passes); the gap slots of a group merged on the
 //             host from the runs; k_spell_groups spells the rows.
@@ -39,6 +43,10 @@ constexpr u64 GA_MAX_DIAG = 1ull << 23;                // 75 (n + m) stays clear
 constexpr unsigned GA_W0 = 64;
 constexpr size_t GA_PAIR_CAP = (size_t)8 << 30, GA_TOTAL_CAP = (size_t)32 << 30;
 constexpr unsigned GA_ALIGN = 256;
+// gap opening cost o > 0: three score arrays in the same 64 KiB of LDS, 12 (W + 2) + 2 (W / 2 + 40) <= 65536; one wave in registers / 256 lanes / 640 lanes
+constexpr unsigned GA3_REG_W = 512, GA3_MID_W = 2048, GA3_MAX_W = 4992;
+constexpr unsigned GA3_THREADS = 640;
+constexpr unsigned GA_MAX_OPEN = 100000;               // GA_NEG - o - 75 and -(2 o + 75 (n + m)) stay inside 32 bits
 
 struct GaJob {
 	u64 src_a, src_b;                // first byte of the range in the sequence buffer
@@ -208,6 +216,185 @@ template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_a
 	if (tid == 0) out[blockIdx.x] = GaOut{score, nruns, 1, 0};
 }
 
+// ---- gap opening cost: H[i][j] the best score of a[i:] against b[j:], E / F the best that starts with a[i] over '-' /
+// '-' over b[j]; a gap run of L columns costs go + 75 L.  Codes take 4 bits per cell: bits 0-1 H's choice (0 diagonal / equal, 1
+// diagonal / unequal, 2 enter E, 3 enter F), bit 2 "E came by extension" (the run does not close after this column), bit 3 the same for F.
+
+// one cell: the neighbours' scores in -- hd: H two diagonals back; hu, eu: H, E of (i + 1, j); hl, fl: H, F of (i, j + 1)
+__device__ inline unsigned ga3_cell(int hd, int hu, int eu, int hl, int fl, bool eq, int go, int &h, int &e, int &f)
+{
+	const int eo = hu - go - AL_PENALTY, fo = hl - go - AL_PENALTY, ex = eu - AL_PENALTY, fx = fl - AL_PENALTY;
+	e = ex > eo ? ex : eo;
+	f = fx > fo ? fx : fo;
+	const int dg = hd + (eq ? AL_MATCH : -AL_PENALTY);
+	int val = dg > e ? dg : e;
+	val = f > val ? f : val;
+	h = val;
+	return (dg == val ? (eq ? 0u : 1u) : e == val ? 2u : 3u) | (e != eo ? 4u : 0u) | (f != fo ? 8u : 0u);
+}
+
+// a border cell (i == n or j == m): one gap run to the end
+__device__ inline void ga3_border(const GaView &V, int i, int j, int go, int &h, int &e, int &f)
+{
+	const int rest = (V.n - i) + (V.m - j);
+	h = rest ? -go - AL_PENALTY * rest : 0;
+	e = i < V.n ? h : GA_NEG;
+	f = j < V.m ? h : GA_NEG;
+}
+
+// the 4 cells of diagonal d among offsets 8 q + P + 2 c; h, e, f: the lane's 8 offsets of each state (REG) -- hp, ep: h[7], e[7] of lane
+// q - 1; hn, fn: h[0], f[0] of lane q + 1
+template <int P> __device__ inline unsigned ga3_quad_reg(const GaView &V, int go, int d, int q, int (&h)[8], int (&e)[8], int (&f)[8], int hp, int ep, int hn, int fn, int &score)
+{
+	unsigned half = 0;
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		const int k = 8 * q + 2 * c + P;
+		if (k >= V.W) continue;
+		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
+		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
+		int hv, ev, fv;
+		unsigned code = 0;
+		if (i == V.n || j == V.m) ga3_border(V, i, j, go, hv, ev, fv);
+		else {
+			const int xu = 2 * c + P - 1 < 0 ? 0 : 2 * c + P - 1, xl = 2 * c + P + 1 > 7 ? 7 : 2 * c + P + 1;
+			const bool from_prev = P == 0 && c == 0, from_next = P == 1 && c == 3;
+			code = ga3_cell(h[2 * c + P], from_prev ? hp : h[xu], from_prev ? ep : e[xu], from_next ? hn : h[xl], from_next ? fn : f[xl],
+			                V.sa[i - V.imin] == V.sb[j - V.jmin], go, hv, ev, fv);
+		}
+		h[2 * c + P] = hv; e[2 * c + P] = ev; f[2 * c + P] = fv;
+		if (d == 0) score = hv;
+		half |= code << (4 * c);
+	}
+	return half;
+}
+
+// the same over the score arrays in LDS (X[k + 1] = offset k; X[0] and X[W + 1] are minus infinity)
+__device__ inline unsigned ga3_quad_lds(const GaView &V, int go, int d, int q, int p, int *H, int *E, int *F, int &score)
+{
+	unsigned half = 0;
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		const int k = 8 * q + 2 * c + p;
+		if (k >= V.W) break;
+		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
+		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
+		int hv, ev, fv;
+		unsigned code = 0;
+		if (i == V.n || j == V.m) ga3_border(V, i, j, go, hv, ev, fv);
+		else code = ga3_cell(H[k + 1], H[k], E[k], H[k + 2], F[k + 2], V.sa[i - V.imin] == V.sb[j - V.jmin], go, hv, ev, fv);
+		H[k + 1] = hv; E[k + 1] = ev; F[k + 1] = fv;
+		if (d == 0) score = hv;
+		half |= code << (4 * c);
+	}
+	return half;
+}
+
+// the 4 bits of cell (ci, cj); 16: beyond the matrix or the band.  A lane's two bytes of a diagonal hold its cells c = 0 .. 3 in ascending nibbles.
+__device__ inline unsigned ga3_fetch(const uint8_t *codes, const GaJob &J, int lo, int ci, int cj)
+{
+	if (ci >= (int)J.n || cj >= (int)J.m) return 16;
+	const int k = cj - ci - lo + (int)J.w;
+	if (k < 0 || k >= (int)J.W) return 16;
+	return (codes[(u64)(unsigned)(ci + cj) * J.B + (unsigned)(k >> 2)] >> (4 * ((k >> 1) & 1))) & 15;
+}
+
+// k_block_align with the gap opening cost go (J.B: code bytes per diagonal, two per lane that holds cells).  REG: one wave, 24 score
+// registers per lane, four cross-lane moves per diagonal.  Otherwise three arrays of W + 2 scores in LDS and one barrier per diagonal:
+// every cell reads the other parity and writes its own.
+template <bool REG> __global__ __launch_bounds__(REG ? 64 : GA3_THREADS) void k_block_align3(const uint8_t *__restrict__ seq, const GaJob *__restrict__ jobs, int go,
+                                                                                             uint8_t *codes_all, sbl_align_run *runs_all, GaOut *__restrict__ out)
+{
+	extern __shared__ int ga_lds[];
+	__shared__ int s_score;
+	const GaJob J = jobs[blockIdx.x];
+	const int n = (int)J.n, m = (int)J.m, w = (int)J.w, W = (int)J.W, B = (int)J.B, Q = B / 2;
+	const int lo = m - n < 0 ? m - n : 0, omin = lo - w, omax = omin + W - 1;
+	const int tid = (int)threadIdx.x, T = (int)blockDim.x;
+	int *const H = ga_lds, *const E = H + (W + 2), *const F = E + (W + 2);      // LDS kernel only
+	uint8_t *const sa = reinterpret_cast<uint8_t *>(ga_lds + (REG ? 0 : 3 * (W + 2)));
+	uint8_t *const sb = sa + ga_seg((unsigned)W);
+	uint8_t *const mycodes = codes_all + J.code_off;                        // 256-byte aligned, B even: every 16-bit store is aligned
+	GaView V{n, m, lo, w, W, 0, 0, sa, sb};
+	int h[8], e[8], f[8];
+	int score = 0;
+	if (REG) { for (int c = 0; c < 8; c++) h[c] = e[c] = f[c] = GA_NEG; }
+	else { for (int k = tid; k < 3 * (W + 2); k += T) H[k] = GA_NEG; }
+	if (tid == 0) s_score = 0;
+
+	for (int dtop = n + m; dtop >= 0; dtop -= GA_CHUNK) {
+		const int dbot = dtop - (GA_CHUNK - 1) > 0 ? dtop - (GA_CHUNK - 1) : 0;
+		int imin = (dbot - omax) >> 1, imax = (dtop - omin) >> 1, jmin = (dbot + omin) >> 1, jmax = (dtop + omax) >> 1;      // as in k_block_align
+		imin = imin < 0 ? 0 : imin; imax = imax > n - 1 ? n - 1 : imax;
+		jmin = jmin < 0 ? 0 : jmin; jmax = jmax > m - 1 ? m - 1 : jmax;
+		__syncthreads();
+		for (int t = tid; t <= imax - imin; t += T) sa[t] = strand_base(seq, J.src_a, J.n, (unsigned)(imin + t), J.rev_a);
+		for (int t = tid; t <= jmax - jmin; t += T) sb[t] = strand_base(seq, J.src_b, J.m, (unsigned)(jmin + t), J.rev_b);
+		V.imin = imin; V.jmin = jmin;
+		__syncthreads();
+		for (int d = dtop; d >= dbot; d--) {
+			const int p = (d - lo + w) & 1;
+			if (REG) {
+				int hp = __shfl_up(h[7], 1), ep = __shfl_up(e[7], 1), hn = __shfl_down(h[0], 1), fn = __shfl_down(f[0], 1);
+				if (tid == 0) hp = ep = GA_NEG;
+				if (tid == 63) hn = fn = GA_NEG;
+				const unsigned half = p ? ga3_quad_reg<1>(V, go, d, tid, h, e, f, hp, ep, hn, fn, score) : ga3_quad_reg<0>(V, go, d, tid, h, e, f, hp, ep, hn, fn, score);
+				if (tid < Q) *reinterpret_cast<uint16_t *>(mycodes + (u64)(unsigned)d * (unsigned)B + 2u * (unsigned)tid) = (uint16_t)half;
+			} else {
+				for (int q = tid; q < Q; q += T)
+					*reinterpret_cast<uint16_t *>(mycodes + (u64)(unsigned)d * (unsigned)B + 2u * (unsigned)q) = (uint16_t)ga3_quad_lds(V, go, d, q, p, H, E, F, score);
+				__syncthreads();
+			}
+		}
+	}
+	{
+		const int k0 = w - lo, q0 = k0 >> 3;                                  // exactly one lane filled (0, 0)
+		if ((REG ? tid : q0 % T) == (REG ? q0 : tid)) s_score = score;
+	}
+	__threadfence_block();
+	__syncthreads();
+	if (tid >= 64) return;
+	score = s_score;
+	if (!J.full && !(score > ga_bound(n, m, w))) {
+		if (tid == 0) out[blockIdx.x] = GaOut{score, 0, 0, 0};
+		return;
+	}
+
+	sbl_align_run *const runs = runs_all + J.run_off;
+	unsigned nruns = 0, cur_op = 0, cur_len = 0;
+	auto emit = [&](unsigned op, unsigned len) {
+		if (op == cur_op) { cur_len += len; return; }
+		if (cur_len) { if (tid == 0) runs[nruns] = sbl_align_run{cur_op, cur_len}; nruns++; }
+		cur_op = op; cur_len = len;
+	};
+	// state 0: H -- lane t looks t diagonal steps ahead, one ballot consumes a run of equal codes.  State 1 / 2: inside an I / D run --
+	// lane t looks t columns ahead along i / j; the run closes after the first column whose extension bit is clear.
+	int i = 0, j = 0, state = 0;
+	while (i < n && j < m) {
+		if (state == 0) {
+			const unsigned x = ga3_fetch(mycodes, J, lo, i + tid, j + tid), c = x == 16 ? 4 : x & 3;
+			const unsigned c0 = (unsigned)__shfl((int)c, 0);
+			if (c0 >= 2) { state = (int)c0 - 1; continue; }
+			const u64 other = __ballot(c != c0);
+			const int len = other ? __ffsll((long long)other) - 1 : 64;
+			emit(c0 == 0 ? '=' : 'X', (unsigned)len); i += len; j += len;
+		} else {
+			const unsigned x = state == 1 ? ga3_fetch(mycodes, J, lo, i + tid, j) : ga3_fetch(mycodes, J, lo, i, j + tid);
+			const u64 closes = __ballot(x == 16 || !((x >> (state + 1)) & 1));
+			int len = closes ? __ffsll((long long)closes) : 64;
+			const int room = state == 1 ? n - i : m - j;
+			len = len > room ? room : len;
+			emit(state == 1 ? 'I' : 'D', (unsigned)len);
+			if (state == 1) i += len; else j += len;
+			if (closes) state = 0;
+		}
+	}
+	if (i < n) emit('I', (unsigned)(n - i));
+	if (j < m) emit('D', (unsigned)(m - j));
+	emit(0, 0);
+	if (tid == 0) out[blockIdx.x] = GaOut{score, nruns, 1, 0};
+}
+
 // ---- spelling: the rows of a centre-star multiple alignment; the two rows of a pair are those of a group of one member
 
 constexpr unsigned GS_THREADS = 256;
@@ -301,13 +488,22 @@ unsigned ga_env(const char *name, unsigned fallback)
 
 struct Pending { size_t at; unsigned w; };
 
+// the three-state kernel runs: a gap opening cost is set (SBL_TEST_GALIGN_AFFINE=1: test switch, sends o == 0 through it as well)
+bool ga_affine(const sbl_ctx *c)
+{
+	const char *e = getenv("SBL_TEST_GALIGN_AFFINE");
+	return c->gap_open > 0 || (e && atoi(e) == 1);
+}
+
 // one pass: the pending pairs of one band class at their current w, chunked under the total cap.  Fills res (score, status) and appends
 // the runs of the pairs that pass the certificate; returns those that have to run again.
 void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<size_t> &which, int cls, std::vector<uint8_t> &passed)
 {
 	const size_t total_cap = getenv("SBL_TEST_GALIGN_TOTAL_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_TOTAL_KB", 1) << 10 : GA_TOTAL_CAP;
 	hipStream_t s = c->stream;
-	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : 1024;
+	const bool affine = ga_affine(c);
+	const int go = (int)c->gap_open;
+	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : affine ? GA3_THREADS : 1024;
 	std::vector<GaJob> chunk;
 	std::vector<GaOut> got;
 	for (size_t at = 0; at < which.size();) {
@@ -321,7 +517,7 @@ void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<siz
 			if (!chunk.empty() && bytes + need > total_cap) break;
 			j.code_off = bytes; j.run_off = nrun;
 			bytes += need; nrun += (u64)j.n + j.m + 1;
-			lds = std::max(lds, (cls ? (size_t)(j.W + 2) * 4 : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
+			lds = std::max(lds, (cls ? (size_t)(j.W + 2) * (affine ? 12 : 4) : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
 			chunk.push_back(j);
 			c->align_stats.cells += (u64)(j.n + j.m + 1) * ((j.W + 1) / 2);
 		}
@@ -329,7 +525,9 @@ void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<siz
 		c->d_ga_runs.ensure((size_t)nrun * sizeof(sbl_align_run));
 		got.resize(chunk.size());
 		c->align_stats.kernel_ms += al_timed_launch(c, [&] {
-			if (cls == 0) k_block_align<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+			if (affine && cls == 0) k_block_align3<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), go, c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+			else if (affine) k_block_align3<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), go, c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
+			else if (cls == 0) k_block_align<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
 			else k_block_align<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
 		}, got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut));
 		c->align_stats.launches++;
@@ -359,6 +557,8 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 	const size_t N = desc.size();
 	const size_t pair_cap = getenv("SBL_TEST_GALIGN_CAP_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_CAP_KB", 1) << 10 : GA_PAIR_CAP;
 	const unsigned w0 = ga_env("SBL_TEST_GALIGN_W0", GA_W0);
+	const bool affine = ga_affine(c);
+	const unsigned reg_w = affine ? GA3_REG_W : GA_REG_W, mid_w = affine ? GA3_MID_W : GA_MID_W, max_w = affine ? GA3_MAX_W : GA_MAX_W;
 	c->align_stats = sbl_align_stats_t{};
 	c->align_stats.pairs = N;
 	c->ga_res.assign(N, sbl_pair_result{});
@@ -375,7 +575,7 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 		if (n + m >= GA_MAX_DIAG) { r.status = SBL_GALIGN_SKIPPED; continue; }
 		j.n = (unsigned)n; j.m = (unsigned)m; j.rev_a = d.rev_a != 0; j.rev_b = d.rev_b != 0;
 		if (n == 0 || m == 0) {                                               // all gaps: nothing to fill
-			r.score = -AL_PENALTY * (int)(n + m);
+			r.score = n + m ? -(int)c->gap_open - AL_PENALTY * (int)(n + m) : 0;
 			r.first_run = c->ga_runs.size();
 			if (n + m) { c->ga_runs.push_back(sbl_align_run{n ? (uint32_t)'I' : (uint32_t)'D', (uint32_t)(n + m)}); r.nruns = 1; }
 			continue;
@@ -392,9 +592,9 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 			j.w = std::min(p.w, mn);                                          // w = min(n, m): the band covers the matrix
 			j.full = j.w >= mn;
 			j.W = diff + 2 * j.w + 1;
-			j.B = ((j.W + 1) / 2 + 3) / 4;
-			if (j.W > GA_MAX_W || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
-			cls[j.W <= GA_REG_W ? 0 : j.W <= GA_MID_W ? 1 : 2].push_back(p.at);
+			j.B = ((j.W + 1) / 2 + 3) / 4 * (affine ? 2 : 1);                 // a lane's 4 cells of a diagonal: 2 bits each, 4 with an opening cost
+			if (j.W > max_w || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
+			cls[j.W <= reg_w ? 0 : j.W <= mid_w ? 1 : 2].push_back(p.at);
 		}
 		for (int k = 0; k < 3; k++) if (!cls[k].empty()) ga_launch(c, jobs, cls[k], k, passed);
 		std::vector<Pending> again;
@@ -571,6 +771,21 @@ extern "C" sbl_status sbl_align_stats(const sbl_ctx *c, sbl_align_stats_t *out)
 {
 	if (!c || !out) return SBL_ERR_BAD_ARG;
 	*out = c->align_stats;
+	return SBL_OK;
+}
+
+extern "C" sbl_status sbl_align_set_gap_open(sbl_ctx *c, uint32_t open)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(open <= GA_MAX_OPEN, SBL_ERR_BAD_ARG, "a gap opening cost above 100000");
+		c->gap_open = open;
+	});
+}
+
+extern "C" sbl_status sbl_align_get_gap_open(const sbl_ctx *c, uint32_t *open)
+{
+	if (!c || !open) return SBL_ERR_BAD_ARG;
+	*open = c->gap_open;
 	return SBL_OK;
 }
 

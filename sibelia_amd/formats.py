@@ -102,9 +102,10 @@ def maf_line(name: str, start: int, end: int, reverse: bool, record_size: int, r
     return b"s %s %d %d %s %d %s" % (name.encode(), at, end - start, b"-" if reverse else b"+", record_size, row)
 
 
-def maf_text(groups) -> bytes:
-    """write_alignments_maf: `##maf version=1`, an empty line, then per group `a`, its `s` lines (maf_line) and an empty line."""
-    out = [b"##maf version=1\n"]
+def maf_text(groups, gap_open: int = 0) -> bytes:
+    """write_alignments_maf: `##maf version=1`, an empty line, then per group `a`, its `s` lines (maf_line) and an empty line.
+    gap_open > 0 (--gapopen) is recorded in a comment line `# gapopen=N` after the first."""
+    out = [b"##maf version=1\n" if not gap_open else b"##maf version=1\n# gapopen=%d\n" % gap_open]
     for lines in groups:
         out.append(b"a")
         out += list(lines)
@@ -162,18 +163,19 @@ def variants_from_runs(runs, row_a: bytes, row_b: bytes, start: int, end: int, r
     return out
 
 
-def vcf_text(reference_name: str, records) -> bytes:
+def vcf_text(reference_name: str, records, gap_open: int = 0) -> bytes:
     """write_vcf_header (C-Sibelia.py:433-440) with ##source=sibelia_amd, then Variant.get_vcf_record (:177-180) per record
     (reference record description, POS, REF, ALT), sorted by (description, POS) as variant_key does (:502-503): eight tab-separated
     columns, '.' for an empty allele."""
-    out = vcf_header_lines(reference_name)
+    out = vcf_header_lines(reference_name, gap_open)
     for name, pos, ref, alt in sorted(records, key=lambda r: (r[0], r[1])):
         out.append("\t".join([strip_chr_id(name), str(pos), ".", ref.decode("latin1") or ".", alt.decode("latin1") or ".", ".", ".", "."]))
     return ("\n".join(out) + "\n").encode("latin1")
 
 
-def vcf_header_lines(reference_name: str):
-    return ["##fileformat=VCFv4.1", "##source=sibelia_amd", "##reference=" + strip_chr_id(reference_name),
+def vcf_header_lines(reference_name: str, gap_open: int = 0):
+    """gap_open > 0 (--gapopen) is recorded in a line `##sibelia_amd_gapopen=N` after `##source`."""
+    return ["##fileformat=VCFv4.1", "##source=sibelia_amd"] + (["##sibelia_amd_gapopen=%d" % gap_open] if gap_open else []) + ["##reference=" + strip_chr_id(reference_name),
             '##INFO=<ID=SVTYPE,Number=1,Type=String,Description="Type of structural variant">',
             '##INFO=<ID=IMPRECISE,Number=0,Type=Flag,Description="Imprecise structural variation">',
             '##INFO=<ID=CIPOS,Number=2,Type=Integer,Description="Confidence interval around POS for imprecise variants">',
@@ -213,7 +215,7 @@ class TextPieces:
         return np.array(self._pieces, dtype=PIECE_DTYPE) if self._pieces else np.zeros(0, dtype=PIECE_DTYPE)
 
 
-def vcf_pieces(names: Sequence[str], first_size: int, first_base: bytes, records, calls, breakends: bool) -> TextPieces:
+def vcf_pieces(names: Sequence[str], first_size: int, first_base: bytes, records, calls, breakends: bool, gap_open: int = 0) -> TextPieces:
     """The VCF of --variants --uncovered as pieces (C-Sibelia.py:433-463, :575-585): the header; with `breakends` two records
     bnd_<2i> / bnd_<2i + 1> per unmapped insertion i (write_insertions_vcf: on the first reference record at POS 1, REF = `first_base`,
     that record's first base as its file spells it, CIPOS = 0,<first_size>); then all variant records sorted stably by (description,
@@ -222,7 +224,7 @@ def vcf_pieces(names: Sequence[str], first_size: int, first_base: bytes, records
       deletion [s, e) of record c     POS s, REF c[s - 1, e), ALT c[s - 1, s)   (s = 0: REF c[0, e), ALT '.')
       insertion [s, e) at p of r      POS p, REF r[p - 1, p), ALT r[p - 1, p) c[s, e)"""
     t = TextPieces()
-    t.lit(("\n".join(vcf_header_lines(names[0])) + "\n").encode("latin1"))
+    t.lit(("\n".join(vcf_header_lines(names[0], gap_open)) + "\n").encode("latin1"))
     if breakends:
         chrom, ref = strip_chr_id(names[0]), first_base.decode("latin1")
         info = "IMPRECISE;SVTYPE=BND;CIPOS=0,%d" % first_size

@@ -6,7 +6,8 @@ with and without -r, and the choice of which files are written.  `run` returns (
 standard output); `main` writes the files and prints the text (python -m sibelia_amd).
 
 --maf / --variants (two input files) add what the reference's comparison tool C-Sibelia.py makes of such a run: the alignments of the
-unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).  --multimaf (any number of input files) writes a
+unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).  --gapopen N gives those alignments and the ones of
+--multimaf an affine gap cost (N for opening a gap run).  --multimaf (any number of input files) writes a
 multiple alignment of every block with at least two instances (`align_block_groups`).  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
@@ -45,6 +46,12 @@ UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's com
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
                   "a deletion, such a region of the second file as an insertion behind the unique block that ends before it, and "
                   "where there is no such block as two breakend records (bnd_<n>).")
+
+GAPOPEN_MAX = 100000
+GAPOPEN_HELP = ("With --maf, --variants or --multimaf: the cost of opening a gap run in their alignments, 0 .. 100000, default 0.  A run of L gap "
+                "columns costs N + 75 L (match +25, mismatch -75), so that one insertion or deletion is reported as one run, not as pieces "
+                "around stray matches.  The files record a value above 0 in a header line.  Not applied to --correctboundaries, whose "
+                "alignment is the reference program's own.")
 
 NOT_WRITTEN = ("The Circos files (circos/) and d3_blocks_diagram.html of the reference program are not written: "
                "they are instantiated from templates embedded in the reference's sources.")
@@ -131,6 +138,13 @@ def _unsigned(s: str) -> int:
     return v
 
 
+def _gap_open(s: str) -> int:
+    v = int(s)
+    if v < 0 or v > GAPOPEN_MAX:
+        raise argparse.ArgumentTypeError("integer from 0 to %d expected" % GAPOPEN_MAX)
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = _Parser(prog="python -m sibelia_amd", description="Program for finding synteny blocks in closely related genomes "
                 "(Sibelia 3.0.7's command line over the MI355X library).  " + NOT_WRITTEN)
@@ -160,6 +174,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--unmapped", default=None, metavar="FILE", help="With --uncovered: write the insertions that cannot be placed to FILE in FASTA format "
                    "instead of as breakend records.")
     p.add_argument("--multimaf", default=None, metavar="FILE", help=MULTI_HELP)
+    p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
     return p
@@ -185,6 +200,9 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
     if opt.unmapped is not None and not opt.uncovered:
         raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
+    if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None:
+        raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
+    opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
     if opt.maf is not None or opt.variants is not None or opt.multimaf is not None:
         _check_alignment_files(opt)
     return opt
@@ -408,11 +426,11 @@ def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirs
             records += [(names[ca],) + v for v in formats.variants_from_runs(al.runs, al.row_a, al.row_b, sa, ea, ra)]
     out = {}
     if opt.maf is not None:
-        out[opt.maf] = formats.maf_text(groups)
+        out[opt.maf] = formats.maf_text(groups, opt.gapopen)
     if opt.variants is not None and opt.uncovered:
         out.update(uncovered_files(bf, opt, names, nfirst, records, history))
     elif opt.variants is not None:
-        out[opt.variants] = formats.vcf_text(names[0], records)
+        out[opt.variants] = formats.vcf_text(names[0], records, opt.gapopen)
     return out
 
 
@@ -425,7 +443,7 @@ def uncovered_files(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: i
     from .api import SibeliaError
     try:
         calls = bf.uncovered_calls(history, opt.minblocksize, nfirst)
-        vcf = formats.vcf_pieces(names, bf.record_sizes()[0], first_base(opt.filenames[0]), records, calls, opt.unmapped is None)
+        vcf = formats.vcf_pieces(names, bf.record_sizes()[0], first_base(opt.filenames[0]), records, calls, opt.unmapped is None, opt.gapopen)
         out = {opt.variants: bf.spell_text(vcf.pieces(), vcf.literals)}
         if opt.unmapped is not None:
             fa = formats.unmapped_fasta_pieces(names, calls)
@@ -452,7 +470,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
                      "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2]))
             continue
         groups.append([formats.maf_line(names[c], s, e, rev, size[c], row) for (c, s, e, rev), row in zip(inst, al.rows)])
-    return {opt.multimaf: formats.maf_text(groups)}
+    return {opt.multimaf: formats.maf_text(groups, opt.gapopen)}
 
 
 # ------------------------------------------------------------------------------------------ main
@@ -517,6 +535,8 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
             files["coverage_report.txt"] = coverage
             if opt.sequencesfile:
                 files["blocks_sequences.fasta"] = bf.blocks_sequences(None, names)
+            if opt.gapopen:                       # after the boundary correction, which keeps the reference's own alignment
+                bf.set_gap_open(opt.gapopen)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
             if opt.multimaf is not None:          # likewise on the final list
