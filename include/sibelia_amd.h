@@ -336,6 +336,28 @@ typedef struct {
 } sbl_align_stats_t;
 sbl_status sbl_align_stats(const sbl_ctx *ctx, sbl_align_stats_t *out);
 
+/* Variant segments of the multiple alignments (csrc/group_variants.hip): parse_alignment's rules (src/csibelia/
+ * C-Sibelia.py:206-252) for the r rows of L columns of a group, on the groups of the context's LAST sbl_align_groups /
+ * sbl_align_block_groups call, read from the rows that call left on the device.  A column is EQUAL if all r rows hold the same byte,
+ * otherwise UNEQUAL, and then GAPPED if any row holds '-'.  The columns fall into maximal runs of equal and of unequal columns; an equal
+ * run is KEPT if it starts at column 0, ends at column L or has at least 30 columns (MINIMUM_CONTEXT_SIZE); every other equal run is
+ * merged into its unequal neighbours.  A SEGMENT [start, end) is a maximal stretch between kept equal runs.  Per segment: `lead` is 0 if
+ * start == 0 or if the segment is one column that is not gapped (a single substitution), else 1 -- the base before the segment is
+ * quoted; `before` is the number of centre-row bytes other than '-' in columns [0, start); `gapped` is 1 if any of its columns is.
+ * sbl_group_segment: `group` indexes the groups of that call; the r slices rows[i][start - lead, end) -- gaps included, centre first, row
+ * after row, end - start + lead bytes each -- lie at text[text_off ...].  Segments come in ascending (group, start).  Groups that were
+ * skipped, groups with want[g] == 0 (want: one byte per group, NULL: all), r == 1 and L == 0 give no segments; no segments at all is a
+ * result (nsegs = 0, an empty text).  Column classes, segment bounds and the slices are made by kernels; only the segments and the
+ * slices come back, into buffers of their own: the `rows` of the groups call stay valid and unchanged.  Everything returned is owned by
+ * the ctx until the next sbl_group_variants.
+ * SBL_ERR_BAD_ARG: no groups call yet, or the last sbl_align_* call was sbl_align_pairs / sbl_align_unique_blocks (they spell their rows
+ * through the same device buffers).
+ * sbl_group_variants_times: device time of the last call's kernels and of the device-to-host copy of the slices (event pairs). */
+typedef struct { uint64_t group, start, end, before, text_off; uint32_t lead, gapped; } sbl_group_segment;
+sbl_status sbl_group_variants(sbl_ctx *ctx, const uint8_t *want, const sbl_group_segment **segs, uint64_t *nsegs,
+                              const char **text, uint64_t *text_len);
+sbl_status sbl_group_variants_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

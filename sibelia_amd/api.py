@@ -30,7 +30,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
-           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times"]
+           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -101,6 +101,8 @@ class GroupInst(C.Structure):
 
 GROUP_RESULT_DTYPE = np.dtype([("status", "<u4"), ("ninst", "<u4"), ("L", "<u8"), ("row_off", "<u8")])
 MEMBER_RESULT_DTYPE = np.dtype([("score", "<i4"), ("band_w", "<u4"), ("passes", "<u4")])
+SEGMENT_DTYPE = np.dtype([("group", "<u8"), ("start", "<u8"), ("end", "<u8"), ("before", "<u8"), ("text_off", "<u8"),
+                          ("lead", "<u4"), ("gapped", "<u4")])                                        # sbl_group_segment
 
 
 class GroupAlignment:
@@ -183,6 +185,8 @@ def load_library():
         L.sbl_uncovered_calls.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_spell_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_spell_text_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_variants.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_group_variants_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -385,6 +389,7 @@ class BlockFinder:
         r = _view(res.value, len(first) - 1, GROUP_RESULT_DTYPE)
         m = _view(members.value, int(first[-1]), MEMBER_RESULT_DTYPE)
         text = C.string_at(rows.value, rows_len.value) if rows_len.value else b""
+        self._group_ninst = [int(x) for x in r["ninst"]]      # for group_variants: rows per group of the last groups call
         return [GroupAlignment(x, m[int(first[g]):int(first[g + 1])], text) for g, x in enumerate(r)]
 
     def align_groups(self, groups: Sequence[Sequence[Tuple[int, int, int, bool]]]) -> List[GroupAlignment]:
@@ -415,6 +420,35 @@ class BlockFinder:
         d = C.cast(inst, C.POINTER(GroupInst))
         insts = [[(d[i].chr, d[i].start, d[i].end, bool(d[i].rev)) for i in range(f[g], f[g + 1])] for g in range(n.value)]
         return [int(x) for x in _view(ids.value, n.value, np.dtype("<i4"))], insts, self._group_alignments(f, res, members, rows, rows_len)
+
+    def group_variants(self, want: Optional[Sequence[bool]] = None):
+        """The variant segments of the groups of the LAST align_groups / align_block_groups call (csrc/group_variants.hip; defined in
+        include/sibelia_amd.h), read off the rows that call left on the device.  want: one flag per group (None: all).
+        -> [(group, start, end, before, lead, [gapped slice rows[i][start - lead:end] per row, centre first])] in ascending
+        (group, start).  The records as the library returns them (SEGMENT_DTYPE, `gapped` included) stay in `last_group_segments`."""
+        ninst = getattr(self, "_group_ninst", [])
+        mask = None
+        if want is not None:
+            if len(want) != len(ninst):
+                raise ValueError("group_variants: %d flags for %d groups" % (len(want), len(ninst)))
+            mask = bytes(1 if w else 0 for w in want) + b"\0"
+        segs, text = C.c_void_p(), C.c_void_p()
+        n, ln = C.c_uint64(), C.c_uint64()
+        self._check(self.L.sbl_group_variants(self.h, mask, C.byref(segs), C.byref(n), C.byref(text), C.byref(ln)), "sbl_group_variants")
+        self.last_group_segments = v = _view(segs.value, n.value, SEGMENT_DTYPE)
+        packed = C.string_at(text.value, ln.value) if ln.value else b""
+        out = []
+        for x in v:
+            g, s, e, lead, at = int(x["group"]), int(x["start"]), int(x["end"]), int(x["lead"]), int(x["text_off"])
+            w = e - s + lead
+            out.append((g, s, e, int(x["before"]), lead, [packed[at + i * w:at + (i + 1) * w] for i in range(ninst[g])]))
+        return out
+
+    def group_variants_times(self) -> Tuple[float, float]:
+        """(kernel ms, device-to-host copy ms of the slices) of the last group_variants call, from event pairs."""
+        k, d = C.c_double(), C.c_double()
+        self._check(self.L.sbl_group_variants_times(self.h, C.byref(k), C.byref(d)), "sbl_group_variants_times")
+        return k.value, d.value
 
     def align_stats(self) -> dict:
         """Counters of the last align_pairs / align_unique_blocks / align_groups / align_block_groups: pairs, skipped, passes, launches,

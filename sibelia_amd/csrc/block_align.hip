@@ -399,19 +399,8 @@ template <bool REG> __global__ __launch_bounds__(REG ? 64 : GA3_THREADS) void k_
 
 constexpr unsigned GS_THREADS = 256;
 
-template <class F> __device__ inline u64 ga_find(u64 lo, u64 hi, F le)   // largest x in [lo, hi) with le(x) (le(lo) holds)
-{
-	while (hi - lo > 1) {
-		const u64 mid = lo + (hi - lo) / 2;
-		if (le(mid)) lo = mid; else hi = mid;
-	}
-	return lo;
-}
-
 struct GaSpan { u64 col; unsigned ai, bj, op, len; };                       // a run: first column in its pair's two rows, first base of a / b
 struct GmInst { u64 src, first_span; unsigned len, rev, nspans, pad_; };       // a row: its range; a member's spans (of the pair centre / member)
-struct GmSlot { u64 col; unsigned p, G; };                                    // gap slot p: G columns from column col = p + the G of the slots before it
-struct GmGroup { u64 toff, L, first_inst, first_slot; unsigned ninst, nslots; };      // toff: the group's text (ninst L bytes); slot 0 always listed
 
 // Output-stationary like blockseq.hip: a lane owns 16 bytes of the text and writes them with one vector store.  Group by binary search
 // over text offsets, then row and column; the column's slot by binary search over the group's merged slots, a member's run by binary
@@ -634,6 +623,7 @@ u64 gm_spell(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<GmWan
 	std::vector<GaSpan> spans;
 	std::vector<std::pair<unsigned, unsigned>> runs_d;                          // (slot, length) of the 'D' runs of a group's members
 	u64 total = 0;
+	c->gv_rows_valid = false;                                                 // the rows and tables sbl_group_variants reads are about to be replaced
 	text.assign(want.size(), GmText{});
 	for (size_t g = 0; g < want.size(); g++) {
 		const GmWant &w = want[g];
@@ -727,6 +717,7 @@ void gm_run(sbl_ctx *c, u64 *rows_len)
 			c->gm_members[first[g] + 1 + k] = sbl_member_result{text[g].ok ? pr.score : 0, pr.band_w, pr.passes};
 		}
 	}
+	c->gv_rows_valid = true;                                                  // d_ga_text / d_gm_* hold the rows of these groups until the next gm_spell
 }
 
 void gm_check(const sbl_ctx *c, u64 ngroups, const uint64_t *first, const sbl_group_inst *inst)

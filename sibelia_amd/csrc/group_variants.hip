@@ -1,0 +1,273 @@
+// group_variants.hip -- the variant segments of the multiple alignments (include/sibelia_amd.h): the N-row form of the
+// rules parse_alignment (reference src/csibelia/C-Sibelia.py:206-252) applies to the two rows of a pair, on the rows the last
+// sbl_align_groups / sbl_align_block_groups call left on the device (d_ga_text, spelled by k_spell_groups through d_gm_group / d_gm_slot).
+// The rows hold as many bytes as the blocks have bases times instances; the segments follow the edits.  So the column-wise pass runs
+// where the rows are and only the segments and their slices come back.
+//
+//   classes   k_column_classes, output-stationary over the columns of the wanted groups, every group padded to a multiple of 16 columns:
+//             a lane owns 16 consecutive columns of ONE group, reads those 16 bytes of every row -- neighbouring lanes read neighbouring
+//             bytes of a row: 1 KiB per wave and row -- as two aligned 16-byte words shifted in registers (window16, as blockseq.hip
+//             does: toff + i L is not aligned in general), compares them 8 bytes at a time and writes 16 class bytes with one vector
+//             store: 0 equal, 1 unequal, 3 unequal and gapped.
+//   bounds    k_segment_bounds, one lane per column: an unequal column OPENS a segment if it is column 0 or the equal run that ends before
+//             it is kept, and CLOSES one if it is column L - 1 or the equal run that starts behind it is kept.  "Kept" (the run touches
+//             column 0 or L, or has 30 columns) is decided by looking at most 30 class bytes back / ahead.  The lane writes two flag
+//             bytes; the flagged columns are compacted in ascending order by rocPRIM's select (sbl_prim.h), opens and closes apart.
+//   segments  k_segment_fill, one lane per segment: the i-th open pairs with the i-th close; lead, `before` from the group's merged gap
+//             slots (the arithmetic of k_spell_groups' seek) and where its slices lie in the rows.  k_segment_gapped, one lane per
+//             column: a gapped column finds its segment by binary search over the opens and marks it.
+//   slices    k_gather_slices, output-stationary like k_spell_groups: a lane owns 16 bytes of the packed text, finds its segment by
+//             binary search over the text offsets, then row and column; 16 bytes inside one slice are cut out of two aligned words,
+//             everything else steps byte by byte.  One vector store per lane.
+//   host      the group table, the 64-bit prefix of the padded L and, between the launches, the two counts and the prefix of the slice
+//             lengths (their number follows the edits).  The slices come back into a buffer of their own, not the pinned text buffer.
+#include <algorithm>
+#include <cstring>
+
+#include "sbl_align.h"
+#include "sbl_prim.h"
+#include "sbl_text.h"
+
+namespace {
+
+constexpr unsigned GV_THREADS = 256;
+constexpr unsigned GV_CONTEXT = 30;                    // MINIMUM_CONTEXT_SIZE (C-Sibelia.py:20)
+
+struct GvGroup { u64 group, dg; };                     // a wanted group: its index in the call; its index in d_gm_group
+struct GvSlice { u64 src, L, len; };                   // a segment's slices: first byte of the centre's in the rows, row stride, bytes per row
+
+// bytes [at, at + 16) of text as two 64-bit words; words that lie wholly beyond text[0, bytes) are not loaded (bytes: a multiple of 16)
+__device__ inline B16 gv_load16(const uint8_t *__restrict__ text, u64 bytes, u64 at)
+{
+	const u64 base = at & ~15ull;
+	const unsigned sh = (unsigned)(at & 15);
+	const uint4 zero = make_uint4(0, 0, 0, 0);
+	const uint4 a = base < bytes ? *reinterpret_cast<const uint4 *>(text + base) : zero;
+	const uint4 b = sh && base + 16 < bytes ? *reinterpret_cast<const uint4 *>(text + base + 16) : zero;
+	return window16(a, b, sh);
+}
+
+// 0x80 in every byte of v that is not zero
+__device__ inline u64 nonzero8(u64 v) { return ~zero8(v) & 0x8080808080808080ull; }
+
+__global__ __launch_bounds__(GV_THREADS) void k_column_classes(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
+                                                               const GvGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                               u64 padded_cols, uint4 *__restrict__ cls)
+{
+	const u64 x0 = ((u64)blockIdx.x * GV_THREADS + threadIdx.x) * 16;
+	if (x0 >= padded_cols) return;
+	const unsigned gi = bs_find(cbase, ngroups, x0);
+	const GmGroup Q = gm[groups[gi].dg];
+	const u64 col0 = x0 - cbase[gi];                                          // < L: the padding of a group is less than 16 columns
+	const unsigned n = Q.L - col0 < 16 ? (unsigned)(Q.L - col0) : 16;        // columns of the group in this piece
+	const u64 gaps = 0x2D2D2D2D2D2D2D2Dull;                                   // '-'
+	const B16 ref = gv_load16(text, text_bytes, Q.toff + col0);
+	u64 dlo = 0, dhi = 0, glo = zero8(ref.lo ^ gaps), ghi = zero8(ref.hi ^ gaps);
+	for (unsigned i = 1; i < Q.ninst; i++) {
+		const B16 w = gv_load16(text, text_bytes, Q.toff + (u64)i * Q.L + col0);
+		dlo |= w.lo ^ ref.lo; dhi |= w.hi ^ ref.hi;
+		glo |= zero8(w.lo ^ gaps); ghi |= zero8(w.hi ^ gaps);
+	}
+	const u64 ulo = nonzero8(dlo), uhi = nonzero8(dhi);
+	u64 clo = (ulo >> 7) | ((ulo & glo) >> 6), chi = (uhi >> 7) | ((uhi & ghi) >> 6);
+	// the bytes behind column L belong to the next row or to nothing: class 0
+	if (n < 16) {
+		if (n <= 8) { chi = 0; clo = n == 8 ? clo : clo & ((1ull << (8 * n)) - 1); }
+		else chi &= (1ull << (8 * (n - 8))) - 1;
+	}
+	cls[x0 / 16] = make_uint4((unsigned)clo, (unsigned)(clo >> 32), (unsigned)chi, (unsigned)(chi >> 32));
+}
+
+__global__ __launch_bounds__(GV_THREADS) void k_segment_bounds(const uint8_t *__restrict__ cls, const GmGroup *__restrict__ gm, const GvGroup *__restrict__ groups,
+                                                               const u64 *__restrict__ cbase, u64 ngroups, u64 padded_cols,
+                                                               uint8_t *__restrict__ opens, uint8_t *__restrict__ closes)
+{
+	const u64 x = (u64)blockIdx.x * GV_THREADS + threadIdx.x;
+	if (x >= padded_cols) return;
+	const unsigned gi = bs_find(cbase, ngroups, x);
+	const u64 L = gm[groups[gi].dg].L, c = x - cbase[gi];
+	const uint8_t *const k = cls + cbase[gi];                                 // the group's class bytes
+	uint8_t open = 0, close = 0;
+	if (c < L && k[c]) {
+		// the equal run that ends at column c - 1: kept if it reaches column 0 or has GV_CONTEXT columns
+		u64 back = 0;
+		while (back < GV_CONTEXT && back < c && !k[c - 1 - back]) back++;
+		open = c == 0 || (back > 0 && (back == c || back == GV_CONTEXT));
+		// the equal run that starts at column c + 1: kept if it reaches column L or has GV_CONTEXT columns
+		const u64 room = L - 1 - c;
+		u64 ahead = 0;
+		while (ahead < GV_CONTEXT && ahead < room && !k[c + 1 + ahead]) ahead++;
+		close = room == 0 || (ahead > 0 && (ahead == room || ahead == GV_CONTEXT));
+	}
+	opens[x] = open; closes[x] = close;
+}
+
+__global__ __launch_bounds__(GV_THREADS) void k_segment_fill(const uint8_t *__restrict__ cls, const GmGroup *__restrict__ gm, const GmSlot *__restrict__ slots,
+                                                             const GvGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                             const u64 *__restrict__ opens, const u64 *__restrict__ closes, u64 nsegs,
+                                                             sbl_group_segment *__restrict__ segs, GvSlice *__restrict__ slices)
+{
+	const u64 i = (u64)blockIdx.x * GV_THREADS + threadIdx.x;
+	if (i >= nsegs) return;
+	const u64 x = opens[i];
+	const unsigned gi = bs_find(cbase, ngroups, x);
+	const GmGroup Q = gm[groups[gi].dg];
+	const u64 s = x - cbase[gi], e = closes[i] + 1 - cbase[gi];
+	const unsigned lead = s == 0 || (e - s == 1 && cls[x] == 1) ? 0u : 1u;
+	// the centre index column s belongs to = the centre bases before it (k_spell_groups' seek)
+	const u64 si = ga_find(0, Q.nslots, [&](u64 y) { return slots[Q.first_slot + y].col <= s; });
+	const GmSlot S = slots[Q.first_slot + si];
+	const u64 o = s - S.col, before = o < S.G ? S.p : S.p + (o - S.G);
+	segs[i] = sbl_group_segment{groups[gi].group, s, e, before, 0, lead, 0};
+	slices[i] = GvSlice{Q.toff + s - lead, Q.L, e - s + lead};
+}
+
+__global__ __launch_bounds__(GV_THREADS) void k_segment_gapped(const uint8_t *__restrict__ cls, u64 padded_cols, const u64 *__restrict__ opens, u64 nsegs,
+                                                               sbl_group_segment *__restrict__ segs)
+{
+	const u64 x = (u64)blockIdx.x * GV_THREADS + threadIdx.x;
+	if (x >= padded_cols || cls[x] != 3) return;
+	segs[bs_find(opens, nsegs, x)].gapped = 1;                                // every unequal column lies in a segment: opens[0] <= x
+}
+
+__global__ __launch_bounds__(GV_THREADS) void k_gather_slices(const uint8_t *__restrict__ text, u64 text_bytes, const GvSlice *__restrict__ slices,
+                                                              const u64 *__restrict__ toff /* nsegs + 1 */, u64 nsegs, u64 total, uint4 *__restrict__ out)
+{
+	const u64 t0 = ((u64)blockIdx.x * GV_THREADS + threadIdx.x) * 16;
+	if (t0 >= total) return;
+	u64 si = bs_find(toff, nsegs, t0);
+	GvSlice V = slices[si];
+	u64 off = t0 - toff[si], row = off / V.len, k = off - row * V.len;       // a slice holds at least one byte
+	B16 w;
+	if (k + 16 <= V.len) w = gv_load16(text, text_bytes, V.src + row * V.L + k);
+	else {
+		w.lo = w.hi = 0;
+		u64 end = toff[si + 1];
+		for (unsigned b = 0; b < 16 && t0 + b < total; b++) {
+			if (t0 + b == end) { si++; V = slices[si]; end = toff[si + 1]; row = 0; k = 0; }
+			else if (k == V.len) { row++; k = 0; }
+			const u64 ch = text[V.src + row * V.L + k];
+			if (b < 8) w.lo |= ch << (8 * b); else w.hi |= ch << (8 * (b - 8));
+			k++;
+		}
+	}
+	out[t0 / 16] = make_uint4((unsigned)w.lo, (unsigned)(w.lo >> 32), (unsigned)w.hi, (unsigned)(w.hi >> 32));
+}
+
+unsigned gv_blocks(u64 lanes)
+{
+	const u64 blocks = (lanes + GV_THREADS - 1) / GV_THREADS;
+	SBL_CHECK(blocks < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
+	return (unsigned)blocks;
+}
+
+float gv_elapsed(sbl_ctx *c, int a, int b)
+{
+	float ms = 0;
+	(void)hipEventElapsedTime(&ms, c->ev[a], c->ev[b]);
+	return ms;
+}
+
+}  // namespace
+
+extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const sbl_group_segment **segs, uint64_t *nsegs,
+                                         const char **text, uint64_t *text_len)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(c->gv_rows_valid, SBL_ERR_BAD_ARG, "no rows of groups on the device: the last sbl_align_* call must be sbl_align_groups or sbl_align_block_groups");
+		hipStream_t s = c->stream;
+		c->gv_segs.clear(); c->gv_text.clear();
+		c->gv_kernel_ms = c->gv_copy_ms = 0;
+		// the wanted groups that have columns to compare; dg: d_gm_group lists the aligned groups with L > 0, in order
+		std::vector<GvGroup> groups;
+		std::vector<u64> cbase(1, 0);
+		u64 dg = 0, text_end = 0;
+		for (size_t g = 0; g < c->gm_res.size(); g++) {
+			const sbl_group_result &r = c->gm_res[g];
+			if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
+			text_end = std::max<u64>(text_end, r.row_off + (u64)r.ninst * r.L);
+			if (r.ninst >= 2 && (!want || want[g])) {
+				groups.push_back(GvGroup{g, dg});
+				cbase.push_back(cbase.back() + (r.L + 15) / 16 * 16);
+			}
+			dg++;
+		}
+		const u64 ng = groups.size(), P = cbase.back(), text_bytes = (text_end + 15) / 16 * 16;
+		u64 nseg = 0, total = 0;
+		if (ng) {
+			SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes && c->d_gm_group.cap >= dg * sizeof(GmGroup), SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
+			const uint8_t *rows = c->d_ga_text.as<uint8_t>();
+			const GmGroup *gm = c->d_gm_group.as<GmGroup>();
+			al_upload(c, c->d_gv_group, groups); al_upload(c, c->d_gv_cbase, cbase);
+			c->d_gv_class.ensure((size_t)P); c->d_gv_flag.ensure((size_t)(2 * P));
+			c->d_gv_open.ensure((size_t)P * 8); c->d_gv_close.ensure((size_t)P * 8); c->d_gv_count.ensure(16);
+			uint8_t *const f_open = c->d_gv_flag.as<uint8_t>(), *const f_close = f_open + P;
+			u64 count[2] = {0, 0};
+			HIP_TRY(hipEventRecord(c->ev[0], s));
+			k_column_classes<<<gv_blocks(P / 16), GV_THREADS, 0, s>>>(rows, text_bytes, gm, c->d_gv_group.as<GvGroup>(), c->d_gv_cbase.as<u64>(), ng, P, c->d_gv_class.as<uint4>());
+			HIP_TRY(hipGetLastError());
+			k_segment_bounds<<<gv_blocks(P), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), gm, c->d_gv_group.as<GvGroup>(), c->d_gv_cbase.as<u64>(), ng, P, f_open, f_close);
+			HIP_TRY(hipGetLastError());
+			prim::select(s, c->d_gv_tmp, rocprim::counting_iterator<u64>(0), f_open, c->d_gv_open.as<u64>(), c->d_gv_count.as<u64>(), (size_t)P);
+			prim::select(s, c->d_gv_tmp, rocprim::counting_iterator<u64>(0), f_close, c->d_gv_close.as<u64>(), c->d_gv_count.as<u64>() + 1, (size_t)P);
+			HIP_TRY(hipMemcpyAsync(count, c->d_gv_count.p, 16, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			SBL_CHECK(count[0] == count[1], SBL_ERR_INTERNAL, "the segments of the alignments do not close");
+			nseg = count[0];
+		}
+		if (nseg) {
+			c->d_gv_seg.ensure((size_t)nseg * sizeof(sbl_group_segment)); c->d_gv_slice.ensure((size_t)nseg * sizeof(GvSlice));
+			c->gv_segs.resize((size_t)nseg);
+			std::vector<GvSlice> slices((size_t)nseg);
+			k_segment_fill<<<gv_blocks(nseg), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), c->d_gm_slot.as<GmSlot>(), c->d_gv_group.as<GvGroup>(),
+			                                                      c->d_gv_cbase.as<u64>(), ng, c->d_gv_open.as<u64>(), c->d_gv_close.as<u64>(), nseg,
+			                                                      c->d_gv_seg.as<sbl_group_segment>(), c->d_gv_slice.as<GvSlice>());
+			HIP_TRY(hipGetLastError());
+			k_segment_gapped<<<gv_blocks(P), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), P, c->d_gv_open.as<u64>(), nseg, c->d_gv_seg.as<sbl_group_segment>());
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipEventRecord(c->ev[2], s));
+			HIP_TRY(hipMemcpyAsync(c->gv_segs.data(), c->d_gv_seg.p, (size_t)nseg * sizeof(sbl_group_segment), hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync(slices.data(), c->d_gv_slice.p, (size_t)nseg * sizeof(GvSlice), hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			// where the slices of every segment start in the packed text: ninst slices of `len` bytes each
+			std::vector<u64> toff((size_t)nseg + 1, 0);
+			for (size_t i = 0; i < nseg; i++) {
+				sbl_group_segment &g = c->gv_segs[i];
+				g.text_off = toff[i];
+				toff[i + 1] = toff[i] + (u64)c->gm_res[g.group].ninst * slices[i].len;
+			}
+			total = toff.back();
+			const size_t padded = (size_t)((total + 15) / 16 * 16);
+			al_upload(c, c->d_gv_toff, toff);
+			c->d_gv_text.ensure(padded);
+			c->gv_text.resize(padded);
+			HIP_TRY(hipEventRecord(c->ev[3], s));
+			k_gather_slices<<<gv_blocks(padded / 16), GV_THREADS, 0, s>>>(c->d_ga_text.as<uint8_t>(), text_bytes, c->d_gv_slice.as<GvSlice>(), c->d_gv_toff.as<u64>(), nseg, total,
+			                                                              c->d_gv_text.as<uint4>());
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipEventRecord(c->ev[4], s));
+			HIP_TRY(hipMemcpyAsync(c->gv_text.data(), c->d_gv_text.p, padded, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipEventRecord(c->ev[5], s));
+			HIP_TRY(hipStreamSynchronize(s));
+			c->gv_kernel_ms = gv_elapsed(c, 0, 2) + gv_elapsed(c, 3, 4);      // the prefix of the slice lengths on the host lies between
+			c->gv_copy_ms = gv_elapsed(c, 4, 5);
+		} else if (ng) {
+			HIP_TRY(hipEventRecord(c->ev[2], s));
+			HIP_TRY(hipStreamSynchronize(s));
+			c->gv_kernel_ms = gv_elapsed(c, 0, 2);
+		}
+		c->stats.device_bytes = sbl_devbuf_total().load();
+		if (segs) *segs = c->gv_segs.data();
+		if (nsegs) *nsegs = nseg;
+		if (text) *text = total ? c->gv_text.data() : "";
+		if (text_len) *text_len = total;
+	});
+}
+
+extern "C" sbl_status sbl_group_variants_times(const sbl_ctx *c, double *kernel_ms, double *copyback_ms)
+{
+	if (!c) return SBL_ERR_BAD_ARG;
+	if (kernel_ms) *kernel_ms = c->gv_kernel_ms;
+	if (copyback_ms) *copyback_ms = c->gv_copy_ms;
+	return SBL_OK;
+}

@@ -1,5 +1,5 @@
 // sbl_align.h -- what boundary_align.hip and block_align.hip share: the scores, the read of a base on its strand, the timed launch, the
-// argument checks and the walk over the instances of one block.
+// argument checks, the walk over the instances of one block and the group tables of the row speller.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -16,6 +16,19 @@ __device__ inline unsigned char strand_base(const uint8_t *__restrict__ seq, u64
 {
 	return rev ? complement1(seq[src + (len - 1 - i)]) : seq[src + i];
 }
+
+template <class F> __device__ inline u64 ga_find(u64 lo, u64 hi, F le)   // largest x in [lo, hi) with le(x) (le(lo) holds)
+{
+	while (hi - lo > 1) {
+		const u64 mid = lo + (hi - lo) / 2;
+		if (le(mid)) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+// the tables k_spell_groups spells the rows of the groups from (block_align.hip); group_variants.hip reads the rows through them
+struct GmSlot { u64 col; unsigned p, G; };                                    // gap slot p: G columns from column col = p + the G of the slots before it
+struct GmGroup { u64 toff, L, first_inst, first_slot; unsigned ninst, nslots; };      // toff: the group's text (ninst L bytes); slot 0 always listed
 
 // `launch` between ev[0] and ev[1], `bytes` of its results back to the host and one synchronise -> the milliseconds between the events
 template <class F> float al_timed_launch(sbl_ctx *c, F launch, void *back, const void *d_from, size_t bytes)

@@ -119,6 +119,15 @@ struct sbl_ctx {
 	std::vector<sbl_group_inst> gm_inst;
 	std::vector<sbl_group_result> gm_res;
 	std::vector<sbl_member_result> gm_members;
+	// sbl_group_variants (group_variants.hip): reads d_ga_text and d_gm_group / d_gm_slot as the last groups call left them -- valid while
+	// gv_rows_valid holds (set by gm_run, cleared wherever those buffers are reused: gm_spell).  Group and column tables, class bytes,
+	// open / close flags and the compacted columns, segments, slice tables and the packed slices on the device; the slices come back
+	// into a host buffer of their own (NOT h_bs_text: the rows of the groups call stay where they are)
+	bool gv_rows_valid = false;
+	DevBuf d_gv_group, d_gv_cbase, d_gv_class, d_gv_flag, d_gv_open, d_gv_close, d_gv_count, d_gv_seg, d_gv_slice, d_gv_toff, d_gv_text, d_gv_tmp;
+	std::vector<sbl_group_segment> gv_segs;
+	std::vector<char> gv_text;
+	double gv_kernel_ms = 0, gv_copy_ms = 0;   // event pairs around the kernels / the device-to-host copy of the slices of the last call
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;

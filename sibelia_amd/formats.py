@@ -182,6 +182,45 @@ def vcf_header_lines(reference_name: str, gap_open: int = 0):
             "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"])]
 
 
+# ------------------------------------------------------------------------------------------ calls from the multiple alignments (--multivariants)
+
+def group_variants_records(segments, start: int, end: int, reverse: bool):
+    """The calls of ONE aligned group from its segments as BlockFinder.group_variants returns them -- (group, first
+    column, one past the last, centre bases before it, lead, [gapped slice per row, centre first]) -- and the centre's instance
+    [start, end) (0-based, half-open; reverse: read on '-').  -> [(POS, [allele per row])]: POS and alleles exactly as
+    variants_from_runs makes them for two rows -- lead is its shift, the alleles are the slices without gaps, reverse-complemented
+    for a centre on '-'."""
+    first, step = (end, -1) if reverse else (start + 1, 1)
+    out = []
+    for _, _s, _e, before, lead, slices in segments:
+        alleles = [x.replace(b"-", b"") for x in slices]
+        if reverse:
+            alleles = [x.translate(_COMPLEMENT)[::-1] for x in alleles]
+        out.append((first + step * before - lead, alleles))
+    return out
+
+
+FORMAT_GT_LINE = '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">'
+
+
+def multi_vcf_text(reference_name: str, sample_names: Sequence[str], records, gap_open: int = 0) -> bytes:
+    """A multi-sample VCF: the header of vcf_text with the FORMAT line of GT before the column line, which gets FORMAT and one column
+    per sample.  records: (description of the centre's record, POS, block id, REF allele, [allele per sample, None where the sample has
+    no instance in the block]), sorted here by (description, POS, block id).  ALT holds the distinct alleles other than REF in order of
+    first appearance over the samples; an empty allele is written '.'; a sample holds the index of its allele (0 REF, 1 .. ALT) or '.'."""
+    head = vcf_header_lines(reference_name, gap_open)
+    out = head[:-1] + [FORMAT_GT_LINE, head[-1] + "\t" + "\t".join(["FORMAT"] + list(sample_names))]
+    for name, pos, _block, ref, alleles in sorted(records, key=lambda r: (r[0], r[1], r[2])):
+        seen = [ref]
+        for x in alleles:
+            if x is not None and x not in seen:
+                seen.append(x)
+        alt = ",".join(x.decode("latin1") or "." for x in seen[1:]) or "."
+        gt = ["." if x is None else str(seen.index(x)) for x in alleles]
+        out.append("\t".join([strip_chr_id(name), str(pos), ".", ref.decode("latin1") or ".", alt, ".", ".", ".", "GT"] + gt))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
 # ------------------------------------------------------------------------------------------ calls from uncovered regions (--uncovered, --unmapped)
 
 CALL_DELETION, CALL_INSERTION, CALL_UNMAPPED = 0, 1, 2      # SBL_CALL_* (include/sibelia_amd.h)

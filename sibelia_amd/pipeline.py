@@ -8,7 +8,9 @@ standard output); `main` writes the files and prints the text (python -m sibelia
 --maf / --variants (two input files) add what the reference's comparison tool C-Sibelia.py makes of such a run: the alignments of the
 unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).  --gapopen N gives those alignments and the ones of
 --multimaf an affine gap cost (N for opening a gap run).  --multimaf (any number of input files) writes a
-multiple alignment of every block with at least two instances (`align_block_groups`).  --uncovered adds the rest of C-Sibelia's VCF to
+multiple alignment of every block with at least two instances (`align_block_groups`); --multivariants (two or more input files) reads
+the calls off those alignments for the blocks with one instance in the first file and at most one in each other file and writes them as
+a multi-sample VCF.  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -42,13 +44,18 @@ MULTI_HELP = ("Any number of input files: align every synteny block with at leas
               "end, strand): every other instance is aligned to it as under --maf and the gaps are merged.  It is this program's own "
               "definition, not mlagan's, which the reference's comparison tool runs on such blocks.")
 
+MULTIVARIANTS_HELP = ("Two or more input files: write the SNVs and indels read off the multiple alignments of --multimaf in VCF format, one sample "
+                      "column per input file after the first (named by the file's base name; positions on the records of the first file).  A "
+                      "block is used if all its instances are at least the minimum block size long, exactly one of them lies in the first file "
+                      "and at most one in each other file; a file without an instance gets the genotype '.'.")
+
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
                   "a deletion, such a region of the second file as an insertion behind the unique block that ends before it, and "
                   "where there is no such block as two breakend records (bnd_<n>).")
 
 GAPOPEN_MAX = 100000
-GAPOPEN_HELP = ("With --maf, --variants or --multimaf: the cost of opening a gap run in their alignments, 0 .. 100000, default 0.  A run of L gap "
+GAPOPEN_HELP = ("With --maf, --variants, --multimaf or --multivariants: the cost of opening a gap run in their alignments, 0 .. 100000, default 0.  A run of L gap "
                 "columns costs N + 75 L (match +25, mismatch -75), so that one insertion or deletion is reported as one run, not as pieces "
                 "around stray matches.  The files record a value above 0 in a header line.  Not applied to --correctboundaries, whose "
                 "alignment is the reference program's own.")
@@ -174,6 +181,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--unmapped", default=None, metavar="FILE", help="With --uncovered: write the insertions that cannot be placed to FILE in FASTA format "
                    "instead of as breakend records.")
     p.add_argument("--multimaf", default=None, metavar="FILE", help=MULTI_HELP)
+    p.add_argument("--multivariants", default=None, metavar="FILE", help=MULTIVARIANTS_HELP)
     p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
@@ -194,24 +202,39 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
             raise PipelineError("--maf and --variants need the synteny blocks: they cannot be combined with --noblocks")
     if opt.multimaf is not None and opt.noblocks:
         raise PipelineError("--multimaf needs the synteny blocks: it cannot be combined with --noblocks")
+    if opt.multivariants is not None:
+        if len(opt.filenames) < 2:                             # before any file is read
+            raise PipelineError("--multivariants compares files: it needs at least two")
+        if opt.noblocks:
+            raise PipelineError("--multivariants needs the synteny blocks: it cannot be combined with --noblocks")
+        samples = sample_names(opt.filenames)
+        for a in sorted(set(samples)):
+            if samples.count(a) > 1:
+                raise PipelineError("--multivariants names a sample by its file's base name: two files are called %s" % a)
     if opt.uncovered and opt.variants is None:
         raise PipelineError("--uncovered adds its records to the file of --variants: it needs --variants")
     if opt.uncovered and not opt.allstages:
         raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
     if opt.unmapped is not None and not opt.uncovered:
         raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
-    if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None:
+    if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
-    if opt.maf is not None or opt.variants is not None or opt.multimaf is not None:
+    if opt.maf is not None or opt.variants is not None or opt.multimaf is not None or opt.multivariants is not None:
         _check_alignment_files(opt)
     return opt
 
 
+def sample_names(filenames: Sequence[str]) -> List[str]:
+    """The sample columns of --multivariants: one per input file after the first, named by the file's base name."""
+    return [os.path.basename(os.path.normpath(f)) for f in filenames[1:]]
+
+
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants / --unmapped / --multimaf name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --unmapped / --multimaf / --multivariants name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
-    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--unmapped", opt.unmapped), ("--multimaf", opt.multimaf)) if f is not None]
+    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--unmapped", opt.unmapped), ("--multimaf", opt.multimaf),
+                                    ("--multivariants", opt.multivariants)) if f is not None]
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -277,7 +300,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf) if f is not None]      # relative names: under the output directory
+        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf, opt.multivariants) if f is not None]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -342,7 +365,8 @@ def _fasta_error(path: str) -> Optional[str]:
 
 
 def load_input(filenames: Sequence[str], device: int = -1):
-    """-> (finder, names, records in the first file (None for a single file)).  One file goes through the FASTA loader on the device; several are read on the host and appended to one
+    """-> (finder, names, records in the first file (None for a single file)); the finder carries the record count of every file as
+    `file_records` (--multivariants tells the files apart by it).  One file goes through the FASTA loader on the device; several are read on the host and appended to one
     record list, as the reference does (src/sibelia.cpp:209-225)."""
     from . import workloads
     from .api import BlockFinder, SibeliaError
@@ -352,8 +376,9 @@ def load_input(filenames: Sequence[str], device: int = -1):
     try:
         if len(filenames) == 1:
             bf = BlockFinder.from_fasta(filenames[0], device=device)
+            bf.file_records = [len(bf.record_names())]
             return bf, None, None
-        names, seqs, nfirst = [], [], None
+        names, seqs, nfirst, counts = [], [], None, []
         for f in filenames:
             try:
                 n, s = workloads.read_fasta(f)
@@ -361,11 +386,13 @@ def load_input(filenames: Sequence[str], device: int = -1):
                 raise PipelineError(_fasta_error(f) or "parse error in %s: %s" % (f, e))
             names += n
             seqs += s
+            counts.append(len(n))
             if nfirst is None:
                 nfirst = len(n)                 # referenceChrId: the records of the first file (src/sibelia.cpp:218-224)
         if sum(len(s) for s in seqs) > MAX_INPUT_SIZE:
             raise PipelineError("Input is larger than 1 GB, can't proceed")
         bf = BlockFinder(seqs, device=device)
+        bf.file_records = counts
         return bf, names, nfirst
     except SibeliaError as e:
         text = str(e)
@@ -453,9 +480,32 @@ def uncovered_files(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: i
     return out
 
 
-def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], complain: Callable[[str], None]) -> Dict[str, bytes]:
+def qualifying_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
+    """The ids --multivariants calls from, on a block list (formats.BLOCK_DTYPE): EVERY instance of the id is at least min_block_size
+    long, there are at least two, exactly one lies on the records of the first file and at most one on those of each other file.  For
+    two files this is determine_unique_block (C-Sibelia.py:314-323)."""
+    import bisect
+    first = [0]
+    for n in file_records:
+        first.append(first[-1] + n)
+    by_id: Dict[int, List[Tuple[int, int]]] = {}
+    for b in blocks:
+        by_id.setdefault(abs(int(b["id"])), []).append((bisect.bisect_right(first, int(b["chr"])) - 1, int(b["end"]) - int(b["start"])))
+    out = []
+    for block, inst in sorted(by_id.items()):
+        files = [f for f, _ in inst]
+        if len(inst) >= 2 and all(n >= min_block_size for _, n in inst) and files.count(0) == 1 and len(set(files)) == len(files):
+            out.append(block)
+    return out
+
+
+def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], complain: Callable[[str], None], blocks=None) -> Dict[str, bytes]:
     """--multimaf: one MAF paragraph per block with at least two instances, in ascending id, its `s` lines in the order of the alignment
-    (centre first: BlockFinder.align_block_groups).  A skipped block is named through `complain` in one line and is absent."""
+    (centre first: BlockFinder.align_block_groups).  A skipped block is named through `complain` in one line and is absent.
+    --multivariants: the calls read off the SAME alignments (one align_block_groups call serves both; BlockFinder.group_variants,
+    DESIGN.md 0.6) for the qualifying blocks of the final list `blocks` (qualifying_blocks) as a multi-sample VCF; the first-file
+    instance sorts first, so it is the centre and its alleles are REF."""
+    import bisect
     from . import formats
     from .api import GALIGN_OK, SibeliaError
     try:
@@ -463,14 +513,40 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     except SibeliaError as e:
         raise PipelineError(str(e))
     size = bf.record_sizes()
+    qualify = set(qualifying_blocks(blocks, bf.file_records, opt.minblocksize)) if opt.multivariants is not None else set()
     groups = []
     for block, inst, al in zip(ids, insts, aligned):
         if al.status != GALIGN_OK:
-            complain("block %d not aligned: one of its %d instances against %s:%d-%d is beyond the limits of one alignment "
-                     "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2]))
+            if opt.multimaf is not None or block in qualify:
+                complain("block %d not aligned: one of its %d instances against %s:%d-%d is beyond the limits of one alignment "
+                         "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2]))
             continue
-        groups.append([formats.maf_line(names[c], s, e, rev, size[c], row) for (c, s, e, rev), row in zip(inst, al.rows)])
-    return {opt.multimaf: formats.maf_text(groups, opt.gapopen)}
+        if opt.multimaf is not None:
+            groups.append([formats.maf_line(names[c], s, e, rev, size[c], row) for (c, s, e, rev), row in zip(inst, al.rows)])
+    out = {}
+    if opt.multimaf is not None:
+        out[opt.multimaf] = formats.maf_text(groups, opt.gapopen)
+    if opt.multivariants is not None:
+        try:
+            segments = bf.group_variants([block in qualify for block in ids])
+        except SibeliaError as e:
+            raise PipelineError(str(e))
+        first = [0]
+        for n in bf.file_records:
+            first.append(first[-1] + n)
+        by_group: Dict[int, list] = {}
+        for seg in segments:
+            by_group.setdefault(seg[0], []).append(seg)
+        records = []
+        for g, segs in sorted(by_group.items()):
+            inst = insts[g]
+            row_of = {bisect.bisect_right(first, c) - 1: i for i, (c, _, _, _) in enumerate(inst)}      # file -> row (at most one each)
+            c0, s0, e0, rev0 = inst[0]
+            for pos, alleles in formats.group_variants_records(segs, s0, e0, rev0):
+                records.append((names[c0], pos, ids[g], alleles[0],
+                                [alleles[row_of[f]] if f in row_of else None for f in range(1, len(bf.file_records))]))
+        out[opt.multivariants] = formats.multi_vcf_text(names[0], sample_names(opt.filenames), records, opt.gapopen)
+    return out
 
 
 # ------------------------------------------------------------------------------------------ main
@@ -539,8 +615,8 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 bf.set_gap_open(opt.gapopen)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
-            if opt.multimaf is not None:          # likewise on the final list
-                files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write))
+            if opt.multimaf is not None or opt.multivariants is not None:      # likewise on the final list
+                files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write, blocks))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
     finally:
