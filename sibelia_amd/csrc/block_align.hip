@@ -7,25 +7,26 @@
 //             parity hold a cell; the three neighbours of a cell are offset k two diagonals back (i + 1, j + 1) and offsets k - 1,
 //             k + 1 one diagonal back ((i + 1, j), (i, j + 1)).  So ONE score array indexed by k serves all three diagonals: a diagonal
 //             writes its own parity and reads the other one.  Offsets outside [0, W) read as minus infinity; the matrix borders
-//             (i == n or j == m) are cells of the sweep with the closed form -75 ((n - i) + (m - j)).
-//   kernel    one workgroup per pair, diagonals from n + m down to 0.  A lane owns the 8 consecutive offsets 8 q .. 8 q + 7: the 4
-//             cells of a diagonal among them give one byte of trace codes (2 bits: 0 diagonal / equal, 1 diagonal / unequal, 2 i step,
-//             3 j step -- decided at fill time), stored BY DIAGONAL, so a wave writes consecutive bytes and the offset of a diagonal
-//             is d * B.  W <= 512: one wave, the scores live in registers, the two neighbours beyond a lane's offsets come by one
-//             cross-lane move per diagonal, no barrier.  Wider bands: the score array lives in LDS, 256 or 1024 lanes, one barrier per
-//             diagonal.  The bases never fit the LDS as a whole: per 64 diagonals the stretch of a and of b those diagonals touch is
-//             staged from the original records (a reverse instance downwards through complement1).
+//             (i == n or j == m) are cells of the sweep with a closed form.
+//   model     what the gap costs decide is a type (GaLinear, GaAffine): the score states of a cell (1, or H / E / F), its update and its
+//             border form, the bits of a trace code (2 or 4), one round of the trace walk and the limits of the band classes.  A gap
+//             opening cost o > 0 (sbl_align_set_gap_open) takes the affine model, o == 0 the linear one; kernel, launcher
+//             and pass loop exist once and are instantiated or filled from the model.
+//   kernel    k_block_align<M, REG>: one workgroup per pair, diagonals from n + m down to 0.  A lane owns the 8 consecutive offsets
+//             8 q .. 8 q + 7: the 4 cells of a diagonal among them give one byte of trace codes (two with the affine model), decided at
+//             fill time and stored BY DIAGONAL, so a wave writes consecutive bytes and the offset of a diagonal is d * B.  W <= 512: one
+//             wave, the scores live in registers, the neighbours beyond a lane's offsets come by one cross-lane move per state read and
+//             side (two per diagonal, four with the affine model), no barrier.  Wider bands: one score array per state in LDS, 256 or
+//             M::WIDE_THREADS lanes, one barrier per diagonal.  The bases never fit the LDS as a whole: per 64 diagonals the stretch of
+//             a and of b those diagonals touch is staged from the original records (a reverse instance downwards through complement1).
 //   trace     one wave: lane t fetches the code t steps ahead along the direction of the current step, one ballot consumes the run.
 //             It emits runs (op, length); the certificate is checked first -- a pair that fails it is not traced.
 //   spelling  k_spell_groups, output-stationary like blockseq.hip: a lane owns 16 bytes of the rows, finds its group, its row and its
 //             run by binary search over tables the host made from the runs, and writes them with one vector store.  The two gapped
 //             rows of a pair are the rows of a group of one member (gm_spell).
-//   affine    a gap opening cost o > 0 (sbl_align_set_gap_open) runs k_block_align3 instead: the same sweep over three
-//             score states H / E / F, each one array by offset parity, 4 bits of codes per cell (H's choice, "E / F came by
-//             extension"), a trace walk with a state.  o == 0 runs k_block_align as before.
 //   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
-//             grouped by band class (register / LDS 256 / LDS 1024; with an opening cost register / LDS 256 / LDS 640) and chunked under
-//             the total cap on the trace codes.
+//             grouped by band class (register / LDS 256 / LDS wide, the limits the model's) and chunked under the total cap on the
+//             trace codes.
 //   groups    sbl_align_groups / sbl_align_block_groups: a centre-star multiple alignment per group of instances.  Every
 //             member against the group's first instance through the same passes (ga_passes); the gap slots of a group merged on the
 //             host from the runs; k_spell_groups spells the rows.
@@ -38,14 +39,11 @@ namespace {
 
 constexpr int GA_NEG = -(1 << 30);
 constexpr int GA_CHUNK = 64;                           // diagonals per staged stretch of bases
-constexpr unsigned GA_REG_W = 512, GA_MID_W = 4096, GA_MAX_W = 12288;      // band offsets: one wave in registers / 256 lanes / 1024 lanes (LDS: 4 (W + 2) + 2 (W / 2 + 40) <= 64 KiB)
+constexpr int GA_MAX_STATES = 3;                       // score states of a gap model
 constexpr u64 GA_MAX_DIAG = 1ull << 23;                // 75 (n + m) stays clear of GA_NEG
 constexpr unsigned GA_W0 = 64;
 constexpr size_t GA_PAIR_CAP = (size_t)8 << 30, GA_TOTAL_CAP = (size_t)32 << 30;
 constexpr unsigned GA_ALIGN = 256;
-// gap opening cost o > 0: three score arrays in the same 64 KiB of LDS, 12 (W + 2) + 2 (W / 2 + 40) <= 65536; one wave in registers / 256 lanes / 640 lanes
-constexpr unsigned GA3_REG_W = 512, GA3_MID_W = 2048, GA3_MAX_W = 4992;
-constexpr unsigned GA3_THREADS = 640;
 constexpr unsigned GA_MAX_OPEN = 100000;               // GA_NEG - o - 75 and -(2 o + 75 (n + m)) stay inside 32 bits
 
 struct GaJob {
@@ -64,94 +62,213 @@ __host__ __device__ inline int ga_bound(int n, int m, int w)
 
 __device__ inline unsigned ga_seg(unsigned W) { return (W + GA_CHUNK) / 2 + 8; }      // bytes of a staged stretch
 
-// one cell: the neighbours' scores in, score and trace code out
-__device__ inline int ga_cell(int g, int up, int lf, bool eq, unsigned &code)
+// the code of cell (ci, cj), M::CODE_BITS wide; 1 << M::CODE_BITS: beyond the matrix or the band.  The cells of a diagonal lie at every
+// second offset, in ascending bits of ascending bytes.
+template <class M> __device__ inline unsigned ga_fetch(const uint8_t *codes, const GaJob &J, int lo, int ci, int cj)
 {
-	const int dg = g + (eq ? AL_MATCH : -AL_PENALTY), u = up - AL_PENALTY, l = lf - AL_PENALTY;
-	int val = dg > u ? dg : u;
-	val = l > val ? l : val;
-	code = dg == val ? (eq ? 0u : 1u) : u == val ? 2u : 3u;
-	return val;
+	constexpr unsigned PER_BYTE = 8 / M::CODE_BITS, NONE = 1u << M::CODE_BITS;
+	if (ci >= (int)J.n || cj >= (int)J.m) return NONE;
+	const int k = cj - ci - lo + (int)J.w;
+	if (k < 0 || k >= (int)J.W) return NONE;
+	const unsigned cell = (unsigned)k >> 1;
+	return (codes[(u64)(unsigned)(ci + cj) * J.B + cell / PER_BYTE] >> (M::CODE_BITS * (cell % PER_BYTE))) & (NONE - 1);
 }
 
+struct GaPos { int i, j, state; };                     // where the trace walk stands; state: the model's own, 0 at the start
+
+// ---- the gap models.  Scores come as arrays over the model's states: dg of (i + 1, j + 1), up of (i + 1, j), lf of (i, j + 1), v the
+// cell's own.  UP / LF: bit s set when a cell reads state s of up / lf -- the register path moves only those across lanes.
+
+// linear gap costs: one state, 2 bits of codes (0 diagonal / equal, 1 diagonal / unequal, 2 i step, 3 j step).  LDS
+// classes: 4 (W + 2) + 2 (W / 2 + 40) <= 64 KiB
+struct GaLinear {
+	static constexpr int STATES = 1, CODE_BITS = 2;
+	static constexpr unsigned UP = 1, LF = 1;
+	static constexpr unsigned REG_W = 512, MID_W = 4096, MAX_W = 12288, WIDE_THREADS = 1024;
+	typedef uint8_t Code;                                                   // a lane's 4 cells of a diagonal
+
+	__device__ static unsigned cell(const int (&dg)[1], const int (&up)[1], const int (&lf)[1], bool eq, int, int (&v)[1])
+	{
+		const int d = dg[0] + (eq ? AL_MATCH : -AL_PENALTY), u = up[0] - AL_PENALTY, l = lf[0] - AL_PENALTY;
+		int val = d > u ? d : u;
+		val = l > val ? l : val;
+		v[0] = val;
+		return d == val ? (eq ? 0u : 1u) : u == val ? 2u : 3u;
+	}
+
+	// a border cell (i == n or j == m): `rest` gap columns to the end
+	__device__ static void border(int rest, bool, bool, int, int (&v)[1]) { v[0] = -AL_PENALTY * rest; }
+
+	// one round of the walk at (i, j): lane t looks t steps ahead along the direction of the first step, one ballot consumes the run
+	template <class Emit> __device__ static GaPos walk(const uint8_t *codes, const GaJob &J, int lo, int tid, GaPos at, Emit &emit)
+	{
+		int i = at.i, j = at.j;
+		unsigned c = ga_fetch<GaLinear>(codes, J, lo, i + tid, j + tid);
+		const unsigned c0 = (unsigned)__shfl((int)c, 0);
+		if (c0 >= 2) c = c0 == 2 ? ga_fetch<GaLinear>(codes, J, lo, i + tid, j) : ga_fetch<GaLinear>(codes, J, lo, i, j + tid);
+		const u64 other = __ballot(c != c0);
+		const int f = other ? __ffsll((long long)other) - 1 : 64;
+		if (c0 < 2) { emit(c0 == 0 ? '=' : 'X', (unsigned)f); i += f; j += f; }
+		else if (c0 == 2) { emit('I', (unsigned)f); i += f; }
+		else { emit('D', (unsigned)f); j += f; }
+		return GaPos{i, j, 0};
+	}
+};
+
+// a gap opening cost go: H[i][j] the best score of a[i:] against b[j:], E / F the best that starts with a[i] over '-' /
+// '-' over b[j]; a gap run of L columns costs go + 75 L.  Codes take 4 bits per cell: bits 0-1 H's choice (0 diagonal / equal, 1
+// diagonal / unequal, 2 enter E, 3 enter F), bit 2 "E came by extension" (the run does not close after this column), bit 3 the same for
+// F.  Three score arrays in the same 64 KiB of LDS, 12 (W + 2) + 2 (W / 2 + 40) <= 65536: the classes are narrower.
+struct GaAffine {
+	static constexpr int STATES = 3, CODE_BITS = 4;                         // H, E, F
+	static constexpr unsigned UP = 1 | 2, LF = 1 | 4;                       // H, E of (i + 1, j); H, F of (i, j + 1)
+	static constexpr unsigned REG_W = 512, MID_W = 2048, MAX_W = 4992, WIDE_THREADS = 640;
+	typedef uint16_t Code;                                                  // 256-byte aligned codes, an even B: every 16-bit store is aligned
+
+	__device__ static unsigned cell(const int (&dg)[3], const int (&up)[3], const int (&lf)[3], bool eq, int go, int (&v)[3])
+	{
+		const int eo = up[0] - go - AL_PENALTY, fo = lf[0] - go - AL_PENALTY, ex = up[1] - AL_PENALTY, fx = lf[2] - AL_PENALTY;
+		const int e = ex > eo ? ex : eo, f = fx > fo ? fx : fo;
+		const int d = dg[0] + (eq ? AL_MATCH : -AL_PENALTY);
+		int val = d > e ? d : e;
+		val = f > val ? f : val;
+		v[0] = val; v[1] = e; v[2] = f;
+		return (d == val ? (eq ? 0u : 1u) : e == val ? 2u : 3u) | (e != eo ? 4u : 0u) | (f != fo ? 8u : 0u);
+	}
+
+	// a border cell (i == n or j == m): one gap run of `rest` columns to the end; in_a / in_b: i < n / j < m
+	__device__ static void border(int rest, bool in_a, bool in_b, int go, int (&v)[3])
+	{
+		v[0] = rest ? -go - AL_PENALTY * rest : 0;
+		v[1] = in_a ? v[0] : GA_NEG;
+		v[2] = in_b ? v[0] : GA_NEG;
+	}
+
+	// one round of the walk.  State 0: H -- lane t looks t diagonal steps ahead, one ballot consumes a run of equal codes.  State 1 / 2:
+	// inside an I / D run -- lane t looks t columns ahead along i / j; the run closes after the first column whose extension bit is clear.
+	template <class Emit> __device__ static GaPos walk(const uint8_t *codes, const GaJob &J, int lo, int tid, GaPos at, Emit &emit)
+	{
+		int i = at.i, j = at.j, state = at.state;
+		if (state == 0) {
+			const unsigned x = ga_fetch<GaAffine>(codes, J, lo, i + tid, j + tid), c = x == 16 ? 4 : x & 3;
+			const unsigned c0 = (unsigned)__shfl((int)c, 0);
+			if (c0 >= 2) return GaPos{i, j, (int)c0 - 1};
+			const u64 other = __ballot(c != c0);
+			const int len = other ? __ffsll((long long)other) - 1 : 64;
+			emit(c0 == 0 ? '=' : 'X', (unsigned)len); i += len; j += len;
+		} else {
+			const unsigned x = state == 1 ? ga_fetch<GaAffine>(codes, J, lo, i + tid, j) : ga_fetch<GaAffine>(codes, J, lo, i, j + tid);
+			const u64 closes = __ballot(x == 16 || !((x >> (state + 1)) & 1));
+			int len = closes ? __ffsll((long long)closes) : 64;
+			const int room = state == 1 ? (int)J.n - i : (int)J.m - j;
+			len = len > room ? room : len;
+			emit(state == 1 ? 'I' : 'D', (unsigned)len);
+			if (state == 1) i += len; else j += len;
+			if (closes) state = 0;
+		}
+		return GaPos{i, j, state};
+	}
+};
+
 struct GaView {                                         // what a cell needs to find itself
-	int n, m, lo, w, W, imin, jmin;
+	int n, m, lo, w, W, imin, jmin, go;
 	const uint8_t *sa, *sb;
 };
 
-// the 4 cells of diagonal d among offsets 8 q + P + 2 c; s: the lane's 8 scores (REG) -- prev / next: s[7] of lane q - 1, s[0] of lane q + 1
-template <int P> __device__ inline unsigned ga_quad_reg(const GaView &V, int d, int q, int (&s)[8], int prev, int next, int &score)
+// the 4 cells of diagonal d among offsets 8 q + P + 2 c -> their codes.  s: the lane's 8 offsets of every state (REG) -- prev / next:
+// s[.][7] of lane q - 1, s[.][0] of lane q + 1
+template <class M, int P> __device__ inline unsigned ga_quad_reg(const GaView &V, int d, int q, int *const (&s)[GA_MAX_STATES], const int (&prev)[M::STATES],
+                                                                 const int (&next)[M::STATES], int &score)
 {
-	unsigned byte = 0;
+	unsigned bits = 0;
 #pragma unroll
 	for (int c = 0; c < 4; c++) {
 		const int k = 8 * q + 2 * c + P;
 		if (k >= V.W) continue;
 		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
 		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
-		int val;
+		int v[M::STATES];
 		unsigned code = 0;
-		if (i == V.n || j == V.m) val = -AL_PENALTY * ((V.n - i) + (V.m - j));
+		if (i == V.n || j == V.m) M::border((V.n - i) + (V.m - j), i < V.n, j < V.m, V.go, v);
 		else {
-			const int up = P == 0 && c == 0 ? prev : s[2 * c + P - 1 < 0 ? 0 : 2 * c + P - 1];
-			const int lf = P == 1 && c == 3 ? next : s[2 * c + P + 1 > 7 ? 7 : 2 * c + P + 1];
-			val = ga_cell(s[2 * c + P], up, lf, V.sa[i - V.imin] == V.sb[j - V.jmin], code);
+			const int xu = 2 * c + P - 1 < 0 ? 0 : 2 * c + P - 1, xl = 2 * c + P + 1 > 7 ? 7 : 2 * c + P + 1;
+			int dg[M::STATES], up[M::STATES], lf[M::STATES];
+#pragma unroll
+			for (int t = 0; t < M::STATES; t++) {
+				dg[t] = s[t][2 * c + P];
+				up[t] = P == 0 && c == 0 ? prev[t] : s[t][xu];
+				lf[t] = P == 1 && c == 3 ? next[t] : s[t][xl];
+			}
+			code = M::cell(dg, up, lf, V.sa[i - V.imin] == V.sb[j - V.jmin], V.go, v);
 		}
-		s[2 * c + P] = val;
-		if (d == 0) score = val;
-		byte |= code << (2 * c);
+#pragma unroll
+		for (int t = 0; t < M::STATES; t++) s[t][2 * c + P] = v[t];
+		if (d == 0) score = v[0];
+		bits |= code << (M::CODE_BITS * c);
 	}
-	return byte;
+	return bits;
 }
 
-// the same over the score array S in LDS (S[k + 1] = offset k; S[0] and S[W + 1] are minus infinity)
-__device__ inline unsigned ga_quad_lds(const GaView &V, int d, int q, int p, int *S, int &score)
+// the same over the score arrays in LDS: state t at S + t (W + 2), S[k + 1] = offset k, S[0] and S[W + 1] are minus infinity
+template <class M> __device__ inline unsigned ga_quad_lds(const GaView &V, int d, int q, int p, int *S, int &score)
 {
-	unsigned byte = 0;
+	unsigned bits = 0;
 #pragma unroll
 	for (int c = 0; c < 4; c++) {
 		const int k = 8 * q + 2 * c + p;
 		if (k >= V.W) break;
 		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
 		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
-		int val;
+		int v[M::STATES];
 		unsigned code = 0;
-		if (i == V.n || j == V.m) val = -AL_PENALTY * ((V.n - i) + (V.m - j));
-		else val = ga_cell(S[k + 1], S[k], S[k + 2], V.sa[i - V.imin] == V.sb[j - V.jmin], code);
-		S[k + 1] = val;
-		if (d == 0) score = val;
-		byte |= code << (2 * c);
+		if (i == V.n || j == V.m) M::border((V.n - i) + (V.m - j), i < V.n, j < V.m, V.go, v);
+		else {
+			int dg[M::STATES], up[M::STATES], lf[M::STATES];
+#pragma unroll
+			for (int t = 0; t < M::STATES; t++) {
+				const int *X = S + t * (V.W + 2);
+				dg[t] = X[k + 1]; up[t] = X[k]; lf[t] = X[k + 2];
+			}
+			code = M::cell(dg, up, lf, V.sa[i - V.imin] == V.sb[j - V.jmin], V.go, v);
+		}
+#pragma unroll
+		for (int t = 0; t < M::STATES; t++) S[t * (V.W + 2) + k + 1] = v[t];
+		if (d == 0) score = v[0];
+		bits |= code << (M::CODE_BITS * c);
 	}
-	return byte;
+	return bits;
 }
 
-// code of cell (ci, cj); 4: beyond the matrix or the band
-__device__ inline unsigned ga_fetch(const uint8_t *codes, const GaJob &J, int lo, int ci, int cj)
+// M: the gap model; go: its opening cost (the linear model ignores it).  REG: one wave, 8 score registers per state and lane.  Otherwise
+// M::STATES arrays of W + 2 scores in LDS and one barrier per diagonal: every cell reads the other parity and writes its own.
+template <class M, bool REG> __global__ __launch_bounds__(REG ? 64 : M::WIDE_THREADS) void k_block_align(const uint8_t *__restrict__ seq, const GaJob *__restrict__ jobs, int go,
+                                                                                                       uint8_t *codes_all, sbl_align_run *runs_all, GaOut *__restrict__ out)
 {
-	if (ci >= (int)J.n || cj >= (int)J.m) return 4;
-	const int k = cj - ci - lo + (int)J.w;
-	if (k < 0 || k >= (int)J.W) return 4;
-	return (codes[(u64)(unsigned)(ci + cj) * J.B + (unsigned)(k >> 3)] >> (2 * ((k >> 1) & 3))) & 3;
-}
-
-template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_align(const uint8_t *__restrict__ seq, const GaJob *__restrict__ jobs,
-                                                                                     uint8_t *codes_all, sbl_align_run *runs_all, GaOut *__restrict__ out)
-{
+	typedef typename M::Code Code;
+	static_assert(8 * sizeof(Code) == 4 * M::CODE_BITS, "a lane's 4 cells of a diagonal are one store");
 	extern __shared__ int ga_lds[];
 	__shared__ int s_score;
 	const GaJob J = jobs[blockIdx.x];
-	const int n = (int)J.n, m = (int)J.m, w = (int)J.w, W = (int)J.W, B = (int)J.B;
+	const int n = (int)J.n, m = (int)J.m, w = (int)J.w, W = (int)J.W, B = (int)J.B, Q = B / (int)sizeof(Code);      // Q: lanes that hold cells
 	const int lo = m - n < 0 ? m - n : 0, omin = lo - w, omax = omin + W - 1;
 	const int tid = (int)threadIdx.x, T = (int)blockDim.x;
-	int *const S = ga_lds;                                                  // LDS kernel only: W + 2 scores
-	uint8_t *const sa = reinterpret_cast<uint8_t *>(ga_lds + (REG ? 0 : W + 2));
+	int *const S = ga_lds;                                                  // LDS kernel only
+	uint8_t *const sa = reinterpret_cast<uint8_t *>(ga_lds + (REG ? 0 : M::STATES * (W + 2)));
 	uint8_t *const sb = sa + ga_seg((unsigned)W);
 	uint8_t *const mycodes = codes_all + J.code_off;
-	GaView V{n, m, lo, w, W, 0, 0, sa, sb};
-	int s[8];
+	GaView V{n, m, lo, w, W, 0, 0, go, sa, sb};
+	// REG: the lane's 8 offsets of state t are s[t][0 .. 7].  One array per state: as a single [STATES][8] object the compiler's resource
+	// report shows 78 VGPRs and 6 waves for the affine model instead of 59 and 7.  s[] is a view for the loops over the states: they are
+	// unrolled (the pragmas say so), every index is then a constant and the arrays stay in registers.
+	static_assert(M::STATES <= GA_MAX_STATES, "a register array per state");
+	int s0[8], s1[8], s2[8];
+	int *const s[GA_MAX_STATES] = {s0, s1, s2};
 	int score = 0;
-	if (REG) { for (int c = 0; c < 8; c++) s[c] = GA_NEG; }
-	else { for (int k = tid; k < W + 2; k += T) S[k] = GA_NEG; }
+	if (REG) {
+#pragma unroll
+		for (int t = 0; t < M::STATES; t++) for (int c = 0; c < 8; c++) s[t][c] = GA_NEG;
+	}
+	else { for (int k = tid; k < M::STATES * (W + 2); k += T) S[k] = GA_NEG; }
 	if (tid == 0) s_score = 0;
 
 	for (int dtop = n + m; dtop >= 0; dtop -= GA_CHUNK) {
@@ -167,13 +284,19 @@ template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_a
 		__syncthreads();
 		for (int d = dtop; d >= dbot; d--) {
 			const int p = (d - lo + w) & 1;                                  // the parity of the offsets that hold a cell on this diagonal
+			Code *const row = reinterpret_cast<Code *>(mycodes + (u64)(unsigned)d * (unsigned)B);
 			if (REG) {
-				const int prev = __shfl_up(s[7], 1), next = __shfl_down(s[0], 1);
-				const unsigned byte = p ? ga_quad_reg<1>(V, d, tid, s, tid == 0 ? GA_NEG : prev, tid == 63 ? GA_NEG : next, score)
-				                        : ga_quad_reg<0>(V, d, tid, s, tid == 0 ? GA_NEG : prev, tid == 63 ? GA_NEG : next, score);
-				if (tid < B) mycodes[(u64)(unsigned)d * (unsigned)B + (unsigned)tid] = (uint8_t)byte;
+				int prev[M::STATES], next[M::STATES];
+#pragma unroll
+				for (int t = 0; t < M::STATES; t++) {                       // every lane takes part in a move; which moves exist is the model's
+					const int below = M::UP >> t & 1 ? __shfl_up(s[t][7], 1) : GA_NEG, above = M::LF >> t & 1 ? __shfl_down(s[t][0], 1) : GA_NEG;
+					prev[t] = tid == 0 ? GA_NEG : below;
+					next[t] = tid == 63 ? GA_NEG : above;
+				}
+				const unsigned bits = p ? ga_quad_reg<M, 1>(V, d, tid, s, prev, next, score) : ga_quad_reg<M, 0>(V, d, tid, s, prev, next, score);
+				if (tid < Q) row[tid] = (Code)bits;
 			} else {
-				for (int q = tid; q < B; q += T) mycodes[(u64)(unsigned)d * (unsigned)B + (unsigned)q] = (uint8_t)ga_quad_lds(V, d, q, p, S, score);
+				for (int q = tid; q < Q; q += T) row[q] = (Code)ga_quad_lds<M>(V, d, q, p, S, score);
 				__syncthreads();
 			}
 		}
@@ -199,198 +322,10 @@ template <bool REG> __global__ __launch_bounds__(REG ? 64 : 1024) void k_block_a
 		if (cur_len) { if (tid == 0) runs[nruns] = sbl_align_run{cur_op, cur_len}; nruns++; }
 		cur_op = op; cur_len = len;
 	};
-	int i = 0, j = 0;
-	while (i < n && j < m) {
-		unsigned c = ga_fetch(mycodes, J, lo, i + tid, j + tid);
-		const unsigned c0 = (unsigned)__shfl((int)c, 0);
-		if (c0 >= 2) c = c0 == 2 ? ga_fetch(mycodes, J, lo, i + tid, j) : ga_fetch(mycodes, J, lo, i, j + tid);
-		const u64 other = __ballot(c != c0);
-		const int f = other ? __ffsll((long long)other) - 1 : 64;
-		if (c0 < 2) { emit(c0 == 0 ? '=' : 'X', (unsigned)f); i += f; j += f; }
-		else if (c0 == 2) { emit('I', (unsigned)f); i += f; }
-		else { emit('D', (unsigned)f); j += f; }
-	}
-	if (i < n) emit('I', (unsigned)(n - i));
-	if (j < m) emit('D', (unsigned)(m - j));
-	emit(0, 0);
-	if (tid == 0) out[blockIdx.x] = GaOut{score, nruns, 1, 0};
-}
-
-// ---- gap opening cost: H[i][j] the best score of a[i:] against b[j:], E / F the best that starts with a[i] over '-' /
-// '-' over b[j]; a gap run of L columns costs go + 75 L.  Codes take 4 bits per cell: bits 0-1 H's choice (0 diagonal / equal, 1
-// diagonal / unequal, 2 enter E, 3 enter F), bit 2 "E came by extension" (the run does not close after this column), bit 3 the same for F.
-
-// one cell: the neighbours' scores in -- hd: H two diagonals back; hu, eu: H, E of (i + 1, j); hl, fl: H, F of (i, j + 1)
-__device__ inline unsigned ga3_cell(int hd, int hu, int eu, int hl, int fl, bool eq, int go, int &h, int &e, int &f)
-{
-	const int eo = hu - go - AL_PENALTY, fo = hl - go - AL_PENALTY, ex = eu - AL_PENALTY, fx = fl - AL_PENALTY;
-	e = ex > eo ? ex : eo;
-	f = fx > fo ? fx : fo;
-	const int dg = hd + (eq ? AL_MATCH : -AL_PENALTY);
-	int val = dg > e ? dg : e;
-	val = f > val ? f : val;
-	h = val;
-	return (dg == val ? (eq ? 0u : 1u) : e == val ? 2u : 3u) | (e != eo ? 4u : 0u) | (f != fo ? 8u : 0u);
-}
-
-// a border cell (i == n or j == m): one gap run to the end
-__device__ inline void ga3_border(const GaView &V, int i, int j, int go, int &h, int &e, int &f)
-{
-	const int rest = (V.n - i) + (V.m - j);
-	h = rest ? -go - AL_PENALTY * rest : 0;
-	e = i < V.n ? h : GA_NEG;
-	f = j < V.m ? h : GA_NEG;
-}
-
-// the 4 cells of diagonal d among offsets 8 q + P + 2 c; h, e, f: the lane's 8 offsets of each state (REG) -- hp, ep: h[7], e[7] of lane
-// q - 1; hn, fn: h[0], f[0] of lane q + 1
-template <int P> __device__ inline unsigned ga3_quad_reg(const GaView &V, int go, int d, int q, int (&h)[8], int (&e)[8], int (&f)[8], int hp, int ep, int hn, int fn, int &score)
-{
-	unsigned half = 0;
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		const int k = 8 * q + 2 * c + P;
-		if (k >= V.W) continue;
-		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
-		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
-		int hv, ev, fv;
-		unsigned code = 0;
-		if (i == V.n || j == V.m) ga3_border(V, i, j, go, hv, ev, fv);
-		else {
-			const int xu = 2 * c + P - 1 < 0 ? 0 : 2 * c + P - 1, xl = 2 * c + P + 1 > 7 ? 7 : 2 * c + P + 1;
-			const bool from_prev = P == 0 && c == 0, from_next = P == 1 && c == 3;
-			code = ga3_cell(h[2 * c + P], from_prev ? hp : h[xu], from_prev ? ep : e[xu], from_next ? hn : h[xl], from_next ? fn : f[xl],
-			                V.sa[i - V.imin] == V.sb[j - V.jmin], go, hv, ev, fv);
-		}
-		h[2 * c + P] = hv; e[2 * c + P] = ev; f[2 * c + P] = fv;
-		if (d == 0) score = hv;
-		half |= code << (4 * c);
-	}
-	return half;
-}
-
-// the same over the score arrays in LDS (X[k + 1] = offset k; X[0] and X[W + 1] are minus infinity)
-__device__ inline unsigned ga3_quad_lds(const GaView &V, int go, int d, int q, int p, int *H, int *E, int *F, int &score)
-{
-	unsigned half = 0;
-#pragma unroll
-	for (int c = 0; c < 4; c++) {
-		const int k = 8 * q + 2 * c + p;
-		if (k >= V.W) break;
-		const int o = k + V.lo - V.w, i = (d - o) >> 1, j = d - i;
-		if (i < 0 || j < 0 || i > V.n || j > V.m) continue;
-		int hv, ev, fv;
-		unsigned code = 0;
-		if (i == V.n || j == V.m) ga3_border(V, i, j, go, hv, ev, fv);
-		else code = ga3_cell(H[k + 1], H[k], E[k], H[k + 2], F[k + 2], V.sa[i - V.imin] == V.sb[j - V.jmin], go, hv, ev, fv);
-		H[k + 1] = hv; E[k + 1] = ev; F[k + 1] = fv;
-		if (d == 0) score = hv;
-		half |= code << (4 * c);
-	}
-	return half;
-}
-
-// the 4 bits of cell (ci, cj); 16: beyond the matrix or the band.  A lane's two bytes of a diagonal hold its cells c = 0 .. 3 in ascending nibbles.
-__device__ inline unsigned ga3_fetch(const uint8_t *codes, const GaJob &J, int lo, int ci, int cj)
-{
-	if (ci >= (int)J.n || cj >= (int)J.m) return 16;
-	const int k = cj - ci - lo + (int)J.w;
-	if (k < 0 || k >= (int)J.W) return 16;
-	return (codes[(u64)(unsigned)(ci + cj) * J.B + (unsigned)(k >> 2)] >> (4 * ((k >> 1) & 1))) & 15;
-}
-
-// k_block_align with the gap opening cost go (J.B: code bytes per diagonal, two per lane that holds cells).  REG: one wave, 24 score
-// registers per lane, four cross-lane moves per diagonal.  Otherwise three arrays of W + 2 scores in LDS and one barrier per diagonal:
-// every cell reads the other parity and writes its own.
-template <bool REG> __global__ __launch_bounds__(REG ? 64 : GA3_THREADS) void k_block_align3(const uint8_t *__restrict__ seq, const GaJob *__restrict__ jobs, int go,
-                                                                                             uint8_t *codes_all, sbl_align_run *runs_all, GaOut *__restrict__ out)
-{
-	extern __shared__ int ga_lds[];
-	__shared__ int s_score;
-	const GaJob J = jobs[blockIdx.x];
-	const int n = (int)J.n, m = (int)J.m, w = (int)J.w, W = (int)J.W, B = (int)J.B, Q = B / 2;
-	const int lo = m - n < 0 ? m - n : 0, omin = lo - w, omax = omin + W - 1;
-	const int tid = (int)threadIdx.x, T = (int)blockDim.x;
-	int *const H = ga_lds, *const E = H + (W + 2), *const F = E + (W + 2);      // LDS kernel only
-	uint8_t *const sa = reinterpret_cast<uint8_t *>(ga_lds + (REG ? 0 : 3 * (W + 2)));
-	uint8_t *const sb = sa + ga_seg((unsigned)W);
-	uint8_t *const mycodes = codes_all + J.code_off;                        // 256-byte aligned, B even: every 16-bit store is aligned
-	GaView V{n, m, lo, w, W, 0, 0, sa, sb};
-	int h[8], e[8], f[8];
-	int score = 0;
-	if (REG) { for (int c = 0; c < 8; c++) h[c] = e[c] = f[c] = GA_NEG; }
-	else { for (int k = tid; k < 3 * (W + 2); k += T) H[k] = GA_NEG; }
-	if (tid == 0) s_score = 0;
-
-	for (int dtop = n + m; dtop >= 0; dtop -= GA_CHUNK) {
-		const int dbot = dtop - (GA_CHUNK - 1) > 0 ? dtop - (GA_CHUNK - 1) : 0;
-		int imin = (dbot - omax) >> 1, imax = (dtop - omin) >> 1, jmin = (dbot + omin) >> 1, jmax = (dtop + omax) >> 1;      // as in k_block_align
-		imin = imin < 0 ? 0 : imin; imax = imax > n - 1 ? n - 1 : imax;
-		jmin = jmin < 0 ? 0 : jmin; jmax = jmax > m - 1 ? m - 1 : jmax;
-		__syncthreads();
-		for (int t = tid; t <= imax - imin; t += T) sa[t] = strand_base(seq, J.src_a, J.n, (unsigned)(imin + t), J.rev_a);
-		for (int t = tid; t <= jmax - jmin; t += T) sb[t] = strand_base(seq, J.src_b, J.m, (unsigned)(jmin + t), J.rev_b);
-		V.imin = imin; V.jmin = jmin;
-		__syncthreads();
-		for (int d = dtop; d >= dbot; d--) {
-			const int p = (d - lo + w) & 1;
-			if (REG) {
-				int hp = __shfl_up(h[7], 1), ep = __shfl_up(e[7], 1), hn = __shfl_down(h[0], 1), fn = __shfl_down(f[0], 1);
-				if (tid == 0) hp = ep = GA_NEG;
-				if (tid == 63) hn = fn = GA_NEG;
-				const unsigned half = p ? ga3_quad_reg<1>(V, go, d, tid, h, e, f, hp, ep, hn, fn, score) : ga3_quad_reg<0>(V, go, d, tid, h, e, f, hp, ep, hn, fn, score);
-				if (tid < Q) *reinterpret_cast<uint16_t *>(mycodes + (u64)(unsigned)d * (unsigned)B + 2u * (unsigned)tid) = (uint16_t)half;
-			} else {
-				for (int q = tid; q < Q; q += T)
-					*reinterpret_cast<uint16_t *>(mycodes + (u64)(unsigned)d * (unsigned)B + 2u * (unsigned)q) = (uint16_t)ga3_quad_lds(V, go, d, q, p, H, E, F, score);
-				__syncthreads();
-			}
-		}
-	}
-	{
-		const int k0 = w - lo, q0 = k0 >> 3;                                  // exactly one lane filled (0, 0)
-		if ((REG ? tid : q0 % T) == (REG ? q0 : tid)) s_score = score;
-	}
-	__threadfence_block();
-	__syncthreads();
-	if (tid >= 64) return;
-	score = s_score;
-	if (!J.full && !(score > ga_bound(n, m, w))) {
-		if (tid == 0) out[blockIdx.x] = GaOut{score, 0, 0, 0};
-		return;
-	}
-
-	sbl_align_run *const runs = runs_all + J.run_off;
-	unsigned nruns = 0, cur_op = 0, cur_len = 0;
-	auto emit = [&](unsigned op, unsigned len) {
-		if (op == cur_op) { cur_len += len; return; }
-		if (cur_len) { if (tid == 0) runs[nruns] = sbl_align_run{cur_op, cur_len}; nruns++; }
-		cur_op = op; cur_len = len;
-	};
-	// state 0: H -- lane t looks t diagonal steps ahead, one ballot consumes a run of equal codes.  State 1 / 2: inside an I / D run --
-	// lane t looks t columns ahead along i / j; the run closes after the first column whose extension bit is clear.
-	int i = 0, j = 0, state = 0;
-	while (i < n && j < m) {
-		if (state == 0) {
-			const unsigned x = ga3_fetch(mycodes, J, lo, i + tid, j + tid), c = x == 16 ? 4 : x & 3;
-			const unsigned c0 = (unsigned)__shfl((int)c, 0);
-			if (c0 >= 2) { state = (int)c0 - 1; continue; }
-			const u64 other = __ballot(c != c0);
-			const int len = other ? __ffsll((long long)other) - 1 : 64;
-			emit(c0 == 0 ? '=' : 'X', (unsigned)len); i += len; j += len;
-		} else {
-			const unsigned x = state == 1 ? ga3_fetch(mycodes, J, lo, i + tid, j) : ga3_fetch(mycodes, J, lo, i, j + tid);
-			const u64 closes = __ballot(x == 16 || !((x >> (state + 1)) & 1));
-			int len = closes ? __ffsll((long long)closes) : 64;
-			const int room = state == 1 ? n - i : m - j;
-			len = len > room ? room : len;
-			emit(state == 1 ? 'I' : 'D', (unsigned)len);
-			if (state == 1) i += len; else j += len;
-			if (closes) state = 0;
-		}
-	}
-	if (i < n) emit('I', (unsigned)(n - i));
-	if (j < m) emit('D', (unsigned)(m - j));
+	GaPos at{0, 0, 0};
+	while (at.i < n && at.j < m) at = M::walk(mycodes, J, lo, tid, at, emit);
+	if (at.i < n) emit('I', (unsigned)(n - at.i));
+	if (at.j < m) emit('D', (unsigned)(m - at.j));
 	emit(0, 0);
 	if (tid == 0) out[blockIdx.x] = GaOut{score, nruns, 1, 0};
 }
@@ -477,22 +412,37 @@ unsigned ga_env(const char *name, unsigned fallback)
 
 struct Pending { size_t at; unsigned w; };
 
-// the three-state kernel runs: a gap opening cost is set (SBL_TEST_GALIGN_AFFINE=1: test switch, sends o == 0 through it as well)
-bool ga_affine(const sbl_ctx *c)
+// the one launch of a chunk of jobs of one band class (reg: the register class)
+template <class M> void ga_launch_cls(sbl_ctx *c, bool reg, unsigned blocks, unsigned threads, size_t lds)
 {
-	const char *e = getenv("SBL_TEST_GALIGN_AFFINE");
-	return c->gap_open > 0 || (e && atoi(e) == 1);
+	const uint8_t *seq = c->d_orig_ch.as<uint8_t>();
+	const GaJob *jobs = c->d_ga_job.as<GaJob>();
+	const int go = (int)c->gap_open;
+	uint8_t *codes = c->d_ga_codes.as<uint8_t>();
+	sbl_align_run *runs = c->d_ga_runs.as<sbl_align_run>();
+	GaOut *out = c->d_ga_out.as<GaOut>();
+	if (reg) k_block_align<M, true><<<blocks, threads, lds, c->stream>>>(seq, jobs, go, codes, runs, out);
+	else k_block_align<M, false><<<blocks, threads, lds, c->stream>>>(seq, jobs, go, codes, runs, out);
+}
+
+// what the host needs of a gap model
+struct GaModel {
+	unsigned reg_w, mid_w, max_w;        // the most offsets of the register class, of the LDS class of 256 lanes, of all
+	unsigned wide_threads;               // lanes of the widest class
+	unsigned score_bytes, code_bytes;    // LDS bytes of scores per offset; code bytes of a lane's 4 cells of a diagonal
+	void (*launch)(sbl_ctx *, bool, unsigned, unsigned, size_t);
+};
+template <class M> GaModel ga_model()
+{
+	return GaModel{M::REG_W, M::MID_W, M::MAX_W, M::WIDE_THREADS, 4 * M::STATES, sizeof(typename M::Code), ga_launch_cls<M>};
 }
 
 // one pass: the pending pairs of one band class at their current w, chunked under the total cap.  Fills res (score, status) and appends
 // the runs of the pairs that pass the certificate; returns those that have to run again.
-void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<size_t> &which, int cls, std::vector<uint8_t> &passed)
+void ga_launch(sbl_ctx *c, const GaModel &model, const std::vector<GaJob> &jobs, const std::vector<size_t> &which, int cls, std::vector<uint8_t> &passed)
 {
 	const size_t total_cap = getenv("SBL_TEST_GALIGN_TOTAL_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_TOTAL_KB", 1) << 10 : GA_TOTAL_CAP;
-	hipStream_t s = c->stream;
-	const bool affine = ga_affine(c);
-	const int go = (int)c->gap_open;
-	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : affine ? GA3_THREADS : 1024;
+	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : model.wide_threads;
 	std::vector<GaJob> chunk;
 	std::vector<GaOut> got;
 	for (size_t at = 0; at < which.size();) {
@@ -506,19 +456,15 @@ void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<siz
 			if (!chunk.empty() && bytes + need > total_cap) break;
 			j.code_off = bytes; j.run_off = nrun;
 			bytes += need; nrun += (u64)j.n + j.m + 1;
-			lds = std::max(lds, (cls ? (size_t)(j.W + 2) * (affine ? 12 : 4) : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
+			lds = std::max(lds, (cls ? (size_t)(j.W + 2) * model.score_bytes : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
 			chunk.push_back(j);
 			c->align_stats.cells += (u64)(j.n + j.m + 1) * ((j.W + 1) / 2);
 		}
 		al_upload(c, c->d_ga_job, chunk); c->d_ga_codes.ensure((size_t)bytes); c->d_ga_out.ensure(chunk.size() * sizeof(GaOut));
 		c->d_ga_runs.ensure((size_t)nrun * sizeof(sbl_align_run));
 		got.resize(chunk.size());
-		c->align_stats.kernel_ms += al_timed_launch(c, [&] {
-			if (affine && cls == 0) k_block_align3<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), go, c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
-			else if (affine) k_block_align3<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), go, c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
-			else if (cls == 0) k_block_align<true><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
-			else k_block_align<false><<<(unsigned)chunk.size(), threads, lds, s>>>(c->d_orig_ch.as<uint8_t>(), c->d_ga_job.as<GaJob>(), c->d_ga_codes.as<uint8_t>(), c->d_ga_runs.as<sbl_align_run>(), c->d_ga_out.as<GaOut>());
-		}, got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut));
+		c->align_stats.kernel_ms += al_timed_launch(c, [&] { model.launch(c, cls == 0, (unsigned)chunk.size(), threads, lds); },
+		                                            got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut));
 		c->align_stats.launches++;
 		c->align_stats.passes += chunk.size();
 		u64 more = 0;
@@ -532,10 +478,10 @@ void ga_launch(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<siz
 			if (!got[k].ok) continue;
 			passed[which[first + k]] = 1;
 			r.status = SBL_GALIGN_OK; r.score = got[k].score; r.first_run = fill; r.nruns = got[k].nruns;
-			if (got[k].nruns) HIP_TRY(hipMemcpyAsync(&c->ga_runs[fill], c->d_ga_runs.as<sbl_align_run>() + chunk[k].run_off, (size_t)got[k].nruns * sizeof(sbl_align_run), hipMemcpyDeviceToHost, s));
+			if (got[k].nruns) HIP_TRY(hipMemcpyAsync(&c->ga_runs[fill], c->d_ga_runs.as<sbl_align_run>() + chunk[k].run_off, (size_t)got[k].nruns * sizeof(sbl_align_run), hipMemcpyDeviceToHost, c->stream));
 			fill += got[k].nruns;
 		}
-		HIP_TRY(hipStreamSynchronize(s));
+		HIP_TRY(hipStreamSynchronize(c->stream));
 	}
 }
 
@@ -546,8 +492,11 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 	const size_t N = desc.size();
 	const size_t pair_cap = getenv("SBL_TEST_GALIGN_CAP_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_CAP_KB", 1) << 10 : GA_PAIR_CAP;
 	const unsigned w0 = ga_env("SBL_TEST_GALIGN_W0", GA_W0);
-	const bool affine = ga_affine(c);
-	const unsigned reg_w = affine ? GA3_REG_W : GA_REG_W, mid_w = affine ? GA3_MID_W : GA_MID_W, max_w = affine ? GA3_MAX_W : GA_MAX_W;
+	// the one place that decides the gap model: a gap opening cost is set (SBL_TEST_GALIGN_AFFINE=1: test switch, sends o == 0 through
+	// the affine model as well)
+	const char *e = getenv("SBL_TEST_GALIGN_AFFINE");
+	const bool affine = c->gap_open > 0 || (e && atoi(e) == 1);
+	const GaModel model = affine ? ga_model<GaAffine>() : ga_model<GaLinear>();
 	c->align_stats = sbl_align_stats_t{};
 	c->align_stats.pairs = N;
 	c->ga_res.assign(N, sbl_pair_result{});
@@ -581,11 +530,11 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 			j.w = std::min(p.w, mn);                                          // w = min(n, m): the band covers the matrix
 			j.full = j.w >= mn;
 			j.W = diff + 2 * j.w + 1;
-			j.B = ((j.W + 1) / 2 + 3) / 4 * (affine ? 2 : 1);                 // a lane's 4 cells of a diagonal: 2 bits each, 4 with an opening cost
-			if (j.W > max_w || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
-			cls[j.W <= reg_w ? 0 : j.W <= mid_w ? 1 : 2].push_back(p.at);
+			j.B = ((j.W + 1) / 2 + 3) / 4 * model.code_bytes;                 // the lanes that hold cells on a diagonal, each with the codes of its 4
+			if (j.W > model.max_w || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
+			cls[j.W <= model.reg_w ? 0 : j.W <= model.mid_w ? 1 : 2].push_back(p.at);
 		}
-		for (int k = 0; k < 3; k++) if (!cls[k].empty()) ga_launch(c, jobs, cls[k], k, passed);
+		for (int k = 0; k < 3; k++) if (!cls[k].empty()) ga_launch(c, model, jobs, cls[k], k, passed);
 		std::vector<Pending> again;
 		for (const Pending &p : pending) if (!passed[p.at]) again.push_back(Pending{p.at, jobs[p.at].w * 2});
 		pending.swap(again);

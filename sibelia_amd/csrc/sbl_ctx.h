@@ -111,7 +111,7 @@ struct sbl_ctx {
 	std::vector<sbl_pair_desc> ga_desc;
 	std::vector<int32_t> ga_ids;
 	sbl_align_stats_t align_stats{};
-	uint32_t gap_open = 0;               // sbl_align_set_gap_open: the cost of opening a gap run (0: linear gap costs, k_block_align)
+	uint32_t gap_open = 0;               // sbl_align_set_gap_open: the cost of opening a gap run (0: the linear model of k_block_align, else the affine one)
 	// sbl_align_groups / sbl_align_block_groups: the same pair passes (ga_desc: centre against member); what the calls hand out.  Instances,
 	// merged gap slots and groups of k_spell_groups: every sbl_align_* call spells through them, a pair as a group of one member
 	DevBuf d_gm_inst, d_gm_slot, d_gm_group;

@@ -8,78 +8,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import galign_model as GM                          # noqa: E402
+from galign_cases import Batch, mutated, rand      # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
-
-
-def rc(s):
-    return s.translate(_COMPLEMENT)[::-1]
-
-
-def rand(rng, n, alphabet=b"ACGT"):
-    return bytes(rng.choice(np.frombuffer(alphabet, dtype=np.uint8), n))
-
-
-def mutated(rng, a, rate=0.03, max_indel=12):
-    b = bytearray()
-    i = 0
-    while i < len(a):
-        u = rng.random()
-        if u < rate / 3:
-            i += int(rng.integers(1, max_indel + 1))
-        elif u < 2 * rate / 3:
-            b += rand(rng, int(rng.integers(1, max_indel + 1)))
-        else:
-            b += rand(rng, 1) if rng.random() < rate else a[i:i + 1]
-            i += 1
-    return bytes(b)
-
-
-class Batch:
-    """pairs of strings laid out as ranges of two records (all a's, all b's); a reverse range holds the reverse complement, so that
-    the strings the kernel reads are the ones given"""
-
-    def __init__(self, pairs, revs=None):
-        self.pairs = [(bytes(a), bytes(b)) for a, b in pairs]
-        self.revs = revs or [(False, False)] * len(pairs)
-        ra, rb, self.desc = bytearray(b"G"), bytearray(b"T"), []
-        for (a, b), (va, vb) in zip(self.pairs, self.revs):
-            self.desc.append((0, len(ra), len(ra) + len(a), va, 1, len(rb), len(rb) + len(b), vb))
-            ra += rc(a) if va else a
-            rb += rc(b) if vb else b
-        self.records = [bytes(ra) + b"C", bytes(rb) + b"A"]
-        self._want = None
-
-    def want(self):
-        if self._want is None:
-            self._want = []
-            for a, b in self.pairs:
-                score, steps = GM.align(a, b)
-                self._want.append((score, GM.runs(a, b, steps), GM.rows(a, b, steps)))
-        return self._want
-
-    def run(self):
-        from sibelia_amd import BlockFinder
-        bf = BlockFinder(self.records, device=0)
-        try:
-            return bf.align_pairs(self.desc), bf.align_stats()
-        finally:
-            bf.close()
-
-    def check(self, got, skipped=()):
-        assert len(got) == len(self.pairs)
-        for k, (g, (score, runs, rows)) in enumerate(zip(got, self.want())):
-            a, b = self.pairs[k]
-            if k in skipped:
-                assert (g.status, g.score, g.runs, g.row_a, g.row_b) == (1, None, [], b"", b""), k
-                continue
-            assert g.status == 0, (k, len(a), len(b))
-            assert g.score == score, (k, len(a), len(b), a[:60], b[:60])
-            assert g.runs == runs, (k, len(a), len(b), a[:60], b[:60])
-            assert (g.row_a, g.row_b) == rows, (k, len(a), len(b))
 
 
 def edge_pairs():
@@ -96,8 +27,8 @@ def edge_pairs():
 def test_edge_shapes():
     pairs = edge_pairs()
     b = Batch(pairs)
-    got, st = b.run()
-    b.check(got)
+    got, st = b.run(0)
+    b.check(got, b.want(0, linear=True))
     assert st["pairs"] == len(pairs) and st["skipped"] == 0 and st["launches"] >= 1 and st["cells"] > 0 and st["kernel_ms"] > 0 and st["spell_ms"] > 0
 
 
@@ -111,8 +42,8 @@ def test_length_differences_and_homopolymers():
     pairs += [(b"A" * 70, b"A" * 70), (b"A" * 33, b"A" * 90), (b"A" * 90, b"A" * 33), (b"AC" * 40, b"AC" * 33), (b"T" * 600, b"T" * 590),
               (b"GATTACA" + b"T" * 200 + b"GATTACA", b"GATTACA" + b"T" * 180 + b"GATTACA")]
     b = Batch(pairs)
-    got, _ = b.run()
-    b.check(got)
+    got, _ = b.run(0)
+    b.check(got, b.want(0, linear=True))
     assert got[8].runs == [("=", 70)] and got[9].runs == [("=", 33), ("D", 57)] and got[10].runs == [("=", 33), ("I", 57)]      # diagonal steps first
 
 
@@ -125,8 +56,8 @@ def test_reverse_ranges_and_bytes_outside_acgt():
     pairs = [(a, b)] * 4 + [(n1, n2)] * 4 + [(rand(rng, 200, b"ACGTN"), rand(rng, 190, b"ACGTN")), (b"NNNN", b"TNNNNT")]
     revs = [(False, False), (True, False), (False, True), (True, True)] * 2 + [(True, False), (False, False)]
     bt = Batch(pairs, revs)
-    got, _ = bt.run()
-    bt.check(got)
+    got, _ = bt.run(0)
+    bt.check(got, bt.want(0, linear=True))
     assert got[0].runs == got[1].runs == got[2].runs == got[3].runs
 
 
@@ -147,8 +78,8 @@ def random_batch():
 
 
 def test_a_batch_of_random_pairs(random_batch):
-    got, st = random_batch.run()
-    random_batch.check(got)
+    got, st = random_batch.run(0)
+    random_batch.check(got, random_batch.want(0, linear=True))
     assert st["pairs"] == 200 and st["passes"] >= 200
 
 
@@ -156,8 +87,8 @@ def test_results_do_not_depend_on_the_first_band(random_batch, monkeypatch):
     passes = {}
     for w0 in (1, 8, 64):
         monkeypatch.setenv("SBL_TEST_GALIGN_W0", str(w0))
-        got, st = random_batch.run()
-        random_batch.check(got)
+        got, st = random_batch.run(0)
+        random_batch.check(got, random_batch.want(0, linear=True))
         passes[w0] = st["passes"]
     assert passes[1] > passes[8] > passes[64] >= 200, passes      # doubling ran
 
@@ -186,7 +117,7 @@ def tiny_pairs():
 def test_a_batch_of_tiny_pairs():
     pairs, revs = tiny_pairs()
     bt = Batch(pairs, revs)
-    want = bt.want()
+    want = bt.want(0, linear=True)
     lens = [2 * len(rows[0]) for _, _, rows in want]
     assert len(pairs) == 300 and max(max(len(a), len(b)) for a, b in pairs) <= 12
     assert {(b"", b""), } <= set(pairs) and any(a and not b for a, b in pairs) and any(b and not a for a, b in pairs)
@@ -194,8 +125,8 @@ def test_a_batch_of_tiny_pairs():
     assert lens[21] == lens[23] == 0 and sum(lens[20:25]) < 16               # one lane's 16 bytes: five groups, two of them without text
     assert any(all(0 < x < 16 for x in lens[k:k + 3]) for k in range(298))
     assert sum(lens) % 16 != 0 and lens[-1] > 0                               # the last pair ends off a 16-byte boundary
-    got, st = bt.run()
-    bt.check(got)
+    got, st = bt.run(0)
+    bt.check(got, bt.want(0, linear=True))
     assert st["pairs"] == 300 and st["skipped"] == 0
 
 
@@ -207,8 +138,8 @@ def test_wide_bands():
     c = a[:500] + rand(rng, 300) + a[500:2500] + a[2800:]     # equal lengths, the middle 300 off the main diagonal: w doubles up to 512
     u, v = b"A" * 2200, b"C" * 2200                           # nothing matches: -165000 clears U(w) = 55000 - 175 (w + 1) only at w = 2048 (4097 offsets)
     bt = Batch([(a, b), (b, a), (a, c), (u, v)])
-    got, st = bt.run()
-    bt.check(got)
+    got, st = bt.run(0)
+    bt.check(got, bt.want(0, linear=True))
     assert sum(n for op, n in got[0].runs if op == "D") == 500 and got[0].score == 3000 * 25 - 500 * 75
     assert got[2].passes == 4 and got[2].band_w == 512, (got[2].passes, got[2].band_w)
     assert got[3].band_w == 2048 and got[3].passes == 6 and got[3].runs == [("X", 2200)], (got[3].passes, got[3].band_w)
@@ -225,15 +156,15 @@ def test_the_per_alignment_cap_skips_long_pairs_only(monkeypatch):
             long_ones.add(k)
     bt = Batch(pairs)
     monkeypatch.setenv("SBL_TEST_GALIGN_CAP_KB", "4")
-    got, st = bt.run()
-    bt.check(got, skipped=long_ones)
+    got, st = bt.run(0)
+    bt.check(got, bt.want(0, linear=True), skipped=long_ones)
     assert st["skipped"] == len(long_ones) == 6
     monkeypatch.delenv("SBL_TEST_GALIGN_CAP_KB")
     monkeypatch.setenv("SBL_TEST_GALIGN_TOTAL_KB", "64")         # a small total cap: several launches, the same results
-    split, st2 = bt.run()
+    split, st2 = bt.run(0)
     monkeypatch.delenv("SBL_TEST_GALIGN_TOTAL_KB")
-    single, st1 = bt.run()
-    bt.check(single)
+    single, st1 = bt.run(0)
+    bt.check(single, bt.want(0, linear=True))
     assert st2["launches"] > st1["launches"] and st2["skipped"] == st1["skipped"] == 0
     for x, y in zip(split, single):
         assert (x.status, x.score, x.runs, x.row_a, x.row_b) == (y.status, y.score, y.runs, y.row_a, y.row_b)

@@ -1,5 +1,6 @@
-"""The alignment with a gap opening cost (sbl_align_set_gap_open, k_block_align3 of csrc/block_align.hip, --gapopen)
-against the numpy model tests/gapopen_model.py: status, score, runs and the device-spelled rows must equal the UNBANDED model."""
+"""The alignment with a gap opening cost (sbl_align_set_gap_open, the affine model of k_block_align in csrc/block_align.hip, --gapopen;
+DESIGN.md 0.5) against the numpy model tests/gapopen_model.py: status, score, runs and the device-spelled rows must equal the UNBANDED
+model."""
 import os
 import sys
 
@@ -10,85 +11,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import galign_model as GM                          # noqa: E402
 import gapopen_model as AM                         # noqa: E402
+from galign_cases import Batch, mutated, rand, rc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 PAIR_A = b"CACTGGAGACACACCGAGTGGATAGTCCTATCCCATGAGC"
 PAIR_B = b"CACTGGAGACACATCGTCCTATCCCATGAGC"
 PAIR_RUNS = [("=", 13), ("X", 1), ("=", 2), ("I", 9), ("=", 15)]
-
-_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
-
-
-def rc(s):
-    return s.translate(_COMPLEMENT)[::-1]
-
-
-def rand(rng, n, alphabet=b"ACGT"):
-    return bytes(rng.choice(np.frombuffer(alphabet, dtype=np.uint8), n))
-
-
-def mutated(rng, a, rate=0.03, max_indel=12):
-    b = bytearray()
-    i = 0
-    while i < len(a):
-        u = rng.random()
-        if u < rate / 3:
-            i += int(rng.integers(1, max_indel + 1))
-        elif u < 2 * rate / 3:
-            b += rand(rng, int(rng.integers(1, max_indel + 1)))
-        else:
-            b += rand(rng, 1) if rng.random() < rate else a[i:i + 1]
-            i += 1
-    return bytes(b)
-
-
-class Batch:
-    """pairs of strings laid out as ranges of two records (all a's, all b's); a reverse range holds the reverse complement, so that the
-    strings the kernel reads are the ones given.  The model's results are computed once per opening cost and kept."""
-
-    def __init__(self, pairs, revs=None):
-        self.pairs = [(bytes(a), bytes(b)) for a, b in pairs]
-        self.revs = revs or [(False, False)] * len(pairs)
-        ra, rb, self.desc = bytearray(b"G"), bytearray(b"T"), []
-        for (a, b), (va, vb) in zip(self.pairs, self.revs):
-            self.desc.append((0, len(ra), len(ra) + len(a), va, 1, len(rb), len(rb) + len(b), vb))
-            ra += rc(a) if va else a
-            rb += rc(b) if vb else b
-        self.records = [bytes(ra) + b"C", bytes(rb) + b"A"]
-        self._want = {}
-
-    def want(self, o, linear=False):
-        key = "linear" if linear else o
-        if key not in self._want:
-            out = []
-            for a, b in self.pairs:
-                score, steps = GM.align(a, b) if linear else AM.align(a, b, o)
-                out.append((score, GM.runs(a, b, steps), GM.rows(a, b, steps)))
-            self._want[key] = out
-        return self._want[key]
-
-    def run(self, o):
-        from sibelia_amd import BlockFinder
-        bf = BlockFinder(self.records, device=0)
-        try:
-            bf.set_gap_open(o)
-            assert bf.gap_open == o
-            return bf.align_pairs(self.desc), bf.align_stats()
-        finally:
-            bf.close()
-
-    def check(self, got, want, skipped=()):
-        assert len(got) == len(self.pairs)
-        for k, (g, (score, runs, rows)) in enumerate(zip(got, want)):
-            a, b = self.pairs[k]
-            if k in skipped:
-                assert (g.status, g.score, g.runs, g.row_a, g.row_b) == (1, None, [], b"", b""), k
-                continue
-            assert g.status == 0, (k, len(a), len(b))
-            assert g.score == score, (k, len(a), len(b), a[:60], b[:60])
-            assert g.runs == runs, (k, len(a), len(b), a[:60], b[:60])
-            assert (g.row_a, g.row_b) == rows, (k, len(a), len(b))
 
 
 def edge_pairs():
@@ -140,14 +69,23 @@ def test_edge_shapes(edges, o):
     assert got[n - 7].runs == [("=", 33), ("D", 57)] and got[n - 6].runs == [("=", 33), ("I", 57)]
 
 
-def test_every_launch_class():
-    """one wave in registers (129 offsets), 256 lanes over LDS (629), 640 lanes over LDS (4097)"""
+def launch_class_pairs():
+    """one wave in registers (129 offsets), 256 lanes over LDS (629), the widest class (4097: 640 lanes, 1024 without an opening cost)"""
     rng = np.random.default_rng(45)
     s = rand(rng, 400)
     a = rand(rng, 3000)
     b = a[:1400] + rand(rng, 500) + a[1400:]
     u, v = b"A" * 2200, b"C" * 2200              # nothing matches: -165000 clears U(w) = 55000 - 175 (w + 1) only at w = 2048
-    bt = Batch([(s, mutated(rng, s)), (a, b), (u, v)])
+    return [(s, mutated(rng, s)), (a, b), (u, v)]
+
+
+@pytest.fixture(scope="module")
+def launch_classes():
+    return Batch(launch_class_pairs())
+
+
+def test_every_launch_class(launch_classes):
+    bt = launch_classes
     got, st = bt.run(300)
     bt.check(got, bt.want(300))
     assert got[0].band_w == 64 and got[0].passes == 1
@@ -181,6 +119,22 @@ def test_no_opening_cost_through_the_new_kernel_is_the_linear_alignment(edges, r
     random_batch.check(got_old, random_batch.want(0, linear=True))
     assert [(g.score, g.runs, g.band_w, g.passes) for g in got] == [(g.score, g.runs, g.band_w, g.passes) for g in got_old]
     assert (st["passes"], st["cells"]) == (st_old["passes"], st_old["cells"])
+
+
+def test_no_opening_cost_is_the_linear_alignment_in_every_launch_class(launch_classes, monkeypatch):
+    """o = 0 through the affine model against the linear one beyond the register class: both over LDS with 256 lanes (629 offsets) and
+    in the widest class of either (4097 offsets: 640 lanes against 1024)"""
+    bt = launch_classes
+    want = bt.want(0, linear=True)
+    monkeypatch.setenv("SBL_TEST_GALIGN_AFFINE", "1")
+    affine, _ = bt.run(0)
+    monkeypatch.delenv("SBL_TEST_GALIGN_AFFINE")
+    linear, _ = bt.run(0)
+    for got in (affine, linear):
+        bt.check(got, want)
+        assert got[2].band_w == 2048 and got[2].passes == 6, (got[2].passes, got[2].band_w)
+    assert [(g.score, g.runs, g.band_w, g.passes) for g in affine] == [(g.score, g.runs, g.band_w, g.passes) for g in linear]
+    assert [(g.row_a, g.row_b) for g in affine] == [(g.row_a, g.row_b) for g in linear]
 
 
 def test_the_band_limit_with_an_opening_cost():

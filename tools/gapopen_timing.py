@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Times the alignment of the unique blocks with and without a gap opening cost (--gapopen; k_block_align3 against k_block_align of
-csrc/block_align.hip) on the Staphylococcus aureus case of tools/block_align_timing.py: the pipeline runs up to the
-corrected block list once; then sbl_align_unique_blocks runs RUNS + 1 times on that list (the first is a warm-up) at o = 0 and again at
-o = 300, in one process.  Kernel times are the library's own counters (sbl_align_stats: event pairs), medians; the bytes of trace codes
+"""Times the alignment of the unique blocks with and without a gap opening cost (--gapopen; the affine against the linear model of
+k_block_align in csrc/block_align.hip) on the Staphylococcus aureus case of tools/block_align_timing.py: the pipeline
+runs up to the corrected block list once; then sbl_align_unique_blocks runs RUNS + 1 times on that list (the first is a warm-up) at
+o = 0 and again at o = 300, in one process.  Kernel times are the library's own counters (sbl_align_stats: event pairs), medians; the bytes of trace codes
 are computed from the band every pair ended at and the passes it took.  Writes one JSON document (default:
 profiles/gapopen_timing.json)."""
 import json
