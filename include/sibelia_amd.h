@@ -147,6 +147,29 @@ typedef struct { int32_t id; uint32_t chr; uint64_t start, end; } sbl_block;
 sbl_status sbl_generate_blocks(sbl_ctx *ctx, uint32_t k, uint32_t trim_k, uint32_t min_size, int shared_only,
                                const sbl_block **blocks, uint64_t *n);
 
+/* Which way the candidate blocks of the last sbl_generate_blocks were indexed at trim_k (csrc/synteny.hip): by the small-block
+ * kernel -- speculated for a whole chunk of groups in one batch launch, or one block in one launch after a speculation miss and on
+ * every further trim iteration -- or by the general child index (gather + the full enumeration).  A block goes to the small-block
+ * kernel when it has at most 1024 elements (bases + sequences + 1) in at most 16 sequences and trim_k <= 32; the kernel declines a
+ * block that holds a character other than A, C, G, T, which then takes the general path.  Host counters only: they cost no device
+ * work and change no result.  With SBL_NO_TINY_INDEX set every small-block counter stays 0. */
+typedef struct {
+	uint64_t groups_resolved;        /* groups of at least 2 edges with one on the positive strand: those that reach ResolveOverlap */
+	uint64_t batch_launches;         /* launches of the batched small-block kernel (one per chunk of groups that queued an index) */
+	uint64_t batch_indices;          /* indices queued in those launches */
+	uint64_t speculated_used;        /* queued indices that were used: the candidate block came out as speculated and was indexed */
+	uint64_t single_launches;        /* launches of the one-block small-block kernel */
+	uint64_t batch_declines;         /* queued indices that were consulted and had declined (each is then tried once more by a single launch) */
+	uint64_t single_declines;        /* one-block launches that declined */
+	uint64_t general_indices;        /* general child indices */
+	uint64_t tiny_max_elements;      /* largest block indexed by the small-block kernel (declined ones excluded): elements ... */
+	uint64_t tiny_max_records;       /* ... and sequences (each the maximum over those blocks) */
+	uint64_t general_max_elements;   /* the same over the blocks that took the general child index */
+	uint64_t general_max_records;
+	uint64_t tiny_max_keys;          /* largest bifurcation count (both orientations) a small-block index reported */
+} sbl_synteny_stats_t;
+sbl_status sbl_synteny_stats(const sbl_ctx *ctx, sbl_synteny_stats_t *out);
+
 /* what the reference's main runs after GenerateSyntenyBlocks (src/sibelia.cpp:287-315) on the blocks of the last
  * sbl_generate_blocks: Postprocessor::GlueStripes (src/postprocessor.cpp:37-154; skipped when glue == 0) and the texts of
  * blocks_coords.txt (OutputGenerator::ListBlocksIndices, src/outputgenerator.cpp:227-233), genomes_permutations.txt

@@ -18,6 +18,7 @@ SRC = os.path.join(HERE, "sibelia_oracle.c")
 
 BLOCK_DTYPE = np.dtype([("id", "<i4"), ("chr", "<u4"), ("start", "<u8"), ("end", "<u8")])
 INST_DTYPE = np.dtype([("id", "<u4"), ("chr", "<u4"), ("pos", "<u4")])
+TRIM_DTYPE = np.dtype([("group", "<u4"), ("iteration", "<u4"), ("records", "<u4"), ("ambiguous", "<u4"), ("elements", "<u8")])
 EDGE_DTYPE = np.dtype([("chr", "<u4"), ("strand", "<u4"), ("start_vertex", "<u4"), ("end_vertex", "<u4"),
                        ("pos", "<u4"), ("len", "<u4"), ("orig_pos", "<u4"), ("orig_len", "<u4"),
                        ("first_char", "S1"), ("_pad", "V3")])
@@ -58,6 +59,7 @@ def lib():
         L.orc_list_edges.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.orc_generate_blocks.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.orc_trim_trace.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.orc_postprocess.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.orc_serialize_graph.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -152,6 +154,12 @@ class Oracle:
         a = _view(v.value, m.value, BLOCK_DTYPE)
         self.L.orc_free(v)
         return a
+
+    def trim_trace(self) -> np.ndarray:
+        """Every TrimBlocks call of the last generate_blocks, in order (test hook, see sibelia_oracle.h)."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self.L.orc_trim_trace(C.byref(p), C.byref(n))
+        return _view(p.value, n.value, TRIM_DTYPE)
 
     def postprocess(self, blocks: np.ndarray, names: Sequence[str], glue: bool = True):
         """GlueStripes + the three writers: (blocks, [blocks_coords.txt, genomes_permutations.txt, coverage_report.txt])."""

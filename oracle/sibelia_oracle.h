@@ -83,6 +83,11 @@ int orc_serialize_graph(orc_ctx *c, uint32_t k, char **out, uint64_t *n);
 /* test hooks */
 void orc_force_long_k_path(orc_ctx *c, int on);      /* use the rank-doubling grouping even for k <= 32 */
 uint32_t orc_rand(orc_ctx *c);                       /* next value of the ctx's glibc rand() stream   */
+/* every TrimBlocks call of the last orc_generate_blocks (of any ctx; not thread safe), in order: the group it belongs to (index among
+ * the resolved groups), which iteration of `while (TrimBlocks(...))` it is (1 = first), the block it indexed as sequences and elements
+ * (bases + sequences + 1), and whether the block holds a byte other than ACGT.  Owned by the library until the next call. */
+typedef struct { uint32_t group, iteration, records, ambiguous; uint64_t elements; } orc_trim_call;
+void orc_trim_trace(const orc_trim_call **calls, uint64_t *n);
 /* Boost 1.54 unordered_map<size_t,...> iteration order for a key insertion sequence (test hook). */
 size_t orc_boost_order(const uint64_t *keys, size_t n, uint64_t *out);
 

@@ -73,6 +73,9 @@ struct Ctx {
 	std::vector<std::string> original;          /* originalChrList_ sequences */
 };
 
+std::vector<orc_trim_call> trimTrace;          /* test hook: the TrimBlocks calls of the last orc_generate_blocks */
+uint32_t trimGroup = 0, trimIteration = 0;
+
 /* TrimBlocks, src/synteny.cpp:31-122.  The IndexedSequence over the block sequences is a child oracle context that shares
  * the parent's rand() stream (sanitising the copy consumes it, src/indexedsequence.cpp:31-37). */
 bool TrimBlocks(Ctx &cx, std::vector<Edge> &block, size_t trimK, size_t minSize)
@@ -81,6 +84,14 @@ bool TrimBlocks(Ctx &cx, std::vector<Edge> &block, size_t trimK, size_t minSize)
 	std::vector<std::string> blockSeq(block.size());
 	for (size_t i = 0; i < block.size(); i++)
 		blockSeq[i] = cx.original[block[i].chr].substr(block[i].originalPosition, block[i].originalLength);
+	{	/* test hook (orc_trim_trace): what this call indexes */
+		orc_trim_call t = { trimGroup, ++trimIteration, (uint32_t)block.size(), 0u, 1 };
+		for (size_t i = 0; i < blockSeq.size(); i++) {
+			t.elements += blockSeq[i].size() + 1;
+			if (blockSeq[i].find_first_not_of("ACGT") != std::string::npos) t.ambiguous = 1;
+		}
+		trimTrace.push_back(t);
+	}
 	const size_t oo = UINT32_MAX;
 	/* IndexedSequence iseq(blockSeq, trimK, ""): enumeration of a fresh index */
 	orc_ctx *child = orc_create();
@@ -157,6 +168,11 @@ bool TrimBlocks(Ctx &cx, std::vector<Edge> &block, size_t trimK, size_t minSize)
 
 }  // namespace
 
+extern "C" void orc_trim_trace(const orc_trim_call **calls, uint64_t *n)
+{
+	*calls = trimTrace.data(); *n = trimTrace.size();
+}
+
 /* GenerateSyntenyBlocks, src/synteny.cpp:229-286.  orig_seq / orig_len: the FASTA records the BlockFinder was built from
  * (originalChrList_).  out (malloc'd, orc_free): per BlockInstance i32 signed id, u32 chr, u64 start, u64 end = 24 bytes. */
 extern "C" int orc_generate_blocks(orc_ctx *c, const uint8_t *const *orig_seq, const uint64_t *orig_len, uint32_t k, uint32_t trimK, uint32_t minSize,
@@ -177,6 +193,7 @@ extern "C" int orc_generate_blocks(orc_ctx *c, const uint8_t *const *orig_seq, c
 	}
 	std::vector<orc_block> block;
 	int blockCount = 1;
+	trimTrace.clear(); trimGroup = 0;
 	edge.erase(std::remove_if(edge.begin(), edge.end(), [&](const Edge &a) { return a.originalLength < minSize; }), edge.end());      /* EdgeEmpty */
 	std::vector<std::pair<size_t, size_t> > group;
 	std::sort(edge.begin(), edge.end(), CompareEdgesNaturally);                                                                      /* GroupBy, src/common.h:150-160 */
@@ -193,7 +210,9 @@ extern "C" int orc_generate_blocks(orc_ctx *c, const uint8_t *const *orig_seq, c
 		std::vector<Edge> nowBlock;
 		std::vector<size_t> occur(nchr, 0);
 		ResolveOverlap(firstEdge, lastEdge, minSize, overlap, nowBlock);
+		trimIteration = 0;
 		while (TrimBlocks(cx, nowBlock, trimK, minSize));
+		trimGroup++;
 		for (size_t i = 0; i < nowBlock.size(); i++) occur[nowBlock[i].chr]++;
 		if (nowBlock.size() > 1 && (!sharedOnly || (size_t)std::count(occur.begin(), occur.end(), (size_t)1) == nchr)) {
 			for (size_t i = 0; i < nowBlock.size(); i++) {

@@ -23,7 +23,7 @@ PROGRESS_FN = C.CFUNCTYPE(None, C.c_size_t, C.c_int, C.c_void_p)
 
 EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simplify_stage", "sbl_get_state", "sbl_nchr",
            "sbl_list_edges", "sbl_last_stats", "sbl_last_error", "sbl_strerror", "sbl_set_window",
-           "sbl_save_state", "sbl_restore_state", "sbl_load_fasta", "sbl_record_name", "sbl_kmer_hashes", "sbl_generate_blocks", "sbl_postprocess", "sbl_serialize_graph",
+           "sbl_save_state", "sbl_restore_state", "sbl_load_fasta", "sbl_record_name", "sbl_kmer_hashes", "sbl_generate_blocks", "sbl_synteny_stats", "sbl_postprocess", "sbl_serialize_graph",
            "sbl_set_tempfile_mode", "sbl_rand_advance", "sbl_shard_layout", "sbl_shard_exchange_plan", "sbl_glue_stripes", "sbl_comm_unique_id", "sbl_comm_attach_rccl", "sbl_comm_attach_local", "sbl_comm_detach",
            "sbl_longk_slices", "sbl_longk_value_bounds", "sbl_longk_owner", "sbl_longk_halo_plan",
            "sbl_blocks_sequences", "sbl_blocks_sequences_times", "sbl_blocks_gff", "sbl_blocks_coords",
@@ -55,6 +55,12 @@ class StageStats(C.Structure):
 class CorrectStats(C.Structure):
     _fields_ = [("groups", C.c_uint64), ("alignments", C.c_uint64), ("levels", C.c_uint64), ("launches", C.c_uint64), ("cells", C.c_uint64),
                 ("kernel_ms", C.c_double)]
+
+
+class SyntenyStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("groups_resolved", "batch_launches", "batch_indices", "speculated_used", "single_launches",
+                                          "batch_declines", "single_declines", "general_indices", "tiny_max_elements", "tiny_max_records",
+                                          "general_max_elements", "general_max_records", "tiny_max_keys")]
 
 
 class AlignDesc(C.Structure):
@@ -162,6 +168,7 @@ def load_library():
         L.sbl_record_size.argtypes = [C.c_void_p, C.c_uint32]
         L.sbl_record_size.restype = C.c_uint64
         L.sbl_generate_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_synteny_stats.argtypes = [C.c_void_p, C.POINTER(SyntenyStats)]
         L.sbl_postprocess.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         L.sbl_serialize_graph.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -309,6 +316,13 @@ class BlockFinder:
         return _view(b.value, n.value, formats.BLOCK_DTYPE)
 
     generate_blocks = GenerateSyntenyBlocks
+
+    def synteny_stats(self) -> dict:
+        """Path counters of the last GenerateSyntenyBlocks (sbl_synteny_stats_t, include/sibelia_amd.h): how many candidate blocks the
+        small-block kernel indexed (batched / single), how many it declined, how many took the general child index, and the largest of each."""
+        s = SyntenyStats()
+        self._check(self.L.sbl_synteny_stats(self.h, C.byref(s)), "sbl_synteny_stats")
+        return {f: int(getattr(s, f)) for f, _ in s._fields_}
 
     def _names_array(self, what: str, names: Optional[Sequence[str]]):
         """`names` as the `const char *const *` of the C entry points, which read one name per loaded record (include/sibelia_amd.h);

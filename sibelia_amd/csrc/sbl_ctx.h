@@ -30,6 +30,7 @@ struct sbl_ctx {
 	std::vector<uint32_t> orig_sepidx;
 	sbl_ctx *child = nullptr;            // index over block sequences (TrimBlocks), same device
 	void *tiny_out = nullptr;            // mapped host buffer of the small-block index (synteny.hip), hipHostFree'd with the context
+	sbl_synteny_stats_t synteny_stats{}; // path counters of the last sbl_generate_blocks
 
 	// stage-boundary checkpoint (sbl_save_state / sbl_restore_state)
 	DevBuf d_save_ch, d_save_op;

@@ -197,6 +197,7 @@ inline bool natural_less(const BEdge &a, const BEdge &b)      // CompareEdgesNat
 struct Synteny {
 	sbl_ctx *c;
 	sbl_ctx *child;
+	sbl_synteny_stats_t *st;                      // path counters of this call (sbl_synteny_stats): host increments only
 	uint32_t trimK, minSize;
 	std::vector<std::vector<uint8_t>> occupied;   // overlap[chr][original position] (POS_FREE / POS_OCCUPIED)
 	std::vector<std::vector<uint8_t>> local;      // localOverlap of the group being resolved, cleared through `undo`
@@ -232,6 +233,11 @@ struct Synteny {
 	// small blocks: one workgroup, one launch, result in mapped host memory (k_tiny_enumerate); false = not applicable, take the general path
 	TinyOut *tiny_out = nullptr, *tiny_out_dev = nullptr;
 	std::vector<sbl_inst> tiny_neg;
+	void count_tiny(uint64_t elements, uint64_t records, uint64_t keys)
+	{
+		st->tiny_max_elements = std::max(st->tiny_max_elements, elements); st->tiny_max_records = std::max(st->tiny_max_records, records);
+		st->tiny_max_keys = std::max(st->tiny_max_keys, keys);
+	}
 	bool tiny_index(const std::vector<BEdge> &block, uint64_t L, uint32_t *bif_count, const sbl_inst **inst, uint64_t *ninst)
 	{
 		const uint32_t nrec = (uint32_t)block.size();
@@ -246,9 +252,11 @@ struct Synteny {
 		k_tiny_enumerate<<<1, TE_THREADS, 0, c->stream>>>(c->d_orig_ch.as<uint8_t>(), d, tiny_out_dev);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (tiny_out->status == 1) return false;                   // a non-ACGT character: the general path draws rand() for it
+		st->single_launches++;
+		if (tiny_out->status == 1) { st->single_declines++; return false; }      // a non-ACGT character: the general path draws rand() for it
 		SBL_CHECK(tiny_out->status == 0, SBL_ERR_INTERNAL, "small-block index did not report");
 		const unsigned head[4] = { 0u, tiny_out->bif_count, tiny_out->n[0], 0u };
+		count_tiny(L + nrec + 1, nrec, head[1]);
 		tiny_result(head, tiny_out->inst[0], tiny_out->inst[1], bif_count, inst, ninst);
 		return true;
 	}
@@ -294,6 +302,7 @@ struct Synteny {
 		HIP_TRY(hipMemcpyAsync(bheads.data(), d_bheads.p, nb * 16, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpyAsync(bpool.data(), d_bpool.p, words * 4, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
+		st->batch_launches++; st->batch_indices += nb;
 	}
 	// the negative list is reported per sequence in descending element order (sbl_enumerate: each chromosome's run reversed)
 	void tiny_result(const unsigned *head, const unsigned *inst0, const unsigned *inst1, uint32_t *bif_count, const sbl_inst **inst, uint64_t *ninst)
@@ -321,11 +330,19 @@ struct Synteny {
 		if (pre_head) {                                          // speculated with the rest of its chunk, and the speculation held
 			const unsigned *h = pre_head, *i0 = pre_inst; const unsigned cap = pre_cap;
 			pre_head = nullptr;
-			if (h[0] == 0) { tiny_result(h, i0, i0 + 3ull * cap, bif_count, inst, ninst); return; }
+			if (h[0] == 0) {
+				st->speculated_used++;
+				count_tiny(L + nrec + 1, nrec, h[1]);
+				tiny_result(h, i0, i0 + 3ull * cap, bif_count, inst, ninst);
+				return;
+			}
+			st->batch_declines++;
 			// (status 1: a non-ACGT character -- the general path below draws rand() for it, now, in the reference's order)
 		}
 		if (tiny_index(block, L, bif_count, inst, ninst)) return;
 		const size_t E = (size_t)L + nrec + 1, Epad = (E + 31) / 32 * 32 + 64;
+		st->general_indices++;
+		st->general_max_elements = std::max<uint64_t>(st->general_max_elements, E); st->general_max_records = std::max<uint64_t>(st->general_max_records, nrec);
 		hipStream_t s = child->stream;
 		child->d_ch.ensure(Epad);
 		HIP_TRY(hipMemsetAsync(child->d_ch.p, '$', Epad, s));
@@ -435,6 +452,7 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 	return guarded(c, [&] {
 		SBL_CHECK(k >= 2 && trim_k >= 2, SBL_ERR_BAD_ARG, "vertex sizes must be at least 2");
 		SBL_CHECK(c->d_orig_ch.p && c->orig_sepidx.size() == (size_t)c->nchr + 1, SBL_ERR_BAD_ARG, "no original records (load first)");
+		c->synteny_stats = sbl_synteny_stats_t{};
 		// ---- ListEdges of a fresh index at k (serialization.cpp:56-86) on the GPU
 		const sbl_edge *ge = nullptr; uint64_t ne = 0;
 		sbl_status st = sbl_list_edges(c, k, &ge, &ne);
@@ -448,7 +466,7 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 			edge.push_back(e);
 		}
 		Synteny sy;
-		sy.c = c; sy.trimK = trim_k; sy.minSize = min_size;
+		sy.c = c; sy.st = &c->synteny_stats; sy.trimK = trim_k; sy.minSize = min_size;
 		if (!c->child) {
 			sbl_status cs = sbl_create(&c->child, c->device);
 			if (cs != SBL_OK) throw SblError{cs, "cannot create the trim context"};
@@ -510,6 +528,7 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 				sy.batch_run();
 			}
 			if (last - first < 2 || first->dir != 0) continue;          // fewer than two edges, or none on the positive strand (sorted: it would be first)
+			sy.st->groups_resolved++;
 			sy.resolve_overlap(first, last, now);
 			{
 				const Spec &sp = spec[gi % CHUNK];
@@ -538,4 +557,11 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 		if (blocks) *blocks = c->blocks.data();
 		if (n) *n = c->blocks.size();
 	});
+}
+
+extern "C" sbl_status sbl_synteny_stats(const sbl_ctx *c, sbl_synteny_stats_t *out)
+{
+	if (!c || !out) return SBL_ERR_BAD_ARG;
+	*out = c->synteny_stats;
+	return SBL_OK;
 }

@@ -22,6 +22,24 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "missing export " + name
 
 
+def test_synteny_stats_layout_matches_the_header():
+    # sbl_synteny_stats_t (path counters of sbl_generate_blocks): the ctypes mirror has the header's fields in the header's order, all
+    # 64-bit; the entry point is exported, listed, and refuses a missing context instead of writing
+    import __graft_entry__ as g
+    g.build()
+    from sibelia_amd import api
+    hdr = open(os.path.join(ROOT, "include", "sibelia_amd.h")).read()
+    body = re.search(r"typedef struct \{([^}]*)\} sbl_synteny_stats_t;", hdr).group(1)
+    fields = re.findall(r"uint64_t\s+(\w+);", body)
+    assert len(fields) == 13 and fields == [f for f, _ in api.SyntenyStats._fields_]
+    assert ctypes.sizeof(api.SyntenyStats) == 8 * len(fields)
+    assert "sbl_synteny_stats" in api.EXPORTS
+    lib = api.load_library()
+    out = api.SyntenyStats()
+    assert lib.sbl_synteny_stats(None, ctypes.byref(out)) != 0
+    assert hasattr(api.BlockFinder, "synteny_stats")
+
+
 def test_no_host_compute_path_without_a_gpu():
     import torch
     if torch.cuda.is_available():
