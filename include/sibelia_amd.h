@@ -170,6 +170,29 @@ typedef struct {
 } sbl_synteny_stats_t;
 sbl_status sbl_synteny_stats(const sbl_ctx *ctx, sbl_synteny_stats_t *out);
 
+/* TEST ENTRY POINT: the small-block index on its own -- for every candidate block given, the index at trim_k that
+ * sbl_generate_blocks' TrimBlocks would read, built by the same host code and the same kernels (csrc/synteny.hip: batched != 0 queues
+ * every eligible block and runs ONE launch of the batched kernel; batched == 0 runs one launch of the one-block kernel per eligible
+ * block).  Block b is ranges[block_first[b], block_first[b + 1]) (nblocks + 1 ascending offsets, the first one 0); a range is bases
+ * [start, end) of ORIGINAL record chr, whatever stages have run since the load.
+ * sbl_tiny_result: status SBL_TINY_INDEXED -- bif_count and the instance lists pos[first_pos, first_pos + npos) and
+ * neg[first_neg, first_neg + nneg) are those of sbl_enumerate(trim_k) on the block's sequences as records 0, 1, ..., the negative list
+ * with each sequence's run in descending element order like sbl_enumerate's; SBL_TINY_DECLINED -- the kernel met a byte other than
+ * A, C, G, T (sbl_generate_blocks then takes the general child index); SBL_TINY_NOT_ELIGIBLE -- no range, more than 16 ranges, more
+ * than 1024 elements (bases + ranges + 1) or trim_k > 32: nothing was launched for it.  The last two carry no count and no instances.
+ * Every argument is checked on the host before anything is launched.  SBL_ERR_BAD_ARG: trim_k < 2, no records loaded, offsets that do
+ * not start at 0 or descend, chr >= sbl_nchr(ctx), an empty range, a range beyond its record.
+ * Draws nothing from the rand() stream and leaves the context's block list and the counters of sbl_synteny_stats as they are.
+ * SBL_NO_TINY_INDEX is IGNORED here: the call exists to run the small-block index.  Everything returned is copied into arrays owned
+ * by the ctx, valid until the next sbl_tiny_index. */
+#define SBL_TINY_INDEXED 0
+#define SBL_TINY_DECLINED 1
+#define SBL_TINY_NOT_ELIGIBLE 2
+typedef struct { uint32_t chr, pad_; uint64_t start, end; } sbl_tiny_range;
+typedef struct { uint32_t status, bif_count; uint64_t first_pos, npos, first_neg, nneg; } sbl_tiny_result;
+sbl_status sbl_tiny_index(sbl_ctx *ctx, uint64_t nblocks, const uint64_t *block_first, const sbl_tiny_range *ranges, uint32_t trim_k,
+                          int batched, const sbl_tiny_result **res, const sbl_inst **pos, const sbl_inst **neg);
+
 /* what the reference's main runs after GenerateSyntenyBlocks (src/sibelia.cpp:287-315) on the blocks of the last
  * sbl_generate_blocks: Postprocessor::GlueStripes (src/postprocessor.cpp:37-154; skipped when glue == 0) and the texts of
  * blocks_coords.txt (OutputGenerator::ListBlocksIndices, src/outputgenerator.cpp:227-233), genomes_permutations.txt

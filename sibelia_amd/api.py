@@ -30,7 +30,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
-           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times"]
+           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_tiny_index"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -61,6 +61,18 @@ class SyntenyStats(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("groups_resolved", "batch_launches", "batch_indices", "speculated_used", "single_launches",
                                           "batch_declines", "single_declines", "general_indices", "tiny_max_elements", "tiny_max_records",
                                           "general_max_elements", "general_max_records", "tiny_max_keys")]
+
+
+TINY_INDEXED, TINY_DECLINED, TINY_NOT_ELIGIBLE = 0, 1, 2      # SBL_TINY_*
+
+
+class TinyRange(C.Structure):
+    _fields_ = [("chr", C.c_uint32), ("pad_", C.c_uint32), ("start", C.c_uint64), ("end", C.c_uint64)]
+
+
+class TinyResult(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("bif_count", C.c_uint32), ("first_pos", C.c_uint64), ("npos", C.c_uint64),
+                ("first_neg", C.c_uint64), ("nneg", C.c_uint64)]
 
 
 class AlignDesc(C.Structure):
@@ -169,6 +181,8 @@ def load_library():
         L.sbl_record_size.restype = C.c_uint64
         L.sbl_generate_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_synteny_stats.argtypes = [C.c_void_p, C.POINTER(SyntenyStats)]
+        L.sbl_tiny_index.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(TinyRange), C.c_uint32, C.c_int,
+                                     C.POINTER(C.POINTER(TinyResult)), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sbl_postprocess.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
         L.sbl_serialize_graph.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
@@ -323,6 +337,29 @@ class BlockFinder:
         s = SyntenyStats()
         self._check(self.L.sbl_synteny_stats(self.h, C.byref(s)), "sbl_synteny_stats")
         return {f: int(getattr(s, f)) for f, _ in s._fields_}
+
+    def tiny_index(self, blocks: Sequence[Sequence[Tuple[int, int, int]]], k: int, batched: bool):
+        """TEST ENTRY POINT (sbl_tiny_index, include/sibelia_amd.h): the small-block index at k of every candidate block -- a list of
+        (chr, start, end) ranges of the ORIGINAL records -- as GenerateSyntenyBlocks' TrimBlocks reads it; batched: all eligible blocks in
+        one launch of the batched kernel, else one launch of the one-block kernel each.  -> per block (status, bif_count, pos, neg) with
+        status TINY_INDEXED / TINY_DECLINED / TINY_NOT_ELIGIBLE and INST_DTYPE arrays (count 0 and empty arrays unless indexed)."""
+        first = [0]
+        for b in blocks:
+            first.append(first[-1] + len(b))
+        flat = [r for b in blocks for r in b]
+        ranges = (TinyRange * max(1, len(flat)))()
+        for d, (c, s, e) in zip(ranges, flat):
+            d.chr, d.start, d.end = int(c), int(s), int(e)
+        res, pos, neg = C.POINTER(TinyResult)(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.sbl_tiny_index(self.h, len(blocks), (C.c_uint64 * len(first))(*first), ranges, k, int(bool(batched)),
+                                          C.byref(res), C.byref(pos), C.byref(neg)), "sbl_tiny_index")
+        out = []
+        for i in range(len(blocks)):
+            r = res[i]
+            p = _view((pos.value or 0) + r.first_pos * INST_DTYPE.itemsize, r.npos, INST_DTYPE)
+            q = _view((neg.value or 0) + r.first_neg * INST_DTYPE.itemsize, r.nneg, INST_DTYPE)
+            out.append((int(r.status), int(r.bif_count), p, q))
+        return out
 
     def _names_array(self, what: str, names: Optional[Sequence[str]]):
         """`names` as the `const char *const *` of the C entry points, which read one name per loaded record (include/sibelia_amd.h);

@@ -31,6 +31,8 @@ struct sbl_ctx {
 	sbl_ctx *child = nullptr;            // index over block sequences (TrimBlocks), same device
 	void *tiny_out = nullptr;            // mapped host buffer of the small-block index (synteny.hip), hipHostFree'd with the context
 	sbl_synteny_stats_t synteny_stats{}; // path counters of the last sbl_generate_blocks
+	std::vector<sbl_tiny_result> ti_res; // sbl_tiny_index: what the last call hands out
+	std::vector<sbl_inst> ti_inst[2];
 
 	// stage-boundary checkpoint (sbl_save_state / sbl_restore_state)
 	DevBuf d_save_ch, d_save_op;

@@ -194,41 +194,12 @@ inline bool natural_less(const BEdge &a, const BEdge &b)      // CompareEdgesNat
 	return static_cast<size_t>(a.firstChar) < static_cast<size_t>(b.firstChar);
 }
 
-struct Synteny {
+// The small-block index as its two callers reach it: sbl_generate_blocks (through Synteny::child_index) and the test entry point
+// sbl_tiny_index
+struct TinyIndex {
 	sbl_ctx *c;
-	sbl_ctx *child;
 	sbl_synteny_stats_t *st;                      // path counters of this call (sbl_synteny_stats): host increments only
-	uint32_t trimK, minSize;
-	std::vector<std::vector<uint8_t>> occupied;   // overlap[chr][original position] (POS_FREE / POS_OCCUPIED)
-	std::vector<std::vector<uint8_t>> local;      // localOverlap of the group being resolved, cleared through `undo`
-	std::vector<std::pair<uint32_t, std::pair<uint64_t, uint64_t>>> undo;
-
-	// ResolveOverlap (src/synteny.cpp:124-166): per edge the longest run of original positions that is free both globally and
-	// within the group (the first one among equals), kept when it is at least minSize long
-	void resolve_overlap(const BEdge *first, const BEdge *last, std::vector<BEdge> &now)
-	{
-		now.clear();
-		for (; first != last; ++first) {
-			const uint8_t *occ = occupied[first->chr].data(), *loc = local[first->chr].data();
-			const uint64_t begin = first->origPos, end = first->origPos + first->origLen;
-			uint64_t bestStart = 0, bestEnd = 0;
-			for (uint64_t s = begin; s < end;) {
-				uint64_t e = s;
-				while (e < end && occ[e] == 0 && loc[e] == 0) e++;
-				if (e - s > bestEnd - bestStart) { bestStart = s; bestEnd = e; }
-				s = e == s ? e + 1 : e;
-			}
-			if (bestEnd - bestStart >= minSize) {
-				BEdge x = *first;
-				x.origPos = bestStart; x.origLen = bestEnd - bestStart;
-				now.push_back(x);
-				memset(local[first->chr].data() + bestStart, 1, bestEnd - bestStart);
-				undo.push_back({first->chr, {bestStart, bestEnd}});
-			}
-		}
-		for (auto &u : undo) memset(local[u.first].data() + u.second.first, 0, u.second.second - u.second.first);
-		undo.clear();
-	}
+	uint32_t trimK;
 
 	// small blocks: one workgroup, one launch, result in mapped host memory (k_tiny_enumerate); false = not applicable, take the general path
 	TinyOut *tiny_out = nullptr, *tiny_out_dev = nullptr;
@@ -265,7 +236,6 @@ struct Synteny {
 	DevBuf d_bdesc, d_bheads, d_bpool;
 	std::vector<TinyBatchDesc> bdesc;
 	std::vector<unsigned> bheads, bpool;
-	const unsigned *pre_head = nullptr, *pre_inst = nullptr; unsigned pre_cap = 0;      // index speculated for the NEXT child_index call (one use)
 	bool tiny_eligible(const std::vector<BEdge> &block) const
 	{
 		if (!tiny_out || trimK > 32 || block.empty() || block.size() > TE_MAX_REC) return false;
@@ -320,6 +290,62 @@ struct Synteny {
 		inst[0] = reinterpret_cast<const sbl_inst *>(inst0); inst[1] = tiny_neg.data();
 		ninst[0] = n; ninst[1] = n;
 	}
+	// the index of slot `slot` of the last batch_run: the status its workgroup reported (0: the result is handed out, 1: it declined)
+	unsigned batch_result(unsigned slot, uint32_t *bif_count, const sbl_inst **inst, uint64_t *ninst)
+	{
+		const TinyBatchDesc &bd = bdesc[slot];
+		const unsigned *h = bheads.data() + 4 * (size_t)slot, *i0 = bpool.data() + bd.out_off;
+		if (h[0] == 0) tiny_result(h, i0, i0 + 3ull * bd.cap, bif_count, inst, ninst);
+		return h[0];
+	}
+	// the mapped host buffer of the one-block kernel, owned by the context; without it nothing is eligible
+	void attach_out()
+	{
+		if (!c->tiny_out) {
+			void *h = nullptr;
+			HIP_TRY(hipHostMalloc(&h, sizeof(TinyOut), hipHostMallocMapped));
+			c->tiny_out = h;
+		}
+		void *dv = nullptr;
+		HIP_TRY(hipHostGetDevicePointer(&dv, c->tiny_out, 0));
+		tiny_out = static_cast<TinyOut *>(c->tiny_out); tiny_out_dev = static_cast<TinyOut *>(dv);
+	}
+};
+
+struct Synteny : TinyIndex {
+	sbl_ctx *child;
+	uint32_t minSize;
+	int pre_slot = -1;                            // batch slot of the index speculated for the NEXT child_index call (one use)
+	std::vector<std::vector<uint8_t>> occupied;   // overlap[chr][original position] (POS_FREE / POS_OCCUPIED)
+	std::vector<std::vector<uint8_t>> local;      // localOverlap of the group being resolved, cleared through `undo`
+	std::vector<std::pair<uint32_t, std::pair<uint64_t, uint64_t>>> undo;
+
+	// ResolveOverlap (src/synteny.cpp:124-166): per edge the longest run of original positions that is free both globally and
+	// within the group (the first one among equals), kept when it is at least minSize long
+	void resolve_overlap(const BEdge *first, const BEdge *last, std::vector<BEdge> &now)
+	{
+		now.clear();
+		for (; first != last; ++first) {
+			const uint8_t *occ = occupied[first->chr].data(), *loc = local[first->chr].data();
+			const uint64_t begin = first->origPos, end = first->origPos + first->origLen;
+			uint64_t bestStart = 0, bestEnd = 0;
+			for (uint64_t s = begin; s < end;) {
+				uint64_t e = s;
+				while (e < end && occ[e] == 0 && loc[e] == 0) e++;
+				if (e - s > bestEnd - bestStart) { bestStart = s; bestEnd = e; }
+				s = e == s ? e + 1 : e;
+			}
+			if (bestEnd - bestStart >= minSize) {
+				BEdge x = *first;
+				x.origPos = bestStart; x.origLen = bestEnd - bestStart;
+				now.push_back(x);
+				memset(local[first->chr].data() + bestStart, 1, bestEnd - bestStart);
+				undo.push_back({first->chr, {bestStart, bestEnd}});
+			}
+		}
+		for (auto &u : undo) memset(local[u.first].data() + u.second.first, 0, u.second.second - u.second.first);
+		undo.clear();
+	}
 
 	// a fresh index at trimK over the block sequences (IndexedSequence iseq(blockSeq, trimK, ""), synteny.cpp:44): on the GPU
 	void child_index(const std::vector<BEdge> &block, uint32_t *bif_count, const sbl_inst **inst, uint64_t *ninst)
@@ -327,13 +353,12 @@ struct Synteny {
 		const uint32_t nrec = (uint32_t)block.size();
 		uint64_t L = 0;
 		for (auto &b : block) L += b.origLen;
-		if (pre_head) {                                          // speculated with the rest of its chunk, and the speculation held
-			const unsigned *h = pre_head, *i0 = pre_inst; const unsigned cap = pre_cap;
-			pre_head = nullptr;
-			if (h[0] == 0) {
+		if (pre_slot >= 0) {                                     // speculated with the rest of its chunk, and the speculation held
+			const unsigned slot = (unsigned)pre_slot;
+			pre_slot = -1;
+			if (batch_result(slot, bif_count, inst, ninst) == 0) {
 				st->speculated_used++;
-				count_tiny(L + nrec + 1, nrec, h[1]);
-				tiny_result(h, i0, i0 + 3ull * cap, bif_count, inst, ninst);
+				count_tiny(L + nrec + 1, nrec, *bif_count);
 				return;
 			}
 			st->batch_declines++;
@@ -472,16 +497,7 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 			if (cs != SBL_OK) throw SblError{cs, "cannot create the trim context"};
 		}
 		sy.child = c->child;
-		if (!c->tiny_out && !getenv("SBL_NO_TINY_INDEX")) {          // mapped host buffer of the small-block index, owned by the context
-			void *h = nullptr;
-			HIP_TRY(hipHostMalloc(&h, sizeof(TinyOut), hipHostMallocMapped));
-			c->tiny_out = h;
-		}
-		if (c->tiny_out && !getenv("SBL_NO_TINY_INDEX")) {
-			void *dv = nullptr;
-			HIP_TRY(hipHostGetDevicePointer(&dv, c->tiny_out, 0));
-			sy.tiny_out = static_cast<TinyOut *>(c->tiny_out); sy.tiny_out_dev = static_cast<TinyOut *>(dv);
-		}
+		if (!getenv("SBL_NO_TINY_INDEX")) sy.attach_out();
 		sy.occupied.resize(c->nchr); sy.local.resize(c->nchr);
 		for (uint32_t i = 0; i < c->nchr; i++) {
 			const size_t len = c->orig_sepidx[i + 1] - c->orig_sepidx[i] - 1;          // originalSize_
@@ -535,13 +551,10 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 				bool same = sp.slot >= 0 && sp.now.size() == now.size();
 				for (size_t i = 0; same && i < now.size(); i++)
 					same = sp.now[i].chr == now[i].chr && sp.now[i].origPos == now[i].origPos && sp.now[i].origLen == now[i].origLen && sp.now[i].dir == now[i].dir;
-				if (same) {
-					const TinyBatchDesc &bd = sy.bdesc[sp.slot];
-					sy.pre_head = sy.bheads.data() + 4 * (size_t)sp.slot; sy.pre_inst = sy.bpool.data() + bd.out_off; sy.pre_cap = bd.cap;
-				}
+				if (same) sy.pre_slot = sp.slot;
 			}
 			while (sy.trim_blocks(now)) { }
-			sy.pre_head = nullptr;                                      // (an empty candidate block makes no index)
+			sy.pre_slot = -1;                                           // (an empty candidate block makes no index)
 			std::fill(occur.begin(), occur.end(), 0u);
 			for (const BEdge &e : now) occur[e.chr]++;
 			if (now.size() > 1 && (!shared_only || (size_t)std::count(occur.begin(), occur.end(), 1u) == c->nchr)) {
@@ -556,6 +569,62 @@ extern "C" sbl_status sbl_generate_blocks(sbl_ctx *c, uint32_t k, uint32_t trim_
 		std::sort(c->blocks.begin(), c->blocks.end(), [](const sbl_block &a, const sbl_block &b) { return std::make_pair(a.chr, a.start) < std::make_pair(b.chr, b.start); });
 		if (blocks) *blocks = c->blocks.data();
 		if (n) *n = c->blocks.size();
+	});
+}
+
+// The small-block index of every block given, through TinyIndex as sbl_generate_blocks drives it (include/sibelia_amd.h).  Everything
+// is checked here, before any launch: a block that reaches a kernel has 1 .. TE_MAX_REC non-empty ranges inside their records, at most
+// TE_MAX_ELEM elements, and 2 <= trim_k <= 32.
+extern "C" sbl_status sbl_tiny_index(sbl_ctx *c, uint64_t nblocks, const uint64_t *block_first, const sbl_tiny_range *ranges, uint32_t trim_k, int batched,
+                                     const sbl_tiny_result **res, const sbl_inst **pos, const sbl_inst **neg)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(trim_k >= 2, SBL_ERR_BAD_ARG, "vertex sizes must be at least 2");
+		SBL_CHECK(block_first && res && pos && neg && (ranges || !nblocks), SBL_ERR_BAD_ARG, "null pointer");
+		require_records(c);
+		SBL_CHECK(block_first[0] == 0, SBL_ERR_BAD_ARG, "block offsets must start at 0");
+		std::vector<std::vector<BEdge>> block(nblocks);
+		for (uint64_t b = 0; b < nblocks; b++) {
+			SBL_CHECK(block_first[b] <= block_first[b + 1], SBL_ERR_BAD_ARG, "block offsets must ascend");
+			for (uint64_t i = block_first[b]; i < block_first[b + 1]; i++) {
+				const sbl_tiny_range &r = ranges[i];
+				SBL_CHECK(r.chr < c->nchr, SBL_ERR_BAD_ARG, "a range on a record that does not exist");
+				SBL_CHECK(r.start < r.end && r.end <= (uint64_t)c->orig_sepidx[r.chr + 1] - c->orig_sepidx[r.chr] - 1, SBL_ERR_BAD_ARG, "an empty range or a range beyond its record");
+				BEdge e{};
+				e.chr = r.chr; e.origPos = r.start; e.origLen = r.end - r.start;
+				block[b].push_back(e);
+			}
+		}
+		sbl_synteny_stats_t stats{};                             // the counters of the last sbl_generate_blocks stay as they are
+		TinyIndex ti;
+		ti.c = c; ti.st = &stats; ti.trimK = trim_k;
+		ti.attach_out();
+		c->ti_res.assign(nblocks, sbl_tiny_result{SBL_TINY_NOT_ELIGIBLE, 0, 0, 0, 0, 0});
+		c->ti_inst[0].clear(); c->ti_inst[1].clear();
+		std::vector<int> slot(nblocks, -1);
+		if (batched) {
+			for (uint64_t b = 0; b < nblocks; b++) if (ti.tiny_eligible(block[b])) slot[b] = (int)ti.batch_add(block[b]);
+			ti.batch_run();
+		}
+		for (uint64_t b = 0; b < nblocks; b++) {
+			if (!ti.tiny_eligible(block[b])) continue;
+			uint32_t bif = 0; const sbl_inst *inst[2] = {nullptr, nullptr}; uint64_t ninst[2] = {0, 0};
+			sbl_tiny_result &r = c->ti_res[b];
+			if (batched) {
+				r.status = ti.batch_result((unsigned)slot[b], &bif, inst, ninst);
+				SBL_CHECK(r.status == SBL_TINY_INDEXED || r.status == SBL_TINY_DECLINED, SBL_ERR_INTERNAL, "small-block index did not report");
+			} else {
+				uint64_t L = 0;
+				for (auto &e : block[b]) L += e.origLen;
+				r.status = ti.tiny_index(block[b], L, &bif, inst, ninst) ? SBL_TINY_INDEXED : SBL_TINY_DECLINED;
+			}
+			if (r.status != SBL_TINY_INDEXED) continue;
+			r.bif_count = bif;
+			r.first_pos = c->ti_inst[0].size(); r.npos = ninst[0];
+			r.first_neg = c->ti_inst[1].size(); r.nneg = ninst[1];
+			for (int s = 0; s < 2; s++) c->ti_inst[s].insert(c->ti_inst[s].end(), inst[s], inst[s] + ninst[s]);
+		}
+		*res = c->ti_res.data(); *pos = c->ti_inst[0].data(); *neg = c->ti_inst[1].data();
 	});
 }
 

@@ -40,6 +40,31 @@ def test_synteny_stats_layout_matches_the_header():
     assert hasattr(api.BlockFinder, "synteny_stats")
 
 
+def test_tiny_index_layout_matches_the_header():
+    # sbl_tiny_index (the small-block index on its own, a test entry point): exported and listed; the ctypes mirrors of its range and
+    # result structs have the header's fields in the header's order and its sizes; the status constants agree; a missing context is
+    # refused before anything is read
+    import __graft_entry__ as g
+    g.build()
+    from sibelia_amd import api
+    hdr = open(os.path.join(ROOT, "include", "sibelia_amd.h")).read()
+    width = {"uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+    for cname, mirror, size in (("sbl_tiny_range", api.TinyRange, 24), ("sbl_tiny_result", api.TinyResult, 40)):
+        body = re.search(r"typedef struct \{([^}]*)\} %s;" % cname, hdr).group(1)
+        fields = [(f.strip(), width[t]) for t, names in re.findall(r"(uint32_t|uint64_t)\s+([^;]+);", body) for f in names.split(",")]
+        assert fields == list(mirror._fields_), cname
+        assert ctypes.sizeof(mirror) == size
+    for name, value in (("SBL_TINY_INDEXED", api.TINY_INDEXED), ("SBL_TINY_DECLINED", api.TINY_DECLINED), ("SBL_TINY_NOT_ELIGIBLE", api.TINY_NOT_ELIGIBLE)):
+        assert int(re.search(r"#define %s (\d+)" % name, hdr).group(1)) == value
+    assert "sbl_tiny_index" in api.EXPORTS and hasattr(ctypes.CDLL(api.LIB), "sbl_tiny_index")
+    lib = api.load_library()
+    first = (ctypes.c_uint64 * 1)(0)
+    ranges = (api.TinyRange * 1)()
+    res, pos, neg = ctypes.POINTER(api.TinyResult)(), ctypes.c_void_p(), ctypes.c_void_p()
+    assert lib.sbl_tiny_index(None, 0, first, ranges, 8, 1, ctypes.byref(res), ctypes.byref(pos), ctypes.byref(neg)) == 1      # SBL_ERR_BAD_ARG
+    assert hasattr(api.BlockFinder, "tiny_index")
+
+
 def test_no_host_compute_path_without_a_gpu():
     import torch
     if torch.cuda.is_available():

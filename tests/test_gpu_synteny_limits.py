@@ -6,11 +6,9 @@ reference's (tests/golden/synteny_limits.json), and the library's path counters 
 is about took the path it is about.  A second context under SBL_NO_TINY_INDEX=1 must give the same blocks through the general child
 index alone.
 
-KNOWN BLIND SPOT, not a verified property: these tests compare block lists only; the small-block index itself is never compared with
-the general index's instance lists.  By the way TrimBlocks reads an index, a block list cannot show the order of the instances within
-one id's list (only minima over the list are taken, ties go to the smaller id) nor a uniform shift of all ids (only their order is
-used).  So a wrong negative-strand order (dropping the per-sequence reversal in tiny_result) and an off-by-one in every rank (`<=` in the
-rank loop) pass everything here; a caller that read the instance lists in order would see them."""
+These tests compare block lists only, and by the way TrimBlocks reads an index a block list cannot show the order of the instances
+within one id's list nor a uniform shift of all ids.  The small-block index itself -- every (id, chr, pos) of both instance lists -- is
+compared with the oracle, the reference and the general index by tests/test_gpu_tiny_index.py (cases: tests/tiny_index_cases.py)."""
 import json
 import os
 
