@@ -108,7 +108,7 @@ struct GraphView {
 	// Parked transactions (round 5, commit.hip): a launch of k_commit lasts as long as its slowest transaction, and that is one with
 	// several collapses.  A transaction that has made park_cap collapses in a launch and has decided another one PARKS: its LDS state goes
 	// to the end of its arena slice, the id stays pending (the probes take a parked id for live without a verdict), and the next round
-	// in which it owns its claims resumes it where it stopped (k_resume, beside k_commit on a second stream).  park_of[id]: 0 = never
+	// in which it owns its claims resumes it where it stopped (the resume workgroups at the front of k_commit's grid).  park_of[id]: 0 = never
 	// parked; bits 0-19 = its arena slice + 1, bits 20-30 = the round it parked in (it is resumed in a LATER round: both kernels have a
 	// workgroup for every window entry, and an entry must be one kernel's for the whole launch), bit 31 = finished in the round of bits
 	// 20-30 (k_commit leaves it alone in that round, afterwards it is an ordinary id again).  slice_busy[w] != 0: the slice of window
@@ -119,7 +119,7 @@ struct GraphView {
 	// parked transactions still resume, and run to their end).  any_parked != 0 -- something was parked when this launch started (the host
 	// knows from the counters of the round before): only then may a list hold fewer live nodes than its size says (the deferred Cleanup
 	// of a parked transaction); otherwise that is list corruption and stays a hard error.  park_list: window positions of the parked
-	// entries of this round (appended by k_reserve, ctr[CTR_PLIST] of them): k_resume's grid is the parked transactions, not the window.
+	// entries of this round (appended by k_reserve, ctr[CTR_PLIST] of them): the resume workgroups of k_commit are the parked transactions, not the window.
 	uint32_t park_hold, any_parked; uint32_t *park_list;
 };
 // The LDS state of a parked transaction (Txn first) sits in the last PARK_IMG bytes of its arena slice (commit.hip: park_store / park_load).
@@ -518,6 +518,9 @@ struct BulgeWork {
 	// mq_* with all lanes -- one look-up per lane, the same stamps -- into mres[], set mready, call again).
 	uint32_t nold;               // SBL_PHASES=1: collapses of this transaction that took the round-3 form
 	bool mscan, mready;
+	uint8_t resumed;             // parked transactions: 0 = taken up fresh by this launch; bit 0 = resumed from its image (park_load), bit 1 = ... and
+	                             // its decided collapse is still to be performed (commit_body reads both from LDS: a register kept across the body spills)
+	bool can_park;               // ... works in a slice of its own (not a shadow slice, not the big arena) that has room for the image: it may park
 	// FillVisit by the caller's 64 lanes (commit.hip: wave_fill_visit) instead of one thread's shell sort: with wfill set bt_rb_run returns 5
 	// (fill_i = the instance) where it would call bt_fill_visit; the caller clears need_fill
 	bool wfill; uint32_t fill_i;
@@ -526,7 +529,7 @@ struct BulgeWork {
 	bool pscan, pready, pjknown; uint32_t pj;
 	uint32_t ret0;               // parked transactions (GraphView::park_of): value of ret when this launch took the transaction up
 	uint32_t mscan_min;          // ... with more than this many marks inside the two branches together (BT_MSCAN_MIN; read as a member, the
-	                             // constant itself made k_resume spill 16 B more)
+	                             // constant itself made the resuming kernel spill 16 B more)
 	uint32_t mq_i, mq_di, mq_j, mq_dj, mres[2];
 	uint64_t *visit; uint32_t nvisit, visit_cap;      // FillVisit result sorted by (bif, distance)
 	uint32_t *occ; uint32_t occ_cap;

@@ -1175,8 +1175,8 @@ __device__ __forceinline__ int wave_any_bulges(const GraphView &g, Txn &t, Bulge
 // the decisions on the cached windows and all lanes rescanning them after every collapse.
 // ---- parked transactions (GraphView::park_of): the LDS state of a transaction at the end of its arena slice (PARK_IMG bytes, bulge_txn.h)
 // The image holds raw LDS addresses (t.fscr, the w.* arrays laid out in `fast`, absh.skey / sval): it is only valid in a kernel that
-// places t, w, absh and fast where the parking kernel had them.  k_commit and k_resume instantiate the same declarations
-// (commit_kernel), so they do; the image records the four addresses and park_load refuses (BT_ERR_LAYOUT) an image from another layout.
+// places t, w, absh and fast where the parking kernel had them.  Fresh and resumed transactions run in the one kernel
+// (k_commit), so they do; the image records the four addresses and park_load refuses (BT_ERR_LAYOUT) an image from another layout.
 #define PARK_OFF_LAYOUT (PARK_IMG - 16u)
 #define PARK_OFF_W ((unsigned)((sizeof(Txn) + 15u) & ~15u))
 #define PARK_OFF_AB (PARK_OFF_W + (unsigned)((sizeof(BulgeWork) + 15u) & ~15u))
@@ -1185,10 +1185,13 @@ static_assert(sizeof(Txn) % 4 == 0 && sizeof(BulgeWork) % 4 == 0 && sizeof(ABSha
 static_assert(PARK_OFF_FAST + COMMIT_FAST_BYTES <= PARK_OFF_LAYOUT, "the LDS image of a transaction must fit PARK_IMG");
 __device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void *)p; }
 __device__ __forceinline__ void park_move(unsigned *dst, const unsigned *src, unsigned words, unsigned lane) { for (unsigned i = lane; i < words; i += 64) dst[i] = src[i]; }
-__device__ __forceinline__ void park_store(const GraphView &g, Txn &t, BulgeWork &w, ABShared &absh, uint8_t *fast, unsigned fast_bytes, uint8_t *image, unsigned id, unsigned slice)
+// (everything but the LDS objects comes from LDS or memory, not from the caller's registers -- commit_body: the image lies behind the
+// scratch of the transaction, the slice is the window position of a fresh transaction and the one park_of names for a resumed one)
+__device__ __forceinline__ void park_store(const GraphView &g, Txn &t, BulgeWork &w, ABShared &absh, uint8_t *fast, unsigned fast_bytes, unsigned id)
 {
 	const unsigned lane = threadIdx.x;
 	WSYNC();
+	uint8_t *image = t.scr + t.scr_cap;
 	park_move(reinterpret_cast<unsigned *>(image), reinterpret_cast<const unsigned *>(&t), sizeof(Txn) / 4, lane);
 	park_move(reinterpret_cast<unsigned *>(image + PARK_OFF_W), reinterpret_cast<const unsigned *>(&w), sizeof(BulgeWork) / 4, lane);
 	park_move(reinterpret_cast<unsigned *>(image + PARK_OFF_AB), reinterpret_cast<const unsigned *>(&absh), sizeof(ABShared) / 4, lane);
@@ -1196,6 +1199,7 @@ __device__ __forceinline__ void park_store(const GraphView &g, Txn &t, BulgeWork
 	if (lane == 0) {
 		unsigned *lay = reinterpret_cast<unsigned *>(image + PARK_OFF_LAYOUT);
 		lay[0] = lds_addr(&t); lay[1] = lds_addr(&w); lay[2] = lds_addr(&absh); lay[3] = lds_addr(fast);
+		const unsigned slice = w.resumed ? (g.park_of[id] & 0xFFFFFu) - 1u : t.stamp & 0xFFFFFu;
 		g.park_of[id] = (slice + 1u) | (bt_round_tag(g) << 20); g.slice_busy[slice] = 1; g.need[id] = 2; atomicAdd(&g.ctr[CTR_PARKED], 1u);
 #ifdef SBL_DBG_IDRET
 		if (id < (1u << 20)) atomicCAS(&g_dbg_park[id], 0u, ((SS_ROUND_MAX - (g.round_bits >> 20)) << 8) | (w.ret & 255u));      // first park: round, ret
@@ -1216,27 +1220,29 @@ __device__ __forceinline__ bool park_load(const GraphView &g, Txn &t, BulgeWork 
 	park_move(reinterpret_cast<unsigned *>(&absh), reinterpret_cast<const unsigned *>(image + PARK_OFF_AB), sizeof(ABShared) / 4, lane);
 	park_move(reinterpret_cast<unsigned *>(fast), reinterpret_cast<const unsigned *>(image + PARK_OFF_FAST), fast_bytes / 4, lane);
 	WSYNC();
-	if (lane == 0) { t.g = g; t.stamp = g.round_bits | wi; t.prof = prof != 0; w.ret0 = w.ret - 1; atomicSub(&g.ctr[CTR_PARKED], 1u); }      // (ret0: the collapse it parked with belongs to this launch)
+	if (lane == 0) { t.g = g; t.stamp = g.round_bits | wi; t.prof = prof != 0; w.ret0 = w.ret - 1; w.resumed = 3; atomicSub(&g.ctr[CTR_PARKED], 1u); }      // (ret0: the collapse it parked with belongs to this launch; resumed: ... and is decided already)
 	WSYNC();
 	return true;
 }
 // The transaction proper (RemoveBulges for one id) on one wave; t, w, flag, absh and fast live in LDS.
 // solo: 0 = ordered round (the probe found bulges, the entry owns its claims), 1 = the id runs with nothing else in flight
 // (big-arena solo round, or the serial chain: stampv == BT_NONE, no reservation exists and none is checked).
-template <bool RESUME = false>
 __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWork &w, int &flag, ABShared &absh, uint8_t *fast, unsigned fast_bytes,
                                             unsigned wi, unsigned id, unsigned stampv, int solo, bool prepass, uint8_t *mine, unsigned arena_bytes, int prof,
                                             const unsigned *sepl = nullptr /* LDS copy of the separators' slots (SepBounds), or none */,
-                                            unsigned park_slice = BT_NONE /* may park (GraphView::park_of): its arena slice; RESUME: it is parked there */)
+                                            bool own_slice = false /* mine is the arena slice of window entry wi (not its shadow slice, not the big arena): it may park there (GraphView::park_of) */,
+                                            bool resume = false /* mine is the slice the id parked in: take it up from the image there */)
+// (own_slice, resume, wi, mine and arena_bytes are only read up to the start of the writer pass / park_load: from there on BulgeWork::can_park /
+// resumed and the transaction's own fields say the same from LDS -- k_commit's registers do not hold one more value across the loops)
 {
 	const unsigned lane = threadIdx.x, tid = id + 1;
 	PH_T0();
 	// parking: the last PARK_IMG bytes of the slice are kept for the LDS image (t, w, absh, fast)
-	const bool can_park = park_slice != BT_NONE && g.park_cap != 0 && arena_bytes >= 4u * PARK_IMG;
+	const bool can_park = (own_slice || resume) && g.park_cap != 0 && arena_bytes >= 4u * PARK_IMG;
 	if (can_park) arena_bytes -= PARK_IMG;
 	// ---- the probe of this round found bulges (solo entries were not probed: verdict pass first)
 	if (lane == 0) { g.need[id] = 0; g.touch[id] = 1; flag = 1; }
-	if (RESUME) {                                                     // the state it parked with; what belongs to the round is renewed
+	if (resume) {                                                     // the state it parked with; what belongs to the round is renewed
 		if (!park_load(g, t, w, absh, fast, fast_bytes, mine + arena_bytes, id, wi, prof)) return;      // (an image of another LDS layout: CTR_ERR, the stage ends with an internal error)
 		if (lane == 0) flag = 1;
 		WSYNC();
@@ -1262,7 +1268,7 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 	// waves at once stood in front of the first barrier of each of them -- the wait for the acknowledgement, not the atomic, is what costs)
 	if (!flag) { if (lane == 0) { atomicAdd(&g.ctr[CTR_COMMITTED], 1u); atomicAdd(&g.ctr[CTR_TXN], 1u); } return; }
 	// ---- writer pass: reads and writes are published for order validation
-	if (lane == 0) { t.init(g, id, wi, 2, mine, arena_bytes); t.chain = stampv == BT_NONE; t.defer_push = true; t.ext_stamps = true; t.fscr = fast; t.fscr_cap = fast_bytes; w.ret = 0;
+	if (lane == 0) { t.init(g, id, wi, 2, mine, arena_bytes); t.chain = stampv == BT_NONE; t.defer_push = true; t.ext_stamps = true; t.fscr = fast; t.fscr_cap = fast_bytes; w.ret = 0; w.resumed = 0; w.can_park = can_park;
 	                 t.tc_cap = 1024; t.tc_list = (uint32_t *)t.alloc(t.tc_cap * 4); if (!t.tc_list) t.tc_cap = 0; t.err = 0; t.defer_cleanup = true; t.prof = prof != 0; }
 	WSYNC();
 	PH_ADD(7);
@@ -1283,7 +1289,7 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 	}
 	PH_ADD(0);
 	if (flag) {
-		if (!RESUME) {
+		if (!w.resumed) {                                             // (a parked transaction has all this in its image)
 		wave_scan_all(g, w, lane, stampv, tid, 2, id);
 		WSYNC();
 		if (w.mk_overflow) {                                          // more marks in a window than the LDS lists hold: use the arena
@@ -1303,10 +1309,11 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 		WSYNC();
 		PH_ADD(2);
 		}
-		bool decided = RESUME;                                        // (a parked transaction stopped with its next collapse decided)
 		while (flag) {
-			if (!RESUME || !decided) {
-			if (lane == 0) { const int r = bt_scratch_in_lds(w) ? bt_rb_run<true>(t, w) : bt_rb_run<false>(t, w); flag = t.err ? 0 : r; }      // (<true>: DS instead of FLAT accesses, bulge_txn.h: BT_ASSUME_LDS)
+			if (lane == 0) {
+				if (w.resumed & 2u) { w.resumed = 1; flag = 1; }          // (a parked transaction stopped with its next collapse decided: flag 1 is what bt_rb_run returned then)
+				else { const int r = bt_scratch_in_lds(w) ? bt_rb_run<true>(t, w) : bt_rb_run<false>(t, w); flag = t.err ? 0 : r; }      // (<true>: DS instead of FLAT accesses, bulge_txn.h: BT_ASSUME_LDS)
+			}
 			WSYNC();
 			PH_ADD(3);
 			if (!flag) break;
@@ -1330,17 +1337,15 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 				PH_ADD(8);
 				continue;
 			}
-			}
-			decided = false;
 			// ---- a collapse has been decided (c_src -> c_tgt).  Enough of them for one launch: park (GraphView::park_of)
-			if (can_park && !t.g.park_hold && !w.lazy && w.ret - w.ret0 > g.park_cap) {      // (ret counts the collapse just decided; park_hold: the driver waits for what is parked to drain -- read from the LDS copy of the view: one more live kernel argument tipped k_commit's scratch from 232 to 584 B)
-				park_store(g, t, w, absh, fast, fast_bytes, mine + arena_bytes, id, park_slice);      // (arena_bytes: already without the image)
+			if (w.can_park && !t.g.park_hold && !w.lazy && w.ret - w.ret0 > g.park_cap) {      // (ret counts the collapse just decided; park_hold: the driver waits for what is parked to drain -- read from the LDS copy of the view: one more live kernel argument tipped k_commit's scratch from 232 to 584 B)
+				park_store(g, t, w, absh, fast, fast_bytes, id);
 				return;                                                    // (no Cleanup, no counters: the transaction is not over)
 			}
 #ifdef SBL_DBG_IDRET
 			if (lane == 0) {
 				const unsigned o = atomicAdd(&g_dbg_nlog, 1u);
-				if (o < (1u << 20)) { unsigned *r = g_dbg_log + (size_t)o * 8u; r[0] = id; r[1] = SS_ROUND_MAX - (g.round_bits >> 20); r[2] = w.ret; r[3] = (g.nslot[w.start[w.c_src] >> 1] << 1) | (w.start[w.c_src] & 1u); r[4] = (g.nslot[w.start[w.c_tgt] >> 1] << 1) | (w.start[w.c_tgt] & 1u); r[5] = w.c_dS; r[6] = w.c_dT; r[7] = RESUME ? 1u : 0u; }
+				if (o < (1u << 20)) { unsigned *r = g_dbg_log + (size_t)o * 8u; r[0] = id; r[1] = SS_ROUND_MAX - (g.round_bits >> 20); r[2] = w.ret; r[3] = (g.nslot[w.start[w.c_src] >> 1] << 1) | (w.start[w.c_src] & 1u); r[4] = (g.nslot[w.start[w.c_tgt] >> 1] << 1) | (w.start[w.c_tgt] & 1u); r[5] = w.c_dS; r[6] = w.c_dT; r[7] = w.resumed ? 1u : 0u; }
 			}
 #endif
 			if (w.lazy) {
@@ -1462,33 +1467,45 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 			atomicMax(&g_round_max[(g.tslot >> 2) & 4095u], (dur << 24) | ((unsigned long long)(w.n < 255u ? w.n : 255u) << 16) | ((unsigned long long)(w.nold < 255u ? w.nold : 255u) << 8) | (w.ret < 255u ? w.ret : 255u));
 		}
 		atomicAdd(&g.ctr[CTR_COMMITTED], 1u); atomicAdd(&g.ctr[CTR_TXN], 1u);
-		if (RESUME) { __threadfence(); g.slice_busy[park_slice] = 0; g.park_of[id] = 0x80000000u | (bt_round_tag(g) << 20); }      // (everything this transaction wrote into the slice is out before somebody else takes it)
+		if (w.resumed) { __threadfence(); g.slice_busy[(g.park_of[id] & 0xFFFFFu) - 1u] = 0; g.park_of[id] = 0x80000000u | (bt_round_tag(g) << 20); }      // (everything this transaction wrote into the slice is out before somebody else takes it)
 		if (t.err) {
 			if (!t.wrote && t.err == BT_ERR_SCRATCH) { ss_mark_big(g, id); return; }
 			atomicOr(&g.ctr[CTR_ERR], t.err);
 		}
 		atomicAdd(&g.ctr[CTR_BULGES], w.ret);
 #ifdef SBL_DBG_IDRET
-		if (id < (1u << 20)) { atomicAdd(&g_dbg_ret[id], w.ret); atomicCAS(&g_dbg_fin[id], 0u, ((SS_ROUND_MAX - (g.round_bits >> 20)) << 8) | (RESUME ? 128u : 0u) | (w.ret & 127u)); }      // first finish: round, resumed, collapses
+		if (id < (1u << 20)) { atomicAdd(&g_dbg_ret[id], w.ret); atomicCAS(&g_dbg_fin[id], 0u, ((SS_ROUND_MAX - (g.round_bits >> 20)) << 8) | (w.resumed ? 128u : 0u) | (w.ret & 127u)); }      // first finish: round, resumed, collapses
 #endif
 	}
 }
 
-template <bool RESUME_KERNEL>
-__device__ __forceinline__ void commit_kernel(const GraphView &g, unsigned nwin, uint8_t *arena, unsigned arena_bytes, int solo, const unsigned *claims, const uint8_t *live, int prof_every)
+// One launch per ordered round: the grid is nres + nwin workgroups (nres = min(transactions parked when the round started, nwin), 0 in a
+// solo launch).  Workgroups [0, nres) take a parked entry of the window from GraphView::park_list (k_reserve's) and run the rest of its
+// loops -- the longest transactions of the round, so they start first; workgroup nres + wi is window entry wi.  Both kinds ran side by
+// side before (two kernels on two streams), so one grid adds no interleaving.  What the body needs to know about a resumed transaction
+// after park_load is in BulgeWork::resumed / can_park (LDS), not in registers.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_commit(GraphView g_arg, unsigned nwin, uint8_t *arena, unsigned arena_bytes, int solo, const unsigned *claims, const uint8_t *live, int prof_every)
 {
+	// The view is read where the dispatch put it: the first kernel argument, at offset 0 of the kernel argument segment.  Through the
+	// parameter itself the compiler kept a private copy of all 344 bytes in scratch once fresh and resumed transactions shared this
+	// kernel (three copies of the view into LDS: prepass, writer pass, park_load) and read every field from there -- THAT was the
+	// "register cliff" of the merged kernel: scratch 232 -> 536 .. 552 B, 1659 scratch loads in the kernel against 108.  So: 200 B.
+	(void)g_arg;
+	const GraphView &g = *(const GraphView *)(const __attribute__((address_space(4))) GraphView *)__builtin_amdgcn_kernarg_segment_ptr();
 	const int prof = prof_every && blockIdx.x % (unsigned)prof_every == 0u;      // SBL_PHASES=N: every Nth entry is timed (all of them distort what they measure)
 	__shared__ Txn t;
 	__shared__ BulgeWork w;
 	__shared__ int flag;
 	__shared__ ABShared absh;
 	__shared__ __attribute__((aligned(16))) uint8_t fast[COMMIT_FAST_BYTES];     // window summaries, mark lists, FillVisit list and AnyBulges map of typical ids
-	unsigned wi = blockIdx.x;
+	const unsigned nres = solo ? 0u : gridDim.x - nwin;
+	const bool resume = blockIdx.x < nres;
+	unsigned wi = blockIdx.x - nres;
 	const unsigned lane = threadIdx.x;
-	if (!RESUME_KERNEL) round_stamp(g, 2);
-	if (RESUME_KERNEL) {                                              // one workgroup per parked entry of the window (GraphView::park_list, filled by k_reserve)
-		if (wi >= __builtin_amdgcn_readfirstlane((int)g.ctr[CTR_PLIST])) return;
-		wi = (unsigned)__builtin_amdgcn_readfirstlane((int)g.park_list[wi]);
+	round_stamp(g, 2);                                                // (workgroup 0 only, whichever kind it is)
+	if (resume) {                                                     // one workgroup per parked entry of the window
+		if (blockIdx.x >= (unsigned)__builtin_amdgcn_readfirstlane((int)g.ctr[CTR_PLIST])) return;
+		wi = (unsigned)__builtin_amdgcn_readfirstlane((int)g.park_list[blockIdx.x]);
 	}
 	if (wi >= nwin) return;
 	if (!solo && !live[wi]) return;                                   // retired by the probe
@@ -1513,40 +1530,25 @@ __device__ __forceinline__ void commit_kernel(const GraphView &g, unsigned nwin,
 	__shared__ unsigned s_sep[64];                                    // the separators' slots (SepBounds), when there are at most 64
 	const unsigned *sepl = g.sep && g.nsep <= 64 ? s_sep : nullptr;
 	if (sepl) s_sep[lane] = lane < g.nsep ? g.sep[lane] : BT_NONE;
-	// parked here in an earlier round (GraphView::park_of): resume in the slice it parked in; a fresh entry whose own slice holds somebody's
-	// parked state waits a round
-	// parked here in an earlier round: k_resume's (same launch configuration, behind this kernel); a fresh entry whose own slice holds
-	// somebody's parked state waits a round
-	if (RESUME_KERNEL) {
+	// parked here in an earlier round (GraphView::park_of): a resume workgroup takes it up in the slice it parked in, its window workgroup
+	// leaves it alone; a fresh entry whose own slice holds somebody's parked state works in the shadow slice and does not park
+	unsigned slice = wi; bool own_slice = false;
+	if (!solo && g.park_cap) {
 		const unsigned pk = (unsigned)__builtin_amdgcn_readfirstlane((int)g.park_of[id]);
-		if (!pk || (pk >> 31) || ((pk >> 20) & 0x7FFu) == bt_round_tag(g)) return;      // not parked / parked in this very launch
-		const unsigned slice = (pk & 0xFFFFFu) - 1u;
-		commit_body<true>(g, t, w, flag, absh, fast, (unsigned)sizeof fast, wi, id, stampv, 0, false, arena + (size_t)slice * arena_bytes, arena_bytes, prof, sepl, slice);
-	} else {
-		if (!solo && g.park_cap) {
-			const unsigned pk = (unsigned)__builtin_amdgcn_readfirstlane((int)g.park_of[id]);
-			if (pk && (!(pk >> 31) || ((pk >> 20) & 0x7FFu) == bt_round_tag(g))) return;      // parked (k_resume's), or finished in this round
+		if (resume) {
+			if (!pk || (pk >> 31) || ((pk >> 20) & 0x7FFu) == bt_round_tag(g)) return;      // not parked / parked in this very launch
+			slice = (pk & 0xFFFFFu) - 1u;
+		} else {
+			if (pk && (!(pk >> 31) || ((pk >> 20) & 0x7FFu) == bt_round_tag(g))) return;      // parked (a resume workgroup's), or finished in this round
+			// my slice held a parked transaction when the round's commits started (k_reserve's copy: a resume workgroup may be releasing it right now): the spare one
+			if (__builtin_amdgcn_readfirstlane((int)g.slice_busy[g.shadow_base + 64u + wi]) != 0) slice = g.shadow_base + wi; else own_slice = true;
 		}
-		const bool shadow = !solo && g.park_cap && __builtin_amdgcn_readfirstlane((int)g.slice_busy[g.shadow_base + 64u + wi]) != 0;      // my slice held a parked transaction when the round's commits started (k_reserve's copy: k_resume may be releasing it right now): the spare one
-		commit_body<false>(g, t, w, flag, absh, fast, (unsigned)sizeof fast, wi, id, stampv, solo, solo != 0, arena + (size_t)(shadow ? g.shadow_base + wi : wi) * arena_bytes, arena_bytes, prof, sepl,
-		                   !solo && g.park_cap && !shadow ? wi : (unsigned)BT_NONE);
 	}
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_commit(GraphView g, unsigned nwin, uint8_t *arena, unsigned arena_bytes, int solo, const unsigned *claims, const uint8_t *live, int prof_every)
-{
-	commit_kernel<false>(g, nwin, arena, arena_bytes, solo, claims, live, prof_every);
-}
-
-// the parked transactions of the window that own their claims this round (GraphView::park_of): the rest of their loops.  A kernel of its
-// own, beside k_commit on a second stream: with both bodies in one kernel every transaction spilled (scratch 232 -> 616 B), and a call
-// made the kernel's scratch 880 B (commit 32 -> 52 ms either way)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_resume(GraphView g, unsigned nwin, uint8_t *arena, unsigned arena_bytes, const unsigned *claims, const uint8_t *live, int prof_every)
-{
-	commit_kernel<true>(g, nwin, arena, arena_bytes, 0, claims, live, prof_every);
+	commit_body(g, t, w, flag, absh, fast, (unsigned)sizeof fast, wi, id, stampv, solo, solo != 0, arena + (size_t)slice * arena_bytes, arena_bytes, prof, sepl, own_slice, resume);
 }
 
 // finished markers of park_of (bit 31 | round tag) are only read in the round they were written in; the tag is 11 bits of a 12-bit round,
-// so they are swept before a round with the same tag comes round again (DeviceBackend::commit, every 1024 rounds)
+// so they are swept before a round with the same tag comes round again (DeviceBackend::park_sweep: every 1024 rounds and at the wrap)
 __global__ void __launch_bounds__(256) k_park_sweep(unsigned *__restrict__ park_of, unsigned n)
 {
 	const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -701,7 +701,7 @@ __global__ void __launch_bounds__(SEL_THREADS) k_select_write(GraphView g, unsig
 		__syncthreads();
 		if (threadIdx.x == 0) { post[CTR_COUNT] = post_seq; __threadfence_system(); }
 	}
-	if (s_last && threadIdx.x == 0) g.ctr[CTR_PLIST] = 0;              // (the list of parked window entries is per round: k_reserve appends, k_resume reads)
+	if (s_last && threadIdx.x == 0) g.ctr[CTR_PLIST] = 0;              // (the list of parked window entries is per round: k_reserve appends, k_commit's resume workgroups read)
 }
 
 // ---- the reservation walks of an instance from the BLOCK INDEX (round 5) ------------------------------------------------------------
@@ -844,9 +844,9 @@ __global__ void __launch_bounds__(64 * RSV_WAVES_MAX) k_reserve(GraphView g, uns
 	if (threadIdx.x == 0) nclaims = 0;
 	unsigned id = g.win[w], st = g.round_bits | w;
 	if (g.park_list && threadIdx.x == 0) {
-		if (bt_parked(g, id)) g.park_list[atomicAdd(&g.ctr[CTR_PLIST], 1u)] = w;      // k_resume's work list: the parked entries of this window
+		if (bt_parked(g, id)) g.park_list[atomicAdd(&g.ctr[CTR_PLIST], 1u)] = w;      // the resume workgroups' work list: the parked entries of this window
 		// slice_busy as of the START of the round's commit launches (second half of the array): whether the entry at position w works in
-		// its own slice (and may park) or in the shadow slice must not depend on whether k_resume, running beside k_commit, has already
+		// its own slice (and may park) or in the shadow slice must not depend on whether a resume workgroup, running beside it in k_commit, has already
 		// released the slice -- either outcome is exact, but the rounds differ, and the ranks of a job on several GPUs (replicated
 		// commits, collectives sized by the window) must stay in step: that race was round 5's crash with a communicator attached
 		g.slice_busy[g.shadow_base + 64u + w] = g.slice_busy[w];

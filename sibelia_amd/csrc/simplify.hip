@@ -18,10 +18,9 @@
 static inline unsigned nblocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // ------------------------------------------------------------------------------------------- device backend
-// What a SimplifyState holds besides device buffers.  A base class, so that it is destroyed AFTER the buffers: the park stream and the
-// events go after the memory that may still be in use on them.
+// What a SimplifyState holds besides device buffers.  A base class, so that it is destroyed AFTER the buffers: the events go after the
+// memory that may still be in use on them.
 struct SimplifyHandles {
-	hipStream_t park_stream = nullptr; hipEvent_t park_ev[2] = {nullptr, nullptr};      // k_resume beside k_commit (GraphView::park_of)
 	unsigned *h_ctr = nullptr;            // pinned, mapped: CTR_COUNT counters + the sequence number of the last post (k_select_write)
 	unsigned *d_hctr = nullptr;           // its device address
 	unsigned post_seq = 0;
@@ -30,8 +29,6 @@ struct SimplifyHandles {
 	unsigned char *h_init = nullptr;      // pinned staging for the small host-to-device initialisations of a stage (no synchronisation needed before the host moves on)
 	~SimplifyHandles()
 	{
-		if (park_stream) (void)hipStreamDestroy(park_stream);
-		for (auto &e : park_ev) if (e) (void)hipEventDestroy(e);
 		if (h_ctr) (void)hipHostFree(h_ctr);
 		if (h_init) (void)hipHostFree(h_init);
 		for (auto &e : ev) if (e) (void)hipEventDestroy(e);
@@ -403,8 +400,12 @@ struct DeviceBackend {
 		}
 		snap_used = 0;
 	}
+	// finished markers of park_of carry 11 bits of a 12-bit round (bt_round_tag): none may survive to the round with the same tag.  Due in
+	// every round with (round & 1023) == 0, whatever kind of round it is, and when the round counter wraps
+	void park_sweep() { if (g.park_cap) k_park_sweep<<<nblocks((size_t)nid_ + 1, 256), 256, 0, c->stream>>>(st->park_of.as<unsigned>(), nid_ + 1); }
 	void reset_round_state(bool stamps_too)
 	{
+		if (!stamps_too) park_sweep();                                 // (the round counter wraps; with stamps_too park_of is cleared below)
 		if (stamps_too && g.park_cap) {                                // (start of an iteration / of a replay: nothing is parked)
 			HIP_TRY(hipMemsetAsync(st->park_of.p, 0, ((size_t)nid_ + 1) * 4, c->stream));
 			HIP_TRY(hipMemsetAsync(st->slice_busy.p, 0, park_slices, c->stream));
@@ -493,6 +494,7 @@ struct DeviceBackend {
 	{
 		g.round_bits = (SS_ROUND_MAX - round) << 20;
 		g.any_parked = parked_known != 0;                            // (exact: nothing parks or resumes between the counters of the round before and this launch)
+		if ((round & 1023u) == 0u) park_sweep();                     // (ordered and chain rounds; a solo round has no probe: commit())
 		begin_round();
 		solo_round = false;
 		if (g.tslot < TS_CAP * 4) ts_kind.back() |= 1;
@@ -540,23 +542,15 @@ struct DeviceBackend {
 		if (g.tslot < TS_CAP * 4) ts_kind.back() |= 4;
 		if (sampled) HIP_TRY(hipEventRecord(ev[2], c->stream));
 		if (solo) {
+			if ((round & 1023u) == 0u) park_sweep();                    // (no probe in this round)
 			st->big_arena.ensure(big_arena_bytes);
 			k_commit<<<1, 64, 0, c->stream>>>(g, 1, st->big_arena.as<uint8_t>(), big_arena_bytes, 1, nullptr, nullptr, prof);
-		} else
-		{
-			// parked transactions resume beside the fresh ones: a second stream between two events (only in rounds that have any -- the
-			// counters of the previous round say so: what is parked now was parked then)
-			const bool resume = g.park_cap && parked_known != 0;
-			if (g.park_cap && (round & 1023u) == 0u) k_park_sweep<<<nblocks((size_t)nid_ + 1, 256), 256, 0, c->stream>>>(st->park_of.as<unsigned>(), nid_ + 1);      // (bt_round_tag)
-			if (resume) {
-				// one workgroup per parked transaction at most (k_reserve has listed those of this window: GraphView::park_list)
-				HIP_TRY(hipEventRecord(st->park_ev[0], c->stream));
-				HIP_TRY(hipStreamWaitEvent(st->park_stream, st->park_ev[0], 0));
-				k_resume<<<std::min<uint32_t>(parked_known, nwin), 64, 0, st->park_stream>>>(g, nwin, st->arena.as<uint8_t>(), arena_bytes, st->claims.as<unsigned>(), st->live.as<uint8_t>(), prof);
-				HIP_TRY(hipEventRecord(st->park_ev[1], st->park_stream));
-			}
-			k_commit<<<nwin, 64, 0, c->stream>>>(g, nwin, st->arena.as<uint8_t>(), arena_bytes, 0, st->claims.as<unsigned>(), st->live.as<uint8_t>(), prof);
-			if (resume) HIP_TRY(hipStreamWaitEvent(c->stream, st->park_ev[1], 0));
+		} else {
+			// parked transactions resume beside the fresh ones, in the same launch: one workgroup per parked transaction at most, in front of
+			// the window's (k_reserve has listed those of this window: GraphView::park_list).  Only in rounds that have any -- the counters
+			// of the previous round say so: what is parked now was parked then
+			const uint32_t nresume = g.park_cap ? std::min<uint32_t>(parked_known, nwin) : 0u;
+			k_commit<<<nresume + nwin, 64, 0, c->stream>>>(g, nwin, st->arena.as<uint8_t>(), arena_bytes, 0, st->claims.as<unsigned>(), st->live.as<uint8_t>(), prof);
 		}
 		if (sampled) HIP_TRY(hipEventRecord(ev[3], c->stream));
 		timed_commit = sampled;
@@ -592,8 +586,8 @@ struct DeviceBackend {
 	{
 		read_ctr();
 		if (sel_pending) sel_ready = true;                          // the snapshot holds the selection launched before it as well
-		float ms = 0;
 		if (timed_commit) {
+			float ms = 0;
 			hipError_t e = hipEventElapsedTime(&ms, ev[2], ev[3]);      // (the post of the selection behind them has arrived: normally complete)
 			if (e == hipErrorNotReady) { HIP_TRY(hipEventSynchronize(ev[3])); e = hipEventElapsedTime(&ms, ev[2], ev[3]); }
 			HIP_TRY(e);
@@ -864,13 +858,12 @@ struct StageAttempt {
 		be.g.k = k; be.g.D = D;
 	}
 
-	// ---- parked transactions: their stream and events (made once per context), park_of and the view's fields
+	// ---- parked transactions: park_of and the view's fields
 	void setup_park()
 	{
 		be.g.park_cap = park_cap; be.g.park_of = nullptr; be.g.slice_busy = nullptr; be.g.shadow_base = 0; be.park_slices = 0;
 		be.g.park_hold = 0; be.g.any_parked = 0; be.g.park_list = nullptr;
 		if (!park_cap) return;
-		if (!st->park_stream) { HIP_TRY(hipStreamCreateWithFlags(&st->park_stream, hipStreamNonBlocking)); for (auto &e : st->park_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
 		st->park_of.ensure(((size_t)be.nid_ + 1) * 4);
 		be.park_slices = (size_t)window_max + 64;
 		be.g.park_of = st->park_of.as<unsigned>(); be.g.slice_busy = st->slice_busy.as<uint8_t>(); be.g.shadow_base = window_max;
