@@ -282,11 +282,14 @@ sbl_status sbl_correct_stats(const sbl_ctx *ctx, sbl_correct_stats_t *out);
  * U(w) = 25 (min(n, m) - (w + 1)) - 75 (|m - n| + 2 (w + 1)) proves that score and trace equal the unbanded ones, otherwise w is doubled
  * and the pair runs again, until the band covers the matrix.  The first w is 64 (SBL_TEST_GALIGN_W0: test switch; results do not
  * depend on it, band_w and passes do).
- * A pair is SKIPPED -- status SBL_GALIGN_SKIPPED, no score, no runs, no rows; never an error, never a partial result -- when the trace
- * codes (2 bits per band cell) at the w it has reached exceed the per-alignment cap (8 GiB; SBL_TEST_GALIGN_CAP_KB: test switch), when
- * the band's score diagonal no longer fits the LDS (more than 12288 band offsets) or when 75 (n + m) does not fit the 32-bit scores
- * (n + m >= 2^23).  A batch is split so that the codes of one launch stay below 32 GiB
- * (SBL_TEST_GALIGN_TOTAL_KB: test switch).
+ * A pair is SKIPPED -- status SBL_GALIGN_SKIPPED, no score, no runs, no rows; never an error, never a partial result -- by one of three
+ * limits.  In either mode of sbl_align_set_wide (below): when the trace codes (2 bits per band cell, 4 with a gap opening cost) at the w
+ * it has reached exceed the per-alignment cap (8 GiB; SBL_TEST_GALIGN_CAP_KB: test switch), and when 75 (n + m) does not fit the 32-bit
+ * scores (n + m >= 2^23).  With the wide setting OFF (the default) also when the band's score diagonal no longer fits the LDS: more
+ * than 12288 band offsets |m - n| + 2 w + 1, 4992 with a gap opening cost -- for pairs of bacterial blocks this is the limit that
+ * binds, at the first w already once the lengths differ by more than 12159 (4863).  With the setting ON the band limit is gone and only
+ * the first two remain: the cap on the codes binds, about (n + m + 1) * offsets / 8 bytes (twice that with a gap opening cost).  A
+ * batch is split so that the codes of one launch stay below 32 GiB (SBL_TEST_GALIGN_TOTAL_KB: test switch).
  *
  * sbl_pair_desc: two half-open ranges of the ORIGINAL records on the device; rev: read downwards through the complement table.
  * sbl_align_run: `len` columns of one kind -- '=' equal, 'X' unequal, 'I' a[i] over '-', 'D' '-' over b[j].
@@ -319,12 +322,34 @@ sbl_status sbl_align_pairs(sbl_ctx *ctx, uint64_t npairs, const sbl_pair_desc *d
  * o == 0 is the alignment above EXACTLY, ties included (E <= H everywhere, so every gap column closes), and runs the same kernel.
  * Band, certificate (the same U(w): o >= 0 only lowers a path that leaves the band) and doubling are unchanged.  With o > 0 the trace
  * codes take 4 bits per band cell -- the two caps apply to the doubled size -- and three score arrays share the 64 KiB of LDS: a pair is
- * SKIPPED beyond 4992 band offsets (12288 with o == 0), so doubling from 64 stops at w = 2048.
+ * SKIPPED beyond 4992 band offsets (12288 with o == 0), so doubling from 64 stops at w = 2048 -- unless sbl_align_set_wide (below) is on.
  * sbl_align_set_gap_open: holds for every later sbl_align_pairs / _unique_blocks / _groups / _block_groups call of the context (default 0);
  * SBL_ERR_BAD_ARG above 100000, the value stays as it was.  Not used by sbl_correct_boundaries, whose alignment is the reference's.
  * SBL_TEST_GALIGN_AFFINE=1: test switch, sends o == 0 through the three-state kernel. */
 sbl_status sbl_align_set_gap_open(sbl_ctx *ctx, uint32_t open);
 sbl_status sbl_align_get_gap_open(const sbl_ctx *ctx, uint32_t *open);
+
+/* Bands beyond the LDS.  on = 1: a pair whose band has more offsets than the widest LDS class holds (12288, 4992 with a
+ * gap opening cost) is no longer skipped but runs in one further band class of the same kernel, whose score arrays lie in a buffer of
+ * the context on the device; nothing bounds the offsets of that class, and doubling goes on into it until the certificate holds or the
+ * band covers the matrix.  The alignment's definition is untouched -- scores, ties, certificate, runs and rows of a pair do not depend
+ * on the class it ran in -- only which pairs get a result changes; the per-alignment cap and n + m >= 2^23 skip as before.  on = 0
+ * (the default): every call behaves as it did without the setting.
+ * sbl_align_set_wide: holds for every later sbl_align_pairs / _unique_blocks / _groups / _block_groups call of the context;
+ * SBL_ERR_BAD_ARG above 1, the value stays as it was.
+ * sbl_align_wide_stats: what that class did in the last sbl_align_* call (all zero with the setting off); sbl_align_stats_t goes on
+ * counting every class, this one included.
+ * SBL_TEST_GALIGN_WIDE_FROM=<offsets>: test switch; with the setting on, pairs with more band offsets than this take the class (default
+ * and most: the model's limit above; 0 sends every pair there).  Results, band_w and passes do not depend on it. */
+typedef struct {
+	uint64_t pairs;                  /* pairs that ran at least one pass in the class */
+	uint64_t passes, launches;       /* alignments run in it; its launches */
+	uint64_t cells;                  /* band slots it swept, counted as in sbl_align_stats_t */
+	double kernel_ms;                /* device time of its launches (event pairs) */
+} sbl_align_wide_stats_t;
+sbl_status sbl_align_set_wide(sbl_ctx *ctx, uint32_t on);
+sbl_status sbl_align_get_wide(const sbl_ctx *ctx, uint32_t *on);
+sbl_status sbl_align_wide_stats(const sbl_ctx *ctx, sbl_align_wide_stats_t *out);
 
 /* The pairs C-Sibelia.py aligns (determine_unique_block, src/csibelia/C-Sibelia.py:314-323) out of the context's CURRENT block list
  * (after sbl_postprocess / sbl_correct_boundaries): the ids with exactly two instances, one on records 0 .. n_reference_chr - 1 and

@@ -30,6 +30,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_correct_boundaries", "sbl_align_windows", "sbl_correct_stats",
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
+           "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_tiny_index"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -95,6 +96,10 @@ ALIGN_RUN_DTYPE = np.dtype([("op", "<u4"), ("len", "<u4")])
 class AlignStats(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("skipped", C.c_uint64), ("passes", C.c_uint64), ("launches", C.c_uint64), ("cells", C.c_uint64),
                 ("kernel_ms", C.c_double), ("spell_ms", C.c_double)]
+
+
+class AlignWideStats(C.Structure):                # sbl_align_wide_stats_t
+    _fields_ = [("pairs", C.c_uint64), ("passes", C.c_uint64), ("launches", C.c_uint64), ("cells", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class PairAlignment:
@@ -203,6 +208,9 @@ def load_library():
         L.sbl_align_block_groups.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)] + gtail
         L.sbl_align_set_gap_open.argtypes = [C.c_void_p, C.c_uint32]
         L.sbl_align_get_gap_open.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.sbl_align_set_wide.argtypes = [C.c_void_p, C.c_uint32]
+        L.sbl_align_get_wide.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.sbl_align_wide_stats.argtypes = [C.c_void_p, C.POINTER(AlignWideStats)]
         L.sbl_uncovered_calls.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_spell_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_spell_text_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -520,6 +528,27 @@ class BlockFinder:
         v = C.c_uint32()
         self._check(self.L.sbl_align_get_gap_open(self.h, C.byref(v)), "sbl_align_get_gap_open")
         return v.value
+
+    def set_wide(self, on) -> None:
+        """Bands beyond the LDS in every later align_* call of this finder (include/sibelia_amd.h): a pair whose band has
+        more offsets than the widest LDS class holds runs in the global band class instead of being skipped.  False (the default): as
+        without the setting.  Anything but 0 / 1 is refused and the value stays as it was."""
+        if not 0 <= int(on) <= 2 ** 32 - 1:
+            raise SibeliaError("sbl_align_set_wide: bad argument (the wide band setting is 0 or 1)")
+        self._check(self.L.sbl_align_set_wide(self.h, int(on)), "sbl_align_set_wide")
+
+    @property
+    def wide(self) -> int:
+        v = C.c_uint32()
+        self._check(self.L.sbl_align_get_wide(self.h, C.byref(v)), "sbl_align_get_wide")
+        return v.value
+
+    def align_wide_stats(self) -> dict:
+        """What the global band class did in the last align_* call: pairs (that ran at least one pass in it), passes, launches, cells,
+        kernel_ms.  All zero with the setting off; align_stats() counts every class, this one included."""
+        s = AlignWideStats()
+        self._check(self.L.sbl_align_wide_stats(self.h, C.byref(s)), "sbl_align_wide_stats")
+        return {f: getattr(s, f) for f, _ in s._fields_}
 
     def uncovered_calls(self, lists: Sequence[np.ndarray], min_block_size: int, n_reference_chr: int) -> np.ndarray:
         """What C-Sibelia.py calls from the regions no block covers (reference src/csibelia/C-Sibelia.py:373-427):

@@ -19,19 +19,22 @@
 //             side (two per diagonal, four with the affine model), no barrier.  Wider bands: one score array per state in LDS, 256 or
 //             M::WIDE_THREADS lanes, one barrier per diagonal.  The bases never fit the LDS as a whole: per 64 diagonals the stretch of
 //             a and of b those diagonals touch is staged from the original records (a reverse instance downwards through complement1).
+//             Beyond the LDS (sbl_align_set_wide): GaWide<M>, the same sweep with the score arrays in the pair's slice of
+//             a device buffer and the bases read from the records; nothing bounds its W.
 //   trace     one wave: lane t fetches the code t steps ahead along the direction of the current step, one ballot consumes the run.
 //             It emits runs (op, length); the certificate is checked first -- a pair that fails it is not traced.
 //   spelling  k_spell_groups, output-stationary like blockseq.hip: a lane owns 16 bytes of the rows, finds its group, its row and its
 //             run by binary search over tables the host made from the runs, and writes them with one vector store.  The two gapped
 //             rows of a pair are the rows of a group of one member (gm_spell).
 //   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
-//             grouped by band class (register / LDS 256 / LDS wide, the limits the model's) and chunked under the total cap on the
-//             trace codes.
+//             grouped by band class (register / LDS 256 / LDS wide, the limits the model's; with sbl_align_set_wide a fourth, the
+//             global one, for the pairs beyond them) and chunked under the total cap on the trace codes.
 //   groups    sbl_align_groups / sbl_align_block_groups: a centre-star multiple alignment per group of instances.  Every
 //             member against the group's first instance through the same passes (ga_passes); the gap slots of a group merged on the
 //             host from the runs; k_spell_groups spells the rows.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "sbl_align.h"
 
@@ -170,10 +173,32 @@ struct GaAffine {
 	}
 };
 
+// the global band class of a model: states, cell, border, codes and walk are M's own; the score arrays lie in the pair's
+// slice of a device buffer, not in LDS, and the bases are read from the records, so no limit on W is left.  1024 lanes with either
+// model: the class starts above 624 (affine) / 1536 (linear) quads of cells a diagonal, so every lane has a quad on every full diagonal,
+// and the 16 waves are what hides the latency of the score loads -- a workgroup has its CU to itself (such pairs are few), and neither
+// model's sweep needs more than the 128 VGPRs that size leaves a lane.
+template <class M> struct GaWide : M {
+	static constexpr bool GLOBAL = true;
+	static constexpr unsigned WIDE_THREADS = 1024;
+};
+template <class M, class = void> struct ga_is_global { static constexpr bool value = false; };
+template <class M> struct ga_is_global<M, std::enable_if_t<M::GLOBAL>> { static constexpr bool value = true; };
+
 struct GaView {                                         // what a cell needs to find itself
 	int n, m, lo, w, W, imin, jmin, go;
-	const uint8_t *sa, *sb;
+	const uint8_t *sa, *sb;                             // the staged stretches of a and b (from imin / jmin)
+	const uint8_t *seq;                                 // the global class: the records, and the job that says where the pair's bases lie in them
+	const GaJob *J;
 };
+
+// a[i] == b[j]: from the staged stretches; the global class reads the records (neighbouring lanes read neighbouring bytes)
+template <class M> __device__ inline bool ga_eq(const GaView &V, int i, int j)
+{
+	if constexpr (ga_is_global<M>::value)
+		return strand_base(V.seq, V.J->src_a, V.J->n, (unsigned)i, V.J->rev_a) == strand_base(V.seq, V.J->src_b, V.J->m, (unsigned)j, V.J->rev_b);
+	else return V.sa[i - V.imin] == V.sb[j - V.jmin];
+}
 
 // the 4 cells of diagonal d among offsets 8 q + P + 2 c -> their codes.  s: the lane's 8 offsets of every state (REG) -- prev / next:
 // s[.][7] of lane q - 1, s[.][0] of lane q + 1
@@ -199,7 +224,7 @@ template <class M, int P> __device__ inline unsigned ga_quad_reg(const GaView &V
 				up[t] = P == 0 && c == 0 ? prev[t] : s[t][xu];
 				lf[t] = P == 1 && c == 3 ? next[t] : s[t][xl];
 			}
-			code = M::cell(dg, up, lf, V.sa[i - V.imin] == V.sb[j - V.jmin], V.go, v);
+			code = M::cell(dg, up, lf, ga_eq<M>(V, i, j), V.go, v);
 		}
 #pragma unroll
 		for (int t = 0; t < M::STATES; t++) s[t][2 * c + P] = v[t];
@@ -209,8 +234,9 @@ template <class M, int P> __device__ inline unsigned ga_quad_reg(const GaView &V
 	return bits;
 }
 
-// the same over the score arrays in LDS: state t at S + t (W + 2), S[k + 1] = offset k, S[0] and S[W + 1] are minus infinity
-template <class M> __device__ inline unsigned ga_quad_lds(const GaView &V, int d, int q, int p, int *S, int &score)
+// the same over the score arrays in memory (LDS, or the pair's slice of the score buffer): state t at S + t (W + 2), S[k + 1] = offset k,
+// S[0] and S[W + 1] are minus infinity
+template <class M> __device__ inline unsigned ga_quad_mem(const GaView &V, int d, int q, int p, int *S, int &score)
 {
 	unsigned bits = 0;
 #pragma unroll
@@ -229,7 +255,7 @@ template <class M> __device__ inline unsigned ga_quad_lds(const GaView &V, int d
 				const int *X = S + t * (V.W + 2);
 				dg[t] = X[k + 1]; up[t] = X[k]; lf[t] = X[k + 2];
 			}
-			code = M::cell(dg, up, lf, V.sa[i - V.imin] == V.sb[j - V.jmin], V.go, v);
+			code = M::cell(dg, up, lf, ga_eq<M>(V, i, j), V.go, v);
 		}
 #pragma unroll
 		for (int t = 0; t < M::STATES; t++) S[t * (V.W + 2) + k + 1] = v[t];
@@ -241,22 +267,27 @@ template <class M> __device__ inline unsigned ga_quad_lds(const GaView &V, int d
 
 // M: the gap model; go: its opening cost (the linear model ignores it).  REG: one wave, 8 score registers per state and lane.  Otherwise
 // M::STATES arrays of W + 2 scores in LDS and one barrier per diagonal: every cell reads the other parity and writes its own.
+// M = GaWide<.>: those arrays in the pair's slice of the score buffer instead -- the host lays a table of the slices' addresses behind the
+// job descriptors, so that GaJob and this signature, and with them the code of the LDS and register classes, stay as they were -- nothing staged.  The one barrier per diagonal orders the workgroup's stores
+// to its slice against its own later loads as it does in LDS; no other workgroup touches the slice.
 template <class M, bool REG> __global__ __launch_bounds__(REG ? 64 : M::WIDE_THREADS) void k_block_align(const uint8_t *__restrict__ seq, const GaJob *__restrict__ jobs, int go,
                                                                                                        uint8_t *codes_all, sbl_align_run *runs_all, GaOut *__restrict__ out)
 {
 	typedef typename M::Code Code;
+	constexpr bool GLOBAL = ga_is_global<M>::value;
 	static_assert(8 * sizeof(Code) == 4 * M::CODE_BITS, "a lane's 4 cells of a diagonal are one store");
+	static_assert(!(GLOBAL && REG), "the global class has no register form");
 	extern __shared__ int ga_lds[];
 	__shared__ int s_score;
 	const GaJob J = jobs[blockIdx.x];
 	const int n = (int)J.n, m = (int)J.m, w = (int)J.w, W = (int)J.W, B = (int)J.B, Q = B / (int)sizeof(Code);      // Q: lanes that hold cells
 	const int lo = m - n < 0 ? m - n : 0, omin = lo - w, omax = omin + W - 1;
 	const int tid = (int)threadIdx.x, T = (int)blockDim.x;
-	int *const S = ga_lds;                                                  // LDS kernel only
+	int *const S = GLOBAL ? reinterpret_cast<int *const *>(jobs + gridDim.x)[blockIdx.x] : ga_lds;      // LDS and global kernels only
 	uint8_t *const sa = reinterpret_cast<uint8_t *>(ga_lds + (REG ? 0 : M::STATES * (W + 2)));
 	uint8_t *const sb = sa + ga_seg((unsigned)W);
 	uint8_t *const mycodes = codes_all + J.code_off;
-	GaView V{n, m, lo, w, W, 0, 0, go, sa, sb};
+	GaView V{n, m, lo, w, W, 0, 0, go, sa, sb, seq, &J};
 	// REG: the lane's 8 offsets of state t are s[t][0 .. 7].  One array per state: as a single [STATES][8] object the compiler's resource
 	// report shows 78 VGPRs and 6 waves for the affine model instead of 59 and 7.  s[] is a view for the loops over the states: they are
 	// unrolled (the pragmas say so), every index is then a constant and the arrays stay in registers.
@@ -277,11 +308,13 @@ template <class M, bool REG> __global__ __launch_bounds__(REG ? 64 : M::WIDE_THR
 		int imin = (dbot - omax) >> 1, imax = (dtop - omin) >> 1, jmin = (dbot + omin) >> 1, jmax = (dtop + omax) >> 1;
 		imin = imin < 0 ? 0 : imin; imax = imax > n - 1 ? n - 1 : imax;
 		jmin = jmin < 0 ? 0 : jmin; jmax = jmax > m - 1 ? m - 1 : jmax;
-		__syncthreads();                                                    // the previous stretch is no longer read
-		for (int t = tid; t <= imax - imin; t += T) sa[t] = strand_base(seq, J.src_a, J.n, (unsigned)(imin + t), J.rev_a);
-		for (int t = tid; t <= jmax - jmin; t += T) sb[t] = strand_base(seq, J.src_b, J.m, (unsigned)(jmin + t), J.rev_b);
-		V.imin = imin; V.jmin = jmin;
-		__syncthreads();
+		__syncthreads();                                                    // the previous stretch is no longer read; the scores are initialised
+		if constexpr (!GLOBAL) {
+			for (int t = tid; t <= imax - imin; t += T) sa[t] = strand_base(seq, J.src_a, J.n, (unsigned)(imin + t), J.rev_a);
+			for (int t = tid; t <= jmax - jmin; t += T) sb[t] = strand_base(seq, J.src_b, J.m, (unsigned)(jmin + t), J.rev_b);
+			V.imin = imin; V.jmin = jmin;
+			__syncthreads();
+		}
 		for (int d = dtop; d >= dbot; d--) {
 			const int p = (d - lo + w) & 1;                                  // the parity of the offsets that hold a cell on this diagonal
 			Code *const row = reinterpret_cast<Code *>(mycodes + (u64)(unsigned)d * (unsigned)B);
@@ -296,7 +329,7 @@ template <class M, bool REG> __global__ __launch_bounds__(REG ? 64 : M::WIDE_THR
 				const unsigned bits = p ? ga_quad_reg<M, 1>(V, d, tid, s, prev, next, score) : ga_quad_reg<M, 0>(V, d, tid, s, prev, next, score);
 				if (tid < Q) row[tid] = (Code)bits;
 			} else {
-				for (int q = tid; q < Q; q += T) row[q] = (Code)ga_quad_lds<M>(V, d, q, p, S, score);
+				for (int q = tid; q < Q; q += T) row[q] = (Code)ga_quad_mem<M>(V, d, q, p, S, score);
 				__syncthreads();
 			}
 		}
@@ -412,8 +445,10 @@ unsigned ga_env(const char *name, unsigned fallback)
 
 struct Pending { size_t at; unsigned w; };
 
-// the one launch of a chunk of jobs of one band class (reg: the register class)
-template <class M> void ga_launch_cls(sbl_ctx *c, bool reg, unsigned blocks, unsigned threads, size_t lds)
+constexpr int GA_CLS_GLOBAL = 3;                       // band classes: 0 register, 1 LDS of 256 lanes, 2 LDS wide, 3 global (sbl_align_set_wide)
+
+// the one launch of a chunk of jobs of one band class
+template <class M> void ga_launch_cls(sbl_ctx *c, int cls, unsigned blocks, unsigned threads, size_t lds)
 {
 	const uint8_t *seq = c->d_orig_ch.as<uint8_t>();
 	const GaJob *jobs = c->d_ga_job.as<GaJob>();
@@ -421,33 +456,37 @@ template <class M> void ga_launch_cls(sbl_ctx *c, bool reg, unsigned blocks, uns
 	uint8_t *codes = c->d_ga_codes.as<uint8_t>();
 	sbl_align_run *runs = c->d_ga_runs.as<sbl_align_run>();
 	GaOut *out = c->d_ga_out.as<GaOut>();
-	if (reg) k_block_align<M, true><<<blocks, threads, lds, c->stream>>>(seq, jobs, go, codes, runs, out);
+	if (cls == 0) k_block_align<M, true><<<blocks, threads, lds, c->stream>>>(seq, jobs, go, codes, runs, out);
+	else if (cls == GA_CLS_GLOBAL) k_block_align<GaWide<M>, false><<<blocks, threads, 0, c->stream>>>(seq, jobs, go, codes, runs, out);
 	else k_block_align<M, false><<<blocks, threads, lds, c->stream>>>(seq, jobs, go, codes, runs, out);
 }
 
 // what the host needs of a gap model
 struct GaModel {
 	unsigned reg_w, mid_w, max_w;        // the most offsets of the register class, of the LDS class of 256 lanes, of all
-	unsigned wide_threads;               // lanes of the widest class
-	unsigned score_bytes, code_bytes;    // LDS bytes of scores per offset; code bytes of a lane's 4 cells of a diagonal
-	void (*launch)(sbl_ctx *, bool, unsigned, unsigned, size_t);
+	unsigned wide_threads, global_threads;      // lanes of the widest LDS class, of the global class
+	unsigned score_bytes, code_bytes;    // bytes of scores per offset; code bytes of a lane's 4 cells of a diagonal
+	void (*launch)(sbl_ctx *, int, unsigned, unsigned, size_t);
 };
 template <class M> GaModel ga_model()
 {
-	return GaModel{M::REG_W, M::MID_W, M::MAX_W, M::WIDE_THREADS, 4 * M::STATES, sizeof(typename M::Code), ga_launch_cls<M>};
+	return GaModel{M::REG_W, M::MID_W, M::MAX_W, M::WIDE_THREADS, GaWide<M>::WIDE_THREADS, 4 * M::STATES, sizeof(typename M::Code), ga_launch_cls<M>};
 }
 
 // one pass: the pending pairs of one band class at their current w, chunked under the total cap.  Fills res (score, status) and appends
 // the runs of the pairs that pass the certificate; returns those that have to run again.
-void ga_launch(sbl_ctx *c, const GaModel &model, const std::vector<GaJob> &jobs, const std::vector<size_t> &which, int cls, std::vector<uint8_t> &passed)
+void ga_launch(sbl_ctx *c, const GaModel &model, const std::vector<GaJob> &jobs, const std::vector<size_t> &which, int cls, std::vector<uint8_t> &passed,
+               std::vector<uint8_t> &ran_global)
 {
+	const bool global = cls == GA_CLS_GLOBAL;
 	const size_t total_cap = getenv("SBL_TEST_GALIGN_TOTAL_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_TOTAL_KB", 1) << 10 : GA_TOTAL_CAP;
-	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : model.wide_threads;
+	const unsigned threads = cls == 0 ? 64 : cls == 1 ? 256 : global ? model.global_threads : model.wide_threads;
 	std::vector<GaJob> chunk;
 	std::vector<GaOut> got;
+	std::vector<u64> slice;                                                   // the global class: first score of each job's slice, then its address
 	for (size_t at = 0; at < which.size();) {
-		chunk.clear();
-		u64 bytes = 0, nrun = 0;
+		chunk.clear(); slice.clear();
+		u64 bytes = 0, nrun = 0, nscore = 0, cells = 0;
 		size_t lds = 0;
 		const size_t first = at;
 		for (; at < which.size(); at++) {
@@ -456,17 +495,35 @@ void ga_launch(sbl_ctx *c, const GaModel &model, const std::vector<GaJob> &jobs,
 			if (!chunk.empty() && bytes + need > total_cap) break;
 			j.code_off = bytes; j.run_off = nrun;
 			bytes += need; nrun += (u64)j.n + j.m + 1;
-			lds = std::max(lds, (cls ? (size_t)(j.W + 2) * model.score_bytes : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
+			if (global) {                                                     // its slice of the score buffer, kept to whole cache lines
+				slice.push_back(nscore);
+				nscore += ((u64)(j.W + 2) * model.score_bytes / 4 + 63) / 64 * 64;
+				ran_global[which[at]] = 1;
+			}
+			else lds = std::max(lds, (cls ? (size_t)(j.W + 2) * model.score_bytes : 0) + 2 * (size_t)((j.W + GA_CHUNK) / 2 + 8));
 			chunk.push_back(j);
-			c->align_stats.cells += (u64)(j.n + j.m + 1) * ((j.W + 1) / 2);
+			cells += (u64)(j.n + j.m + 1) * ((j.W + 1) / 2);
 		}
+		c->d_ga_job.ensure(chunk.size() * (sizeof(GaJob) + sizeof(u64)));
 		al_upload(c, c->d_ga_job, chunk); c->d_ga_codes.ensure((size_t)bytes); c->d_ga_out.ensure(chunk.size() * sizeof(GaOut));
 		c->d_ga_runs.ensure((size_t)nrun * sizeof(sbl_align_run));
+		if (global) {                                                         // the table of slice addresses behind the descriptors
+			c->d_ga_score.ensure((size_t)nscore * sizeof(int));
+			for (u64 &x : slice) x = (u64)(uintptr_t)(c->d_ga_score.as<int>() + x);
+			HIP_TRY(hipMemcpyAsync(c->d_ga_job.as<GaJob>() + chunk.size(), slice.data(), slice.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+		}
 		got.resize(chunk.size());
-		c->align_stats.kernel_ms += al_timed_launch(c, [&] { model.launch(c, cls == 0, (unsigned)chunk.size(), threads, lds); },
-		                                            got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut));
+		const float ms = al_timed_launch(c, [&] { model.launch(c, cls, (unsigned)chunk.size(), threads, lds); }, got.data(), c->d_ga_out.p, chunk.size() * sizeof(GaOut));
+		c->align_stats.kernel_ms += ms;
 		c->align_stats.launches++;
 		c->align_stats.passes += chunk.size();
+		c->align_stats.cells += cells;
+		if (global) {
+			c->wide_stats.kernel_ms += ms;
+			c->wide_stats.launches++;
+			c->wide_stats.passes += chunk.size();
+			c->wide_stats.cells += cells;
+		}
 		u64 more = 0;
 		for (const GaOut &o : got) more += o.ok ? o.nruns : 0;
 		size_t fill = c->ga_runs.size();
@@ -492,12 +549,16 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 	const size_t N = desc.size();
 	const size_t pair_cap = getenv("SBL_TEST_GALIGN_CAP_KB") ? (size_t)ga_env("SBL_TEST_GALIGN_CAP_KB", 1) << 10 : GA_PAIR_CAP;
 	const unsigned w0 = ga_env("SBL_TEST_GALIGN_W0", GA_W0);
+	const auto from_env = [](unsigned most) { const char *v = getenv("SBL_TEST_GALIGN_WIDE_FROM"); return v ? (unsigned)std::min<long long>(std::max(atoll(v), 0ll), most) : most; };
 	// the one place that decides the gap model: a gap opening cost is set (SBL_TEST_GALIGN_AFFINE=1: test switch, sends o == 0 through
 	// the affine model as well)
 	const char *e = getenv("SBL_TEST_GALIGN_AFFINE");
 	const bool affine = c->gap_open > 0 || (e && atoi(e) == 1);
 	const GaModel model = affine ? ga_model<GaAffine>() : ga_model<GaLinear>();
+	// sbl_align_set_wide: the pairs beyond the widest LDS class (SBL_TEST_GALIGN_WIDE_FROM: test switch, beyond fewer offsets) take the global one
+	const unsigned wide_from = from_env(model.max_w);
 	c->align_stats = sbl_align_stats_t{};
+	c->wide_stats = sbl_align_wide_stats_t{};
 	c->align_stats.pairs = N;
 	c->ga_res.assign(N, sbl_pair_result{});
 	c->ga_runs.clear();
@@ -520,8 +581,8 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 		}
 		pending.push_back(Pending{i, w0});
 	}
-	std::vector<uint8_t> passed(N, 0);
-	std::vector<size_t> cls[3];
+	std::vector<uint8_t> passed(N, 0), ran_global(N, 0);
+	std::vector<size_t> cls[GA_CLS_GLOBAL + 1];
 	while (!pending.empty()) {
 		for (auto &v : cls) v.clear();
 		for (Pending &p : pending) {
@@ -531,14 +592,15 @@ void ga_passes(sbl_ctx *c, std::vector<GaJob> &jobs)
 			j.full = j.w >= mn;
 			j.W = diff + 2 * j.w + 1;
 			j.B = ((j.W + 1) / 2 + 3) / 4 * model.code_bytes;                 // the lanes that hold cells on a diagonal, each with the codes of its 4
-			if (j.W > model.max_w || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
-			cls[j.W <= model.reg_w ? 0 : j.W <= model.mid_w ? 1 : 2].push_back(p.at);
+			if ((!c->align_wide && j.W > model.max_w) || (u64)(j.n + j.m + 1) * j.B > pair_cap) { c->ga_res[p.at].status = SBL_GALIGN_SKIPPED; passed[p.at] = 1; continue; }
+			cls[c->align_wide && j.W > wide_from ? GA_CLS_GLOBAL : j.W <= model.reg_w ? 0 : j.W <= model.mid_w ? 1 : 2].push_back(p.at);
 		}
-		for (int k = 0; k < 3; k++) if (!cls[k].empty()) ga_launch(c, model, jobs, cls[k], k, passed);
+		for (int k = 0; k <= GA_CLS_GLOBAL; k++) if (!cls[k].empty()) ga_launch(c, model, jobs, cls[k], k, passed, ran_global);
 		std::vector<Pending> again;
 		for (const Pending &p : pending) if (!passed[p.at]) again.push_back(Pending{p.at, jobs[p.at].w * 2});
 		pending.swap(again);
 	}
+	for (uint8_t g : ran_global) c->wide_stats.pairs += g;
 	c->stats.device_bytes = sbl_devbuf_total().load();
 }
 
@@ -726,6 +788,28 @@ extern "C" sbl_status sbl_align_get_gap_open(const sbl_ctx *c, uint32_t *open)
 {
 	if (!c || !open) return SBL_ERR_BAD_ARG;
 	*open = c->gap_open;
+	return SBL_OK;
+}
+
+extern "C" sbl_status sbl_align_set_wide(sbl_ctx *c, uint32_t on)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(on <= 1, SBL_ERR_BAD_ARG, "the wide band setting is 0 or 1");
+		c->align_wide = on;
+	});
+}
+
+extern "C" sbl_status sbl_align_get_wide(const sbl_ctx *c, uint32_t *on)
+{
+	if (!c || !on) return SBL_ERR_BAD_ARG;
+	*on = c->align_wide;
+	return SBL_OK;
+}
+
+extern "C" sbl_status sbl_align_wide_stats(const sbl_ctx *c, sbl_align_wide_stats_t *out)
+{
+	if (!c || !out) return SBL_ERR_BAD_ARG;
+	*out = c->wide_stats;
 	return SBL_OK;
 }
 

@@ -109,12 +109,15 @@ struct sbl_ctx {
 	// sbl_align_pairs / sbl_align_unique_blocks (block_align.hip): jobs, trace codes, per-job results, runs; the spans and the rows of
 	// k_spell_groups (the rows come back through h_bs_text); what the calls hand out
 	DevBuf d_ga_job, d_ga_codes, d_ga_out, d_ga_runs, d_ga_span, d_ga_text;
+	DevBuf d_ga_score;                   // the global band class: the score arrays of a chunk's pairs, one slice each
 	std::vector<sbl_pair_result> ga_res;
 	std::vector<sbl_align_run> ga_runs;
 	std::vector<sbl_pair_desc> ga_desc;
 	std::vector<int32_t> ga_ids;
 	sbl_align_stats_t align_stats{};
 	uint32_t gap_open = 0;               // sbl_align_set_gap_open: the cost of opening a gap run (0: the linear model of k_block_align, else the affine one)
+	uint32_t align_wide = 0;             // sbl_align_set_wide: pairs beyond the LDS band classes run in the global class instead of being skipped
+	sbl_align_wide_stats_t wide_stats{}; // ... and what that class did in the last call
 	// sbl_align_groups / sbl_align_block_groups: the same pair passes (ga_desc: centre against member); what the calls hand out.  Instances,
 	// merged gap slots and groups of k_spell_groups: every sbl_align_* call spells through them, a pair as a group of one member
 	DevBuf d_gm_inst, d_gm_slot, d_gm_group;

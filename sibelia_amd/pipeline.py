@@ -7,7 +7,8 @@ standard output); `main` writes the files and prints the text (python -m sibelia
 
 --maf / --variants (two input files) add what the reference's comparison tool C-Sibelia.py makes of such a run: the alignments of the
 unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks`).  --gapopen N gives those alignments and the ones of
---multimaf an affine gap cost (N for opening a gap run).  --multimaf (any number of input files) writes a
+--multimaf an affine gap cost (N for opening a gap run); --wideband aligns the blocks whose band is beyond the LDS band
+classes instead of leaving them out.  --multimaf (any number of input files) writes a
 multiple alignment of every block with at least two instances (`align_block_groups`); --multivariants (two or more input files) reads
 the calls off those alignments for the blocks with one instance in the first file and at most one in each other file and writes them as
 a multi-sample VCF.  --uncovered adds the rest of C-Sibelia's VCF to
@@ -59,6 +60,11 @@ GAPOPEN_HELP = ("With --maf, --variants, --multimaf or --multivariants: the cost
                 "columns costs N + 75 L (match +25, mismatch -75), so that one insertion or deletion is reported as one run, not as pieces "
                 "around stray matches.  The files record a value above 0 in a header line.  Not applied to --correctboundaries, whose "
                 "alignment is the reference program's own.")
+
+WIDEBAND_HELP = ("With --maf, --variants, --multimaf or --multivariants: also align the blocks whose instances differ in length by more than "
+                 "the score diagonal in on-chip memory holds (about 12000 bases, 4800 with --gapopen), with the score diagonal in device memory; "
+                 "without it such a block is named on standard error and left out.  The alignments themselves are the same, so the "
+                 "files record nothing about it.")
 
 NOT_WRITTEN = ("The Circos files (circos/) and d3_blocks_diagram.html of the reference program are not written: "
                "they are instantiated from templates embedded in the reference's sources.")
@@ -183,6 +189,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--multimaf", default=None, metavar="FILE", help=MULTI_HELP)
     p.add_argument("--multivariants", default=None, metavar="FILE", help=MULTIVARIANTS_HELP)
     p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
+    p.add_argument("--wideband", action="store_true", help=WIDEBAND_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
     p.add_argument("filenames", nargs="+", metavar="fasta", help="FASTA file(s) with nucleotide sequences.")
     return p
@@ -220,6 +227,8 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
     if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
+    if opt.wideband and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None:
+        raise PipelineError("--wideband widens the bands of the alignments: it needs at least one of --maf, --variants, --multimaf and --multivariants")
     if opt.maf is not None or opt.variants is not None or opt.multimaf is not None or opt.multivariants is not None:
         _check_alignment_files(opt)
     return opt
@@ -429,6 +438,11 @@ def first_base(path: str) -> bytes:
 
 # ------------------------------------------------------------------------------------------ alignments of unique blocks
 
+def skip_limits(opt: argparse.Namespace) -> str:
+    """The limits that can leave a block without an alignment: --wideband takes the band width off the list."""
+    return "trace memory or length" if opt.wideband else "trace memory, band width or length"
+
+
 def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: int, complain: Callable[[str], None],
                         history: Optional[Sequence] = None) -> Dict[str, bytes]:
     """--maf / --variants: what C-Sibelia.py does after the reference program has run (src/csibelia/C-Sibelia.py:343-368, :473-484,
@@ -446,7 +460,7 @@ def align_unique_blocks(bf, opt: argparse.Namespace, names: Sequence[str], nfirs
     for block, (ca, sa, ea, ra, cb, sb, eb, rb), al in zip(ids, descs, aligned):
         if al.status != GALIGN_OK:
             complain("block %d not aligned: %s:%d-%d against %s:%d-%d is beyond the limits of one alignment "
-                     "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, names[ca], sa + 1, ea, names[cb], sb + 1, eb))
+                     "(%s, DESIGN.md 0.2)\n" % (block, names[ca], sa + 1, ea, names[cb], sb + 1, eb, skip_limits(opt)))
             continue
         groups.append([formats.maf_line(names[ca], sa, ea, ra, size[ca], al.row_a), formats.maf_line(names[cb], sb, eb, rb, size[cb], al.row_b)])
         if opt.variants is not None:
@@ -519,7 +533,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
         if al.status != GALIGN_OK:
             if opt.multimaf is not None or block in qualify:
                 complain("block %d not aligned: one of its %d instances against %s:%d-%d is beyond the limits of one alignment "
-                         "(trace memory, band width or length, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2]))
+                         "(%s, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2], skip_limits(opt)))
             continue
         if opt.multimaf is not None:
             groups.append([formats.maf_line(names[c], s, e, rev, size[c], row) for (c, s, e, rev), row in zip(inst, al.rows)])
@@ -613,6 +627,8 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 files["blocks_sequences.fasta"] = bf.blocks_sequences(None, names)
             if opt.gapopen:                       # after the boundary correction, which keeps the reference's own alignment
                 bf.set_gap_open(opt.gapopen)
+            if opt.wideband:
+                bf.set_wide(True)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
             if opt.multimaf is not None or opt.multivariants is not None:      # likewise on the final list
