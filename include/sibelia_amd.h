@@ -193,6 +193,12 @@ typedef struct { uint32_t status, bif_count; uint64_t first_pos, npos, first_neg
 sbl_status sbl_tiny_index(sbl_ctx *ctx, uint64_t nblocks, const uint64_t *block_first, const sbl_tiny_range *ranges, uint32_t trim_k,
                           int batched, const sbl_tiny_result **res, const sbl_inst **pos, const sbl_inst **neg);
 
+/* TEST ENTRY POINT: the kernel that lists the touched ids for an incremental snapshot of the simplification stage, on a caller's
+ * flags.  touch: nid + 1 bytes (ids 0 .. nid; id nid is never listed).  list: room for nid + 1 words -- the touched ids below nid, in any
+ * order, in its first out[0] words.  out[1]: what the kernel leaves in the count word of the walking probe's list (0).  touch_after /
+ * need_after: nid + 1 bytes each, what the kernel leaves in the two flag arrays (0 everywhere). */
+sbl_status sbl_test_touched_list(sbl_ctx *ctx, const uint8_t *touch, uint32_t nid, uint32_t *list, uint32_t *out, uint8_t *touch_after, uint8_t *need_after);
+
 /* what the reference's main runs after GenerateSyntenyBlocks (src/sibelia.cpp:287-315) on the blocks of the last
  * sbl_generate_blocks: Postprocessor::GlueStripes (src/postprocessor.cpp:37-154; skipped when glue == 0) and the texts of
  * blocks_coords.txt (OutputGenerator::ListBlocksIndices, src/outputgenerator.cpp:227-233), genomes_permutations.txt

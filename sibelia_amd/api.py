@@ -31,7 +31,8 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
-           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_tiny_index"]
+           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_tiny_index",
+           "sbl_test_touched_list"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -186,6 +187,7 @@ def load_library():
         L.sbl_record_size.restype = C.c_uint64
         L.sbl_generate_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_synteny_stats.argtypes = [C.c_void_p, C.POINTER(SyntenyStats)]
+        L.sbl_test_touched_list.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sbl_tiny_index.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(TinyRange), C.c_uint32, C.c_int,
                                      C.POINTER(C.POINTER(TinyResult)), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sbl_postprocess.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
@@ -368,6 +370,19 @@ class BlockFinder:
             q = _view((neg.value or 0) + r.first_neg * INST_DTYPE.itemsize, r.nneg, INST_DTYPE)
             out.append((int(r.status), int(r.bif_count), p, q))
         return out
+
+    def test_touched_list(self, touch: np.ndarray):
+        """TEST ENTRY POINT (sbl_test_touched_list, include/sibelia_amd.h): the list of touched ids an incremental snapshot of the
+        simplification stage starts from, for the uint8 flags touch[0 .. nid] (id nid is never listed).
+        -> (listed ids in the kernel's order, the walking probe's count word, touch and need as the kernel leaves them)"""
+        touch = np.ascontiguousarray(touch, dtype=np.uint8)
+        nid = len(touch) - 1
+        lst, out = np.empty(nid + 1, dtype=np.uint32), np.empty(2, dtype=np.uint32)
+        ta, na = np.empty(nid + 1, dtype=np.uint8), np.empty(nid + 1, dtype=np.uint8)
+        self._check(self.L.sbl_test_touched_list(self.h, touch.ctypes.data, nid, lst.ctypes.data, out.ctypes.data, ta.ctypes.data, na.ctypes.data),
+                    "sbl_test_touched_list")
+        assert out[0] <= nid, "k_touched_list counted %d of %d ids" % (out[0], nid)
+        return lst[:int(out[0])].copy(), int(out[1]), ta, na
 
     def _names_array(self, what: str, names: Optional[Sequence[str]]):
         """`names` as the `const char *const *` of the C entry points, which read one name per loaded record (include/sibelia_amd.h);

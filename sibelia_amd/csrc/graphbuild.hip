@@ -244,10 +244,16 @@ __global__ void __launch_bounds__(256) k_clear_counters(unsigned *__restrict__ c
 {
 	for (unsigned i = CTR_ERR + threadIdx.x; i < CTR_COUNT; i += 256) ctr[i] = i == CTR_VIOL ? BT_NONE : 0u;
 }
-// the write stamps are reset with rmax / wmax at the start of every iteration attempt (DeviceBackend::reset_round_state)
-__global__ void __launch_bounds__(256) k_idx_clear_stamps(unsigned long long *__restrict__ bidx, unsigned nblk)
+// What the start of every iteration attempt resets besides rmax / wmax (DeviceBackend::reset_round_state), in ONE launch -- these were
+// three fills and two kernels of a few microseconds each: the owners (own = NONE), the parked transactions (park_of, slice_busy = 0;
+// nullptr: parking is off), the write stamps of the block index (nullptr: no index) and the counters (k_clear_counters).
+__global__ void __launch_bounds__(256) k_reset_iteration(unsigned *__restrict__ ctr, unsigned *__restrict__ own, unsigned *__restrict__ park_of, unsigned nidp,
+                                                         uint8_t *__restrict__ slice_busy, unsigned nslices, unsigned long long *__restrict__ bidx, unsigned nblk)
 {
-	const unsigned blk = blockIdx.x * blockDim.x + threadIdx.x;
-	if (blk < nblk) reinterpret_cast<unsigned *>(bidx + (size_t)blk * BT_IDX_WORDS + 3)[0] = 0u;
+	const unsigned i0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+	if (blockIdx.x == 0) for (unsigned i = CTR_ERR + threadIdx.x; i < CTR_COUNT; i += 256) ctr[i] = i == CTR_VIOL ? BT_NONE : 0u;
+	for (unsigned i = i0; i < nidp; i += stride) { own[i] = BT_NONE; if (park_of) park_of[i] = 0u; }
+	if (slice_busy) for (unsigned i = i0; i < nslices; i += stride) slice_busy[i] = 0;
+	if (bidx) for (unsigned i = i0; i < nblk; i += stride) reinterpret_cast<unsigned *>(bidx + (size_t)i * BT_IDX_WORDS + 3)[0] = 0u;
 }
 

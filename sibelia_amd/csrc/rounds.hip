@@ -229,6 +229,7 @@ __device__ __forceinline__ int probe_endchars(const GraphView &g, const BulgeWor
 // Pass 1 takes the endChars alone (see probe_endchars); pass 2 the marks.
 __device__ unsigned long long g_rsv_ticks[8];      // test_flags & BT_TF_STATS: summed wall-clock ticks of the reservation's phases (set-up, exclusive claims, ordering claims), entries, claims, instances
 __device__ unsigned g_idx_stats[8];          // SBL_TRACE: probes by outcome of k_probe_idx (known live, < 2 instances, clean, live, table full, not served); reservations: instances served / walked
+__device__ unsigned g_walk_stats[4];         // test_flags & BT_TF_STATS: entries of k_probe_listed -- all, those beyond a workgroup's first, those that worked in a shadow slice
 __device__ __forceinline__ unsigned long long idx_bits(int lo, int hi)      // bits lo .. hi-1 of a 64-bit word (clamped)
 {
 	lo = lo < 0 ? 0 : lo; hi = hi > 64 ? 64 : hi;
@@ -451,8 +452,11 @@ __device__ __forceinline__ int probe_idx(const GraphView &g, const VtRef &vt, co
 // (BT_NONE in the first word otherwise): the reservation of the round starts from it instead of following the lists again.
 // snapshot != 0: the entries are the touched ids of an incremental snapshot (DeviceBackend::snapshot_idx) -- same verdict, but the write
 // stamps on the device are the PREVIOUS iteration's (they are reset after the snapshot): no order check, nothing counts as "above".
+// wlist / wcount: the entries this kernel cannot serve are also LISTED (their index wi, any order; *wcount entries) -- a handful per round,
+// one append each -- and the walking probe runs over that list with a small fixed grid (k_probe_listed) instead of one workgroup per window
+// entry that looks at live[] and leaves.  nullptr: no list (the shares of a split probe, whose walker keeps the full grid).
 __global__ void __launch_bounds__(64) k_probe_idx(GraphView g, unsigned nwin, uint8_t *live, unsigned w0, unsigned vbits, unsigned max_inst, unsigned walk_marks,
-                                                  unsigned *__restrict__ instbuf, unsigned istride, int snapshot)
+                                                  unsigned *__restrict__ instbuf, unsigned istride, int snapshot, unsigned *__restrict__ wlist, unsigned *__restrict__ wcount)
 {
 	extern __shared__ unsigned pidx_dyn[];
 	VtRef vt; vt.key = pidx_dyn; vt.mask = pidx_dyn + (1u << vbits); vt.bits = vbits;
@@ -484,7 +488,7 @@ __global__ void __launch_bounds__(64) k_probe_idx(GraphView g, unsigned nwin, ui
 		else { WSYNC(); r = probe_idx(g, vt, s_sel, s_dir, s_own, s_mkstep, s_mkid, walk_marks, n, lane, id, tid); }
 	}
 	if (lane == 0) {
-		if (r < 0) live[wi] = PROBE_UNSERVED;
+		if (r < 0) { live[wi] = PROBE_UNSERVED; if (wlist) wlist[atomicAdd(wcount, 1u)] = wi; }
 		else if (r == 0) { g.need[id] = 0; g.touch[id] = 0; live[wi] = 0; }      // verdict taken now: clean until somebody touches it again
 		else { g.need[id] = 2; live[wi] = 1; }
 		if (g.test_flags & BT_TF_STATS) atomicAdd(&g_idx_stats[n < 2 ? 1 : r == 0 ? 2 : r == 1 ? 3 : r == -1 ? 4 : 5], 1u);
@@ -498,20 +502,14 @@ __global__ void __launch_bounds__(64) k_probe_idx(GraphView g, unsigned nwin, ui
 }
 
 static_assert(PROBE_WAVES == 1u, "k_probe synchronises its lanes with WSYNC(): one wave per workgroup");
-__global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe(GraphView g, unsigned nwin, uint8_t *arena, unsigned arena_bytes, uint8_t *live, unsigned w0, int snapshot)
+// One window entry walked by the wave (t, w, vt, ok, fast: the workgroup's LDS).  slice: the arena slice the entry works in.
+#define PROBE_FAST_BYTES 2048u
+__device__ __forceinline__ void probe_walk_entry(const GraphView &g, Txn &t, BulgeWork &w, VerdictTable &vt, int &ok, uint8_t *fast, unsigned wi, uint8_t *arena, unsigned arena_bytes, unsigned slice,
+                                                 uint8_t *live, int snapshot, unsigned lane)
 {
-	__shared__ Txn t;
-	__shared__ BulgeWork w;
-	__shared__ VerdictTable vt;
-	__shared__ int ok;
-	__shared__ __attribute__((aligned(16))) uint8_t fast[2048];
-	const unsigned wi = blockIdx.x + w0, lane = threadIdx.x & 63u;
-	if (!g.idx_probe && !snapshot) round_stamp(g, 0);                  // (behind k_probe_idx the probe phase started with that kernel)
-	if (wi >= nwin) return;
-	if ((g.idx_probe || snapshot) && live[wi] != PROBE_UNSERVED) return;      // decided by k_probe_idx
 	const unsigned id = g.win[wi], tid = snapshot ? 0xFFFFFFFEu : id + 1;
 	if (!snapshot && g.need[id] == 2) { if (threadIdx.x == 0) live[wi] = 1; return; }     // found live by an earlier probe and not touched since (a push resets it to 1)
-	if (threadIdx.x == 0) { t.init(g, id, wi, snapshot ? 0u : 3u, arena + (size_t)(!snapshot && g.slice_busy && g.slice_busy[wi] ? g.shadow_base + wi : wi) * arena_bytes, arena_bytes); t.ext_stamps = true; t.fscr = fast; t.fscr_cap = sizeof fast; }      // (a slice that holds a parked transaction: the spare one, GraphView::park_of)      // (snapshot: the stamps are the previous iteration's -- no order check)
+	if (threadIdx.x == 0) { t.init(g, id, wi, snapshot ? 0u : 3u, arena + (size_t)slice * arena_bytes, arena_bytes); t.ext_stamps = true; t.fscr = fast; t.fscr_cap = PROBE_FAST_BYTES; }      // (snapshot: the stamps are the previous iteration's -- no order check)
 	WSYNC();
 	wave_setup<true>(g, t, w, true, lane, ok);
 	for (unsigned i = threadIdx.x; i < VT_SLOTS; i += 64 * PROBE_WAVES) { vt.key[i] = BT_NONE; vt.mask[i] = 0; }
@@ -534,6 +532,44 @@ __global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe(GraphView g, unsigne
 		else if (!t.err) g.need[id] = 2;
 		else if (snapshot) g.need[id] = 1;                        // (a snapshot starts from need = 0: an undecidable id must be pending)
 		live[wi] = has ? (t.err ? 2 : 1) : 0;                      // (2: live because undecidable here -- need stays 1; k_apply_probe on the other GPUs)
+	}
+}
+// The walking probe with one workgroup per window entry [w0, w0 + gridDim.x): every entry where there is no index probe, the entries
+// flagged PROBE_UNSERVED in the share of a split probe.  The arena slice of an entry of a ROUND is its own window position -- or the
+// spare one while its own holds a parked transaction (GraphView::park_of).
+__global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe(GraphView g, unsigned nwin, uint8_t *arena, unsigned arena_bytes, uint8_t *live, unsigned w0, int snapshot)
+{
+	__shared__ Txn t;
+	__shared__ BulgeWork w;
+	__shared__ VerdictTable vt;
+	__shared__ int ok;
+	__shared__ __attribute__((aligned(16))) uint8_t fast[PROBE_FAST_BYTES];
+	const unsigned wi = blockIdx.x + w0, lane = threadIdx.x & 63u;
+	if (!g.idx_probe && !snapshot) round_stamp(g, 0);                  // (behind k_probe_idx the probe phase started with that kernel)
+	if (wi >= nwin) return;
+	if ((g.idx_probe || snapshot) && live[wi] != PROBE_UNSERVED) return;      // decided by k_probe_idx
+	probe_walk_entry(g, t, w, vt, ok, fast, wi, arena, arena_bytes, !snapshot && g.slice_busy && g.slice_busy[wi] ? g.shadow_base + wi : wi, live, snapshot, lane);
+}
+// ... and over the *wcount entries k_probe_idx listed in wlist (their window positions wi): a fixed grid striding over the list; a
+// workgroup that finds no entry of its own leaves after one load.  In a round an entry keeps the slice it has under k_probe -- its own wi
+// or the spare one, whichever workgroup walks it: no two workgroups ever hold the same wi.  In a snapshot nothing is parked and there are
+// more entries than slices: the slice is the workgroup's index.
+__global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe_listed(GraphView g, uint8_t *arena, unsigned arena_bytes, uint8_t *live, int snapshot,
+                                                                   const unsigned *__restrict__ wlist, const unsigned *__restrict__ wcount)
+{
+	__shared__ Txn t;
+	__shared__ BulgeWork w;
+	__shared__ VerdictTable vt;
+	__shared__ int ok;
+	__shared__ __attribute__((aligned(16))) uint8_t fast[PROBE_FAST_BYTES];
+	const unsigned lane = threadIdx.x & 63u;
+	const unsigned n = (unsigned)__builtin_amdgcn_readfirstlane((int)*wcount);      // (wave-uniform, and said so: the entry's position and id stay in scalar registers)
+	for (unsigned i = blockIdx.x; i < n; i += gridDim.x) {
+		const unsigned wi = (unsigned)__builtin_amdgcn_readfirstlane((int)wlist[i]);
+		const unsigned slice = snapshot ? blockIdx.x : g.slice_busy && g.slice_busy[wi] ? g.shadow_base + wi : wi;
+		if ((g.test_flags & BT_TF_STATS) && threadIdx.x == 0) { atomicAdd(&g_walk_stats[0], 1u); if (i != blockIdx.x) atomicAdd(&g_walk_stats[1], 1u); if (!snapshot && slice != wi) atomicAdd(&g_walk_stats[2], 1u); }
+		probe_walk_entry(g, t, w, vt, ok, fast, wi, arena, arena_bytes, slice, live, snapshot, lane);
+		WSYNC();                                                          // (the LDS is laid out again for the next entry)
 	}
 }
 // ---- read-only phases split over the attached GPUs (SURVEY.md 8e "Simplification": all GPUs work on disjoint id ranges against the
@@ -581,6 +617,7 @@ __global__ void __launch_bounds__(256) k_apply_probe(GraphView g, unsigned nwin,
 //   k_select_count  pending ids per chunk, first pending id, first pending big id (atomicMin)
 //   k_select_write  every chunk below the window limit places its ids after the chunks ahead of it; the last one finalises
 // sel: [0] first pending big id  [1] first pending id  [2] pending ids below the big id  [3] ticket  [8 ...] per-chunk counts
+//      [SEL_WALK_COUNT] entries of the walking probe's list in a round, [SEL_SNAP_WALK_COUNT] in an incremental snapshot (k_probe_idx, k_probe_listed)
 template <class F>
 __device__ __forceinline__ void select_scan_flags(const GraphView &g, unsigned long long id0, unsigned per_thread, unsigned lo, unsigned limit, F f)
 {
@@ -602,9 +639,9 @@ __device__ __forceinline__ void select_scan_flags(const GraphView &g, unsigned l
 __global__ void __launch_bounds__(SEL_THREADS) k_select_count(GraphView g, unsigned *__restrict__ sel, unsigned lo, unsigned limit, unsigned chunk0, unsigned chunk,
                                                               const uint8_t *__restrict__ live, unsigned probed)
 {
-	__shared__ unsigned s_cnt, s_ret;
+	__shared__ unsigned s_ret, s_wcnt[SEL_THREADS / 64], s_wp[SEL_THREADS / 64], s_wb[SEL_THREADS / 64];
 	round_stamp(g, 3);                                               // the selection behind a round: its start is the end of the round's last kernel
-	if (threadIdx.x == 0) { s_cnt = 0; s_ret = 0; }
+	if (threadIdx.x == 0) s_ret = 0;
 	__syncthreads();
 	if (probed) {
 		const unsigned per = (probed + gridDim.x - 1) / gridDim.x, from = blockIdx.x * per, to = from + per < probed ? from + per : probed;
@@ -622,11 +659,24 @@ __global__ void __launch_bounds__(SEL_THREADS) k_select_count(GraphView g, unsig
 		if (nb && firstp == SBL_NONE) firstp = (unsigned)(idq + (__builtin_ctzll(nb) >> 3));
 		if (bb && firstb == SBL_NONE) firstb = (unsigned)(idq + (__builtin_ctzll(bb) >> 3));
 	});
-	if (cnt) atomicAdd(&s_cnt, cnt);
-	if (firstp != SBL_NONE) atomicMin(&sel[1], firstp);
-	if (firstb != SBL_NONE) atomicMin(&sel[0], firstb);
+	// reduced over the wave in registers, over the workgroup in LDS: one global atomic per workgroup and word (left to the compiler, each
+	// of the three atomics became a loop over the wave's lanes)
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) {
+		cnt += __shfl_xor(cnt, d);
+		const unsigned p = __shfl_xor(firstp, d), b = __shfl_xor(firstb, d);
+		firstp = p < firstp ? p : firstp; firstb = b < firstb ? b : firstb;
+	}
+	if ((threadIdx.x & 63) == 0) { s_wcnt[threadIdx.x >> 6] = cnt; s_wp[threadIdx.x >> 6] = firstp; s_wb[threadIdx.x >> 6] = firstb; }
 	__syncthreads();
-	if (threadIdx.x == 0) { sel[8 + blockIdx.x] = s_cnt; if (s_ret) atomicAdd(&g.ctr[CTR_COMMITTED], s_ret); }
+	if (threadIdx.x == 0) {
+		unsigned c = 0, p = SBL_NONE, b = SBL_NONE;
+		for (unsigned w = 0; w < SEL_THREADS / 64; w++) { c += s_wcnt[w]; p = s_wp[w] < p ? s_wp[w] : p; b = s_wb[w] < b ? s_wb[w] : b; }
+		sel[8 + blockIdx.x] = c;
+		if (p != SBL_NONE) atomicMin(&sel[1], p);
+		if (b != SBL_NONE) atomicMin(&sel[0], b);
+		if (s_ret) atomicAdd(&g.ctr[CTR_COMMITTED], s_ret);
+	}
 }
 // post / post_seq: the last chunk also POSTS the counter block to the host (mapped pinned memory, fine-grained: plain stores cross
 // PCIe) followed by a sequence number the host polls -- the round's counters and the next window arrive without a device-to-host copy
@@ -692,6 +742,7 @@ __global__ void __launch_bounds__(SEL_THREADS) k_select_write(GraphView g, unsig
 		g.ctr[CTR_LO] = first == SBL_NONE ? lo : first;
 		g.ctr[CTR_PUSHED] = solo;
 		sel[0] = SBL_NONE; sel[1] = SBL_NONE; sel[2] = 0; sel[3] = 0;      // ready for the next selection (stream order)
+		sel[SEL_WALK_COUNT] = 0;                                           // ... and the walking probe's list for the next round's probe
 	}
 	if (s_last && post) {
 		__syncthreads();
@@ -979,6 +1030,11 @@ void sbl_rounds_stats_report()
 	fprintf(stderr, "[sbl] block index: probes known-live %u, < 2 instances %u, clean %u, live %u, table full %u, not served %u; reservation instances served %u, walked %u\n", z[0], z[1], z[2], z[3], z[4], z[5], z[6], z[7]);
 	memset(z, 0, sizeof z);
 	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_idx_stats), z, sizeof z));
+	unsigned wz[4];
+	HIP_TRY(hipMemcpyFromSymbol(wz, HIP_SYMBOL(g_walk_stats), sizeof wz));
+	fprintf(stderr, "[sbl] listed walker: entries %u, beyond a workgroup's first %u, in a shadow slice %u\n", wz[0], wz[1], wz[2]);
+	memset(wz, 0, sizeof wz);
+	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_walk_stats), wz, sizeof wz));
 	unsigned long long rz[8];
 	HIP_TRY(hipMemcpyFromSymbol(rz, HIP_SYMBOL(g_rsv_ticks), sizeof rz));
 	if (rz[3]) fprintf(stderr, "[sbl] reservations: %llu entries, %.1f claims and %.1f instances each; per entry (10 ns ticks of the device wall clock): set-up %.0f, records %.0f, exclusive claims %.0f, ordering claims + wait for the other waves %.0f, walked instances %.0f\n",

@@ -39,7 +39,7 @@ struct SimplifyState : SimplifyHandles {
 	DevBuf ch, op, nx, pv, nodeof[2];
 	DevBuf nslot, nnext, nidst, nclr, ndead, head[2], lsize[2];
 	DevBuf ctr, need, big, touch, ck_touch, own, lock, rmax, wmax, win;
-	DevBuf arena, snap_arena, big_arena, claims, live, robuf, bidx, instbuf, snap_list, snap_live, park_of, slice_busy, park_list;
+	DevBuf arena, snap_arena, big_arena, claims, live, robuf, bidx, instbuf, walk_list, snap_list, snap_live, park_of, slice_busy, park_list;
 	DevBuf ck_ch, ck_op, ck_nx, ck_pv, ck_bif[2], ck_nodeof[2], ck_nslot, ck_nnext, ck_ndead, ck_head[2], ck_lsize[2];
 	DevBuf keys, skeys, selem, sorttmp, scantmp, perm, permin;
 	DevBuf nmark, maux[2], iota, sel, tstamp;
@@ -73,6 +73,7 @@ struct StageSwitches {
 	Value test_dense_node_slack; // SBL_TEST_DENSE_NODE_SLACK: test hook, the node slack of the one-launch path -- provokes its fall-back
 	Value test_fail_rank;        // SBL_TEST_FAIL_SIMPLIFY_RANK: test hook, this rank leaves the stage between two collectives
 	Value test_corrupt_mark;     // SBL_TEST_CORRUPT_MARK: test hook, one wrong mark for the dictionary check to find
+	Value test_walk_grid;        // SBL_TEST_WALK_GRID: test hook, workgroups of the walking probe over its list -- a tiny grid makes its stride loop iterate
 };
 static StageSwitches read_switches()
 {
@@ -90,6 +91,7 @@ static StageSwitches read_switches()
 	w.test_flags = (unsigned)(int)value("SBL_TEST_FLAGS").v;
 	w.test_elem_slack = value("SBL_TEST_ELEM_SLACK"); w.test_dense_node_slack = value("SBL_TEST_DENSE_NODE_SLACK");
 	w.test_fail_rank = value("SBL_TEST_FAIL_SIMPLIFY_RANK"); w.test_corrupt_mark = value("SBL_TEST_CORRUPT_MARK");
+	w.test_walk_grid = value("SBL_TEST_WALK_GRID");
 	return w;
 }
 
@@ -324,26 +326,35 @@ struct DeviceBackend {
 	}
 	// slot r (es bytes) of every rank r to everybody, in place
 	void allgather_slots(char *buf, uint32_t R, size_t es) { allgather_shares(buf, R, es); }
-	uint32_t snap_slice = 0;                                          // entries per launch of the walking probe's arena (= the round buffers' window_max)
+	uint32_t walk_slices = 0;                                         // arena slices a walking probe may use (= the round buffers' window_max)
+	// Workgroups of the walking probe over the list k_probe_idx leaves (k_probe_listed).  The list is a handful of entries in a round (~15) and
+	// whatever share of the touched ids the index cannot serve in a snapshot: 1024 workgroups of one wave are four per CU of an MI355X, one per
+	// SIMD -- all resident at once with the kernel's 7 KB of LDS and 153 VGPRs --, so a long list is worked off by the whole chip, a short
+	// one by one workgroup per entry, and an empty one costs one small launch whose workgroups leave after one load.  Never more
+	// than the arena has slices: in a snapshot a workgroup works in the slice of its own index.
+	uint32_t walk_grid() const
+	{
+		const uint32_t want = sw.test_walk_grid.set ? (uint32_t)std::max<long long>(1, sw.test_walk_grid.v) : WALK_GRID;
+		return std::max<uint32_t>(1, std::min<uint32_t>(want, walk_slices));
+	}
 	void snapshot_idx()
 	{
-		unsigned *cnt = st->ctr.as<unsigned>() + CTR_TOUCHED, n = 0;
-		st->snap_list.ensure((size_t)nid_ * 4 + 64); st->snap_live.ensure((size_t)nid_ + 64);
+		unsigned *cnt = st->ctr.as<unsigned>() + CTR_TOUCHED, *wcnt = st->sel.as<unsigned>() + SEL_SNAP_WALK_COUNT, n = 0;
+		st->snap_list.ensure((size_t)nid_ * 4 + 64); st->snap_live.ensure((size_t)nid_ + 64); st->walk_list.ensure((size_t)std::max<uint32_t>(nid_, walk_slices) * 4 + 64);
 		HIP_TRY(hipMemsetAsync(cnt, 0, 4, c->stream));
-		k_touched_list<<<(nid_ + 255) / 256, 256, 0, c->stream>>>(st->touch.as<uint8_t>(), nid_, st->snap_list.as<unsigned>(), cnt);
+		// the list of the touched ids; the kernel also leaves need = 0 (untouched ids: still clean) and touch = 0 (every verdict is taken now)
+		// for every id, and the walking probe's list empty
+		k_touched_list<<<std::min<uint32_t>(1024u, nblocks((size_t)nid_ + 1, TOUCHED_SPAN)), 256, 0, c->stream>>>(st->touch.as<uint8_t>(), st->need.as<uint8_t>(), nid_, st->snap_list.as<unsigned>(), cnt, wcnt);
 		HIP_TRY(hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, c->stream));
-		HIP_TRY(hipMemsetAsync(st->need.p, 0, (size_t)nid_ + 1, c->stream));      // untouched ids: still clean
-		HIP_TRY(hipMemsetAsync(st->touch.p, 0, (size_t)nid_ + 1, c->stream));     // every verdict is taken now
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		const uint32_t slice = std::max<uint32_t>(1, snap_slice);
-		for (uint32_t off = 0; off < n; off += slice) {
-			const uint32_t m = std::min<uint32_t>(slice, n - off);
+		if (n) {
+			// ONE launch of the index probe over all of them (it needs no arena slice per entry), one of the walking probe over what it listed
 			GraphView gs = g;
-			gs.win = st->snap_list.as<unsigned>() + off;
+			gs.win = st->snap_list.as<unsigned>();
 			gs.tstamp = nullptr;
-			uint8_t *lv = st->snap_live.as<uint8_t>() + off;
-			k_probe_idx<<<m, 64, pidx_lds(), c->stream>>>(gs, m, lv, 0u, pidx_vbits, pidx_inst, pidx_marks, nullptr, 0u, 1);
-			k_probe<<<m, 64 * PROBE_WAVES, 0, c->stream>>>(gs, m, st->arena.as<uint8_t>(), arena_bytes, lv, 0u, 1);
+			uint8_t *lv = st->snap_live.as<uint8_t>();
+			k_probe_idx<<<n, 64, pidx_lds(), c->stream>>>(gs, n, lv, 0u, pidx_vbits, pidx_inst, pidx_marks, nullptr, 0u, 1, st->walk_list.as<unsigned>(), wcnt);
+			k_probe_listed<<<walk_grid(), 64 * PROBE_WAVES, 0, c->stream>>>(gs, st->arena.as<uint8_t>(), arena_bytes, lv, 1, st->walk_list.as<unsigned>(), wcnt);
 		}
 		HIP_TRY(hipGetLastError());
 	}
@@ -406,22 +417,26 @@ struct DeviceBackend {
 	void reset_round_state(bool stamps_too)
 	{
 		if (!stamps_too) park_sweep();                                 // (the round counter wraps; with stamps_too park_of is cleared below)
-		if (stamps_too && g.park_cap) {                                // (start of an iteration / of a replay: nothing is parked)
-			HIP_TRY(hipMemsetAsync(st->park_of.p, 0, ((size_t)nid_ + 1) * 4, c->stream));
-			HIP_TRY(hipMemsetAsync(st->slice_busy.p, 0, park_slices, c->stream));
-			parked_known = 0; g.park_hold = 0;
-		}
-		HIP_TRY(hipMemsetAsync(st->own.p, 0xFF, ((size_t)nid_ + 1) * 4, c->stream));
-		if (stamps_too) {
-			HIP_TRY(hipMemsetAsync(st->rmax.p, 0, nres * 4, c->stream));
-			HIP_TRY(hipMemsetAsync(st->wmax.p, 0, nres * 4, c->stream));
-			if (g.bidx) k_idx_clear_stamps<<<(idx_nblk + 255) / 256, 256, 0, c->stream>>>(st->bidx.as<unsigned long long>(), idx_nblk);
-		}
+		if (!stamps_too) { HIP_TRY(hipMemsetAsync(st->own.p, 0xFF, ((size_t)nid_ + 1) * 4, c->stream)); return; }
+		// Start of an iteration / of a replay (nothing is parked).  rmax and wmax -- one stamp per element, 170 MB each on the benchmark
+		// workload -- stay fills: they run at memory bandwidth and a kernel of ours would add nothing.  Everything small goes in ONE kernel
+		// (k_reset_iteration): own, park_of, slice_busy, the write stamps of the block index and the counters the driver asks for next.
+		HIP_TRY(hipMemsetAsync(st->rmax.p, 0, nres * 4, c->stream));
+		HIP_TRY(hipMemsetAsync(st->wmax.p, 0, nres * 4, c->stream));
+		if (g.park_cap) { parked_known = 0; g.park_hold = 0; }
+		const size_t span = std::max<size_t>((size_t)nid_ + 1, std::max<size_t>(idx_nblk, park_slices));
+		k_reset_iteration<<<std::min<unsigned>(2048u, nblocks(span, 256)), 256, 0, c->stream>>>(st->ctr.as<unsigned>(), st->own.as<unsigned>(), g.park_cap ? st->park_of.as<unsigned>() : nullptr, nid_ + 1,
+		                                                                                     g.park_cap ? st->slice_busy.as<uint8_t>() : nullptr, (unsigned)park_slices,
+		                                                                                     g.bidx ? st->bidx.as<unsigned long long>() : nullptr, idx_nblk);
+		HIP_TRY(hipGetLastError());
+		counters_clear = true;
 	}
+	bool counters_clear = false;                                      // k_reset_iteration has just cleared the counters: the driver's clear_counters() behind it has nothing to do
 	void clear_counters()
 	{
-		// everything but the pool cursors (CTR_NE, CTR_NN); one small kernel, no host synchronisation
-		k_clear_counters<<<1, 256, 0, c->stream>>>(st->ctr.as<unsigned>());
+		// everything but the pool cursors (CTR_NE, CTR_NN); no host synchronisation
+		if (!counters_clear) k_clear_counters<<<1, 256, 0, c->stream>>>(st->ctr.as<unsigned>());
+		counters_clear = false;
 		HIP_TRY(hipGetLastError());
 	}
 	// The selection is launched behind a round's last kernel and read with the round's counters: one host round trip per round.
@@ -506,15 +521,22 @@ struct DeviceBackend {
 			const uint32_t R = c->comm->n;
 			const uint32_t stride = (4u + (nwin + R - 1) / R + 1u + 3u) & ~3u;
 			st->robuf.ensure((size_t)R * stride + 64);
-			if (w1 > w0 && g.idx_probe) k_probe_idx<<<w1 - w0, 64, pidx_lds(), c->stream>>>(g, nwin, st->live.as<uint8_t>(), w0, pidx_vbits, pidx_inst, pidx_marks, nullptr, 0u, 0);      // (shares of a split probe: the other ranks' lists would have to travel too)
+			// (a share keeps the walker's full grid over [w0, w1): k_pack_probe / k_apply_probe read live[] of the share, which is the same bytes
+			// either way, and a share is 1 / R of the window -- listing within it would add a second form of the split path for a few microseconds)
+			if (w1 > w0 && g.idx_probe) k_probe_idx<<<w1 - w0, 64, pidx_lds(), c->stream>>>(g, nwin, st->live.as<uint8_t>(), w0, pidx_vbits, pidx_inst, pidx_marks, nullptr, 0u, 0, nullptr, nullptr);      // (shares of a split probe: the other ranks' lists would have to travel too)
 			if (w1 > w0) k_probe<<<w1 - w0, 64 * PROBE_WAVES, 0, c->stream>>>(g, nwin, st->arena.as<uint8_t>(), arena_bytes, st->live.as<uint8_t>(), w0, 0);
 			k_pack_probe<<<std::max<uint32_t>(1u, (w1 - w0 + 255) / 256), 256, 0, c->stream>>>(st->ctr.as<unsigned>(), st->live.as<uint8_t>(), w0, w1, c->comm->rank, stride, st->robuf.as<uint8_t>());
 			HIP_TRY(hipGetLastError());
 			allgather_slots(st->robuf.as<char>(), R, stride);
 			k_apply_probe<<<(nwin + 255) / 256, 256, 0, c->stream>>>(g, nwin, st->live.as<uint8_t>(), w0, w1, st->robuf.as<uint8_t>(), stride, R);
 		} else {
-			if (g.idx_probe) k_probe_idx<<<nwin, 64, pidx_lds(), c->stream>>>(g, nwin, st->live.as<uint8_t>(), 0u, pidx_vbits, pidx_inst, pidx_marks, st->instbuf.as<unsigned>(), istride(), 0);      // the block index first; k_probe walks what it could not serve
-			k_probe<<<nwin, 64 * PROBE_WAVES, 0, c->stream>>>(g, nwin, st->arena.as<uint8_t>(), arena_bytes, st->live.as<uint8_t>(), 0u, 0);
+			// the block index first; k_probe_listed walks the handful of entries it could not serve and listed (sel[SEL_WALK_COUNT]: left 0 by the
+			// selection behind every round).  Without the index probe the walker serves every entry: one workgroup each, as ever
+			unsigned *wcnt = st->sel.as<unsigned>() + SEL_WALK_COUNT;
+			if (g.idx_probe) {
+				k_probe_idx<<<nwin, 64, pidx_lds(), c->stream>>>(g, nwin, st->live.as<uint8_t>(), 0u, pidx_vbits, pidx_inst, pidx_marks, st->instbuf.as<unsigned>(), istride(), 0, st->walk_list.as<unsigned>(), wcnt);
+				k_probe_listed<<<walk_grid(), 64 * PROBE_WAVES, 0, c->stream>>>(g, st->arena.as<uint8_t>(), arena_bytes, st->live.as<uint8_t>(), 0, st->walk_list.as<unsigned>(), wcnt);
+			} else k_probe<<<nwin, 64 * PROBE_WAVES, 0, c->stream>>>(g, nwin, st->arena.as<uint8_t>(), arena_bytes, st->live.as<uint8_t>(), 0u, 0);
 		}
 		probed_nwin = nwin;                                          // (the next selection counts what this probe retired)
 		HIP_TRY(hipGetLastError());
@@ -756,14 +778,15 @@ struct StageAttempt {
 		{
 			// counter block and the header of the selection scratch (k_select_*: header + one count per chunk of ids; the kernels leave the header
 			// reset) from a pinned staging buffer the context keeps: the copies are asynchronous and the host does not wait for them
-			if (!st->h_init) HIP_TRY(hipHostMalloc((void **)&st->h_init, (CTR_COUNT + 4) * 4, hipHostMallocDefault));
+			if (!st->h_init) HIP_TRY(hipHostMalloc((void **)&st->h_init, (CTR_COUNT + 8) * 4, hipHostMallocDefault));
 			HIP_TRY(hipStreamSynchronize(s));                                  // (a previous stage's copies from the buffer have long completed; cheap when idle)
 			unsigned *v = reinterpret_cast<unsigned *>(st->h_init);
 			memset(v, 0, CTR_COUNT * 4);
 			v[CTR_NE] = (unsigned)ne0; v[CTR_NN] = (unsigned)ninst; v[CTR_VIOL] = BT_NONE;
 			v[CTR_COUNT] = SBL_NONE; v[CTR_COUNT + 1] = SBL_NONE; v[CTR_COUNT + 2] = 0u; v[CTR_COUNT + 3] = 0u;
+			for (unsigned i = 4; i < 8; i++) v[CTR_COUNT + i] = 0u;            // (SEL_WALK_COUNT, SEL_SNAP_WALK_COUNT: the walking probe's lists start empty)
 			HIP_TRY(hipMemcpyAsync(st->ctr.p, v, CTR_COUNT * 4, hipMemcpyHostToDevice, s));
-			HIP_TRY(hipMemcpyAsync(st->sel.p, v + CTR_COUNT, 16, hipMemcpyHostToDevice, s));
+			HIP_TRY(hipMemcpyAsync(st->sel.p, v + CTR_COUNT, 32, hipMemcpyHostToDevice, s));
 		}
 		st->need.ensure(nidp); st->big.ensure(nidp); st->touch.ensure(nidp); st->own.ensure(nidp * 4);
 		HIP_TRY(hipMemsetAsync(st->need.p, 0, nidp, s));
@@ -816,11 +839,12 @@ struct StageAttempt {
 			st->arena.ensure((size_t)w * be.arena_bytes * (park_cap ? 2u : 1u));      // (second half: the SHADOW slices -- where the entry of a window position works while its own slice holds a parked transaction)
 			st->claims.ensure((size_t)w * (CLAIM_CAP + 1) * 4);
 			st->live.ensure((size_t)w + 64);
+			st->walk_list.ensure((size_t)w * 4 + 64);                         // (k_probe_idx lists what k_probe_listed has to walk; an incremental snapshot enlarges it: snapshot_idx)
 			st->instbuf.ensure((size_t)w * 129 * 4);                          // (DeviceBackend::istride() <= 129)
 			st->slice_busy.ensure(2 * ((size_t)w + 64));                      // (second half: the copy k_reserve takes for k_commit)
 			st->park_list.ensure((size_t)w * 4 + 64);
 		};
-		be.snap_slice = window_max;
+		be.walk_slices = window_max;
 		if (!dense) {
 			// a smaller or partly occupied GPU: first without the shadow slices (parking is a ~5 % optimisation, a 4 x smaller window is not),
 			// then with the pinned window, which always was enough
@@ -832,7 +856,7 @@ struct StageAttempt {
 				if (!ok) {
 					if (window_max == window) throw;
 					window_max = window;
-					be.snap_slice = window;
+					be.walk_slices = window;
 					round_buffers(window);
 				}
 			}
@@ -1069,4 +1093,27 @@ void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl
 	if (!c->comm) { simplify_run_guarded(c, k, D, max_iter, progress, user, bulges); return; }
 	try { simplify_run_guarded(c, k, D, max_iter, progress, user, bulges); }
 	catch (...) { c->comm->abort_peers(); throw; }
+}
+
+// TEST ENTRY POINT (include/sibelia_amd.h): k_touched_list on a caller's touch flags, as DeviceBackend::snapshot_idx launches it
+extern "C" sbl_status sbl_test_touched_list(sbl_ctx *c, const uint8_t *touch, uint32_t nid, uint32_t *list, uint32_t *out, uint8_t *touch_after, uint8_t *need_after)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(touch && list && out && touch_after && need_after, SBL_ERR_BAD_ARG, "null pointer");
+		const size_t nidp = (size_t)nid + 1;
+		DevBuf d_touch, d_need, d_list, d_cnt;
+		d_touch.ensure(nidp); d_need.ensure(nidp); d_list.ensure(nidp * 4); d_cnt.ensure(8);
+		HIP_TRY(hipMemcpyAsync(d_touch.p, touch, nidp, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipMemsetAsync(d_need.p, 0xFF, nidp, c->stream));
+		HIP_TRY(hipMemsetAsync(d_list.p, 0xFF, nidp * 4, c->stream));
+		const unsigned init[2] = { 0u, 0xFFFFFFFFu };               // the list's count starts at 0; the walking probe's is the kernel's to reset
+		HIP_TRY(hipMemcpyAsync(d_cnt.p, init, 8, hipMemcpyHostToDevice, c->stream));
+		k_touched_list<<<std::min<uint32_t>(1024u, nblocks(nidp, TOUCHED_SPAN)), 256, 0, c->stream>>>(d_touch.as<uint8_t>(), d_need.as<uint8_t>(), nid, d_list.as<unsigned>(), d_cnt.as<unsigned>(), d_cnt.as<unsigned>() + 1);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(out, d_cnt.p, 8, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(list, d_list.p, nidp * 4, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(touch_after, d_touch.p, nidp, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(need_after, d_need.p, nidp, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	});
 }

@@ -9,6 +9,10 @@
 #define PROBE_WAVES 1u                       // waves per probed id (windows dealt out to them, wave 0 takes the verdict); more than one did not pay: most entries are cheap
 #define PROBE_UNSERVED 3u                    // live[] value: k_probe_idx could not serve the entry, the walking probe decides
 #define SEL_THREADS 256
+#define SEL_WALK_COUNT 4u                    // word of the selection scratch: entries of the walking probe's list in a round (k_select_write leaves it 0)
+#define SEL_SNAP_WALK_COUNT 5u               // ... in an incremental snapshot (k_touched_list leaves it 0)
+#define WALK_GRID 1024u                      // workgroups of the walking probe over its list (k_probe_listed, DeviceBackend::walk_grid)
+#define TOUCHED_SPAN 4096u                   // ids per step of a workgroup of k_touched_list
 #define RSV_WAVES_MAX 4u
 struct MarkStream { const unsigned *elem[2], *id[2], *aux[2]; unsigned n[2]; };
 
@@ -43,8 +47,10 @@ __global__ void __launch_bounds__(256) k_mark_aux_lin(const unsigned *__restrict
 __global__ void __launch_bounds__(64) k_snapshot_stream(GraphView g, MarkStream ms, const unsigned *__restrict__ nmark, const unsigned *__restrict__ perm, int incremental, unsigned plo, unsigned phi);
 __global__ void __launch_bounds__(64) k_snapshot(GraphView g, uint8_t *arena, unsigned arena_bytes, int incremental, const unsigned *__restrict__ perm, unsigned plo, unsigned phi);
 __global__ void __launch_bounds__(64) k_probe_idx(GraphView g, unsigned nwin, uint8_t *live, unsigned w0, unsigned vbits, unsigned max_inst, unsigned walk_marks,
-                                                  unsigned *__restrict__ instbuf, unsigned istride, int snapshot);
+                                                  unsigned *__restrict__ instbuf, unsigned istride, int snapshot, unsigned *__restrict__ wlist, unsigned *__restrict__ wcount);
 __global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe(GraphView g, unsigned nwin, uint8_t *arena, unsigned arena_bytes, uint8_t *live, unsigned w0, int snapshot);
+__global__ void __launch_bounds__(64 * PROBE_WAVES) k_probe_listed(GraphView g, uint8_t *arena, unsigned arena_bytes, uint8_t *live, int snapshot,
+                                                                   const unsigned *__restrict__ wlist, const unsigned *__restrict__ wcount);
 __global__ void __launch_bounds__(256) k_pack_need(const unsigned *__restrict__ perm, const uint8_t *__restrict__ need, unsigned lo, unsigned hi, uint8_t *__restrict__ buf);
 __global__ void __launch_bounds__(256) k_unpack_need(const unsigned *__restrict__ perm, const uint8_t *__restrict__ buf, unsigned n, unsigned mylo, unsigned myhi, uint8_t *__restrict__ need);
 __global__ void __launch_bounds__(256) k_apply_probe(GraphView g, unsigned nwin, uint8_t *__restrict__ live, unsigned w0, unsigned w1, const uint8_t *__restrict__ robuf, unsigned stride, unsigned nranks);
@@ -61,7 +67,8 @@ __global__ void __launch_bounds__(256) k_park_sweep(unsigned *__restrict__ park_
 __global__ void __launch_bounds__(64) k_chain(GraphView g, uint8_t *arena, unsigned arena_bytes, unsigned nwin, int prof);
 __global__ void __launch_bounds__(64) k_dense_stage(GraphView g, uint8_t *arena, unsigned arena_bytes, unsigned max_iter, unsigned *out);
 __global__ void __launch_bounds__(256) k_count_touched(const uint8_t *__restrict__ touch, unsigned nid, unsigned *__restrict__ out);
-__global__ void __launch_bounds__(256) k_touched_list(const uint8_t *__restrict__ touch, unsigned nid, unsigned *__restrict__ list, unsigned *__restrict__ count);
+__global__ void __launch_bounds__(256) k_touched_list(uint8_t *__restrict__ touch, uint8_t *__restrict__ need, unsigned nid, unsigned *__restrict__ list, unsigned *__restrict__ count,
+                                                      unsigned *__restrict__ wcount);
 __global__ void __launch_bounds__(256) k_seg_flags(const uint8_t *__restrict__ ch, const unsigned *__restrict__ nx, unsigned ne, unsigned *__restrict__ flag);
 __global__ void __launch_bounds__(256) k_seg_tails(const uint8_t *__restrict__ ch, const unsigned *__restrict__ nx, unsigned ne,
                                                    const unsigned *__restrict__ flag, const unsigned *__restrict__ segidx /* exclusive scan */,
@@ -89,4 +96,5 @@ __global__ void __launch_bounds__(256) k_check_blkidx(const uint8_t *__restrict_
                                                       const unsigned *__restrict__ bif0, const unsigned *__restrict__ bif1, const unsigned *__restrict__ wmax, unsigned norig, unsigned nblk,
                                                       const unsigned long long *__restrict__ bidx, unsigned *__restrict__ out);
 __global__ void __launch_bounds__(256) k_clear_counters(unsigned *__restrict__ ctr);
-__global__ void __launch_bounds__(256) k_idx_clear_stamps(unsigned long long *__restrict__ bidx, unsigned nblk);
+__global__ void __launch_bounds__(256) k_reset_iteration(unsigned *__restrict__ ctr, unsigned *__restrict__ own, unsigned *__restrict__ park_of, unsigned nidp,
+                                                         uint8_t *__restrict__ slice_busy, unsigned nslices, unsigned long long *__restrict__ bidx, unsigned nblk);

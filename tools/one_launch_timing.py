@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""A/B timing of the headline workload for the one-launch commit: `python bench.py --no-cpu-baseline` RUNS times in a built checkout
-of the parent commit and RUNS times in this tree, alternating (parent first), each run a process of its own; then one
-`--full --no-cpu-full --no-cpu-baseline` run per tree for the state hash and the check against the reference's fixture.  Every run is
-kept (ms_per_step, rounds, bulges, phase_ms); the summary holds the medians, the parent's own spread (max - min) and whether the
-head's median is below the parent's by more than three times that spread -- the acceptance bound of the change.
+"""A/B timing of the headline workload against the parent commit (written for the one-launch commit, used again for the listed
+walking probe): `python bench.py --no-cpu-baseline` RUNS times in a built checkout of the parent commit and RUNS times in this tree,
+alternating (parent first), each run a process of its own; then one `--full --no-cpu-full --no-cpu-baseline` run per tree for the state
+hash and the check against the reference's fixture.  Every run is kept (ms_per_step, rounds, bulges, phase_ms);
+the summary holds the medians, the parent's own spread (max - min) and whether the head's median is below the parent's by more than
+three times that spread -- the acceptance bound of both changes.
 
-usage: tools/one_launch_timing.py PARENT_TREE [OUT.json]      (default OUT: profiles/one_launch_timing.json)"""
+usage: tools/one_launch_timing.py PARENT_TREE [OUT.json]      (default OUT: profiles/one_launch_timing.json;
+                                                               the listed probe: profiles/listed_probe_timing.json)"""
 import json
 import os
 import statistics
