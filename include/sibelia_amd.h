@@ -109,7 +109,9 @@ sbl_status sbl_load(sbl_ctx *ctx, uint32_t nchr, const uint8_t *const *seq, cons
  * The file is mapped and copied to the device as text; line splitting, trimming, header / sequence classification,
  * upper-casing, validation ("ACGTURYKMSWBDHWNX-"), concatenation, identity original positions and the scan for non-ACGT
  * characters run in kernels.  Parse errors come back as SBL_ERR_BAD_ARG with the reference's message
- * ("parse error in <file> on line <n>: empty sequence | empty header | illegal character: <c>") in sbl_last_error.
+ * ("parse error in <file> on line <n>: empty sequence | empty header | illegal character: <c>") in sbl_last_error: the first
+ * offending line and, within it, the first offending column, exactly, wherever in the file they lie; <c> is the byte as written.
+ * A load that fails leaves the context without records (sbl_nchr 0); one that succeeds leaves sbl_last_error empty.
  * sbl_record_name: FASTARecord::GetDescription (text between '>' and the first blank), valid until the next load. */
 sbl_status sbl_load_fasta(sbl_ctx *ctx, const char *path);
 const char *sbl_record_name(const sbl_ctx *ctx, uint32_t chr);

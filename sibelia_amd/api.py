@@ -269,7 +269,8 @@ class BlockFinder:
 
     def _check(self, rc, what):
         if rc:
-            msg = self.L.sbl_last_error(self.h).decode() if self.h else ""
+            # (a parse error quotes the offending byte and the path as they are: any byte, so decoded the way Python decodes file names)
+            msg = os.fsdecode(self.L.sbl_last_error(self.h)) if self.h else ""
             raise SibeliaError("%s: %s (%s)" % (what, self.L.sbl_strerror(rc).decode(), msg))
 
     def close(self):

@@ -62,7 +62,9 @@ __global__ void __launch_bounds__(256) k_fa_line_starts(const uint8_t *__restric
 }
 
 enum { FA_EMPTY = 0, FA_HEADER = 1, FA_SEQ = 2 };
-// err: [0] = (line index << 8 | code) of the first offending line (atomicMin); codes: 1 empty header
+// err: (line index << 32 | column in the trimmed line) of the first offence, reduced with atomicMin: the first offending line wins and,
+// within it, the first column -- all 32 bits of each (the file is below 4 GB).  A header line offends only by an empty name (column 0),
+// a sequence line only by an illegal character: the host tells the two apart by isheader[line] and reads the character from the text.
 __global__ void __launch_bounds__(256) k_fa_lines(const uint8_t *__restrict__ txt, size_t n, const unsigned *__restrict__ line_start, unsigned nlines,
                                                   unsigned *__restrict__ la, unsigned *__restrict__ lb, unsigned *__restrict__ nonempty, unsigned *__restrict__ isheader,
                                                   unsigned *__restrict__ seqlen, unsigned long long *__restrict__ err)
@@ -73,7 +75,7 @@ __global__ void __launch_bounds__(256) k_fa_lines(const uint8_t *__restrict__ tx
 	while (a < b && fa_space(txt[a])) a++;
 	while (b > a && fa_space(txt[b - 1])) b--;
 	unsigned kind = a == b ? FA_EMPTY : txt[a] == '>' ? FA_HEADER : FA_SEQ;
-	if (kind == FA_HEADER && (b - a == 1 || txt[a + 1] == ' ')) atomicMin(err, ((unsigned long long)l << 40) | 1ull);   // ValidateHeader: empty name
+	if (kind == FA_HEADER && (b - a == 1 || txt[a + 1] == ' ')) atomicMin(err, (unsigned long long)l << 32);   // ValidateHeader: empty name
 	la[l] = (unsigned)a; lb[l] = (unsigned)b;
 	nonempty[l] = kind != FA_EMPTY; isheader[l] = kind == FA_HEADER; seqlen[l] = kind == FA_SEQ ? (unsigned)(b - a) : 0u;
 }
@@ -95,7 +97,6 @@ __global__ void __launch_bounds__(256) k_fa_place(unsigned nlines, const unsigne
 		elem0[l] = 1 + seq_before[l] + rec;                      // one '$' ahead of every record
 	}
 }
-// codes: 2 illegal character (low byte of the payload = the character as written)
 __global__ void __launch_bounds__(256) k_fa_scatter(const uint8_t *__restrict__ txt, size_t n, const unsigned *__restrict__ line_start, unsigned nlines,
                                                     const unsigned *__restrict__ la, const unsigned *__restrict__ lb, const unsigned *__restrict__ isheader,
                                                     const unsigned *__restrict__ elem0, uint8_t *__restrict__ ch, unsigned long long *__restrict__ err)
@@ -110,7 +111,7 @@ __global__ void __launch_bounds__(256) k_fa_scatter(const uint8_t *__restrict__ 
 	const uint8_t c = orig >= 'a' && orig <= 'z' ? orig - 32 : orig;
 	bool ok = false;
 	switch (c) { case 'A': case 'C': case 'G': case 'T': case 'U': case 'R': case 'Y': case 'K': case 'M': case 'S': case 'W': case 'B': case 'D': case 'H': case 'N': case 'X': case '-': ok = true; }
-	if (!ok) { atomicMin(err, ((unsigned long long)l << 40) | ((unsigned long long)((i - a) < 0xFFFFFFull ? (i - a) : 0xFFFFFFull) << 16) | ((unsigned long long)orig << 8) | 2ull); return; }   // column clamped to its 24-bit field
+	if (!ok) { atomicMin(err, ((unsigned long long)l << 32) | (unsigned long long)(i - a)); return; }   // ValidateSequence: reported as written (orig), by the host
 	ch[(size_t)elem0[l] + (i - a)] = c;
 }
 
@@ -204,6 +205,11 @@ struct Mapped {
 extern "C" sbl_status sbl_load_fasta(sbl_ctx *c, const char *path)
 {
 	return guarded(c, [&] {
+		// the context belongs to this load from here on: one that fails leaves no records, no names and no ambiguity list of the load
+		// before, one that succeeds no message
+		c->err.clear();
+		c->nchr = 0; c->nelem = 0; c->sepidx.clear(); c->orig_sepidx.clear(); c->fa_names.clear(); c->amb_elem.clear(); c->amb_orig.clear();
+		c->host_state_valid = false;
 		SBL_CHECK(path, SBL_ERR_BAD_ARG, "null path");
 		Mapped m;
 		m.fd = open(path, O_RDONLY);
@@ -278,13 +284,16 @@ extern "C" sbl_status sbl_load_fasta(sbl_ctx *c, const char *path)
 		// ---- errors, in the order the reference would meet them: the first offending line wins
 		unsigned long long first = ~0ull; std::string what;
 		if (herr != ~0ull) {
-			unsigned l = (unsigned)(herr >> 40);
+			const unsigned l = (unsigned)(herr >> 32), col = (unsigned)herr;
 			SBL_CHECK(l < nlines, SBL_ERR_INTERNAL, "FASTA loader: corrupt error record");
 			// line number of line l = 1 + non-empty lines before it
-			unsigned before = 0;
+			unsigned before = 0, hdr = 0, a = 0;
 			HIP_TRY(hipMemcpy(&before, ne_before + l, 4, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(&hdr, isheader + l, 4, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(&a, la + l, 4, hipMemcpyDeviceToHost));
+			SBL_CHECK((size_t)a + col < n && (!hdr || col == 0), SBL_ERR_INTERNAL, "FASTA loader: corrupt error record");
 			first = ((unsigned long long)l << 1) | 1ull;
-			what = (herr & 0xFF) == 1 ? "empty header" : std::string("illegal character: ") + (char)((herr >> 8) & 0xFF);
+			what = hdr ? "empty header" : std::string("illegal character: ") + static_cast<const char *>(m.p)[(size_t)a + col];
 			hlineno.push_back(1 + before);
 		}
 		for (unsigned r = 0; r < nrec; r++) {
