@@ -437,6 +437,39 @@ sbl_status sbl_group_variants(sbl_ctx *ctx, const uint8_t *want, const sbl_group
                               const char **text, uint64_t *text_len);
 sbl_status sbl_group_variants_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 
+/* Pairwise counts of the multiple alignments (csrc/group_distances.hip), defined by this project, on the groups of the
+ * context's LAST sbl_align_groups / sbl_align_block_groups call, read from the rows that call left on the device.
+ * COUNTS OF A ROW PAIR.  Rows x, y of one group (L columns, '-' is a gap) are instances i and j, i != j.  Every column is exactly one of
+ *   match       both bytes are one of A C G T (exactly these four upper-case bytes) and equal
+ *   mismatch    both bytes are one of A C G T and unequal
+ *   ambiguous   neither byte is '-' and at least one is not one of A C G T (lower case counts here: bytes are taken as the rows hold them)
+ *   gap(i->j)   x holds a byte other than '-' and y holds '-'
+ *   gap(j->i)   x holds '-' and y holds a byte other than '-'
+ *   (both hold '-': not counted)
+ * so match + mismatch + ambiguous + gap(i->j) is the length of instance i -- if the record holds no '-' itself: a '-' in a record cannot
+ * be told from a gap, as for sbl_group_variants.
+ * CLASS MATRIX.  cls gives every instance of that groups call a class cls[k] < nclass, one entry per instance in the order of `inst`
+ * (the pipeline: the index of the input file).  counts is M[nclass][nclass], row-major: M[f][g] is the sum, over all wanted groups that
+ * were aligned, of the counts of every ORDERED pair (i, j), i != j, with cls[i] = f and cls[j] = g; its `gap` is gap(i->j).  So match,
+ * mismatch and ambiguous are symmetric in (f, g), and a diagonal cell holds every unordered pair of one class twice.  Groups that were
+ * skipped (SBL_GALIGN_SKIPPED), groups with want[g] == 0 (want: one byte per group, NULL: all), r == 1 and L == 0 give nothing; an
+ * all-zero matrix is a result.
+ * DISTANCE.  The p-distance of classes f, g is mismatch / (match + mismatch) of M[f][g]; no correction for multiple hits (no
+ * Jukes-Cantor).  The alignment is centre-star: two members are compared through the columns the centre induces, not by an alignment
+ * of their own.
+ * The row comparisons run in a kernel and only the matrix comes back, into a buffer of its own: the `rows` of the groups call stay
+ * valid and unchanged, and sbl_group_variants and sbl_group_distances may follow one groups call in either order with the same results.
+ * The matrix is owned by the ctx until the next sbl_group_distances.  All sums are integers: they do not depend on the order of work.
+ * SBL_ERR_BAD_ARG, checked on the host before any launch: no groups call yet, or the last sbl_align_* call was sbl_align_pairs /
+ * sbl_align_unique_blocks; cls == NULL while there is at least one instance; nclass == 0 or nclass > 1024 (32 B per cell); a
+ * cls[k] >= nclass.
+ * sbl_group_distances_times: device time of the last call's kernel (with clearing the matrix) and of the device-to-host copy of the
+ * matrix (event pairs). */
+typedef struct { uint64_t match, mismatch, ambiguous, gap; } sbl_pair_counts;
+sbl_status sbl_group_distances(sbl_ctx *ctx, const uint8_t *want, const uint32_t *cls, uint32_t nclass,
+                               const sbl_pair_counts **counts /* nclass * nclass, row-major, owned by ctx */);
+sbl_status sbl_group_distances_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

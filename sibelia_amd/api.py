@@ -31,7 +31,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
-           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_tiny_index",
+           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times", "sbl_tiny_index",
            "sbl_test_touched_list"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -129,6 +129,10 @@ SEGMENT_DTYPE = np.dtype([("group", "<u8"), ("start", "<u8"), ("end", "<u8"), ("
                           ("lead", "<u4"), ("gapped", "<u4")])                                        # sbl_group_segment
 
 
+class PairCounts(C.Structure):                     # sbl_pair_counts
+    _fields_ = [("match", C.c_uint64), ("mismatch", C.c_uint64), ("ambiguous", C.c_uint64), ("gap", C.c_uint64)]
+
+
 class GroupAlignment:
     """One sbl_group_result: status (GALIGN_OK / GALIGN_SKIPPED), L, row_off, the rows (centre first, members in the order given) and
     per member (score, band_w, passes).  A skipped group has L = 0, no rows and member scores None."""
@@ -218,6 +222,8 @@ def load_library():
         L.sbl_spell_text_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_group_variants.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_group_variants_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_distances.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.POINTER(PairCounts))]
+        L.sbl_group_distances_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -523,6 +529,35 @@ class BlockFinder:
         """(kernel ms, device-to-host copy ms of the slices) of the last group_variants call, from event pairs."""
         k, d = C.c_double(), C.c_double()
         self._check(self.L.sbl_group_variants_times(self.h, C.byref(k), C.byref(d)), "sbl_group_variants_times")
+        return k.value, d.value
+
+    def group_distances(self, cls: Sequence[int], nclass: int, want: Optional[Sequence[bool]] = None) -> np.ndarray:
+        """The pairwise counts of the groups of the LAST align_groups / align_block_groups call (csrc/group_distances.hip; defined in
+        include/sibelia_amd.h), counted on the rows that call left on the device.  cls: one class below nclass per
+        instance of that call, flat, in group order; want: one flag per group (None: all).
+        -> uint64 array of shape (nclass, nclass, 4), a copy: [f, g] = (match, mismatch, ambiguous, gap(f -> g)) summed over every
+        ordered pair of rows of classes (f, g)."""
+        ninst = getattr(self, "_group_ninst", [])
+        mask = None
+        if want is not None:
+            if len(want) != len(ninst):
+                raise ValueError("group_distances: %d flags for %d groups" % (len(want), len(ninst)))
+            mask = bytes(1 if w else 0 for w in want) + b"\0"
+        cls = [int(x) for x in cls]
+        if ninst and len(cls) != sum(ninst):
+            raise ValueError("group_distances: %d classes for %d instances" % (len(cls), sum(ninst)))
+        if not 0 <= int(nclass) <= 2 ** 32 - 1 or any(not 0 <= x <= 2 ** 32 - 1 for x in cls):
+            raise SibeliaError("sbl_group_distances: bad argument (a class or their number outside 32 bits)")
+        arr = (C.c_uint32 * max(1, len(cls)))(*cls)
+        out = C.POINTER(PairCounts)()
+        self._check(self.L.sbl_group_distances(self.h, mask, arr, int(nclass), C.byref(out)), "sbl_group_distances")
+        n = int(nclass)
+        return _view(C.cast(out, C.c_void_p).value, n * n * 4, np.dtype("<u8")).reshape(n, n, 4)
+
+    def group_distances_times(self) -> Tuple[float, float]:
+        """(kernel ms, device-to-host copy ms of the matrix) of the last group_distances call, from event pairs."""
+        k, d = C.c_double(), C.c_double()
+        self._check(self.L.sbl_group_distances_times(self.h, C.byref(k), C.byref(d)), "sbl_group_distances_times")
         return k.value, d.value
 
     def align_stats(self) -> dict:

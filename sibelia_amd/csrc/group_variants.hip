@@ -36,17 +36,6 @@ constexpr unsigned GV_CONTEXT = 30;                    // MINIMUM_CONTEXT_SIZE (
 struct GvGroup { u64 group, dg; };                     // a wanted group: its index in the call; its index in d_gm_group
 struct GvSlice { u64 src, L, len; };                   // a segment's slices: first byte of the centre's in the rows, row stride, bytes per row
 
-// bytes [at, at + 16) of text as two 64-bit words; words that lie wholly beyond text[0, bytes) are not loaded (bytes: a multiple of 16)
-__device__ inline B16 gv_load16(const uint8_t *__restrict__ text, u64 bytes, u64 at)
-{
-	const u64 base = at & ~15ull;
-	const unsigned sh = (unsigned)(at & 15);
-	const uint4 zero = make_uint4(0, 0, 0, 0);
-	const uint4 a = base < bytes ? *reinterpret_cast<const uint4 *>(text + base) : zero;
-	const uint4 b = sh && base + 16 < bytes ? *reinterpret_cast<const uint4 *>(text + base + 16) : zero;
-	return window16(a, b, sh);
-}
-
 // 0x80 in every byte of v that is not zero
 __device__ inline u64 nonzero8(u64 v) { return ~zero8(v) & 0x8080808080808080ull; }
 

@@ -134,6 +134,11 @@ struct sbl_ctx {
 	std::vector<sbl_group_segment> gv_segs;
 	std::vector<char> gv_text;
 	double gv_kernel_ms = 0, gv_copy_ms = 0;   // event pairs around the kernels / the device-to-host copy of the slices of the last call
+	// sbl_group_distances (group_distances.hip): reads d_ga_text under the same rule (gv_rows_valid) and nothing of sbl_group_variants':
+	// work items, the classes of the instances and the class matrix on the device; the matrix comes back into a host buffer of its own
+	DevBuf d_gd_item, d_gd_cls, d_gd_mat;
+	std::vector<sbl_pair_counts> gd_counts;
+	double gd_kernel_ms = 0, gd_copy_ms = 0;   // event pairs around clearing the matrix and the kernel / the device-to-host copy of the matrix
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;

@@ -1,6 +1,6 @@
 // sbl_text.h -- what the output-stationary text kernels share (blockseq.hip: k_block_sequences, uncovered.hip: k_spell_text): the search
-// of a text offset in the offsets of the pieces, and 16 bytes of text held in two registers -- cut out of two aligned source words,
-// opened for a line feed.
+// of a text offset in the offsets of the pieces, and 16 bytes of text held in two registers -- cut out of two aligned source words
+// (gv_load16: the readers of the alignment rows, group_variants.hip and group_distances.hip), opened for a line feed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,16 @@ __device__ inline B16 window16(uint4 a, uint4 b, unsigned sh)
 	if (!sh) return {w0, w1};
 	const unsigned r = sh * 8;
 	return {(w0 >> r) | (w1 << (64 - r)), (w1 >> r) | (w2 << (64 - r))};
+}
+// bytes [at, at + 16) of text as two 64-bit words; words that lie wholly beyond text[0, bytes) are not loaded (bytes: a multiple of 16)
+__device__ inline B16 gv_load16(const uint8_t *__restrict__ text, u64 bytes, u64 at)
+{
+	const u64 base = at & ~15ull;
+	const unsigned sh = (unsigned)(at & 15);
+	const uint4 zero = make_uint4(0, 0, 0, 0);
+	const uint4 a = base < bytes ? *reinterpret_cast<const uint4 *>(text + base) : zero;
+	const uint4 b = sh && base + 16 < bytes ? *reinterpret_cast<const uint4 *>(text + base + 16) : zero;
+	return window16(a, b, sh);
 }
 // 16 bytes with '\n' inserted before byte p (p in [0, 16)); the last byte falls off
 __device__ inline B16 insert_newline(B16 w, unsigned p)

@@ -221,6 +221,48 @@ def multi_vcf_text(reference_name: str, sample_names: Sequence[str], records, ga
     return ("\n".join(out) + "\n").encode("latin1")
 
 
+DISTANCE_COUNTS_COLUMNS = ("file_a", "file_b", "blocks", "match", "mismatch", "ambiguous", "gap_a", "gap_b")
+
+
+def distance_counts_text(names: Sequence[str], counts, blocks, gap_open: int = 0) -> bytes:
+    """The file of --distancecounts: tab-separated, a line of column names, then one line per pair of files a < b in
+    input order.  counts[a][b] = (match, mismatch, ambiguous, gap(a -> b)) as BlockFinder.group_distances returns them; blocks[a][b]:
+    the used and aligned blocks with an instance in both.  gap_a = counts[a][b] gap, the bases of a opposite a gap of b; gap_b =
+    counts[b][a] gap.  gap_open > 0 (--gapopen) is recorded in a line `# gapopen=N` before the column names."""
+    out = (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(DISTANCE_COUNTS_COLUMNS)]
+    for a in range(len(names)):
+        for b in range(a + 1, len(names)):
+            match, mismatch, ambiguous, gap_a = (int(x) for x in counts[a][b])
+            out.append("\t".join([names[a], names[b]] + [str(x) for x in (int(blocks[a][b]), match, mismatch, ambiguous, gap_a, int(counts[b][a][3]))]))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
+def p_distance_text(match: int, mismatch: int) -> str:
+    """mismatch / (match + mismatch) to six decimals, made from the integers alone -- (mismatch 10^6 + c / 2) / c with c = match +
+    mismatch, a tie going up -- so that the text is the same on every host; `nan` for c = 0."""
+    c = int(match) + int(mismatch)
+    if c == 0:
+        return "nan"
+    v = (int(mismatch) * 10 ** 6 + c // 2) // c
+    return "%d.%06d" % (v // 10 ** 6, v % 10 ** 6)
+
+
+def distances_text(names: Sequence[str], counts, complain=None) -> bytes:
+    """The file of --distances: a square matrix in PHYLIP format -- the number of files, then per file its name and
+    one value per file, separated by single blanks; 0.000000 on the diagonal, p_distance_text of counts[a][b] elsewhere.  A pair
+    without a column that holds A C G T on both sides is written `nan` and named through `complain`, one line per pair a < b."""
+    out = [str(len(names))]
+    for a in range(len(names)):
+        row = [names[a]]
+        for b in range(len(names)):
+            v = "0.000000" if a == b else p_distance_text(counts[a][b][0], counts[a][b][1])
+            if v == "nan" and a < b and complain is not None:
+                complain("no distance between %s and %s: the blocks used hold no column with one of A C G T in both\n" % (names[a], names[b]))
+            row.append(v)
+        out.append(" ".join(row))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
 # ------------------------------------------------------------------------------------------ calls from uncovered regions (--uncovered, --unmapped)
 
 CALL_DELETION, CALL_INSERTION, CALL_UNMAPPED = 0, 1, 2      # SBL_CALL_* (include/sibelia_amd.h)

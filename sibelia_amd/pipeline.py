@@ -11,7 +11,9 @@ unique blocks in MAF and the variants read off them in VCF (`align_unique_blocks
 classes instead of leaving them out.  --multimaf (any number of input files) writes a
 multiple alignment of every block with at least two instances (`align_block_groups`); --multivariants (two or more input files) reads
 the calls off those alignments for the blocks with one instance in the first file and at most one in each other file and writes them as
-a multi-sample VCF.  --uncovered adds the rest of C-Sibelia's VCF to
+a multi-sample VCF.  --distances / --distancecounts (two or more input files) count, on the same alignments, the matches,
+mismatches and gaps between every two input files over the blocks with at most one instance in each file, on the device, and write a
+distance matrix and the counts behind it.  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -49,6 +51,16 @@ MULTIVARIANTS_HELP = ("Two or more input files: write the SNVs and indels read o
                       "column per input file after the first (named by the file's base name; positions on the records of the first file).  A "
                       "block is used if all its instances are at least the minimum block size long, exactly one of them lies in the first file "
                       "and at most one in each other file; a file without an instance gets the genotype '.'.")
+
+DISTANCES_HELP = ("Two or more input files: write the p-distance of every two input files -- mismatches / (matches + mismatches) over the aligned "
+                  "columns in which both hold one of A C G T -- as a square matrix in PHYLIP format, the files named by their base names.  The "
+                  "columns are those of the multiple alignments of --multimaf; a block is used if it has at least two instances, all at least "
+                  "the minimum block size long, and at most one in each file.  No correction for multiple substitutions; 'nan' where two "
+                  "files share no such column.")
+
+DISTANCECOUNTS_HELP = ("Two or more input files: write the counts behind --distances as tab-separated text, one line per pair of input files: the "
+                       "blocks used, matches, mismatches, ambiguous columns (a base code other than A C G T on either side) and the bases of "
+                       "each file opposite a gap of the other.")
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
@@ -188,6 +200,8 @@ def build_parser() -> argparse.ArgumentParser:
                    "instead of as breakend records.")
     p.add_argument("--multimaf", default=None, metavar="FILE", help=MULTI_HELP)
     p.add_argument("--multivariants", default=None, metavar="FILE", help=MULTIVARIANTS_HELP)
+    p.add_argument("--distances", default=None, metavar="FILE", help=DISTANCES_HELP)
+    p.add_argument("--distancecounts", default=None, metavar="FILE", help=DISTANCECOUNTS_HELP)
     p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
     p.add_argument("--wideband", action="store_true", help=WIDEBAND_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
@@ -218,18 +232,34 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         for a in sorted(set(samples)):
             if samples.count(a) > 1:
                 raise PipelineError("--multivariants names a sample by its file's base name: two files are called %s" % a)
+    for o, f in (("--distances", opt.distances), ("--distancecounts", opt.distancecounts)):
+        if f is None:
+            continue
+        if len(opt.filenames) < 2:                             # before any file is read
+            raise PipelineError("%s compares files: it needs at least two" % o)
+        if opt.noblocks:
+            raise PipelineError("%s needs the synteny blocks: it cannot be combined with --noblocks" % o)
+        names = file_names(opt.filenames)
+        for a in sorted(set(names)):
+            if names.count(a) > 1:
+                raise PipelineError("%s names a file by its base name: two files are called %s" % (o, a))
+        if o == "--distances":
+            for a in names:
+                if a != "".join(a.split()):
+                    raise PipelineError("--distances writes PHYLIP, which separates by blanks: the file name '%s' holds white space" % a)
     if opt.uncovered and opt.variants is None:
         raise PipelineError("--uncovered adds its records to the file of --variants: it needs --variants")
     if opt.uncovered and not opt.allstages:
         raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
     if opt.unmapped is not None and not opt.uncovered:
         raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
-    if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None:
+    distances = opt.distances is not None or opt.distancecounts is not None
+    if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None and not distances:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
-    if opt.wideband and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None:
+    if opt.wideband and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None and not distances:
         raise PipelineError("--wideband widens the bands of the alignments: it needs at least one of --maf, --variants, --multimaf and --multivariants")
-    if opt.maf is not None or opt.variants is not None or opt.multimaf is not None or opt.multivariants is not None:
+    if opt.maf is not None or opt.variants is not None or opt.multimaf is not None or opt.multivariants is not None or distances:
         _check_alignment_files(opt)
     return opt
 
@@ -239,11 +269,16 @@ def sample_names(filenames: Sequence[str]) -> List[str]:
     return [os.path.basename(os.path.normpath(f)) for f in filenames[1:]]
 
 
+def file_names(filenames: Sequence[str]) -> List[str]:
+    """The names of --distances / --distancecounts: one per input file, the first included, the file's base name."""
+    return [os.path.basename(os.path.normpath(f)) for f in filenames]
+
+
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants / --unmapped / --multimaf / --multivariants name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
     given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--unmapped", opt.unmapped), ("--multimaf", opt.multimaf),
-                                    ("--multivariants", opt.multivariants)) if f is not None]
+                                    ("--multivariants", opt.multivariants), ("--distances", opt.distances), ("--distancecounts", opt.distancecounts)) if f is not None]
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -309,7 +344,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf, opt.multivariants) if f is not None]      # relative names: under the output directory
+        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf, opt.multivariants, opt.distances, opt.distancecounts) if f is not None]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -513,12 +548,66 @@ def qualifying_blocks(blocks, file_records: Sequence[int], min_block_size: int) 
     return out
 
 
+def _file_of_record(file_records: Sequence[int]) -> Callable[[int], int]:
+    import bisect
+    first = [0]
+    for n in file_records:
+        first.append(first[-1] + n)
+    return lambda c: bisect.bisect_right(first, int(c)) - 1
+
+
+def distance_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
+    """The ids --distances / --distancecounts count over, on a block list (formats.BLOCK_DTYPE): there are at least two instances of
+    the id, EVERY one is at least min_block_size long, and at most one lies on the records of each file.  Unlike qualifying_blocks it
+    does not ask for an instance in the first file."""
+    file_of = _file_of_record(file_records)
+    by_id: Dict[int, List[Tuple[int, int]]] = {}
+    for b in blocks:
+        by_id.setdefault(abs(int(b["id"])), []).append((file_of(b["chr"]), int(b["end"]) - int(b["start"])))
+    out = []
+    for block, inst in sorted(by_id.items()):
+        files = [f for f, _ in inst]
+        if len(inst) >= 2 and all(n >= min_block_size for _, n in inst) and len(set(files)) == len(files):
+            out.append(block)
+    return out
+
+
+def distance_files(bf, opt: argparse.Namespace, ids: Sequence[int], insts, aligned, used, complain: Callable[[str], None]) -> Dict[str, bytes]:
+    """--distances / --distancecounts from the alignments of one align_block_groups call: the class of an instance is the file of its
+    record, the wanted groups are the blocks `used` (distance_blocks); the row comparisons run on the device
+    (BlockFinder.group_distances) and blocks(f, g) -- the used and aligned blocks with an instance in both files -- is
+    counted here."""
+    from . import formats
+    from .api import GALIGN_OK, SibeliaError
+    file_of = _file_of_record(bf.file_records)
+    n = len(bf.file_records)
+    try:
+        counts = bf.group_distances([file_of(c) for inst in insts for c, _, _, _ in inst], n, [block in used for block in ids])
+    except SibeliaError as e:
+        raise PipelineError(str(e))
+    shared = [[0] * n for _ in range(n)]
+    for block, inst, al in zip(ids, insts, aligned):
+        if block in used and al.status == GALIGN_OK:
+            files = sorted({file_of(c) for c, _, _, _ in inst})
+            for f in files:
+                for g in files:
+                    shared[f][g] += f != g
+    names = file_names(opt.filenames)
+    out = {}
+    if opt.distances is not None:
+        out[opt.distances] = formats.distances_text(names, counts, complain)
+    if opt.distancecounts is not None:
+        out[opt.distancecounts] = formats.distance_counts_text(names, counts, shared, opt.gapopen)
+    return out
+
+
 def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], complain: Callable[[str], None], blocks=None) -> Dict[str, bytes]:
     """--multimaf: one MAF paragraph per block with at least two instances, in ascending id, its `s` lines in the order of the alignment
     (centre first: BlockFinder.align_block_groups).  A skipped block is named through `complain` in one line and is absent.
     --multivariants: the calls read off the SAME alignments (one align_block_groups call serves both; BlockFinder.group_variants,
     DESIGN.md 0.6) for the qualifying blocks of the final list `blocks` (qualifying_blocks) as a multi-sample VCF; the first-file
-    instance sorts first, so it is the centre and its alleles are REF."""
+    instance sorts first, so it is the centre and its alleles are REF.
+    --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two."""
     import bisect
     from . import formats
     from .api import GALIGN_OK, SibeliaError
@@ -528,10 +617,12 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
         raise PipelineError(str(e))
     size = bf.record_sizes()
     qualify = set(qualifying_blocks(blocks, bf.file_records, opt.minblocksize)) if opt.multivariants is not None else set()
+    distances = opt.distances is not None or opt.distancecounts is not None
+    used = set(distance_blocks(blocks, bf.file_records, opt.minblocksize)) if distances else set()
     groups = []
     for block, inst, al in zip(ids, insts, aligned):
         if al.status != GALIGN_OK:
-            if opt.multimaf is not None or block in qualify:
+            if opt.multimaf is not None or block in qualify or block in used:
                 complain("block %d not aligned: one of its %d instances against %s:%d-%d is beyond the limits of one alignment "
                          "(%s, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2], skip_limits(opt)))
             continue
@@ -560,6 +651,8 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
                 records.append((names[c0], pos, ids[g], alleles[0],
                                 [alleles[row_of[f]] if f in row_of else None for f in range(1, len(bf.file_records))]))
         out[opt.multivariants] = formats.multi_vcf_text(names[0], sample_names(opt.filenames), records, opt.gapopen)
+    if distances:
+        out.update(distance_files(bf, opt, ids, insts, aligned, used, complain))
     return out
 
 
@@ -631,7 +724,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 bf.set_wide(True)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
-            if opt.multimaf is not None or opt.multivariants is not None:      # likewise on the final list
+            if opt.multimaf is not None or opt.multivariants is not None or opt.distances is not None or opt.distancecounts is not None:      # likewise on the final list
                 files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write, blocks))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
