@@ -223,8 +223,8 @@ sbl_status sbl_glue_stripes(sbl_block *blocks, uint64_t *n, uint32_t nchr);
  *   >Seq="<description>",Strand='<+|->',Block_id=<|id|>,Start=<from>,End=<to>
  * (1-based; a reverse instance is reported from its far end, as in blocks_coords.txt), the end - start bases in lines of 80 and a
  * line feed.  Reverse instances are spelled downwards through the reference's complement table (src/dnasequence.cpp:11-28):
- * ACGT / acgt swapped, every other character -- ambiguity codes included -- unchanged.  The text is generated by a kernel
- * (csrc/blockseq.hip) and comes back through a pinned buffer of the context, valid until the next sbl_blocks_sequences
+ * ACGT / acgt swapped, every other character -- ambiguity codes included -- unchanged.  The text is spelled by k_spell_text
+ * (csrc/spell_text.hip; csrc/blockseq.hip lists its pieces) and comes back through a pinned buffer of the context, valid until the next sbl_blocks_sequences
  * or sbl_align_pairs / _unique_blocks / _groups / _block_groups or sbl_spell_text call (they share the buffer).  n == 0: empty text.  SBL_ERR_BAD_ARG: chr >= nchr,
  * end < start, end beyond the record, id == 0, no records loaded.
  * sbl_blocks_sequences_times: device time of the last call's kernel and of its device-to-host copy (event pairs). */
@@ -492,7 +492,7 @@ typedef struct { uint32_t kind, chr; uint64_t start, end; uint32_t ref_chr, pad_
 sbl_status sbl_uncovered_calls(sbl_ctx *ctx, uint64_t nlists, const uint64_t *list_first, const sbl_block *blocks, uint32_t min_block_size,
                                uint32_t n_reference_chr, const sbl_uncovered_call **calls, uint64_t *ncalls);
 
-/* Text put together on the device from the ORIGINAL records (csrc/uncovered.hip, k_spell_text): the concatenation of npieces pieces in
+/* Text put together on the device from the ORIGINAL records (csrc/spell_text.hip, k_spell_text): the concatenation of npieces pieces in
  * the order given.  A piece is
  *   SBL_PIECE_LITERAL  bytes [start, end) of `literals` (literal_len bytes), as they are; chr ignored, width 0
  *   SBL_PIECE_RECORD   bases [start, end) of record chr, forward, upper-cased ('a' .. 'z' only); width > 0: in lines -- a line feed

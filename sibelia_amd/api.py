@@ -525,11 +525,14 @@ class BlockFinder:
             out.append((g, s, e, int(x["before"]), lead, [packed[at + i * w:at + (i + 1) * w] for i in range(ninst[g])]))
         return out
 
+    def _times(self, what) -> Tuple[float, float]:
+        k, d = C.c_double(), C.c_double()
+        self._check(getattr(self.L, what)(self.h, C.byref(k), C.byref(d)), what)
+        return k.value, d.value
+
     def group_variants_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms of the slices) of the last group_variants call, from event pairs."""
-        k, d = C.c_double(), C.c_double()
-        self._check(self.L.sbl_group_variants_times(self.h, C.byref(k), C.byref(d)), "sbl_group_variants_times")
-        return k.value, d.value
+        return self._times("sbl_group_variants_times")
 
     def group_distances(self, cls: Sequence[int], nclass: int, want: Optional[Sequence[bool]] = None) -> np.ndarray:
         """The pairwise counts of the groups of the LAST align_groups / align_block_groups call (csrc/group_distances.hip; defined in
@@ -556,9 +559,7 @@ class BlockFinder:
 
     def group_distances_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms of the matrix) of the last group_distances call, from event pairs."""
-        k, d = C.c_double(), C.c_double()
-        self._check(self.L.sbl_group_distances_times(self.h, C.byref(k), C.byref(d)), "sbl_group_distances_times")
-        return k.value, d.value
+        return self._times("sbl_group_distances_times")
 
     def align_stats(self) -> dict:
         """Counters of the last align_pairs / align_unique_blocks / align_groups / align_block_groups: pairs, skipped, passes, launches,
@@ -617,7 +618,7 @@ class BlockFinder:
     def spell_text(self, pieces: np.ndarray, literals: bytes = b"") -> bytes:
         """The concatenation of `pieces` (PIECE_DTYPE, e.g. formats.TextPieces.pieces()): ranges of `literals` as they are, forward ranges
         of the original records upper-cased, wrapped into lines of `width` bases where width > 0.  Spelled by k_spell_text
-        (csrc/uncovered.hip) from the records on the device."""
+        (csrc/spell_text.hip) from the records on the device."""
         arr = np.ascontiguousarray(pieces, dtype=PIECE_DTYPE)
         hold = C.create_string_buffer(PIECE_DTYPE.itemsize)
         t, ln = C.c_void_p(), C.c_uint64()
@@ -627,9 +628,7 @@ class BlockFinder:
 
     def spell_text_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms) of the last spell_text call, from event pairs."""
-        k, d = C.c_double(), C.c_double()
-        self._check(self.L.sbl_spell_text_times(self.h, C.byref(k), C.byref(d)), "sbl_spell_text_times")
-        return k.value, d.value
+        return self._times("sbl_spell_text_times")
 
     def _block_report(self, fn, what, blocks, names) -> bytes:
         nm = self._names_array(what, names)
@@ -646,14 +645,13 @@ class BlockFinder:
 
     def blocks_sequences(self, blocks: Optional[np.ndarray] = None, names: Optional[Sequence[str]] = None) -> bytes:
         """OutputGenerator::ListBlocksSequences (reference src/outputgenerator.cpp:287-318): the text of blocks_sequences.fasta for
-        `blocks` (None: the blocks of the last GenerateSyntenyBlocks / postprocess), generated on the device from the original records."""
+        `blocks` (None: the blocks of the last GenerateSyntenyBlocks / postprocess), spelled by k_spell_text (csrc/spell_text.hip) from
+        the original records on the device."""
         return self._block_report(self.L.sbl_blocks_sequences, "sbl_blocks_sequences", blocks, names)
 
     def blocks_sequences_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms) of the last blocks_sequences call, from event pairs."""
-        k, d = C.c_double(), C.c_double()
-        self._check(self.L.sbl_blocks_sequences_times(self.h, C.byref(k), C.byref(d)), "sbl_blocks_sequences_times")
-        return k.value, d.value
+        return self._times("sbl_blocks_sequences_times")
 
     def blocks_gff(self, blocks: Optional[np.ndarray] = None, names: Optional[Sequence[str]] = None) -> bytes:
         """OutputGenerator::ListBlocksIndicesGFF (reference src/outputgenerator.cpp:598-631): the text of blocks_coords.gff."""

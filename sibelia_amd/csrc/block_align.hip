@@ -23,7 +23,7 @@
 //             a device buffer and the bases read from the records; nothing bounds its W.
 //   trace     one wave: lane t fetches the code t steps ahead along the direction of the current step, one ballot consumes the run.
 //             It emits runs (op, length); the certificate is checked first -- a pair that fails it is not traced.
-//   spelling  k_spell_groups, output-stationary like blockseq.hip: a lane owns 16 bytes of the rows, finds its group, its row and its
+//   spelling  k_spell_groups, output-stationary like spell_text.hip: a lane owns 16 bytes of the rows, finds its group, its row and its
 //             run by binary search over tables the host made from the runs, and writes them with one vector store.  The two gapped
 //             rows of a pair are the rows of a group of one member (gm_spell).
 //   host      passes: every pending pair runs at its current w; those that miss the certificate double w.  Per pass the pairs are
@@ -370,7 +370,7 @@ constexpr unsigned GS_THREADS = 256;
 struct GaSpan { u64 col; unsigned ai, bj, op, len; };                       // a run: first column in its pair's two rows, first base of a / b
 struct GmInst { u64 src, first_span; unsigned len, rev, nspans, pad_; };       // a row: its range; a member's spans (of the pair centre / member)
 
-// Output-stationary like blockseq.hip: a lane owns 16 bytes of the text and writes them with one vector store.  Group by binary search
+// Output-stationary like spell_text.hip: a lane owns 16 bytes of the text and writes them with one vector store.  Group by binary search
 // over text offsets, then row and column; the column's slot by binary search over the group's merged slots, a member's run by binary
 // search over its spans by centre index.
 // From there the lane steps byte by byte: slot, span, row and group advance as the column does.

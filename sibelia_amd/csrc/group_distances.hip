@@ -121,19 +121,12 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_distances(const uint8_t *_
 	}
 }
 
-float gd_elapsed(sbl_ctx *c, int a, int b)
-{
-	float ms = 0;
-	(void)hipEventElapsedTime(&ms, c->ev[a], c->ev[b]);
-	return ms;
-}
-
 }  // namespace
 
 extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const uint32_t *cls, uint32_t nclass, const sbl_pair_counts **counts)
 {
 	return guarded(c, [&] {
-		SBL_CHECK(c->gv_rows_valid, SBL_ERR_BAD_ARG, "no rows of groups on the device: the last sbl_align_* call must be sbl_align_groups or sbl_align_block_groups");
+		require_group_rows(c);
 		const size_t ninst = c->gm_inst.size();
 		SBL_CHECK(cls || !ninst, SBL_ERR_BAD_ARG, "null classes");
 		SBL_CHECK(nclass >= 1 && nclass <= 1024, SBL_ERR_BAD_ARG, "the number of classes must be 1 .. 1024");
@@ -141,20 +134,16 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 		hipStream_t s = c->stream;
 		const size_t cells = (size_t)nclass * nclass;
 		c->gd_counts.assign(cells, sbl_pair_counts{0, 0, 0, 0});
-		c->gd_kernel_ms = c->gd_copy_ms = 0;
+		c->gd_times = SblTimes{};
 		// the wanted groups that have row pairs to compare, and the columns all their block pairs walk
 		struct Wanted { size_t g; u64 nb; };
 		std::vector<Wanted> groups;
-		u64 text_end = 0, work = 0;
-		for (size_t g = 0; g < c->gm_res.size(); g++) {
-			const sbl_group_result &r = c->gm_res[g];
-			if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
-			text_end = std::max<u64>(text_end, r.row_off + (u64)r.ninst * r.L);
-			if (r.ninst < 2 || (want && !want[g])) continue;
+		u64 work = 0;
+		const u64 text_end = for_each_wanted_group(c, want, [&](size_t g, const sbl_group_result &r, u64) {
 			const u64 nb = (r.ninst + GD_ROWS - 1) / GD_ROWS;
 			groups.push_back(Wanted{g, nb});
 			work += nb * (nb + 1) / 2 * r.L;
-		}
+		}).text_end;
 		if (!groups.empty()) {
 			u64 span = std::max(GD_MIN_SPAN, (work / GD_TARGET + GD_TILE) / GD_TILE * GD_TILE);
 			if (const char *e = getenv("SBL_TEST_GDIST_SPAN")) span = (u64)std::max(1ll, atoll(e));
@@ -188,8 +177,8 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 			HIP_TRY(hipMemcpyAsync(c->gd_counts.data(), c->d_gd_mat.p, cells * sizeof(sbl_pair_counts), hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipEventRecord(c->ev[2], s));
 			HIP_TRY(hipStreamSynchronize(s));
-			c->gd_kernel_ms = gd_elapsed(c, 0, 1);
-			c->gd_copy_ms = gd_elapsed(c, 1, 2);
+			c->gd_times.kernel_ms = sbl_elapsed_ms(c, 0, 1);
+			c->gd_times.copy_ms = sbl_elapsed_ms(c, 1, 2);
 			c->stats.device_bytes = sbl_devbuf_total().load();
 		}
 		if (counts) *counts = c->gd_counts.data();
@@ -198,8 +187,5 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 
 extern "C" sbl_status sbl_group_distances_times(const sbl_ctx *c, double *kernel_ms, double *copyback_ms)
 {
-	if (!c) return SBL_ERR_BAD_ARG;
-	if (kernel_ms) *kernel_ms = c->gd_kernel_ms;
-	if (copyback_ms) *copyback_ms = c->gd_copy_ms;
-	return SBL_OK;
+	return sbl_times_out(c, &sbl_ctx::gd_times, kernel_ms, copyback_ms);
 }

@@ -6,7 +6,7 @@
 //
 //   classes   k_column_classes, output-stationary over the columns of the wanted groups, every group padded to a multiple of 16 columns:
 //             a lane owns 16 consecutive columns of ONE group, reads those 16 bytes of every row -- neighbouring lanes read neighbouring
-//             bytes of a row: 1 KiB per wave and row -- as two aligned 16-byte words shifted in registers (window16, as blockseq.hip
+//             bytes of a row: 1 KiB per wave and row -- as two aligned 16-byte words shifted in registers (window16, as spell_text.hip
 //             does: toff + i L is not aligned in general), compares them 8 bytes at a time and writes 16 class bytes with one vector
 //             store: 0 equal, 1 unequal, 3 unequal and gapped.
 //   bounds    k_segment_bounds, one lane per column: an unequal column OPENS a segment if it is column 0 or the equal run that ends before
@@ -150,41 +150,27 @@ unsigned gv_blocks(u64 lanes)
 	return (unsigned)blocks;
 }
 
-float gv_elapsed(sbl_ctx *c, int a, int b)
-{
-	float ms = 0;
-	(void)hipEventElapsedTime(&ms, c->ev[a], c->ev[b]);
-	return ms;
-}
-
 }  // namespace
 
 extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const sbl_group_segment **segs, uint64_t *nsegs,
                                          const char **text, uint64_t *text_len)
 {
 	return guarded(c, [&] {
-		SBL_CHECK(c->gv_rows_valid, SBL_ERR_BAD_ARG, "no rows of groups on the device: the last sbl_align_* call must be sbl_align_groups or sbl_align_block_groups");
+		require_group_rows(c);
 		hipStream_t s = c->stream;
 		c->gv_segs.clear(); c->gv_text.clear();
-		c->gv_kernel_ms = c->gv_copy_ms = 0;
+		c->gv_times = SblTimes{};
 		// the wanted groups that have columns to compare; dg: d_gm_group lists the aligned groups with L > 0, in order
 		std::vector<GvGroup> groups;
 		std::vector<u64> cbase(1, 0);
-		u64 dg = 0, text_end = 0;
-		for (size_t g = 0; g < c->gm_res.size(); g++) {
-			const sbl_group_result &r = c->gm_res[g];
-			if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
-			text_end = std::max<u64>(text_end, r.row_off + (u64)r.ninst * r.L);
-			if (r.ninst >= 2 && (!want || want[g])) {
-				groups.push_back(GvGroup{g, dg});
-				cbase.push_back(cbase.back() + (r.L + 15) / 16 * 16);
-			}
-			dg++;
-		}
-		const u64 ng = groups.size(), P = cbase.back(), text_bytes = (text_end + 15) / 16 * 16;
+		const GmListed listed = for_each_wanted_group(c, want, [&](size_t g, const sbl_group_result &r, u64 dg) {
+			groups.push_back(GvGroup{g, dg});
+			cbase.push_back(cbase.back() + (r.L + 15) / 16 * 16);
+		});
+		const u64 ng = groups.size(), P = cbase.back(), text_bytes = (listed.text_end + 15) / 16 * 16;
 		u64 nseg = 0, total = 0;
 		if (ng) {
-			SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes && c->d_gm_group.cap >= dg * sizeof(GmGroup), SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
+			SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes && c->d_gm_group.cap >= listed.n * sizeof(GmGroup), SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
 			const uint8_t *rows = c->d_ga_text.as<uint8_t>();
 			const GmGroup *gm = c->d_gm_group.as<GmGroup>();
 			al_upload(c, c->d_gv_group, groups); al_upload(c, c->d_gv_cbase, cbase);
@@ -238,12 +224,12 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 			HIP_TRY(hipMemcpyAsync(c->gv_text.data(), c->d_gv_text.p, padded, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipEventRecord(c->ev[5], s));
 			HIP_TRY(hipStreamSynchronize(s));
-			c->gv_kernel_ms = gv_elapsed(c, 0, 2) + gv_elapsed(c, 3, 4);      // the prefix of the slice lengths on the host lies between
-			c->gv_copy_ms = gv_elapsed(c, 4, 5);
+			c->gv_times.kernel_ms = sbl_elapsed_ms(c, 0, 2) + sbl_elapsed_ms(c, 3, 4);      // the prefix of the slice lengths on the host lies between
+			c->gv_times.copy_ms = sbl_elapsed_ms(c, 4, 5);
 		} else if (ng) {
 			HIP_TRY(hipEventRecord(c->ev[2], s));
 			HIP_TRY(hipStreamSynchronize(s));
-			c->gv_kernel_ms = gv_elapsed(c, 0, 2);
+			c->gv_times.kernel_ms = sbl_elapsed_ms(c, 0, 2);
 		}
 		c->stats.device_bytes = sbl_devbuf_total().load();
 		if (segs) *segs = c->gv_segs.data();
@@ -255,8 +241,5 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 
 extern "C" sbl_status sbl_group_variants_times(const sbl_ctx *c, double *kernel_ms, double *copyback_ms)
 {
-	if (!c) return SBL_ERR_BAD_ARG;
-	if (kernel_ms) *kernel_ms = c->gv_kernel_ms;
-	if (copyback_ms) *copyback_ms = c->gv_copy_ms;
-	return SBL_OK;
+	return sbl_times_out(c, &sbl_ctx::gv_times, kernel_ms, copyback_ms);
 }

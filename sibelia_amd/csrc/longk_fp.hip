@@ -943,9 +943,7 @@ bool sbl_run_enumeration_longk_fp(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 	c->stats.exchange_ms = xms;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
-	float ms = 0;
-	HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-	c->stats.kmer_table_ms = ms;
+	c->stats.kmer_table_ms = sbl_elapsed_ms(c, 0, 1);
 	size_t positions = 0;
 	for (uint32_t ch = 0; ch < c->nchr; ch++) { const size_t len = c->sepidx[ch + 1] - c->sepidx[ch] - 1; if (len >= k) positions += len - k + 1; }
 	// algorithmic bytes (k > 32): 2-bit sequence once + one 32-B slot read and written per base position + k/4 B per verified occurrence

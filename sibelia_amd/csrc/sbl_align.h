@@ -40,9 +40,7 @@ template <class F> float al_timed_launch(sbl_ctx *c, F launch, void *back, const
 	HIP_TRY(hipEventRecord(c->ev[1], s));
 	HIP_TRY(hipMemcpyAsync(back, d_from, bytes, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	float ms = 0;
-	(void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-	return ms;
+	return sbl_elapsed_ms(c, 0, 1);
 }
 
 // a table of descriptors into its device buffer, grown to hold it
@@ -63,6 +61,28 @@ inline void check_range(const sbl_ctx *c, uint32_t chr, uint64_t start, uint64_t
 	SBL_CHECK(chr < c->nchr, SBL_ERR_BAD_ARG, no_record);
 	SBL_CHECK(end >= start, SBL_ERR_BAD_ARG, "a range ends before it starts");
 	SBL_CHECK(end <= (uint64_t)(c->orig_sepidx[chr + 1] - c->orig_sepidx[chr] - 1), SBL_ERR_BAD_ARG, "a range runs beyond its record");
+}
+
+// what sbl_group_variants and sbl_group_distances ask for first: the rows of the last groups call are still on the device
+inline void require_group_rows(const sbl_ctx *c)
+{
+	SBL_CHECK(c->gv_rows_valid, SBL_ERR_BAD_ARG, "no rows of groups on the device: the last sbl_align_* call must be sbl_align_groups or sbl_align_block_groups");
+}
+
+// f(g, r, dg) for every wanted group g (want: null or one byte per group) that has rows to compare with each other; r: its result, dg: its
+// place in d_gm_group, which lists the aligned groups with L > 0 in order.  Returns how many those are and where their rows end in d_ga_text
+struct GmListed { u64 n, text_end; };
+template <class F> GmListed for_each_wanted_group(const sbl_ctx *c, const uint8_t *want, F f)
+{
+	GmListed l{0, 0};
+	for (size_t g = 0; g < c->gm_res.size(); g++) {
+		const sbl_group_result &r = c->gm_res[g];
+		if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
+		l.text_end = std::max<u64>(l.text_end, r.row_off + (u64)r.ninst * r.L);
+		if (r.ninst >= 2 && (!want || want[g])) f(g, r, l.n);
+		l.n++;
+	}
+	return l;
 }
 
 // f(i, j) for every run v[i .. j) of equal |id| of a list sorted by |id|; f may change the run it is given

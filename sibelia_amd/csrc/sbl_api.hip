@@ -287,9 +287,7 @@ void sbl_run_enumeration(sbl_ctx *c, uint32_t k, size_t elem_capacity)
 		k_scatter_members<<<nblocks(nmem, 256), 256, 0, s>>>(members, nmem, k, c->d_pairids.as<unsigned>(), c->d_bif[0].as<unsigned>(), c->d_bif[1].as<unsigned>());
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
-	float ms = 0;
-	HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-	c->stats.kmer_table_ms = ms;
+	c->stats.kmer_table_ms = sbl_elapsed_ms(c, 0, 1);
 	// algorithmic bytes of the table build: 2-bit sequence read once + one 16-B slot read and written per base position
 	size_t positions = 0;
 	for (uint32_t ch = 0; ch < c->nchr; ch++) {

@@ -2,6 +2,9 @@
 #pragma once
 #include "sbl_common.h"
 
+// device time of a call's last launch: event pairs around its kernels / around the device-to-host copy of what they made
+struct SblTimes { double kernel_ms = 0, copy_ms = 0; };
+
 struct sbl_ctx {
 	int device = 0;
 	unsigned stage_seq = 0;          // stages run on this context (rotates which launches carry an event pair, simplify.hip)
@@ -88,19 +91,17 @@ struct sbl_ctx {
 	std::string report[3];               // sbl_postprocess: blocks_coords.txt, genomes_permutations.txt, coverage_report.txt
 	std::string gff_text, coords_text;   // sbl_blocks_gff, sbl_blocks_coords
 
-	// sbl_blocks_sequences (blockseq.hip): descriptors, text offsets, header blob and the text on the device; the text comes back
-	// through ONE pinned staging buffer (pageable when the pinned allocation fails: h_bs_pinned), freed with the context
+	// sbl_spell_pieces (spell_text.hip), for sbl_blocks_sequences and sbl_spell_text: descriptors, text offsets, blob of literals and
+	// the text on the device; the text comes back through ONE pinned staging buffer (pageable when the pinned allocation fails:
+	// h_bs_pinned), freed with the context.  The times of the last launch, per entry point
 	DevBuf d_bs_desc, d_bs_off, d_bs_hdr, d_bs_text;
-	std::string bs_headers;
 	char *h_bs_text = nullptr;
 	size_t h_bs_cap = 0;
 	bool h_bs_pinned = true;
-	uint64_t bs_len = 0;
-	double bs_kernel_ms = 0, bs_copy_ms = 0;   // event pairs around the kernel / the device-to-host copy of the last call
+	SblTimes bs_times, st_times;
 
-	// sbl_uncovered_calls / sbl_spell_text (uncovered.hip): what the first hands out; the second spells through d_bs_* and h_bs_text
+	// sbl_uncovered_calls (uncovered.hip): what it hands out
 	std::vector<sbl_uncovered_call> unc_calls;
-	double st_kernel_ms = 0, st_copy_ms = 0;   // event pairs around k_spell_text / the device-to-host copy of the last call
 
 	// sbl_correct_boundaries / sbl_align_windows (boundary_align.hip): descriptors, trace codes, results, caller-supplied strings
 	DevBuf d_ba_desc, d_ba_codes, d_ba_out, d_ba_seq;
@@ -133,12 +134,12 @@ struct sbl_ctx {
 	DevBuf d_gv_group, d_gv_cbase, d_gv_class, d_gv_flag, d_gv_open, d_gv_close, d_gv_count, d_gv_seg, d_gv_slice, d_gv_toff, d_gv_text, d_gv_tmp;
 	std::vector<sbl_group_segment> gv_segs;
 	std::vector<char> gv_text;
-	double gv_kernel_ms = 0, gv_copy_ms = 0;   // event pairs around the kernels / the device-to-host copy of the slices of the last call
+	SblTimes gv_times;                   // the kernels / the copy of the slices
 	// sbl_group_distances (group_distances.hip): reads d_ga_text under the same rule (gv_rows_valid) and nothing of sbl_group_variants':
 	// work items, the classes of the instances and the class matrix on the device; the matrix comes back into a host buffer of its own
 	DevBuf d_gd_item, d_gd_cls, d_gd_mat;
 	std::vector<sbl_pair_counts> gd_counts;
-	double gd_kernel_ms = 0, gd_copy_ms = 0;   // event pairs around clearing the matrix and the kernel / the device-to-host copy of the matrix
+	SblTimes gd_times;                   // clearing the matrix and the kernel / the copy of the matrix
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;
@@ -180,6 +181,23 @@ static sbl_status guarded(sbl_ctx *c, F f)
 	}
 }
 
+// milliseconds between two recorded and completed events of the context
+inline float sbl_elapsed_ms(sbl_ctx *c, int a, int b)
+{
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, c->ev[a], c->ev[b]));
+	return ms;
+}
+
+// the body of every sbl_*_times entry point
+inline sbl_status sbl_times_out(const sbl_ctx *c, SblTimes sbl_ctx::*t, double *kernel_ms, double *copyback_ms)
+{
+	if (!c) return SBL_ERR_BAD_ARG;
+	if (kernel_ms) *kernel_ms = (c->*t).kernel_ms;
+	if (copyback_ms) *copyback_ms = (c->*t).copy_ms;
+	return SBL_OK;
+}
+
 // what the entry points that read the original records / the context's block list ask for first
 inline void require_records(const sbl_ctx *c)
 {
@@ -211,6 +229,7 @@ void sbl_render_reports(sbl_ctx *c, const char *const *names);   // report[0..2]
 void sbl_sort_by_id(std::vector<sbl_block> &v);   // the one unstable sort by |id| the reference's writers apply to a copy of the list
 // implemented in blockseq.hip
 void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n);   // a caller's block list against the loaded records (throws SBL_ERR_BAD_ARG)
+// implemented in spell_text.hip
 void sbl_text_staging(sbl_ctx *c, size_t bytes);   // h_bs_text, the pinned staging buffer of device-made text, grown to `bytes`
 // implemented in simplify.hip
 void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges);

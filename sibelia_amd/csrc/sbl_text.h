@@ -1,10 +1,31 @@
-// sbl_text.h -- what the output-stationary text kernels share (blockseq.hip: k_block_sequences, uncovered.hip: k_spell_text): the search
-// of a text offset in the offsets of the pieces, and 16 bytes of text held in two registers -- cut out of two aligned source words
-// (gv_load16: the readers of the alignment rows, group_variants.hip and group_distances.hip), opened for a line feed.
+// sbl_text.h -- the text kernel's tools (spell_text.hip: k_spell_text): the search of a text offset in the offsets of the pieces, and
+// 16 bytes of text held in two registers -- cut out of two aligned source words (gv_load16: the readers of the alignment rows,
+// group_variants.hip and group_distances.hip), complemented, opened for a line feed.  And the pieces k_spell_text spells, with the one
+// host function that launches it for sbl_spell_text (spell_text.hip) and sbl_blocks_sequences (blockseq.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 typedef unsigned long long u64;
+
+// one piece of text, never empty.  Properties of the piece, whoever asks for it:
+constexpr unsigned ST_LITERAL = 1;   // a range of the blob, copied as it is (width 0); otherwise a range of the original records
+constexpr unsigned ST_REVERSE = 2;   // the range is read downwards through the complement (DNASequence::Translate)
+constexpr unsigned ST_KEEP_CASE = 4; // the bases keep their case; otherwise they are upper-cased
+struct StDesc {
+	u64 src;                         // record range: element index of its first base in d_orig_ch; literal: offset in the blob
+	u64 L;                           // bases / literal bytes
+	unsigned width, flags;           // width > 0: a '\n' after every `width` bases and one after the last
+};
+inline u64 st_text_len(u64 L, unsigned width) { return L + (width ? (L + width - 1) / width : 0); }
+
+struct sbl_ctx;
+struct SblTimes;
+// The text of the pieces `desc` (toff: their desc.size() + 1 text offsets, toff[0] = 0; blob: what the literal pieces cut from) into
+// h_bs_text, the context's staging buffer: uploads, k_spell_text and the copy back between event pairs, one synchronise.  `t`: the
+// times of the kernel and of the copy, untouched when there is no text.  too_large: the caller's words for a text beyond the grid.
+void sbl_spell_pieces(sbl_ctx *c, const std::vector<StDesc> &desc, const std::vector<u64> &toff, const char *blob, size_t blob_len, const char *too_large, SblTimes &t);
 
 // largest i in [0, n) with off[i] <= x (off[0] = 0 <= x)
 template <class P> __device__ inline unsigned bs_find(P off, unsigned long long n, u64 x)
@@ -19,6 +40,15 @@ template <class P> __device__ inline unsigned bs_find(P off, unsigned long long 
 
 // zero8: 0x80 in every byte of v that is zero (exact: no carries cross bytes)
 __device__ inline u64 zero8(u64 v) { return ~(((v & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | v) & 0x8080808080808080ull; }
+
+// DNASequence::Translate (src/dnasequence.cpp:11-28) on 8 bytes at once: A <-> T and C <-> G in either case, every other byte unchanged.
+__device__ inline u64 complement8(u64 x)
+{
+	const u64 f = x & 0xDFDFDFDFDFDFDFDFull;                            // case folded: 0x41 only for 'A' / 'a', ...
+	const u64 at = (zero8(f ^ 0x4141414141414141ull) | zero8(f ^ 0x5454545454545454ull)) >> 7;
+	const u64 cg = (zero8(f ^ 0x4343434343434343ull) | zero8(f ^ 0x4747474747474747ull)) >> 7;
+	return x ^ (at * 0x15) ^ (cg * 0x04);                               // 'A' ^ 'T' = 0x15, 'C' ^ 'G' = 0x04
+}
 
 struct B16 { u64 lo, hi; };
 // bytes [sh, sh + 16) of the 32 bytes (a, b), sh in [0, 16)

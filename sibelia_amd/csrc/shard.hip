@@ -480,9 +480,7 @@ static void run_enumeration_sharded(sbl_ctx *c, uint32_t k, size_t elem_capacity
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
 
-	float ms = 0;
-	HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-	c->stats.kmer_table_ms = ms;
+	c->stats.kmer_table_ms = sbl_elapsed_ms(c, 0, 1);
 	c->stats.exchange_ms = clk.ms;
 	size_t positions = 0;
 	for (uint32_t ch = 0; ch < c->nchr; ch++) {

@@ -1,4 +1,5 @@
-"""blocks_sequences.fasta (generated on the device, csrc/blockseq.hip) and blocks_coords.gff on synthetic block lists.
+"""blocks_sequences.fasta (spelled on the device by k_spell_text, csrc/spell_text.hip, from the pieces csrc/blockseq.hip lists) and
+blocks_coords.gff on synthetic block lists.
 
 The expected text is restated here from the format's description (include/sibelia_amd.h): per instance a header
 `>Seq="<description>",Strand='<+|->',Block_id=<|id|>,Start=<from>,End=<to>`, the bases in lines of 80 without a line feed after the
@@ -140,6 +141,10 @@ def test_empty_list(small):
 
 
 def test_hundred_thousand_tiny_instances(small):
+    """Many pieces per workgroup span.  More pieces in a span than the kernel keeps on chip (ST_LDS = 256) cannot come from a block list:
+    the shortest instance -- empty description, one base, one-digit id and positions -- is 44 bytes of header, the base and a line feed,
+    46 bytes in two pieces, so a span of 4096 bytes holds at most 2 * 91 = 182.  The kernel's path through global memory is covered by
+    tests/test_gpu_uncovered.py::test_more_pieces_in_one_span_than_the_kernel_keeps_on_chip."""
     bf, seqs, names = small
     rng = np.random.default_rng(7)
     n = 100_000
@@ -150,6 +155,102 @@ def test_hundred_thousand_tiny_instances(small):
     blocks["id"] = rng.integers(1, 5000, n) * rng.choice([-1, 1], n)
     blocks["chr"], blocks["start"], blocks["end"] = chr_, start, start + ln
     check_sequences(bf.blocks_sequences(blocks, names), blocks, seqs, names)
+
+
+# ------------------------------------------------------------------------------------------ one mixed-case record
+
+def head_len(bid, frm, to):
+    return len(b'>Seq="m",Strand=\'+\',Block_id=%d,Start=%d,End=%d\n' % (bid, frm, to))
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    """One record of 256 bases, as record 0: base s is element 1 + s on the device.  Mixed case, ambiguity codes sprinkled in."""
+    from sibelia_amd import BlockFinder
+    rng = np.random.default_rng(12)
+    seq = bytearray(np.frombuffer(b"ACGTacgt", np.uint8)[rng.integers(0, 8, 256)].tobytes())
+    for p in rng.choice(256, 40, replace=False):
+        seq[int(p)] = b"NnRrYykMsW"[int(rng.integers(0, 10))]
+    seq[:7] = b"aacgNry"
+    seq = bytes(seq)
+    bf = BlockFinder([seq], device=0)
+    yield bf, [seq], ["m"]
+    bf.close()
+
+
+def record_len(bid, start, end, fwd):
+    frm, to = (start + 1, end) if fwd else (end, start + 1)
+    ln = end - start
+    return head_len(bid, frm, to), head_len(bid, frm, to) + ln + ((ln - 1) // 80 if ln else 0) + 1
+
+
+def with_fillers(wanted, rows=()):
+    """wanted: (sign, start, end, residue) per tested instance; rows: instances that come first.  -> rows with ids ascending in list order
+    (the unstable sort has nothing to reorder), every tested instance after one filler instance [0, f) whose length f in 1 .. 40 brings
+    the first byte after the tested instance's header to `residue` mod 16 in the text."""
+    rows = list(rows)
+    at = sum(record_len(abs(bid), a, b, bid > 0)[1] for bid, _, a, b in rows)
+    for sign, start, end, residue in wanted:
+        bid = len(rows) + 1
+        head, whole = record_len(bid + 1, start, end, sign > 0)
+        f = next(f for f in range(1, 41) if (at + record_len(bid, 0, f, True)[1] + head) % 16 == residue)
+        rows += [(bid, 0, 0, f), (sign * (bid + 1), 0, start, end)]
+        at += record_len(bid, 0, f, True)[1] + whole
+    return rows
+
+
+def expected_text(rows, seqs, names):
+    """-> the text, and per instance the offsets of the first byte after its header and of its last byte"""
+    records = [r for _, r in expected_records(blocks_of(rows), seqs, names)]
+    ends = np.cumsum([len(r) for r in records])
+    return b"".join(records), [int(e) - len(r) + r.index(b"\n") + 1 for e, r in zip(ends, records)], [int(e) - 1 for e in ends]
+
+
+LENGTHS = (1, 15, 16, 17, 79, 80, 81, 96, 97, 161)
+
+
+def test_an_instance_at_every_source_and_output_alignment_on_both_strands(mixed):
+    """What tests/test_gpu_uncovered.py::test_a_range_at_every_source_and_output_alignment asserts on forward pieces: the 16-byte windows
+    at an instance's first and last bases, read upwards and downwards, cut from every source alignment and stored at every output
+    alignment; lengths around the piece and the line, and 15 bases before the final line feed."""
+    bf, seqs, names = mixed
+    wanted = [(sign, start, start + ln, dst) for sign in (1, -1) for ln in LENGTHS for start in range(16) for dst in range(16)]
+    rows = with_fillers(wanted)
+    text, body, _ = expected_text(rows, seqs, names)
+    seen = {}
+    for (sign, start, end, _), at in zip(wanted, body[1::2]):
+        seen.setdefault((sign, end - start), set()).add((start % 16, at % 16))
+    assert len(seen) == 2 * len(LENGTHS) and all(len(v) == 256 for v in seen.values())      # on the inputs: every pair occurs
+    assert len(rows) == 2 * 2 * len(LENGTHS) * 256
+    assert bf.blocks_sequences(blocks_of(rows), names) == text
+
+
+def test_the_case_is_kept_and_spell_text_still_upper_cases_on_the_same_finder(mixed):
+    bf, seqs, names = mixed
+    ranges = [(0, 7), (0, 256), (3, 200), (17, 33), (40, 41), (100, 256)]
+    rows = [(sign * (2 * i + (sign < 0) + 1), 0, a, b) for i, (a, b) in enumerate(ranges) for sign in (1, -1)]
+    text, _, _ = expected_text(rows, seqs, names)
+    assert b"End=7\naacgNry\n" in text and b"End=1\nyrNcgtt\n" in text          # a <-> t, c <-> g in their case; N, r, y as they are
+    first = bf.blocks_sequences(blocks_of(rows), names)
+    assert first == text
+    pieces = np.array([(1, 0, a, b, 80, 0) for a, b in ranges], dtype=F.PIECE_DTYPE)
+    kept = b"".join(seqs[0][o:min(o + 80, b)] + b"\n" for a, b in ranges for o in range(a, b, 80))
+    assert bf.spell_text(pieces) == kept.upper() and kept != kept.upper()
+    assert bf.blocks_sequences(blocks_of(rows), names) == first      # the two share their device buffers and the staging buffer
+
+
+def test_empty_instances_at_the_ends_of_the_text_and_of_a_16_byte_piece(mixed):
+    """An instance without bases is its header and one line feed: first in the text, last in the text, and with the line feed as the
+    last (15) and as the first (0) byte of a lane's 16 bytes."""
+    bf, seqs, names = mixed
+    rows = with_fillers([(1, 5, 5, 15), (-1, 256, 256, 0), (1, 0, 0, 15), (-1, 9, 9, 0)], [(1, 0, 0, 0)])
+    rows.append((-(len(rows) + 1), 0, 256, 256))
+    text, body, last = expected_text(rows, seqs, names)
+    empty = [i for i, r in enumerate(rows) if r[2] == r[3]]
+    assert empty == [0, 2, 4, 6, 8, 9] and all(body[i] == last[i] and text[last[i] - 1:last[i] + 1] == b"\n\n" for i in empty)
+    assert text.startswith(b">Seq=\"m\",Strand='+',Block_id=1,Start=1,End=0\n\n>") and text.endswith(b",Start=256,End=257\n\n")
+    assert [last[i] % 16 for i in empty[1:5]] == [15, 0, 15, 0]
+    assert bf.blocks_sequences(blocks_of(rows), names) == text
 
 
 def test_whole_records_of_4_6_mbp():

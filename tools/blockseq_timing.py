@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Times the block-sequences kernel (csrc/blockseq.hip) next to a device-to-device copy of as many bytes as the text it writes.
+"""Times the text kernel (k_spell_text, csrc/spell_text.hip) on the pieces of blocks_sequences.fasta (csrc/blockseq.hip) next to a
+device-to-device copy of as many bytes as the text it writes.
 
-Two inputs: the final block list of `-s loose -r -q` on tests/golden/data/Helicobacter_pylori.fa.gz, and one forward plus one reverse
-whole-record instance for each of 8 records of 4.6 Mbp.  Kernel and device-to-host times are the library's own event pairs
+Three inputs: the final block list of `-s loose -r -q` on tests/golden/data/Helicobacter_pylori.fa.gz, one forward plus one reverse
+whole-record instance for each of 8 records of 4.6 Mbp, and the 100 000 instances of one to three bases of
+tests/test_gpu_blockseq.py::test_hundred_thousand_tiny_instances (same records, same seed): the shape with the most pieces per
+workgroup span.  Kernel and device-to-host times are the library's own event pairs
 (sbl_blocks_sequences_times); the copy is a hipMemcpyAsync between two device buffers timed by an event pair in the same process.
 One warm-up, then RUNS runs; medians are reported.  Writes one JSON document (default: profiles/blockseq_timing.json)."""
 import ctypes as C
@@ -56,6 +59,25 @@ def measure(bf, blocks, names):
             "kernel_gb_per_s": len(text) / km / 1e6, "d2d_copy_gb_per_s": len(text) / cm / 1e6, "device_to_host_ms": dm}
 
 
+def tiny_instances():
+    """the records of the test module's `small` finder and the list of its test -> (finder, blocks, names)"""
+    rng = np.random.default_rng(11)
+    seqs = [bytearray(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n)].tobytes()) for n in (1000, 161, 3000)]
+    for s in seqs:
+        for p in rng.choice(len(s), len(s) // 7, replace=False):
+            s[int(p)] = b"NRYKMSWBDHX-U"[int(rng.integers(0, 13))]
+    seqs[1][:6], seqs[1][-6:] = b"NRYACG", b"TTYRNA"
+    bf = BlockFinder([bytes(s) for s in seqs], device=0)
+    rng, n = np.random.default_rng(7), 100_000
+    chr_ = rng.integers(0, 3, n)
+    ln = rng.integers(1, 4, n)
+    start = np.array([rng.integers(0, len(seqs[c]) - l + 1) for c, l in zip(chr_, ln)])
+    blocks = np.zeros(n, dtype=F.BLOCK_DTYPE)
+    blocks["id"] = rng.integers(1, 5000, n) * rng.choice([-1, 1], n)
+    blocks["chr"], blocks["start"], blocks["end"] = chr_, start, start + ln
+    return bf, blocks, ["gi|15644634|ref|NC_000915.1|", "plain_name", "a.b.c"]
+
+
 def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "blockseq_timing.json")
     torch.cuda.init()
@@ -79,6 +101,7 @@ def main():
     blocks = np.array([(s * (c + 1), c, 0, len(seqs[c])) for c in range(8) for s in (1, -1)], dtype=F.BLOCK_DTYPE)
     res["whole_records_8x4600k_both_strands"] = measure(bf, blocks, ["strain%d" % c for c in range(8)])
     bf.close()
+    res["tiny_instances_100k"] = measure(*tiny_instances())
     with open(out_path, "w") as f:
         json.dump(res, f, indent=1, sort_keys=True)
     print(json.dumps(res, sort_keys=True))

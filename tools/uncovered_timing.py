@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the text kernel of --uncovered (k_spell_text, csrc/uncovered.hip) next to a device-to-device copy of as many bytes as the text
+"""Times the text kernel of --uncovered (k_spell_text, csrc/spell_text.hip) next to a device-to-device copy of as many bytes as the text
 it writes.
 
 Two inputs: the VCF of the Staphylococcus aureus pair (tests/golden/data) under C-Sibelia's command line with --uncovered -- the piece
