@@ -470,6 +470,44 @@ sbl_status sbl_group_distances(sbl_ctx *ctx, const uint8_t *want, const uint32_t
                                const sbl_pair_counts **counts /* nclass * nclass, row-major, owned by ctx */);
 sbl_status sbl_group_distances_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 
+/* Concatenation of the multiple alignments (csrc/group_concat.hip), defined by this project: the rows of the groups of the
+ * context's LAST sbl_align_groups / sbl_align_block_groups call, read where that call left them on the device, group after group, as one
+ * FASTA record per CLASS (the pipeline: the input file) -- the core-genome alignment and its variable columns.
+ * USED GROUPS.  A group is USED if want[g] != 0 (want: one byte per group, NULL: all), its status is SBL_GALIGN_OK and L > 0.  cls gives
+ * every instance of that groups call a class cls[k] < nclass, one entry per instance in the order of `inst`.  A wanted, aligned group with
+ * L > 0 must hold every class 0 .. nclass - 1 exactly once (so ninst == nclass): otherwise SBL_ERR_BAD_ARG, checked on the host before
+ * any launch, and the message names the group.  Skipped groups, unwanted groups and groups with L == 0 give nothing and are not checked.
+ * The used groups are concatenated in the order of the call; row f of the result is, group after group, the row of the instance with
+ * class f.  Bytes are taken as the rows hold them, case kept.
+ * MODE.  SBL_CONCAT_ALL keeps every column of every used group.  SBL_CONCAT_VARIABLE keeps a column if all nclass rows hold one of the
+ * four upper-case bytes A C G T and the rows are not all equal: the columns that give at least one pair a `mismatch` in
+ * sbl_group_distances' terms and no pair an `ambiguous` or a `gap`.  nclass == 1 keeps nothing.
+ * TEXT.  With C the number of kept columns: for f = 0 .. nclass - 1 the bytes headers[header_first[f] .. header_first[f + 1]) as they
+ * are (the caller includes '>' and the line feed), then the C kept bytes of row f in lines of `width`: a '\n' after every `width` bytes
+ * and one after the last (C + ceil(C / width) bytes, the rule of blocks_sequences.fasta).  C == 0 gives the headers alone.
+ * PARTS.  sbl_concat_part, one per used group in order: the group's kept columns are [first, first + ncols) of the concatenation; in
+ * mode ALL ncols == L, in mode VARIABLE it may be 0.
+ * SITES.  sbl_concat_site, mode VARIABLE only (mode ALL: nsites = 0), one per kept column, ascending: `col` is the column in the group,
+ * `before` the number of centre-row bytes other than '-' in columns [0, col) -- the `before` of sbl_group_segment; the centre holds a
+ * base in a kept column, so this is that base's index in the centre instance.
+ * Column flags, their compaction, the sites and the text are made by kernels; text, parts and sites come back in buffers of their own,
+ * owned by the ctx until the next sbl_group_concat: the `rows` of the groups call stay valid and unchanged, and sbl_group_variants,
+ * sbl_group_distances and sbl_group_concat may follow one groups call in any order with the same results.  All offsets are 64 bit.
+ * SBL_ERR_BAD_ARG, checked on the host before any launch: no groups call yet, or the last sbl_align_* call was sbl_align_pairs /
+ * sbl_align_unique_blocks; width == 0; nclass == 0 or nclass > 1024; an unknown mode; cls == NULL while there is at least one instance;
+ * a cls[k] >= nclass; headers == NULL or header_first == NULL; descending header offsets; a used group that breaks the class rule.
+ * SBL_ERR_TOO_LARGE: a text beyond what one launch's grid covers (2^31 workgroups of 4096 bytes).
+ * sbl_group_concat_times: device time of the last call's kernels and of the device-to-host copy of the text (event pairs). */
+#define SBL_CONCAT_ALL 0
+#define SBL_CONCAT_VARIABLE 1
+typedef struct { uint64_t group, first, ncols; } sbl_concat_part;
+typedef struct { uint64_t group, col, before; } sbl_concat_site;
+sbl_status sbl_group_concat(sbl_ctx *ctx, const uint8_t *want, const uint32_t *cls, uint32_t nclass, uint32_t mode, uint32_t width,
+                            const char *headers, const uint64_t *header_first,
+                            const sbl_concat_part **parts, uint64_t *nparts, const sbl_concat_site **sites, uint64_t *nsites,
+                            const char **text, uint64_t *text_len);
+sbl_status sbl_group_concat_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

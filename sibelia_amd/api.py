@@ -31,7 +31,8 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_pairs", "sbl_align_unique_blocks", "sbl_align_stats", "sbl_record_size",
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
-           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times", "sbl_tiny_index",
+           "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
+           "sbl_group_concat", "sbl_group_concat_times", "sbl_tiny_index",
            "sbl_test_touched_list"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -133,6 +134,17 @@ class PairCounts(C.Structure):                     # sbl_pair_counts
     _fields_ = [("match", C.c_uint64), ("mismatch", C.c_uint64), ("ambiguous", C.c_uint64), ("gap", C.c_uint64)]
 
 
+class ConcatPart(C.Structure):                     # sbl_concat_part
+    _fields_ = [("group", C.c_uint64), ("first", C.c_uint64), ("ncols", C.c_uint64)]
+
+
+class ConcatSite(C.Structure):                     # sbl_concat_site
+    _fields_ = [("group", C.c_uint64), ("col", C.c_uint64), ("before", C.c_uint64)]
+
+
+CONCAT_ALL, CONCAT_VARIABLE = 0, 1                 # SBL_CONCAT_ALL, SBL_CONCAT_VARIABLE
+
+
 class GroupAlignment:
     """One sbl_group_result: status (GALIGN_OK / GALIGN_SKIPPED), L, row_off, the rows (centre first, members in the order given) and
     per member (score, band_w, passes).  A skipped group has L = 0, no rows and member scores None."""
@@ -224,6 +236,10 @@ def load_library():
         L.sbl_group_variants_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_group_distances.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.POINTER(PairCounts))]
         L.sbl_group_distances_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_concat.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.POINTER(ConcatPart)), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(ConcatSite)), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.sbl_group_concat_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -560,6 +576,41 @@ class BlockFinder:
     def group_distances_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms of the matrix) of the last group_distances call, from event pairs."""
         return self._times("sbl_group_distances_times")
+
+    def group_concat(self, cls: Sequence[int], nclass: int, headers: Sequence[bytes], mode: int, width: int = 80, want: Optional[Sequence[bool]] = None):
+        """The concatenation of the groups of the LAST align_groups / align_block_groups call (csrc/group_concat.hip; defined in
+        include/sibelia_amd.h), made from the rows that call left on the device.  cls: one class below nclass per instance
+        of that call, flat, in group order; headers: one byte string per class, written as it is ('>' and line feed included); mode:
+        CONCAT_ALL or CONCAT_VARIABLE; want: one flag per group (None: all).
+        -> (text, [(group, first, ncols)], [(group, col, before)]), all copies."""
+        ninst = getattr(self, "_group_ninst", [])
+        mask = None
+        if want is not None:
+            if len(want) != len(ninst):
+                raise ValueError("group_concat: %d flags for %d groups" % (len(want), len(ninst)))
+            mask = bytes(1 if w else 0 for w in want) + b"\0"
+        cls = [int(x) for x in cls]
+        if ninst and len(cls) != sum(ninst):
+            raise ValueError("group_concat: %d classes for %d instances" % (len(cls), sum(ninst)))
+        if any(not 0 <= int(v) <= 2 ** 32 - 1 for v in (nclass, mode, width)) or any(not 0 <= x <= 2 ** 32 - 1 for x in cls):
+            raise SibeliaError("sbl_group_concat: bad argument (a class, their number, the mode or the width outside 32 bits)")
+        if len(headers) != int(nclass):
+            raise ValueError("group_concat: %d headers for %d classes" % (len(headers), int(nclass)))
+        first = [0]
+        for h in headers:
+            first.append(first[-1] + len(h))
+        arr = (C.c_uint32 * max(1, len(cls)))(*cls)
+        parts, sites, text = C.POINTER(ConcatPart)(), C.POINTER(ConcatSite)(), C.c_void_p()
+        nparts, nsites, ln = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sbl_group_concat(self.h, mask, arr, int(nclass), int(mode), int(width), b"".join(headers) + b"\0", (C.c_uint64 * len(first))(*first),
+                                            C.byref(parts), C.byref(nparts), C.byref(sites), C.byref(nsites), C.byref(text), C.byref(ln)), "sbl_group_concat")
+        p = _view(C.cast(parts, C.c_void_p).value, nparts.value * 3, np.dtype("<u8")).reshape(-1, 3)
+        s = _view(C.cast(sites, C.c_void_p).value, nsites.value * 3, np.dtype("<u8")).reshape(-1, 3)
+        return (C.string_at(text.value, ln.value) if ln.value else b"", [tuple(x) for x in p.tolist()], [tuple(x) for x in s.tolist()])
+
+    def group_concat_times(self) -> Tuple[float, float]:
+        """(kernel ms, device-to-host copy ms of the text) of the last group_concat call, from event pairs."""
+        return self._times("sbl_group_concat_times")
 
     def align_stats(self) -> dict:
         """Counters of the last align_pairs / align_unique_blocks / align_groups / align_block_groups: pairs, skipped, passes, launches,

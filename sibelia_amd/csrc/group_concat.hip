@@ -1,0 +1,311 @@
+// group_concat.hip -- the concatenated alignment of the multiple alignments (include/sibelia_amd.h): the rows of the used
+// groups of the last sbl_align_groups / sbl_align_block_groups call, group after group, as one FASTA record per CLASS the caller gives
+// the instances (the pipeline: the input file) -- all columns (SBL_CONCAT_ALL) or the columns in which all rows hold one of A C G T and
+// not all the same (SBL_CONCAT_VARIABLE).  The text is classes x columns bytes, the order of the rows themselves, and the rows lie on
+// the device (d_ga_text): a column filter and a transposing gather, so they run where the rows are and only the text comes back.
+//
+//   flags     (VARIABLE) k_site_flags, output-stationary over the columns of the used groups, every group padded to a multiple of 16
+//             columns as k_column_classes pads them: a lane owns 16 columns of ONE group, reads those 16 bytes of every row (gv_load16),
+//             accumulates "differs from row 0" and "is one of A C G T" (base_flags8) 8 bytes at a time and writes 16 flag bytes with one
+//             vector store.  Padding columns get flag 0.
+//   sites     (VARIABLE) the flagged columns are compacted in ascending order by rocPRIM's select (sbl_prim.h); the host reads their
+//             number; k_site_fill, one lane per site: the group by binary search over the padded prefix, `before` from the group's merged
+//             gap slots (the arithmetic of k_segment_fill), and for the text kernel the pick (used group, column).
+//   text      k_concat_text, output-stationary like k_spell_text: a lane owns 16 aligned bytes of the text and makes ONE vector store; a
+//             workgroup owns GC_SPAN contiguous bytes and keeps the text offsets of the class rows its span touches in LDS (they differ
+//             only by the header lengths).  A lane finds its class by search over them, then header (literal bytes) or sequence, where
+//             `line = off / (width + 1), col = off % (width + 1)` is derived once.  ALL: the group by bs_find over the parts' first
+//             columns, the source row through roff[used group][class], the start of that class's row of the group in d_ga_text, built on
+//             the host from cls; 16 bytes inside one group's row are cut out of two aligned words (gv_load16) and opened for a line feed
+//             (insert_newline); lanes that straddle a header, a group boundary or two line ends step byte by byte.  VARIABLE: every byte
+//             is one scattered load through the picks -- kept columns are a percent or so of all, so the loads are sparse by nature and
+//             nothing is staged; the stores stay coalesced.
+//   host      every argument is checked before any launch; tables up; event pairs around the kernels and around the copy back; the text
+//             comes back into a pinned buffer of its own that grows on demand (h_gc_text), sites into gc_sites; the parts of mode
+//             VARIABLE are counted on the host from the sites.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "sbl_align.h"
+#include "sbl_prim.h"
+#include "sbl_text.h"
+
+namespace {
+
+constexpr unsigned GC_THREADS = 256, GC_SPAN = GC_THREADS * 16, GC_MAX_CLASS = 1024;
+
+struct GcGroup { u64 group, dg; };                     // a used group: its index in the call; its index in d_gm_group
+struct GcPick { u64 ug, col; };                        // a kept column: its used group and its column there
+
+__global__ __launch_bounds__(GC_THREADS) void k_site_flags(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
+                                                           const GcGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                           u64 padded_cols, unsigned nclass, uint4 *__restrict__ flags)
+{
+	const u64 x0 = ((u64)blockIdx.x * GC_THREADS + threadIdx.x) * 16;
+	if (x0 >= padded_cols) return;
+	const unsigned gi = bs_find(cbase, ngroups, x0);
+	const GmGroup Q = gm[groups[gi].dg];
+	const u64 col0 = x0 - cbase[gi];                                          // < L: the padding of a group is less than 16 columns
+	const unsigned n = Q.L - col0 < 16 ? (unsigned)(Q.L - col0) : 16;        // columns of the group in this piece
+	const B16 ref = gv_load16(text, text_bytes, Q.toff + col0);
+	u64 dlo = 0, dhi = 0, alo = base_flags8(ref.lo), ahi = base_flags8(ref.hi);
+	for (unsigned i = 1; i < nclass; i++) {                                   // a used group has nclass rows
+		const B16 w = gv_load16(text, text_bytes, Q.toff + (u64)i * Q.L + col0);
+		dlo |= w.lo ^ ref.lo; dhi |= w.hi ^ ref.hi;
+		alo &= base_flags8(w.lo); ahi &= base_flags8(w.hi);
+	}
+	u64 flo = (nonzero8(dlo) & alo) >> 7, fhi = (nonzero8(dhi) & ahi) >> 7;
+	// the bytes behind column L belong to the next row or to nothing: flag 0
+	if (n < 16) {
+		if (n <= 8) { fhi = 0; flo = n == 8 ? flo : flo & ((1ull << (8 * n)) - 1); }
+		else fhi &= (1ull << (8 * (n - 8))) - 1;
+	}
+	flags[x0 / 16] = make_uint4((unsigned)flo, (unsigned)(flo >> 32), (unsigned)fhi, (unsigned)(fhi >> 32));
+}
+
+__global__ __launch_bounds__(GC_THREADS) void k_site_fill(const GmGroup *__restrict__ gm, const GmSlot *__restrict__ slots, const GcGroup *__restrict__ groups,
+                                                          const u64 *__restrict__ cbase, u64 ngroups, const u64 *__restrict__ xs, u64 nsites,
+                                                          sbl_concat_site *__restrict__ sites, GcPick *__restrict__ picks)
+{
+	const u64 i = (u64)blockIdx.x * GC_THREADS + threadIdx.x;
+	if (i >= nsites) return;
+	const u64 x = xs[i];
+	const unsigned gi = bs_find(cbase, ngroups, x);
+	const GmGroup Q = gm[groups[gi].dg];
+	const u64 s = x - cbase[gi];
+	// the centre index column s belongs to = the centre bases before it (k_segment_fill)
+	const u64 si = ga_find(0, Q.nslots, [&](u64 y) { return slots[Q.first_slot + y].col <= s; });
+	const GmSlot S = slots[Q.first_slot + si];
+	const u64 o = s - S.col, before = o < S.G ? S.p : S.p + (o - S.G);
+	sites[i] = sbl_concat_site{groups[gi].group, s, before};
+	picks[i] = GcPick{gi, s};
+}
+
+// coff: the nclass + 1 text offsets of the class rows; row f is its header -- hdr[coff[f] - f S ...), S = st_text_len(C, width) -- and the
+// S bytes of its C kept columns in lines.  roff[ug * nclass + f]: where the row of class f of used group ug starts in `text`.
+// ALL: first[ug] (nused + 1): the first column of the used group in the concatenation.  VARIABLE: picks[C].
+template <bool VARIABLE>
+__global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__restrict__ text, u64 text_bytes, const u64 *__restrict__ roff,
+                                                            const u64 *__restrict__ first, u64 nused, const GcPick *__restrict__ picks,
+                                                            const u64 *__restrict__ coff, unsigned nclass, const char *__restrict__ hdr,
+                                                            u64 C, u64 S, unsigned width, u64 total, uint4 *__restrict__ out)
+{
+	__shared__ u64 s_off[GC_MAX_CLASS + 1];
+	__shared__ unsigned s_first, s_last;
+	const u64 span0 = (u64)blockIdx.x * GC_SPAN;
+	if (span0 >= total) return;
+	const u64 span1 = span0 + GC_SPAN < total ? span0 + GC_SPAN : total;      // one past the last byte of text in the span
+	if (threadIdx.x == 0) s_first = bs_find(coff, nclass, span0);
+	if (threadIdx.x == 1) s_last = bs_find(coff, nclass, span1 - 1);
+	__syncthreads();
+	const unsigned f0 = s_first, count = s_last - f0 + 1;                     // the classes whose rows the span touches
+	for (unsigned i = threadIdx.x; i <= count; i += GC_THREADS) s_off[i] = coff[f0 + i];
+	__syncthreads();
+
+	const u64 t0 = span0 + (u64)threadIdx.x * 16;
+	if (t0 >= span1) return;
+	unsigned fi = bs_find(s_off, count, t0);                                  // the class row, counted from f0: never an empty one
+	u64 off = t0 - s_off[fi], rlen = s_off[fi + 1] - s_off[fi], hlen = rlen - S;
+	const u64 line = (u64)width + 1;
+	unsigned col = 0;                                                         // place in the line ...
+	u64 c = 0, g = 0;                                                         // ... the kept column the text goes on with and (ALL) its used group
+	if (off >= hlen) { const u64 q = off - hlen; col = (unsigned)(q % line); c = q / line * width + col; }      // the one division of the lane
+	B16 w;
+	bool fast = false;
+	if (!VARIABLE && off >= hlen && off + 16 <= rlen && width >= 16) {
+		// 16 bytes of one class's sequence.  A line is width + 1 >= 17 bytes: at most one line feed of a full line in the piece, and
+		// perhaps the one after the last column
+		const unsigned full = width - col;                                    // col == width: the piece starts on the line feed
+		const u64 last = rlen - 1 - off;                                      // >= 15
+		unsigned nl = 16;                                                     // where a line feed falls in the piece (16: nowhere)
+		fast = !(full < 16 && last < 16 && full != last);                     // both: a last line of a few columns
+		if (fast) {
+			nl = full < 16 ? full : last < 16 ? (unsigned)last : 16;
+			g = bs_find(first, nused, c);                                     // c < C: the piece holds 15 columns at least
+			fast = c + (nl < 16 ? 15 : 16) <= first[g + 1];                   // all of them in one group's row
+		}
+		if (fast) {
+			w = gv_load16(text, text_bytes, roff[g * nclass + f0 + fi] + (c - first[g]));
+			if (nl < 16) w = insert_newline(w, nl);
+		}
+	}
+	if (!fast) {
+		// ---- headers, boundaries between class rows and between groups, narrow lines, picked columns: byte by byte, (c, col, g) stepped
+		if (!VARIABLE && off >= hlen && c < C) g = bs_find(first, nused, c);
+		w.lo = w.hi = 0;
+		for (unsigned j = 0; j < 16 && t0 + j < total; j++) {
+			while (off == rlen) { fi++; off = 0; rlen = s_off[fi + 1] - s_off[fi]; hlen = rlen - S; col = 0; c = 0; g = 0; }      // the next class row, from its start
+			const u64 f = f0 + fi;
+			unsigned char ch;
+			if (off < hlen) ch = (unsigned char)hdr[s_off[fi] - f * S + off];
+			else if (off + 1 == rlen || col == width) { ch = '\n'; col = 0; }
+			else {
+				if (VARIABLE) { const GcPick p = picks[c]; ch = text[roff[p.ug * nclass + f] + p.col]; }
+				else { while (c >= first[g + 1]) g++; ch = text[roff[g * nclass + f] + (c - first[g])]; }
+				c++; col++;
+			}
+			if (j < 8) w.lo |= (u64)ch << (8 * j); else w.hi |= (u64)ch << (8 * (j - 8));
+			off++;
+		}
+	}
+	out[t0 / 16] = make_uint4((unsigned)w.lo, (unsigned)(w.lo >> 32), (unsigned)w.hi, (unsigned)(w.hi >> 32));
+}
+
+unsigned gc_blocks(u64 lanes)
+{
+	const u64 blocks = (lanes + GC_THREADS - 1) / GC_THREADS;
+	SBL_CHECK(blocks < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
+	return (unsigned)blocks;
+}
+
+// the context's pinned buffer for the concatenated text, at least `bytes` large (pageable when pinning fails, as sbl_text_staging)
+void gc_staging(sbl_ctx *c, size_t bytes)
+{
+	if (bytes <= c->h_gc_cap) return;
+	c->host_free(c->h_gc_text, c->h_gc_pinned);
+	c->h_gc_text = nullptr; c->h_gc_cap = 0;
+	const size_t cap = bytes + bytes / 16 + 4096;
+	c->h_gc_pinned = hipHostMalloc((void **)&c->h_gc_text, cap) == hipSuccess;
+	if (!c->h_gc_pinned) {
+		(void)hipGetLastError();
+		c->h_gc_text = (char *)malloc(cap);
+		if (!c->h_gc_text) throw SblError{SBL_ERR_OOM, "host buffer for the concatenated alignment"};
+	}
+	c->h_gc_cap = cap;
+}
+
+[[noreturn]] void gc_bad_group(size_t g, const char *what)
+{
+	char b[160];
+	snprintf(b, sizeof b, "group %zu %s: a used group holds every class exactly once", g, what);
+	throw SblError{SBL_ERR_BAD_ARG, b};
+}
+
+}  // namespace
+
+extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const uint32_t *cls, uint32_t nclass, uint32_t mode, uint32_t width,
+                                       const char *headers, const uint64_t *header_first,
+                                       const sbl_concat_part **parts, uint64_t *nparts, const sbl_concat_site **sites, uint64_t *nsites,
+                                       const char **text, uint64_t *text_len)
+{
+	return guarded(c, [&] {
+		require_group_rows(c);
+		const size_t ninst = c->gm_inst.size();
+		SBL_CHECK(cls || !ninst, SBL_ERR_BAD_ARG, "null classes");
+		SBL_CHECK(nclass >= 1 && nclass <= GC_MAX_CLASS, SBL_ERR_BAD_ARG, "the number of classes must be 1 .. 1024");
+		SBL_CHECK(mode == SBL_CONCAT_ALL || mode == SBL_CONCAT_VARIABLE, SBL_ERR_BAD_ARG, "unknown mode of concatenation");
+		SBL_CHECK(width >= 1, SBL_ERR_BAD_ARG, "the width of a line must be at least 1");
+		SBL_CHECK(headers && header_first, SBL_ERR_BAD_ARG, "null headers");
+		for (uint32_t f = 0; f < nclass; f++) SBL_CHECK(header_first[f] <= header_first[f + 1], SBL_ERR_BAD_ARG, "descending header offsets");
+		for (size_t k = 0; k < ninst; k++) SBL_CHECK(cls[k] < nclass, SBL_ERR_BAD_ARG, "a class is not below the number of classes");
+		const bool variable = mode == SBL_CONCAT_VARIABLE;
+		hipStream_t s = c->stream;
+		c->gc_parts.clear(); c->gc_sites.clear();
+		c->gc_times = SblTimes{};
+		// the used groups (dg: d_gm_group lists the aligned groups with L > 0, in order), where the row of every class starts, the padded
+		// prefix of their columns (VARIABLE) and the parts of mode ALL
+		std::vector<GcGroup> groups;
+		std::vector<u64> roff, cbase(1, 0), first(1, 0);
+		u64 dg = 0, text_end = 0;
+		for (size_t g = 0; g < c->gm_res.size(); g++) {
+			const sbl_group_result &r = c->gm_res[g];
+			if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
+			text_end = std::max<u64>(text_end, r.row_off + (u64)r.ninst * r.L);
+			if (!want || want[g]) {
+				if (r.ninst != nclass) gc_bad_group(g, r.ninst < nclass ? "has fewer instances than there are classes" : "has more instances than there are classes");
+				const size_t at = roff.size();
+				roff.resize(at + nclass, ~0ull);
+				for (u64 i = 0; i < r.ninst; i++) {
+					u64 &slot = roff[at + cls[c->gm_first[g] + i]];
+					if (slot != ~0ull) gc_bad_group(g, "holds a class twice");
+					slot = r.row_off + i * r.L;
+				}
+				groups.push_back(GcGroup{g, dg});
+				cbase.push_back(cbase.back() + (r.L + 15) / 16 * 16);
+				first.push_back(first.back() + r.L);
+			}
+			dg++;
+		}
+		const u64 ng = groups.size(), P = cbase.back(), text_bytes = (text_end + 15) / 16 * 16;
+		if (ng) SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes && c->d_gm_group.cap >= dg * sizeof(GmGroup), SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
+		const uint8_t *rows = c->d_ga_text.as<uint8_t>();
+		u64 C = variable ? 0 : first.back();
+		float kernel_ms = 0;
+		if (variable && ng) {
+			// ---- the kept columns, ascending, and their number
+			al_upload(c, c->d_gc_group, groups); al_upload(c, c->d_gc_cbase, cbase);
+			c->d_gc_flag.ensure((size_t)P); c->d_gc_x.ensure((size_t)P * 8); c->d_gc_count.ensure(8);
+			HIP_TRY(hipEventRecord(c->ev[0], s));
+			k_site_flags<<<gc_blocks(P / 16), GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gc_group.as<GcGroup>(), c->d_gc_cbase.as<u64>(), ng, P, nclass,
+			                                                      c->d_gc_flag.as<uint4>());
+			HIP_TRY(hipGetLastError());
+			prim::select(s, c->d_gc_tmp, rocprim::counting_iterator<u64>(0), c->d_gc_flag.as<uint8_t>(), c->d_gc_x.as<u64>(), c->d_gc_count.as<u64>(), (size_t)P);
+			HIP_TRY(hipEventRecord(c->ev[1], s));
+			HIP_TRY(hipMemcpyAsync(&C, c->d_gc_count.p, 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			kernel_ms = sbl_elapsed_ms(c, 0, 1);
+		}
+		// ---- the text: nclass rows of header and st_text_len(C, width) bytes
+		const u64 S = st_text_len(C, width), h0 = header_first[0];
+		std::vector<u64> coff(nclass + 1, 0);
+		for (uint32_t f = 0; f < nclass; f++) coff[f + 1] = coff[f] + (header_first[f + 1] - header_first[f]) + S;
+		const u64 total = coff[nclass];
+		const size_t padded = (size_t)((total + 15) / 16 * 16);
+		SBL_CHECK((total + GC_SPAN - 1) / GC_SPAN < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "concatenated alignment too large");
+		if (total) {
+			const size_t hbytes = (size_t)(header_first[nclass] - h0);
+			al_upload(c, c->d_gc_roff, roff); al_upload(c, c->d_gc_coff, coff);
+			if (!variable) al_upload(c, c->d_gc_first, first);
+			c->d_gc_hdr.ensure(std::max<size_t>(1, hbytes));
+			if (hbytes) HIP_TRY(hipMemcpyAsync(c->d_gc_hdr.p, headers + h0, hbytes, hipMemcpyHostToDevice, s));
+			c->d_gc_text.ensure(padded);
+			c->d_gc_site.ensure(std::max<size_t>(1, (size_t)(variable ? C : 0)) * sizeof(sbl_concat_site));
+			c->d_gc_pick.ensure(std::max<size_t>(1, (size_t)(variable ? C : 0)) * sizeof(GcPick));
+			gc_staging(c, padded);
+			if (variable) c->gc_sites.resize((size_t)C);
+			const unsigned blocks = (unsigned)((total + GC_SPAN - 1) / GC_SPAN);
+			HIP_TRY(hipEventRecord(c->ev[2], s));
+			if (variable) {
+				if (C) {
+					k_site_fill<<<gc_blocks(C), GC_THREADS, 0, s>>>(c->d_gm_group.as<GmGroup>(), c->d_gm_slot.as<GmSlot>(), c->d_gc_group.as<GcGroup>(), c->d_gc_cbase.as<u64>(), ng,
+					                                                c->d_gc_x.as<u64>(), C, c->d_gc_site.as<sbl_concat_site>(), c->d_gc_pick.as<GcPick>());
+					HIP_TRY(hipGetLastError());
+				}
+				k_concat_text<true><<<blocks, GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gc_roff.as<u64>(), nullptr, ng, c->d_gc_pick.as<GcPick>(), c->d_gc_coff.as<u64>(), nclass,
+				                                                  c->d_gc_hdr.as<char>(), C, S, width, total, c->d_gc_text.as<uint4>());
+			} else
+				k_concat_text<false><<<blocks, GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gc_roff.as<u64>(), c->d_gc_first.as<u64>(), ng, nullptr, c->d_gc_coff.as<u64>(), nclass,
+				                                                   c->d_gc_hdr.as<char>(), C, S, width, total, c->d_gc_text.as<uint4>());
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipEventRecord(c->ev[3], s));
+			HIP_TRY(hipMemcpyAsync(c->h_gc_text, c->d_gc_text.p, padded, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipEventRecord(c->ev[4], s));
+			if (variable && C) HIP_TRY(hipMemcpyAsync(c->gc_sites.data(), c->d_gc_site.p, (size_t)C * sizeof(sbl_concat_site), hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			kernel_ms += sbl_elapsed_ms(c, 2, 3);
+			c->gc_times.copy_ms = sbl_elapsed_ms(c, 3, 4);
+		}
+		c->gc_times.kernel_ms = kernel_ms;
+		// ---- the parts: in mode VARIABLE the sites of every used group, counted here (they come in ascending group)
+		c->gc_parts.resize((size_t)ng);
+		size_t at = 0;
+		for (size_t u = 0; u < ng; u++) {
+			u64 n = first[u + 1] - first[u];
+			if (variable) { const size_t from = at; while (at < c->gc_sites.size() && c->gc_sites[at].group == groups[u].group) at++; n = at - from; }
+			c->gc_parts[u] = sbl_concat_part{groups[u].group, u ? c->gc_parts[u - 1].first + c->gc_parts[u - 1].ncols : 0, n};
+		}
+		c->stats.device_bytes = sbl_devbuf_total().load();
+		if (parts) *parts = c->gc_parts.data();
+		if (nparts) *nparts = ng;
+		if (sites) *sites = c->gc_sites.data();
+		if (nsites) *nsites = c->gc_sites.size();
+		if (text) *text = total ? c->h_gc_text : "";
+		if (text_len) *text_len = total;
+	});
+}
+
+extern "C" sbl_status sbl_group_concat_times(const sbl_ctx *c, double *kernel_ms, double *copyback_ms)
+{
+	return sbl_times_out(c, &sbl_ctx::gc_times, kernel_ms, copyback_ms);
+}

@@ -52,13 +52,6 @@ __device__ inline B16 gd_keep(B16 w, unsigned n)
 	return {w.lo, (w.hi & m) | (GD_GAPS & ~m)};
 }
 
-// 0x80 in every byte of v that is one of A C G T, 0x40 in every byte that is '-'
-__device__ inline u64 gd_flags(u64 v)
-{
-	const u64 base = zero8(v ^ 0x4141414141414141ull) | zero8(v ^ 0x4343434343434343ull) | zero8(v ^ 0x4747474747474747ull) | zero8(v ^ 0x5454545454545454ull);
-	return base | (zero8(v ^ GD_GAPS) >> 1);
-}
-
 __global__ __launch_bounds__(GD_THREADS) void k_group_distances(const uint8_t *__restrict__ text, u64 text_bytes, const GdItem *__restrict__ items,
                                                                 const unsigned *__restrict__ cls, unsigned nclass, unsigned long long *__restrict__ M)
 {
@@ -87,7 +80,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_distances(const uint8_t *_
 			B16 v = gv_load16(text, text_bytes, T.toff + row * T.L + c0 + 16 * k);
 			if (w - 16 * k < 16) v = gd_keep(v, w - 16 * k);                       // behind the span: the next span, the next row or nothing
 			s_word[side][lr][2 * k] = v.lo; s_word[side][lr][2 * k + 1] = v.hi;
-			s_flag[side][lr][2 * k] = gd_flags(v.lo); s_flag[side][lr][2 * k + 1] = gd_flags(v.hi);
+			s_flag[side][lr][2 * k] = base_flags8(v.lo); s_flag[side][lr][2 * k + 1] = base_flags8(v.hi);
 		}
 		__syncthreads();
 		if (!any) continue;

@@ -36,9 +36,6 @@ constexpr unsigned GV_CONTEXT = 30;                    // MINIMUM_CONTEXT_SIZE (
 struct GvGroup { u64 group, dg; };                     // a wanted group: its index in the call; its index in d_gm_group
 struct GvSlice { u64 src, L, len; };                   // a segment's slices: first byte of the centre's in the rows, row stride, bytes per row
 
-// 0x80 in every byte of v that is not zero
-__device__ inline u64 nonzero8(u64 v) { return ~zero8(v) & 0x8080808080808080ull; }
-
 __global__ __launch_bounds__(GV_THREADS) void k_column_classes(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
                                                                const GvGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
                                                                u64 padded_cols, uint4 *__restrict__ cls)

@@ -62,6 +62,7 @@ struct sbl_ctx {
 		host_free(h_ch, h_pinned); host_free(h_opos, h_pinned); host_free(h_old_ch, h_old_pinned); host_free(h_old_opos, h_old_pinned);
 		h_ch = h_old_ch = nullptr; h_opos = h_old_opos = nullptr; h_cap = 0;
 		host_free(h_bs_text, h_bs_pinned); h_bs_text = nullptr; h_bs_cap = 0;
+		host_free(h_gc_text, h_gc_pinned); h_gc_text = nullptr; h_gc_cap = 0;
 	}
 
 	// ---- enumeration workspace
@@ -140,6 +141,17 @@ struct sbl_ctx {
 	DevBuf d_gd_item, d_gd_cls, d_gd_mat;
 	std::vector<sbl_pair_counts> gd_counts;
 	SblTimes gd_times;                   // clearing the matrix and the kernel / the copy of the matrix
+	// sbl_group_concat (group_concat.hip): reads d_ga_text and d_gm_group / d_gm_slot under the same rule (gv_rows_valid).  Used groups,
+	// padded column prefix, row starts per (used group, class), first kept column per part, header blob and class text offsets; site
+	// flags, compacted columns, sites and the text on the device.  The text comes back through a pinned buffer of its own (pageable when
+	// pinning fails: h_gc_pinned), freed with the context -- NOT h_bs_text, which holds the rows of the groups call
+	DevBuf d_gc_group, d_gc_cbase, d_gc_roff, d_gc_first, d_gc_hdr, d_gc_coff, d_gc_flag, d_gc_x, d_gc_count, d_gc_site, d_gc_pick, d_gc_text, d_gc_tmp;
+	std::vector<sbl_concat_part> gc_parts;
+	std::vector<sbl_concat_site> gc_sites;
+	char *h_gc_text = nullptr;
+	size_t h_gc_cap = 0;
+	bool h_gc_pinned = true;
+	SblTimes gc_times;                   // the kernels / the copy of the text
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;

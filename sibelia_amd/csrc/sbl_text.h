@@ -40,6 +40,15 @@ template <class P> __device__ inline unsigned bs_find(P off, unsigned long long 
 
 // zero8: 0x80 in every byte of v that is zero (exact: no carries cross bytes)
 __device__ inline u64 zero8(u64 v) { return ~(((v & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | v) & 0x8080808080808080ull; }
+// 0x80 in every byte of v that is not zero
+__device__ inline u64 nonzero8(u64 v) { return ~zero8(v) & 0x8080808080808080ull; }
+// 0x80 in every byte of v that is one of A C G T, 0x40 in every byte that is '-' (the readers of the alignment rows: group_distances.hip,
+// group_concat.hip)
+__device__ inline u64 base_flags8(u64 v)
+{
+	const u64 base = zero8(v ^ 0x4141414141414141ull) | zero8(v ^ 0x4343434343434343ull) | zero8(v ^ 0x4747474747474747ull) | zero8(v ^ 0x5454545454545454ull);
+	return base | (zero8(v ^ 0x2D2D2D2D2D2D2D2Dull) >> 1);
+}
 
 // DNASequence::Translate (src/dnasequence.cpp:11-28) on 8 bytes at once: A <-> T and C <-> G in either case, every other byte unchanged.
 __device__ inline u64 complement8(u64 x)

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import hashlib
 import struct
-from typing import Sequence
+from typing import List, Sequence, Tuple
 
 import numpy as np
 
@@ -260,6 +260,41 @@ def distances_text(names: Sequence[str], counts, complain=None) -> bytes:
                 complain("no distance between %s and %s: the blocks used hold no column with one of A C G T in both\n" % (names[a], names[b]))
             row.append(v)
         out.append(" ".join(row))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
+CORE_PARTITIONS_COLUMNS = ("block", "first", "last")
+CORE_SITES_COLUMNS = ("column", "block", "record", "position", "strand")
+CORE_WIDTH = 80                                   # bases per line of --corealignment / --coresnps
+
+
+def core_headers(names: Sequence[str]) -> Tuple[bytes, List[int]]:
+    """The FASTA headers of --corealignment / --coresnps as BlockFinder.group_concat takes them: `>` + the file's base name + a line
+    feed per input file, in one blob, and their len(names) + 1 offsets."""
+    blob, first = bytearray(), [0]
+    for n in names:
+        blob += b">" + n.encode("latin1") + b"\n"
+        first.append(len(blob))
+    return bytes(blob), first
+
+
+def core_partitions_text(rows: Sequence[Tuple[int, int, int]], gap_open: int = 0) -> bytes:
+    """The file of --corepartitions: tab-separated, a line of column names, then one line per used block in ascending
+    id.  rows: (block id, first column, number of columns) with the first column counted from 0 as BlockFinder.group_concat returns the
+    parts; written 1-based and inclusive.  gap_open > 0 (--gapopen) is recorded in a line `# gapopen=N` before the column names."""
+    out = (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(CORE_PARTITIONS_COLUMNS)]
+    out += ["%d\t%d\t%d" % (block, first + 1, first + ncols) for block, first, ncols in rows]
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
+def core_sites_text(rows: Sequence[Tuple[int, str, int, int, bool, int]], gap_open: int = 0) -> bytes:
+    """The file of --coresites: tab-separated, a line of column names, then one line per column of --coresnps, numbered
+    from 1.  rows: (block id, record name, start, end, rev, before) -- the centre instance of the block (0-based, half-open, on the
+    first file) and the index of the column's base in it; the position is 1-based on the record: start + before + 1 for a forward
+    instance, end - before for a reverse one.  gap_open > 0 is recorded as for core_partitions_text."""
+    out = (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(CORE_SITES_COLUMNS)]
+    for i, (block, record, start, end, rev, before) in enumerate(rows):
+        out.append("%d\t%d\t%s\t%d\t%s" % (i + 1, block, record, end - before if rev else start + before + 1, "-" if rev else "+"))
     return ("\n".join(out) + "\n").encode("latin1")
 
 

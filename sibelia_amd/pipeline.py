@@ -13,7 +13,10 @@ multiple alignment of every block with at least two instances (`align_block_grou
 the calls off those alignments for the blocks with one instance in the first file and at most one in each other file and writes them as
 a multi-sample VCF.  --distances / --distancecounts (two or more input files) count, on the same alignments, the matches,
 mismatches and gaps between every two input files over the blocks with at most one instance in each file, on the device, and write a
-distance matrix and the counts behind it.  --uncovered adds the rest of C-Sibelia's VCF to
+distance matrix and the counts behind it.  --corealignment / --corepartitions / --coresnps / --coresites (two or more
+input files) concatenate, on the device, the same alignments of the blocks with exactly one instance in every file into the core-genome
+alignment and its variable columns, one FASTA record per input file, with the tables that say where a block and a column come from
+(DESIGN.md 0.9).  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -61,6 +64,22 @@ DISTANCES_HELP = ("Two or more input files: write the p-distance of every two in
 DISTANCECOUNTS_HELP = ("Two or more input files: write the counts behind --distances as tab-separated text, one line per pair of input files: the "
                        "blocks used, matches, mismatches, ambiguous columns (a base code other than A C G T on either side) and the bases of "
                        "each file opposite a gap of the other.")
+
+COREALIGNMENT_HELP = ("Two or more input files: write the core-genome alignment in FASTA format -- the multiple alignments of --multimaf of the "
+                      "core blocks, one after the other in ascending block id, one record per input file (named by the file's base name), 80 "
+                      "columns per line.  A block is a core block if it has exactly one instance in every input file, all at least the "
+                      "minimum block size long.  The text is put together on the device.")
+
+COREPARTITIONS_HELP = ("Two or more input files: write the columns every core block takes in the alignment of --corealignment as tab-separated "
+                       "text: block, first and last column, counted from 1.")
+
+CORESNPS_HELP = ("Two or more input files: write the variable columns of the core-genome alignment in FASTA format, as --corealignment does: "
+                 "the columns in which every file holds one of A C G T and not all hold the same.")
+
+CORESITES_HELP = ("Two or more input files: write where every column of --coresnps comes from as tab-separated text: column, block, record "
+                  "of the first file, 1-based position on it and strand of the block's instance there.")
+
+CORE_OPTIONS = (("--corealignment", "corealignment"), ("--corepartitions", "corepartitions"), ("--coresnps", "coresnps"), ("--coresites", "coresites"))
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
@@ -202,6 +221,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--multivariants", default=None, metavar="FILE", help=MULTIVARIANTS_HELP)
     p.add_argument("--distances", default=None, metavar="FILE", help=DISTANCES_HELP)
     p.add_argument("--distancecounts", default=None, metavar="FILE", help=DISTANCECOUNTS_HELP)
+    p.add_argument("--corealignment", default=None, metavar="FILE", help=COREALIGNMENT_HELP)
+    p.add_argument("--corepartitions", default=None, metavar="FILE", help=COREPARTITIONS_HELP)
+    p.add_argument("--coresnps", default=None, metavar="FILE", help=CORESNPS_HELP)
+    p.add_argument("--coresites", default=None, metavar="FILE", help=CORESITES_HELP)
     p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
     p.add_argument("--wideband", action="store_true", help=WIDEBAND_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
@@ -232,7 +255,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         for a in sorted(set(samples)):
             if samples.count(a) > 1:
                 raise PipelineError("--multivariants names a sample by its file's base name: two files are called %s" % a)
-    for o, f in (("--distances", opt.distances), ("--distancecounts", opt.distancecounts)):
+    for o, f in (("--distances", opt.distances), ("--distancecounts", opt.distancecounts)) + tuple((o, getattr(opt, a)) for o, a in CORE_OPTIONS):
         if f is None:
             continue
         if len(opt.filenames) < 2:                             # before any file is read
@@ -253,7 +276,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
     if opt.unmapped is not None and not opt.uncovered:
         raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
-    distances = opt.distances is not None or opt.distancecounts is not None
+    distances = opt.distances is not None or opt.distancecounts is not None or core_wanted(opt)      # what else aligns the groups
     if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None and not distances:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
@@ -274,11 +297,17 @@ def file_names(filenames: Sequence[str]) -> List[str]:
     return [os.path.basename(os.path.normpath(f)) for f in filenames]
 
 
+def core_wanted(opt: argparse.Namespace) -> bool:
+    """One of --corealignment / --corepartitions / --coresnps / --coresites is given."""
+    return any(getattr(opt, a) is not None for _, a in CORE_OPTIONS)
+
+
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts and the four --core options name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
     given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--unmapped", opt.unmapped), ("--multimaf", opt.multimaf),
-                                    ("--multivariants", opt.multivariants), ("--distances", opt.distances), ("--distancecounts", opt.distancecounts)) if f is not None]
+                                    ("--multivariants", opt.multivariants), ("--distances", opt.distances), ("--distancecounts", opt.distancecounts))
+                                   + tuple((o, getattr(opt, a)) for o, a in CORE_OPTIONS) if f is not None]
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -344,7 +373,8 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf, opt.multivariants, opt.distances, opt.distancecounts) if f is not None]      # relative names: under the output directory
+        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf, opt.multivariants, opt.distances, opt.distancecounts,
+                            opt.corealignment, opt.corepartitions, opt.coresnps, opt.coresites) if f is not None]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -572,6 +602,54 @@ def distance_blocks(blocks, file_records: Sequence[int], min_block_size: int) ->
     return out
 
 
+def core_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
+    """The ids of the core blocks of a block list (formats.BLOCK_DTYPE), what the four --core options concatenate: the id has exactly
+    one instance on the records of EACH input file -- as many instances as there are files -- and every one is at least min_block_size
+    long.  The subset of distance_blocks that reaches every file; for two files the two are the same."""
+    file_of = _file_of_record(file_records)
+    by_id: Dict[int, List[Tuple[int, int]]] = {}
+    for b in blocks:
+        by_id.setdefault(abs(int(b["id"])), []).append((file_of(b["chr"]), int(b["end"]) - int(b["start"])))
+    out = []
+    for block, inst in sorted(by_id.items()):
+        if all(n >= min_block_size for _, n in inst) and sorted(f for f, _ in inst) == list(range(len(file_records))):
+            out.append(block)
+    return out
+
+
+def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[int], insts, aligned, core, complain: Callable[[str], None]) -> Dict[str, bytes]:
+    """--corealignment / --corepartitions / --coresnps / --coresites from the alignments of one align_block_groups call: the class of an
+    instance is the file of its record, the wanted groups are the aligned blocks of `core` (core_blocks); the rows are concatenated and
+    filtered on the device (BlockFinder.group_concat), one call per mode.  The first file's instance of a core block
+    sorts first, so it is the centre: the positions of --coresites are read on it."""
+    from . import formats
+    from .api import CONCAT_ALL, CONCAT_VARIABLE, GALIGN_OK, SibeliaError
+    file_of = _file_of_record(bf.file_records)
+    n = len(bf.file_records)
+    cls = [file_of(c) for inst in insts for c, _, _, _ in inst]
+    want = [block in core and al.status == GALIGN_OK for block, al in zip(ids, aligned)]
+    if not any(want):
+        complain("no core block: no block has exactly one instance of at least %d bases in every input file and was aligned\n" % opt.minblocksize)
+    headers = [b">" + a.encode("latin1") + b"\n" for a in file_names(opt.filenames)]
+    out = {}
+    try:
+        if opt.corealignment is not None or opt.corepartitions is not None:
+            text, parts, _ = bf.group_concat(cls, n, headers, CONCAT_ALL, formats.CORE_WIDTH, want)
+            if opt.corealignment is not None:
+                out[opt.corealignment] = text
+            if opt.corepartitions is not None:
+                out[opt.corepartitions] = formats.core_partitions_text([(ids[g], first, ncols) for g, first, ncols in parts], opt.gapopen)
+        if opt.coresnps is not None or opt.coresites is not None:
+            text, _, sites = bf.group_concat(cls, n, headers, CONCAT_VARIABLE, formats.CORE_WIDTH, want)
+            if opt.coresnps is not None:
+                out[opt.coresnps] = text
+            if opt.coresites is not None:
+                out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+    except SibeliaError as e:
+        raise PipelineError(str(e))
+    return {f: out[f] for f in (opt.corealignment, opt.corepartitions, opt.coresnps, opt.coresites) if f is not None}
+
+
 def distance_files(bf, opt: argparse.Namespace, ids: Sequence[int], insts, aligned, used, complain: Callable[[str], None]) -> Dict[str, bytes]:
     """--distances / --distancecounts from the alignments of one align_block_groups call: the class of an instance is the file of its
     record, the wanted groups are the blocks `used` (distance_blocks); the row comparisons run on the device
@@ -607,7 +685,8 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     --multivariants: the calls read off the SAME alignments (one align_block_groups call serves both; BlockFinder.group_variants,
     DESIGN.md 0.6) for the qualifying blocks of the final list `blocks` (qualifying_blocks) as a multi-sample VCF; the first-file
     instance sorts first, so it is the centre and its alleles are REF.
-    --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two."""
+    --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two.
+    --corealignment / --corepartitions / --coresnps / --coresites: the concatenation of the same alignments (core_files), after those."""
     import bisect
     from . import formats
     from .api import GALIGN_OK, SibeliaError
@@ -619,10 +698,11 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     qualify = set(qualifying_blocks(blocks, bf.file_records, opt.minblocksize)) if opt.multivariants is not None else set()
     distances = opt.distances is not None or opt.distancecounts is not None
     used = set(distance_blocks(blocks, bf.file_records, opt.minblocksize)) if distances else set()
+    core = set(core_blocks(blocks, bf.file_records, opt.minblocksize)) if core_wanted(opt) else set()
     groups = []
     for block, inst, al in zip(ids, insts, aligned):
         if al.status != GALIGN_OK:
-            if opt.multimaf is not None or block in qualify or block in used:
+            if opt.multimaf is not None or block in qualify or block in used or block in core:
                 complain("block %d not aligned: one of its %d instances against %s:%d-%d is beyond the limits of one alignment "
                          "(%s, DESIGN.md 0.2)\n" % (block, len(inst), names[inst[0][0]], inst[0][1] + 1, inst[0][2], skip_limits(opt)))
             continue
@@ -653,6 +733,8 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
         out[opt.multivariants] = formats.multi_vcf_text(names[0], sample_names(opt.filenames), records, opt.gapopen)
     if distances:
         out.update(distance_files(bf, opt, ids, insts, aligned, used, complain))
+    if core_wanted(opt):
+        out.update(core_files(bf, opt, names, ids, insts, aligned, core, complain))
     return out
 
 
@@ -724,7 +806,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 bf.set_wide(True)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
-            if opt.multimaf is not None or opt.multivariants is not None or opt.distances is not None or opt.distancecounts is not None:      # likewise on the final list
+            if opt.multimaf is not None or opt.multivariants is not None or opt.distances is not None or opt.distancecounts is not None or core_wanted(opt):      # likewise on the final list
                 files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write, blocks))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
