@@ -518,17 +518,30 @@ class BlockFinder:
         insts = [[(d[i].chr, d[i].start, d[i].end, bool(d[i].rev)) for i in range(f[g], f[g + 1])] for g in range(n.value)]
         return [int(x) for x in _view(ids.value, n.value, np.dtype("<i4"))], insts, self._group_alignments(f, res, members, rows, rows_len)
 
+    def _want_mask(self, what: str, want: Optional[Sequence[bool]]) -> Optional[bytes]:
+        """One byte per group of the last groups call for the `want` of group_variants / group_distances / group_concat (None: all)."""
+        ngroups = len(getattr(self, "_group_ninst", []))
+        if want is not None and len(want) != ngroups:
+            raise ValueError("%s: %d flags for %d groups" % (what, len(want), ngroups))
+        return None if want is None else bytes(1 if w else 0 for w in want) + b"\0"
+
+    def _class_array(self, what: str, cls: Sequence[int], scalars: Sequence[int], words: str):
+        """The classes of the instances of the last groups call for the library; scalars: what else must fit 32 bits; words: the error's."""
+        ninst = getattr(self, "_group_ninst", [])
+        cls = [int(x) for x in cls]
+        if ninst and len(cls) != sum(ninst):
+            raise ValueError("%s: %d classes for %d instances" % (what, len(cls), sum(ninst)))
+        if any(not 0 <= int(v) <= 2 ** 32 - 1 for v in scalars) or any(not 0 <= x <= 2 ** 32 - 1 for x in cls):
+            raise SibeliaError("sbl_%s: bad argument (%s outside 32 bits)" % (what, words))
+        return (C.c_uint32 * max(1, len(cls)))(*cls)
+
     def group_variants(self, want: Optional[Sequence[bool]] = None):
         """The variant segments of the groups of the LAST align_groups / align_block_groups call (csrc/group_variants.hip; defined in
         include/sibelia_amd.h), read off the rows that call left on the device.  want: one flag per group (None: all).
         -> [(group, start, end, before, lead, [gapped slice rows[i][start - lead:end] per row, centre first])] in ascending
         (group, start).  The records as the library returns them (SEGMENT_DTYPE, `gapped` included) stay in `last_group_segments`."""
+        mask = self._want_mask("group_variants", want)
         ninst = getattr(self, "_group_ninst", [])
-        mask = None
-        if want is not None:
-            if len(want) != len(ninst):
-                raise ValueError("group_variants: %d flags for %d groups" % (len(want), len(ninst)))
-            mask = bytes(1 if w else 0 for w in want) + b"\0"
         segs, text = C.c_void_p(), C.c_void_p()
         n, ln = C.c_uint64(), C.c_uint64()
         self._check(self.L.sbl_group_variants(self.h, mask, C.byref(segs), C.byref(n), C.byref(text), C.byref(ln)), "sbl_group_variants")
@@ -556,18 +569,8 @@ class BlockFinder:
         instance of that call, flat, in group order; want: one flag per group (None: all).
         -> uint64 array of shape (nclass, nclass, 4), a copy: [f, g] = (match, mismatch, ambiguous, gap(f -> g)) summed over every
         ordered pair of rows of classes (f, g)."""
-        ninst = getattr(self, "_group_ninst", [])
-        mask = None
-        if want is not None:
-            if len(want) != len(ninst):
-                raise ValueError("group_distances: %d flags for %d groups" % (len(want), len(ninst)))
-            mask = bytes(1 if w else 0 for w in want) + b"\0"
-        cls = [int(x) for x in cls]
-        if ninst and len(cls) != sum(ninst):
-            raise ValueError("group_distances: %d classes for %d instances" % (len(cls), sum(ninst)))
-        if not 0 <= int(nclass) <= 2 ** 32 - 1 or any(not 0 <= x <= 2 ** 32 - 1 for x in cls):
-            raise SibeliaError("sbl_group_distances: bad argument (a class or their number outside 32 bits)")
-        arr = (C.c_uint32 * max(1, len(cls)))(*cls)
+        mask = self._want_mask("group_distances", want)
+        arr = self._class_array("group_distances", cls, (nclass,), "a class or their number")
         out = C.POINTER(PairCounts)()
         self._check(self.L.sbl_group_distances(self.h, mask, arr, int(nclass), C.byref(out)), "sbl_group_distances")
         n = int(nclass)
@@ -583,23 +586,13 @@ class BlockFinder:
         of that call, flat, in group order; headers: one byte string per class, written as it is ('>' and line feed included); mode:
         CONCAT_ALL or CONCAT_VARIABLE; want: one flag per group (None: all).
         -> (text, [(group, first, ncols)], [(group, col, before)]), all copies."""
-        ninst = getattr(self, "_group_ninst", [])
-        mask = None
-        if want is not None:
-            if len(want) != len(ninst):
-                raise ValueError("group_concat: %d flags for %d groups" % (len(want), len(ninst)))
-            mask = bytes(1 if w else 0 for w in want) + b"\0"
-        cls = [int(x) for x in cls]
-        if ninst and len(cls) != sum(ninst):
-            raise ValueError("group_concat: %d classes for %d instances" % (len(cls), sum(ninst)))
-        if any(not 0 <= int(v) <= 2 ** 32 - 1 for v in (nclass, mode, width)) or any(not 0 <= x <= 2 ** 32 - 1 for x in cls):
-            raise SibeliaError("sbl_group_concat: bad argument (a class, their number, the mode or the width outside 32 bits)")
+        mask = self._want_mask("group_concat", want)
+        arr = self._class_array("group_concat", cls, (nclass, mode, width), "a class, their number, the mode or the width")
         if len(headers) != int(nclass):
             raise ValueError("group_concat: %d headers for %d classes" % (len(headers), int(nclass)))
         first = [0]
         for h in headers:
             first.append(first[-1] + len(h))
-        arr = (C.c_uint32 * max(1, len(cls)))(*cls)
         parts, sites, text = C.POINTER(ConcatPart)(), C.POINTER(ConcatSite)(), C.c_void_p()
         nparts, nsites, ln = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.sbl_group_concat(self.h, mask, arr, int(nclass), int(mode), int(width), b"".join(headers) + b"\0", (C.c_uint64 * len(first))(*first),

@@ -36,7 +36,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "sbl_align.h"
+#include "sbl_groups.h"
 
 namespace {
 
@@ -365,7 +365,7 @@ template <class M, bool REG> __global__ __launch_bounds__(REG ? 64 : M::WIDE_THR
 
 // ---- spelling: the rows of a centre-star multiple alignment; the two rows of a pair are those of a group of one member
 
-constexpr unsigned GS_THREADS = 256;
+constexpr unsigned GS_THREADS = GM_THREADS;
 
 struct GaSpan { u64 col; unsigned ai, bj, op, len; };                       // a run: first column in its pair's two rows, first base of a / b
 struct GmInst { u64 src, first_span; unsigned len, rev, nspans, pad_; };       // a row: its range; a member's spans (of the pair centre / member)
@@ -399,11 +399,10 @@ __global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__re
 		row = off / Q.L;
 		col = off - row * Q.L;
 		I = insts[Q.first_inst + row];
-		si = ga_find(0, Q.nslots, [&](u64 x) { return slots[Q.first_slot + x].col <= col; });
+		si = gm_slot_at(slots, Q, col);
 		set_slot();
 		if (row && I.nspans) {
-			const u64 o = col - S.col;
-			const unsigned q = o < S.G ? S.p : S.p + (unsigned)(o - S.G);      // the centre index this column belongs to
+			const unsigned q = (unsigned)gm_centre_before(S, col);            // the centre index this column belongs to
 			xi = ga_find(I.first_span, I.first_span + I.nspans, [&](u64 x) { return spans[x].ai <= q; });
 		}
 		return true;
@@ -414,8 +413,8 @@ __global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__re
 		if (col == Q.L) { live = seek(); if (!live) break; }
 		else if (col == next_col) { si++; set_slot(); }
 		const u64 o = col - S.col;
-		const bool in_slot = o < S.G;
-		const unsigned q = in_slot ? S.p : S.p + (unsigned)(o - S.G);
+		const bool in_slot = gm_in_slot(S, col);
+		const unsigned q = (unsigned)gm_centre_before(S, col);
 		unsigned char ch = '-';
 		if (row == 0) {
 			if (!in_slot) ch = strand_base(seq, I.src, I.len, q, I.rev);
@@ -432,7 +431,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_spell_groups(const uint8_t *__re
 		if (b < 8) wlo |= (u64)ch << (8 * b); else whi |= (u64)ch << (8 * (b - 8));
 		col++; off++;
 	}
-	out[t0 / 16] = make_uint4((unsigned)wlo, (unsigned)(wlo >> 32), (unsigned)whi, (unsigned)(whi >> 32));
+	store16(out, t0 / 16, B16{wlo, whi});
 }
 
 // ---- host
@@ -666,15 +665,14 @@ u64 gm_spell(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<GmWan
 	}
 	if (total) {
 		const size_t padded = (size_t)((total + 15) / 16 * 16);
-		const u64 blocks = (padded / 16 + GS_THREADS - 1) / GS_THREADS;
-		SBL_CHECK(blocks < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
+		const unsigned blocks = gm_blocks(padded / 16);
 		al_upload(c, c->d_gm_group, groups); al_upload(c, c->d_gm_inst, rows); al_upload(c, c->d_gm_slot, slots); al_upload(c, c->d_ga_span, spans);
 		c->d_ga_text.ensure(padded);
 		sbl_text_staging(c, padded);
 		c->align_stats.spell_ms = al_timed_launch(c, [&] {
-			k_spell_groups<<<(unsigned)blocks, GS_THREADS, 0, c->stream>>>(c->d_orig_ch.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), groups.size(), c->d_gm_inst.as<GmInst>(),
+			k_spell_groups<<<blocks, GS_THREADS, 0, c->stream>>>(c->d_orig_ch.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), groups.size(), c->d_gm_inst.as<GmInst>(),
 			                                                                 c->d_gm_slot.as<GmSlot>(), c->d_ga_span.as<GaSpan>(), total, c->d_ga_text.as<uint4>());
-		}, c->h_bs_text, c->d_ga_text.p, padded);
+		}, c->h_bs_text.p, c->d_ga_text.p, padded);
 		c->stats.device_bytes = sbl_devbuf_total().load();
 	}
 	return total;
@@ -744,7 +742,7 @@ void gm_hand_out(sbl_ctx *c, u64 rows_len, const sbl_group_result **res, const s
 {
 	if (res) *res = c->gm_res.data();
 	if (members) *members = c->gm_members.data();
-	if (rows) *rows = rows_len ? c->h_bs_text : "";
+	if (rows) *rows = rows_len ? c->h_bs_text.p : "";
 	if (rl) *rl = rows_len;
 }
 
@@ -763,7 +761,7 @@ void ga_hand_out(sbl_ctx *c, u64 rows_len, const sbl_pair_result **res, const sb
 	if (res) *res = c->ga_res.data();
 	if (runs) *runs = c->ga_runs.data();
 	if (nruns) *nruns = c->ga_runs.size();
-	if (rows) *rows = rows_len ? c->h_bs_text : "";
+	if (rows) *rows = rows_len ? c->h_bs_text.p : "";
 	if (rl) *rl = rows_len;
 }
 

@@ -54,7 +54,7 @@ extern "C" sbl_status sbl_blocks_sequences(sbl_ctx *c, const sbl_block *blocks, 
 			toff.push_back(toff.back() + st_text_len(L, 80));
 		}
 		sbl_spell_pieces(c, desc, toff, hdr.data(), hdr.size(), "blocks_sequences text too large", c->bs_times);
-		if (text) *text = toff.back() ? c->h_bs_text : "";
+		if (text) *text = toff.back() ? c->h_bs_text.p : "";
 		if (len) *len = toff.back();
 	});
 }

@@ -4,13 +4,12 @@
 // not all the same (SBL_CONCAT_VARIABLE).  The text is classes x columns bytes, the order of the rows themselves, and the rows lie on
 // the device (d_ga_text): a column filter and a transposing gather, so they run where the rows are and only the text comes back.
 //
-//   flags     (VARIABLE) k_site_flags, output-stationary over the columns of the used groups, every group padded to a multiple of 16
-//             columns as k_column_classes pads them: a lane owns 16 columns of ONE group, reads those 16 bytes of every row (gv_load16),
-//             accumulates "differs from row 0" and "is one of A C G T" (base_flags8) 8 bytes at a time and writes 16 flag bytes with one
-//             vector store.  Padding columns get flag 0.
+//   flags     (VARIABLE) k_site_flags, the column walk of sbl_groups.h (gm_walk16: a lane owns 16 columns of ONE group, every group padded
+//             to a multiple of 16 columns) with "every row holds one of A C G T" (base_flags8) gathered next to "differs from row 0": 16
+//             flag bytes per lane.  Padding columns get flag 0.
 //   sites     (VARIABLE) the flagged columns are compacted in ascending order by rocPRIM's select (sbl_prim.h); the host reads their
 //             number; k_site_fill, one lane per site: the group by binary search over the padded prefix, `before` from the group's merged
-//             gap slots (the arithmetic of k_segment_fill), and for the text kernel the pick (used group, column).
+//             gap slots (gm_centre_before), and for the text kernel the pick (used group, column).
 //   text      k_concat_text, output-stationary like k_spell_text: a lane owns 16 aligned bytes of the text and makes ONE vector store; a
 //             workgroup owns GC_SPAN contiguous bytes and keeps the text offsets of the class rows its span touches in LDS (they differ
 //             only by the header lengths).  A lane finds its class by search over them, then header (literal bytes) or sequence, where
@@ -20,51 +19,41 @@
 //             (insert_newline); lanes that straddle a header, a group boundary or two line ends step byte by byte.  VARIABLE: every byte
 //             is one scattered load through the picks -- kept columns are a percent or so of all, so the loads are sparse by nature and
 //             nothing is staged; the stores stay coalesced.
-//   host      every argument is checked before any launch; tables up; event pairs around the kernels and around the copy back; the text
-//             comes back into a pinned buffer of its own that grows on demand (h_gc_text), sites into gc_sites; the parts of mode
-//             VARIABLE are counted on the host from the sites.
+//   host      every argument is checked before any launch; the used groups by the walk of sbl_groups.h (gm_columns: a group of ONE row is
+//             used when there is one class), tables up; event pairs around the kernels and around the copy back; the text comes back
+//             into a pinned buffer of its own that grows on demand (h_gc_text), sites into gc_sites; the parts of mode VARIABLE are
+//             counted on the host from the sites.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 
-#include "sbl_align.h"
+#include "sbl_groups.h"
 #include "sbl_prim.h"
-#include "sbl_text.h"
 
 namespace {
 
-constexpr unsigned GC_THREADS = 256, GC_SPAN = GC_THREADS * 16, GC_MAX_CLASS = 1024;
+constexpr unsigned GC_THREADS = GM_THREADS, GC_SPAN = GC_THREADS * 16;
 
-struct GcGroup { u64 group, dg; };                     // a used group: its index in the call; its index in d_gm_group
 struct GcPick { u64 ug, col; };                        // a kept column: its used group and its column there
 
+// gm_walk16's reader of the flags: 0x80 in every byte whose column holds one of A C G T in all of the group's rows
+struct GcFlags {
+	unsigned nclass;                                                          // a used group has nclass rows
+	u64 alo, ahi;
+	__device__ unsigned rows(const GmGroup &) const { return nclass; }
+	__device__ void first(B16 ref) { alo = base_flags8(ref.lo); ahi = base_flags8(ref.hi); }
+	__device__ void next(B16 w) { alo &= base_flags8(w.lo); ahi &= base_flags8(w.hi); }
+	__device__ B16 bytes(u64 ulo, u64 uhi) const { return {(ulo & alo) >> 7, (uhi & ahi) >> 7}; }
+};
+
 __global__ __launch_bounds__(GC_THREADS) void k_site_flags(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
-                                                           const GcGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                           const GmUsed *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
                                                            u64 padded_cols, unsigned nclass, uint4 *__restrict__ flags)
 {
-	const u64 x0 = ((u64)blockIdx.x * GC_THREADS + threadIdx.x) * 16;
-	if (x0 >= padded_cols) return;
-	const unsigned gi = bs_find(cbase, ngroups, x0);
-	const GmGroup Q = gm[groups[gi].dg];
-	const u64 col0 = x0 - cbase[gi];                                          // < L: the padding of a group is less than 16 columns
-	const unsigned n = Q.L - col0 < 16 ? (unsigned)(Q.L - col0) : 16;        // columns of the group in this piece
-	const B16 ref = gv_load16(text, text_bytes, Q.toff + col0);
-	u64 dlo = 0, dhi = 0, alo = base_flags8(ref.lo), ahi = base_flags8(ref.hi);
-	for (unsigned i = 1; i < nclass; i++) {                                   // a used group has nclass rows
-		const B16 w = gv_load16(text, text_bytes, Q.toff + (u64)i * Q.L + col0);
-		dlo |= w.lo ^ ref.lo; dhi |= w.hi ^ ref.hi;
-		alo &= base_flags8(w.lo); ahi &= base_flags8(w.hi);
-	}
-	u64 flo = (nonzero8(dlo) & alo) >> 7, fhi = (nonzero8(dhi) & ahi) >> 7;
-	// the bytes behind column L belong to the next row or to nothing: flag 0
-	if (n < 16) {
-		if (n <= 8) { fhi = 0; flo = n == 8 ? flo : flo & ((1ull << (8 * n)) - 1); }
-		else fhi &= (1ull << (8 * (n - 8))) - 1;
-	}
-	flags[x0 / 16] = make_uint4((unsigned)flo, (unsigned)(flo >> 32), (unsigned)fhi, (unsigned)(fhi >> 32));
+	gm_walk16(text, text_bytes, gm, groups, cbase, ngroups, padded_cols, GcFlags{nclass, 0, 0}, flags);
 }
 
-__global__ __launch_bounds__(GC_THREADS) void k_site_fill(const GmGroup *__restrict__ gm, const GmSlot *__restrict__ slots, const GcGroup *__restrict__ groups,
+__global__ __launch_bounds__(GC_THREADS) void k_site_fill(const GmGroup *__restrict__ gm, const GmSlot *__restrict__ slots, const GmUsed *__restrict__ groups,
                                                           const u64 *__restrict__ cbase, u64 ngroups, const u64 *__restrict__ xs, u64 nsites,
                                                           sbl_concat_site *__restrict__ sites, GcPick *__restrict__ picks)
 {
@@ -74,11 +63,7 @@ __global__ __launch_bounds__(GC_THREADS) void k_site_fill(const GmGroup *__restr
 	const unsigned gi = bs_find(cbase, ngroups, x);
 	const GmGroup Q = gm[groups[gi].dg];
 	const u64 s = x - cbase[gi];
-	// the centre index column s belongs to = the centre bases before it (k_segment_fill)
-	const u64 si = ga_find(0, Q.nslots, [&](u64 y) { return slots[Q.first_slot + y].col <= s; });
-	const GmSlot S = slots[Q.first_slot + si];
-	const u64 o = s - S.col, before = o < S.G ? S.p : S.p + (o - S.G);
-	sites[i] = sbl_concat_site{groups[gi].group, s, before};
+	sites[i] = sbl_concat_site{groups[gi].group, s, gm_centre_before(slots, Q, s)};
 	picks[i] = GcPick{gi, s};
 }
 
@@ -91,7 +76,7 @@ __global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__res
                                                             const u64 *__restrict__ coff, unsigned nclass, const char *__restrict__ hdr,
                                                             u64 C, u64 S, unsigned width, u64 total, uint4 *__restrict__ out)
 {
-	__shared__ u64 s_off[GC_MAX_CLASS + 1];
+	__shared__ u64 s_off[GM_MAX_CLASS + 1];
 	__shared__ unsigned s_first, s_last;
 	const u64 span0 = (u64)blockIdx.x * GC_SPAN;
 	if (span0 >= total) return;
@@ -149,30 +134,7 @@ __global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__res
 			off++;
 		}
 	}
-	out[t0 / 16] = make_uint4((unsigned)w.lo, (unsigned)(w.lo >> 32), (unsigned)w.hi, (unsigned)(w.hi >> 32));
-}
-
-unsigned gc_blocks(u64 lanes)
-{
-	const u64 blocks = (lanes + GC_THREADS - 1) / GC_THREADS;
-	SBL_CHECK(blocks < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
-	return (unsigned)blocks;
-}
-
-// the context's pinned buffer for the concatenated text, at least `bytes` large (pageable when pinning fails, as sbl_text_staging)
-void gc_staging(sbl_ctx *c, size_t bytes)
-{
-	if (bytes <= c->h_gc_cap) return;
-	c->host_free(c->h_gc_text, c->h_gc_pinned);
-	c->h_gc_text = nullptr; c->h_gc_cap = 0;
-	const size_t cap = bytes + bytes / 16 + 4096;
-	c->h_gc_pinned = hipHostMalloc((void **)&c->h_gc_text, cap) == hipSuccess;
-	if (!c->h_gc_pinned) {
-		(void)hipGetLastError();
-		c->h_gc_text = (char *)malloc(cap);
-		if (!c->h_gc_text) throw SblError{SBL_ERR_OOM, "host buffer for the concatenated alignment"};
-	}
-	c->h_gc_cap = cap;
+	store16(out, t0 / 16, w);
 }
 
 [[noreturn]] void gc_bad_group(size_t g, const char *what)
@@ -191,58 +153,44 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 {
 	return guarded(c, [&] {
 		require_group_rows(c);
-		const size_t ninst = c->gm_inst.size();
-		SBL_CHECK(cls || !ninst, SBL_ERR_BAD_ARG, "null classes");
-		SBL_CHECK(nclass >= 1 && nclass <= GC_MAX_CLASS, SBL_ERR_BAD_ARG, "the number of classes must be 1 .. 1024");
+		check_classes(c, cls, nclass);
 		SBL_CHECK(mode == SBL_CONCAT_ALL || mode == SBL_CONCAT_VARIABLE, SBL_ERR_BAD_ARG, "unknown mode of concatenation");
 		SBL_CHECK(width >= 1, SBL_ERR_BAD_ARG, "the width of a line must be at least 1");
 		SBL_CHECK(headers && header_first, SBL_ERR_BAD_ARG, "null headers");
 		for (uint32_t f = 0; f < nclass; f++) SBL_CHECK(header_first[f] <= header_first[f + 1], SBL_ERR_BAD_ARG, "descending header offsets");
-		for (size_t k = 0; k < ninst; k++) SBL_CHECK(cls[k] < nclass, SBL_ERR_BAD_ARG, "a class is not below the number of classes");
 		const bool variable = mode == SBL_CONCAT_VARIABLE;
 		hipStream_t s = c->stream;
 		c->gc_parts.clear(); c->gc_sites.clear();
 		c->gc_times = SblTimes{};
-		// the used groups (dg: d_gm_group lists the aligned groups with L > 0, in order), where the row of every class starts, the padded
-		// prefix of their columns (VARIABLE) and the parts of mode ALL
-		std::vector<GcGroup> groups;
-		std::vector<u64> roff, cbase(1, 0), first(1, 0);
-		u64 dg = 0, text_end = 0;
-		for (size_t g = 0; g < c->gm_res.size(); g++) {
-			const sbl_group_result &r = c->gm_res[g];
-			if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
-			text_end = std::max<u64>(text_end, r.row_off + (u64)r.ninst * r.L);
-			if (!want || want[g]) {
-				if (r.ninst != nclass) gc_bad_group(g, r.ninst < nclass ? "has fewer instances than there are classes" : "has more instances than there are classes");
-				const size_t at = roff.size();
-				roff.resize(at + nclass, ~0ull);
-				for (u64 i = 0; i < r.ninst; i++) {
-					u64 &slot = roff[at + cls[c->gm_first[g] + i]];
-					if (slot != ~0ull) gc_bad_group(g, "holds a class twice");
-					slot = r.row_off + i * r.L;
-				}
-				groups.push_back(GcGroup{g, dg});
-				cbase.push_back(cbase.back() + (r.L + 15) / 16 * 16);
-				first.push_back(first.back() + r.L);
+		// the used groups -- one row is enough where there is one class --, where the row of every class starts and the parts of mode ALL;
+		// with VARIABLE the used groups and the padded prefix of their columns go up (d_gm_used, d_gm_cbase)
+		std::vector<u64> roff, first(1, 0);
+		const GmColumns cols = gm_columns(c, want, 1, variable, [&](size_t g, const sbl_group_result &r, u64) {
+			if (r.ninst != nclass) gc_bad_group(g, r.ninst < nclass ? "has fewer instances than there are classes" : "has more instances than there are classes");
+			const size_t at = roff.size();
+			roff.resize(at + nclass, ~0ull);
+			for (u64 i = 0; i < r.ninst; i++) {
+				u64 &slot = roff[at + cls[c->gm_first[g] + i]];
+				if (slot != ~0ull) gc_bad_group(g, "holds a class twice");
+				slot = r.row_off + i * r.L;
 			}
-			dg++;
-		}
-		const u64 ng = groups.size(), P = cbase.back(), text_bytes = (text_end + 15) / 16 * 16;
-		if (ng) SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes && c->d_gm_group.cap >= dg * sizeof(GmGroup), SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
+			first.push_back(first.back() + r.L);
+		});
+		const std::vector<GmUsed> &groups = cols.used;
+		const u64 ng = groups.size(), P = cols.cbase.back(), text_bytes = cols.text_bytes;
 		const uint8_t *rows = c->d_ga_text.as<uint8_t>();
 		u64 C = variable ? 0 : first.back();
 		float kernel_ms = 0;
 		if (variable && ng) {
 			// ---- the kept columns, ascending, and their number
-			al_upload(c, c->d_gc_group, groups); al_upload(c, c->d_gc_cbase, cbase);
-			c->d_gc_flag.ensure((size_t)P); c->d_gc_x.ensure((size_t)P * 8); c->d_gc_count.ensure(8);
+			c->d_gc_flag.ensure((size_t)P); c->d_gc_x.ensure((size_t)P * 8); c->d_gm_count.ensure(16);
 			HIP_TRY(hipEventRecord(c->ev[0], s));
-			k_site_flags<<<gc_blocks(P / 16), GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gc_group.as<GcGroup>(), c->d_gc_cbase.as<u64>(), ng, P, nclass,
+			k_site_flags<<<gm_blocks(P / 16), GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gm_used.as<GmUsed>(), c->d_gm_cbase.as<u64>(), ng, P, nclass,
 			                                                      c->d_gc_flag.as<uint4>());
 			HIP_TRY(hipGetLastError());
-			prim::select(s, c->d_gc_tmp, rocprim::counting_iterator<u64>(0), c->d_gc_flag.as<uint8_t>(), c->d_gc_x.as<u64>(), c->d_gc_count.as<u64>(), (size_t)P);
+			prim::select(s, c->d_gm_tmp, rocprim::counting_iterator<u64>(0), c->d_gc_flag.as<uint8_t>(), c->d_gc_x.as<u64>(), c->d_gm_count.as<u64>(), (size_t)P);
 			HIP_TRY(hipEventRecord(c->ev[1], s));
-			HIP_TRY(hipMemcpyAsync(&C, c->d_gc_count.p, 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync(&C, c->d_gm_count.p, 8, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
 			kernel_ms = sbl_elapsed_ms(c, 0, 1);
 		}
@@ -262,13 +210,13 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 			c->d_gc_text.ensure(padded);
 			c->d_gc_site.ensure(std::max<size_t>(1, (size_t)(variable ? C : 0)) * sizeof(sbl_concat_site));
 			c->d_gc_pick.ensure(std::max<size_t>(1, (size_t)(variable ? C : 0)) * sizeof(GcPick));
-			gc_staging(c, padded);
+			c->h_gc_text.ensure(padded, "host buffer for the concatenated alignment");
 			if (variable) c->gc_sites.resize((size_t)C);
 			const unsigned blocks = (unsigned)((total + GC_SPAN - 1) / GC_SPAN);
 			HIP_TRY(hipEventRecord(c->ev[2], s));
 			if (variable) {
 				if (C) {
-					k_site_fill<<<gc_blocks(C), GC_THREADS, 0, s>>>(c->d_gm_group.as<GmGroup>(), c->d_gm_slot.as<GmSlot>(), c->d_gc_group.as<GcGroup>(), c->d_gc_cbase.as<u64>(), ng,
+					k_site_fill<<<gm_blocks(C), GC_THREADS, 0, s>>>(c->d_gm_group.as<GmGroup>(), c->d_gm_slot.as<GmSlot>(), c->d_gm_used.as<GmUsed>(), c->d_gm_cbase.as<u64>(), ng,
 					                                                c->d_gc_x.as<u64>(), C, c->d_gc_site.as<sbl_concat_site>(), c->d_gc_pick.as<GcPick>());
 					HIP_TRY(hipGetLastError());
 				}
@@ -279,7 +227,7 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 				                                                   c->d_gc_hdr.as<char>(), C, S, width, total, c->d_gc_text.as<uint4>());
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipEventRecord(c->ev[3], s));
-			HIP_TRY(hipMemcpyAsync(c->h_gc_text, c->d_gc_text.p, padded, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync(c->h_gc_text.p, c->d_gc_text.p, padded, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipEventRecord(c->ev[4], s));
 			if (variable && C) HIP_TRY(hipMemcpyAsync(c->gc_sites.data(), c->d_gc_site.p, (size_t)C * sizeof(sbl_concat_site), hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
@@ -300,7 +248,7 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 		if (nparts) *nparts = ng;
 		if (sites) *sites = c->gc_sites.data();
 		if (nsites) *nsites = c->gc_sites.size();
-		if (text) *text = total ? c->h_gc_text : "";
+		if (text) *text = total ? c->h_gc_text.p : "";
 		if (text_len) *text_len = total;
 	});
 }

@@ -12,7 +12,7 @@
 //   kernel    k_group_distances, one workgroup of 256 lanes per item, tile by tile (GD_TILE = 256 columns) over its span:
 //     stage   the tile of both row blocks (of one, on the diagonal I == J) into LDS by aligned 16-byte loads shifted in registers
 //             (gv_load16: toff + i L is not aligned in general).  Bytes behind the span's last column belong to the next span, the
-//             next row or nothing: they are staged as '-', and a column of two gaps counts nowhere.  Next to the 8 bytes of a word the
+//             next row or nothing: they are staged as '-' (keep16, sbl_groups.h), and a column of two gaps counts nowhere.  Next to the 8 bytes of a word the
 //             lane stages their FLAGS, once per row and tile instead of once per pair: 0x80 in a byte that is one of A C G T, 0x40 in
 //             a byte that is '-' (zero8).  The LDS row stride is 264 bytes: 66 dwords, so the 32 lanes of a half wave that read one
 //             word of 32 different rows take 32 different bank pairs (a stride of 256 would be one bank for all).
@@ -22,13 +22,12 @@
 //             32-bit registers kept for the whole span (a span has at most 2^30 columns).
 //     fold    at the end of the span, not per tile, the lane adds the non-zero counters of its pairs to M[cls i][cls j] and
 //             M[cls j][cls i] with 64-bit atomicAdd in device memory: integer sums, the same in any order of arrival.
-//   host      argument checks before any launch, the item list, the matrix cleared on the device before the launch and copied back after
+//   host      argument checks before any launch (the walk over the groups and the checks of sbl_groups.h), the item list, the matrix cleared on the device before the launch and copied back after
 //             it, both timed by event pairs.  SBL_TEST_GDIST_SPAN: test switch, the columns per span.
 #include <algorithm>
 #include <cstring>
 
-#include "sbl_align.h"
-#include "sbl_text.h"
+#include "sbl_groups.h"
 
 namespace {
 
@@ -42,15 +41,6 @@ constexpr u64 GD_MIN_SPAN = 4096, GD_MAX_SPAN = 1ull << 30;      // columns of a
 constexpr u64 GD_HIGH = 0x8080808080808080ull, GD_GAPS = 0x2D2D2D2D2D2D2D2Dull;
 
 struct GdItem { u64 toff, L, col0, col1, inst0; unsigned i0, ni, j0, nj; };      // rows [i0, i0 + ni) against [j0, j0 + nj), columns [col0, col1); inst0: the group's first instance
-
-// the first n bytes of w (0 < n < 16), '-' behind them
-__device__ inline B16 gd_keep(B16 w, unsigned n)
-{
-	if (n < 8) { const u64 m = (1ull << (8 * n)) - 1; return {(w.lo & m) | (GD_GAPS & ~m), GD_GAPS}; }
-	if (n == 8) return {w.lo, GD_GAPS};
-	const u64 m = (1ull << (8 * (n - 8))) - 1;
-	return {w.lo, (w.hi & m) | (GD_GAPS & ~m)};
-}
 
 __global__ __launch_bounds__(GD_THREADS) void k_group_distances(const uint8_t *__restrict__ text, u64 text_bytes, const GdItem *__restrict__ items,
                                                                 const unsigned *__restrict__ cls, unsigned nclass, unsigned long long *__restrict__ M)
@@ -78,7 +68,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_distances(const uint8_t *_
 			const unsigned r = x / chunks, k = x - r * chunks, side = r >= T.ni ? 1 : 0, lr = side ? r - T.ni : r;
 			const u64 row = side ? T.j0 + lr : T.i0 + lr;
 			B16 v = gv_load16(text, text_bytes, T.toff + row * T.L + c0 + 16 * k);
-			if (w - 16 * k < 16) v = gd_keep(v, w - 16 * k);                       // behind the span: the next span, the next row or nothing
+			if (w - 16 * k < 16) v = keep16(v, w - 16 * k, GD_GAPS);                      // behind the span: the next span, the next row or nothing
 			s_word[side][lr][2 * k] = v.lo; s_word[side][lr][2 * k + 1] = v.hi;
 			s_flag[side][lr][2 * k] = base_flags8(v.lo); s_flag[side][lr][2 * k + 1] = base_flags8(v.hi);
 		}
@@ -120,10 +110,8 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 {
 	return guarded(c, [&] {
 		require_group_rows(c);
+		check_classes(c, cls, nclass);
 		const size_t ninst = c->gm_inst.size();
-		SBL_CHECK(cls || !ninst, SBL_ERR_BAD_ARG, "null classes");
-		SBL_CHECK(nclass >= 1 && nclass <= 1024, SBL_ERR_BAD_ARG, "the number of classes must be 1 .. 1024");
-		for (size_t k = 0; k < ninst; k++) SBL_CHECK(cls[k] < nclass, SBL_ERR_BAD_ARG, "a class is not below the number of classes");
 		hipStream_t s = c->stream;
 		const size_t cells = (size_t)nclass * nclass;
 		c->gd_counts.assign(cells, sbl_pair_counts{0, 0, 0, 0});
@@ -132,11 +120,11 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 		struct Wanted { size_t g; u64 nb; };
 		std::vector<Wanted> groups;
 		u64 work = 0;
-		const u64 text_end = for_each_wanted_group(c, want, [&](size_t g, const sbl_group_result &r, u64) {
+		const GmListed listed = for_each_wanted_group(c, want, 2, [&](size_t g, const sbl_group_result &r, u64) {
 			const u64 nb = (r.ninst + GD_ROWS - 1) / GD_ROWS;
 			groups.push_back(Wanted{g, nb});
 			work += nb * (nb + 1) / 2 * r.L;
-		}).text_end;
+		});
 		if (!groups.empty()) {
 			u64 span = std::max(GD_MIN_SPAN, (work / GD_TARGET + GD_TILE) / GD_TILE * GD_TILE);
 			if (const char *e = getenv("SBL_TEST_GDIST_SPAN")) span = (u64)std::max(1ll, atoll(e));
@@ -155,8 +143,8 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 							                       (unsigned)std::min<u64>(GD_ROWS, r.ninst - I * GD_ROWS), (unsigned)(J * GD_ROWS),
 							                       (unsigned)std::min<u64>(GD_ROWS, r.ninst - J * GD_ROWS)});
 			}
-			const u64 text_bytes = (text_end + 15) / 16 * 16;
-			SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes, SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
+			const u64 text_bytes = listed.text_bytes();
+			require_rows_on_device(c, text_bytes, listed.n);
 			al_upload(c, c->d_gd_item, items);
 			c->d_gd_cls.ensure(ninst * sizeof(uint32_t));
 			HIP_TRY(hipMemcpyAsync(c->d_gd_cls.p, cls, ninst * sizeof(uint32_t), hipMemcpyHostToDevice, s));

@@ -4,67 +4,52 @@
 // The rows hold as many bytes as the blocks have bases times instances; the segments follow the edits.  So the column-wise pass runs
 // where the rows are and only the segments and their slices come back.
 //
-//   classes   k_column_classes, output-stationary over the columns of the wanted groups, every group padded to a multiple of 16 columns:
-//             a lane owns 16 consecutive columns of ONE group, reads those 16 bytes of every row -- neighbouring lanes read neighbouring
-//             bytes of a row: 1 KiB per wave and row -- as two aligned 16-byte words shifted in registers (window16, as spell_text.hip
-//             does: toff + i L is not aligned in general), compares them 8 bytes at a time and writes 16 class bytes with one vector
-//             store: 0 equal, 1 unequal, 3 unequal and gapped.
+//   classes   k_column_classes, the column walk of sbl_groups.h (gm_walk16: a lane owns 16 consecutive columns of ONE group, every group
+//             padded to a multiple of 16 columns) with "any row holds '-'" gathered next to "differs from row 0": 16 class bytes per
+//             lane, 0 equal, 1 unequal, 3 unequal and gapped.
 //   bounds    k_segment_bounds, one lane per column: an unequal column OPENS a segment if it is column 0 or the equal run that ends before
 //             it is kept, and CLOSES one if it is column L - 1 or the equal run that starts behind it is kept.  "Kept" (the run touches
 //             column 0 or L, or has 30 columns) is decided by looking at most 30 class bytes back / ahead.  The lane writes two flag
 //             bytes; the flagged columns are compacted in ascending order by rocPRIM's select (sbl_prim.h), opens and closes apart.
 //   segments  k_segment_fill, one lane per segment: the i-th open pairs with the i-th close; lead, `before` from the group's merged gap
-//             slots (the arithmetic of k_spell_groups' seek) and where its slices lie in the rows.  k_segment_gapped, one lane per
-//             column: a gapped column finds its segment by binary search over the opens and marks it.
+//             slots (gm_centre_before) and where its slices lie in the rows.  k_segment_gapped, one lane per column: a gapped column
+//             finds its segment by binary search over the opens and marks it.
 //   slices    k_gather_slices, output-stationary like k_spell_groups: a lane owns 16 bytes of the packed text, finds its segment by
 //             binary search over the text offsets, then row and column; 16 bytes inside one slice are cut out of two aligned words,
 //             everything else steps byte by byte.  One vector store per lane.
-//   host      the group table, the 64-bit prefix of the padded L and, between the launches, the two counts and the prefix of the slice
-//             lengths (their number follows the edits).  The slices come back into a buffer of their own, not the pinned text buffer.
+//   host      the group table and the 64-bit prefix of the padded L (gm_columns, sbl_groups.h) and, between the launches, the two counts
+//             and the prefix of the slice lengths (their number follows the edits).  The slices come back into a buffer of their own.
 #include <algorithm>
 #include <cstring>
 
-#include "sbl_align.h"
+#include "sbl_groups.h"
 #include "sbl_prim.h"
-#include "sbl_text.h"
 
 namespace {
 
-constexpr unsigned GV_THREADS = 256;
+constexpr unsigned GV_THREADS = GM_THREADS;
 constexpr unsigned GV_CONTEXT = 30;                    // MINIMUM_CONTEXT_SIZE (C-Sibelia.py:20)
+constexpr u64 GV_GAPS = 0x2D2D2D2D2D2D2D2Dull;         // '-'
 
-struct GvGroup { u64 group, dg; };                     // a wanted group: its index in the call; its index in d_gm_group
 struct GvSlice { u64 src, L, len; };                   // a segment's slices: first byte of the centre's in the rows, row stride, bytes per row
 
+// gm_walk16's reader of the classes: 0x80 in every byte whose column holds a '-' in any of the group's rows
+struct GvClasses {
+	u64 glo, ghi;
+	__device__ unsigned rows(const GmGroup &Q) const { return Q.ninst; }
+	__device__ void first(B16 ref) { glo = zero8(ref.lo ^ GV_GAPS); ghi = zero8(ref.hi ^ GV_GAPS); }
+	__device__ void next(B16 w) { glo |= zero8(w.lo ^ GV_GAPS); ghi |= zero8(w.hi ^ GV_GAPS); }
+	__device__ B16 bytes(u64 ulo, u64 uhi) const { return {(ulo >> 7) | ((ulo & glo) >> 6), (uhi >> 7) | ((uhi & ghi) >> 6)}; }
+};
+
 __global__ __launch_bounds__(GV_THREADS) void k_column_classes(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
-                                                               const GvGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                               const GmUsed *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
                                                                u64 padded_cols, uint4 *__restrict__ cls)
 {
-	const u64 x0 = ((u64)blockIdx.x * GV_THREADS + threadIdx.x) * 16;
-	if (x0 >= padded_cols) return;
-	const unsigned gi = bs_find(cbase, ngroups, x0);
-	const GmGroup Q = gm[groups[gi].dg];
-	const u64 col0 = x0 - cbase[gi];                                          // < L: the padding of a group is less than 16 columns
-	const unsigned n = Q.L - col0 < 16 ? (unsigned)(Q.L - col0) : 16;        // columns of the group in this piece
-	const u64 gaps = 0x2D2D2D2D2D2D2D2Dull;                                   // '-'
-	const B16 ref = gv_load16(text, text_bytes, Q.toff + col0);
-	u64 dlo = 0, dhi = 0, glo = zero8(ref.lo ^ gaps), ghi = zero8(ref.hi ^ gaps);
-	for (unsigned i = 1; i < Q.ninst; i++) {
-		const B16 w = gv_load16(text, text_bytes, Q.toff + (u64)i * Q.L + col0);
-		dlo |= w.lo ^ ref.lo; dhi |= w.hi ^ ref.hi;
-		glo |= zero8(w.lo ^ gaps); ghi |= zero8(w.hi ^ gaps);
-	}
-	const u64 ulo = nonzero8(dlo), uhi = nonzero8(dhi);
-	u64 clo = (ulo >> 7) | ((ulo & glo) >> 6), chi = (uhi >> 7) | ((uhi & ghi) >> 6);
-	// the bytes behind column L belong to the next row or to nothing: class 0
-	if (n < 16) {
-		if (n <= 8) { chi = 0; clo = n == 8 ? clo : clo & ((1ull << (8 * n)) - 1); }
-		else chi &= (1ull << (8 * (n - 8))) - 1;
-	}
-	cls[x0 / 16] = make_uint4((unsigned)clo, (unsigned)(clo >> 32), (unsigned)chi, (unsigned)(chi >> 32));
+	gm_walk16(text, text_bytes, gm, groups, cbase, ngroups, padded_cols, GvClasses{}, cls);
 }
 
-__global__ __launch_bounds__(GV_THREADS) void k_segment_bounds(const uint8_t *__restrict__ cls, const GmGroup *__restrict__ gm, const GvGroup *__restrict__ groups,
+__global__ __launch_bounds__(GV_THREADS) void k_segment_bounds(const uint8_t *__restrict__ cls, const GmGroup *__restrict__ gm, const GmUsed *__restrict__ groups,
                                                                const u64 *__restrict__ cbase, u64 ngroups, u64 padded_cols,
                                                                uint8_t *__restrict__ opens, uint8_t *__restrict__ closes)
 {
@@ -89,7 +74,7 @@ __global__ __launch_bounds__(GV_THREADS) void k_segment_bounds(const uint8_t *__
 }
 
 __global__ __launch_bounds__(GV_THREADS) void k_segment_fill(const uint8_t *__restrict__ cls, const GmGroup *__restrict__ gm, const GmSlot *__restrict__ slots,
-                                                             const GvGroup *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                             const GmUsed *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
                                                              const u64 *__restrict__ opens, const u64 *__restrict__ closes, u64 nsegs,
                                                              sbl_group_segment *__restrict__ segs, GvSlice *__restrict__ slices)
 {
@@ -100,11 +85,7 @@ __global__ __launch_bounds__(GV_THREADS) void k_segment_fill(const uint8_t *__re
 	const GmGroup Q = gm[groups[gi].dg];
 	const u64 s = x - cbase[gi], e = closes[i] + 1 - cbase[gi];
 	const unsigned lead = s == 0 || (e - s == 1 && cls[x] == 1) ? 0u : 1u;
-	// the centre index column s belongs to = the centre bases before it (k_spell_groups' seek)
-	const u64 si = ga_find(0, Q.nslots, [&](u64 y) { return slots[Q.first_slot + y].col <= s; });
-	const GmSlot S = slots[Q.first_slot + si];
-	const u64 o = s - S.col, before = o < S.G ? S.p : S.p + (o - S.G);
-	segs[i] = sbl_group_segment{groups[gi].group, s, e, before, 0, lead, 0};
+	segs[i] = sbl_group_segment{groups[gi].group, s, e, gm_centre_before(slots, Q, s), 0, lead, 0};
 	slices[i] = GvSlice{Q.toff + s - lead, Q.L, e - s + lead};
 }
 
@@ -137,14 +118,7 @@ __global__ __launch_bounds__(GV_THREADS) void k_gather_slices(const uint8_t *__r
 			k++;
 		}
 	}
-	out[t0 / 16] = make_uint4((unsigned)w.lo, (unsigned)(w.lo >> 32), (unsigned)w.hi, (unsigned)(w.hi >> 32));
-}
-
-unsigned gv_blocks(u64 lanes)
-{
-	const u64 blocks = (lanes + GV_THREADS - 1) / GV_THREADS;
-	SBL_CHECK(blocks < 0x7FFFFFFFull, SBL_ERR_TOO_LARGE, "alignment rows too large");
-	return (unsigned)blocks;
+	store16(out, t0 / 16, w);
 }
 
 }  // namespace
@@ -157,32 +131,27 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 		hipStream_t s = c->stream;
 		c->gv_segs.clear(); c->gv_text.clear();
 		c->gv_times = SblTimes{};
-		// the wanted groups that have columns to compare; dg: d_gm_group lists the aligned groups with L > 0, in order
-		std::vector<GvGroup> groups;
-		std::vector<u64> cbase(1, 0);
-		const GmListed listed = for_each_wanted_group(c, want, [&](size_t g, const sbl_group_result &r, u64 dg) {
-			groups.push_back(GvGroup{g, dg});
-			cbase.push_back(cbase.back() + (r.L + 15) / 16 * 16);
-		});
-		const u64 ng = groups.size(), P = cbase.back(), text_bytes = (listed.text_end + 15) / 16 * 16;
+		// the wanted groups that have columns to compare, checked and up (d_gm_used, d_gm_cbase)
+		const GmColumns cols = gm_columns(c, want, 2, true, [](size_t, const sbl_group_result &, u64) {});
+		const u64 ng = cols.used.size(), P = cols.cbase.back(), text_bytes = cols.text_bytes;
+		const GmUsed *const used = c->d_gm_used.as<GmUsed>();
+		const u64 *const cbase = c->d_gm_cbase.as<u64>();
 		u64 nseg = 0, total = 0;
 		if (ng) {
-			SBL_CHECK(c->d_ga_text.p && c->d_ga_text.cap >= text_bytes && c->d_gm_group.cap >= listed.n * sizeof(GmGroup), SBL_ERR_INTERNAL, "the rows of the groups are not on the device");
 			const uint8_t *rows = c->d_ga_text.as<uint8_t>();
 			const GmGroup *gm = c->d_gm_group.as<GmGroup>();
-			al_upload(c, c->d_gv_group, groups); al_upload(c, c->d_gv_cbase, cbase);
 			c->d_gv_class.ensure((size_t)P); c->d_gv_flag.ensure((size_t)(2 * P));
-			c->d_gv_open.ensure((size_t)P * 8); c->d_gv_close.ensure((size_t)P * 8); c->d_gv_count.ensure(16);
+			c->d_gv_open.ensure((size_t)P * 8); c->d_gv_close.ensure((size_t)P * 8); c->d_gm_count.ensure(16);
 			uint8_t *const f_open = c->d_gv_flag.as<uint8_t>(), *const f_close = f_open + P;
 			u64 count[2] = {0, 0};
 			HIP_TRY(hipEventRecord(c->ev[0], s));
-			k_column_classes<<<gv_blocks(P / 16), GV_THREADS, 0, s>>>(rows, text_bytes, gm, c->d_gv_group.as<GvGroup>(), c->d_gv_cbase.as<u64>(), ng, P, c->d_gv_class.as<uint4>());
+			k_column_classes<<<gm_blocks(P / 16), GV_THREADS, 0, s>>>(rows, text_bytes, gm, used, cbase, ng, P, c->d_gv_class.as<uint4>());
 			HIP_TRY(hipGetLastError());
-			k_segment_bounds<<<gv_blocks(P), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), gm, c->d_gv_group.as<GvGroup>(), c->d_gv_cbase.as<u64>(), ng, P, f_open, f_close);
+			k_segment_bounds<<<gm_blocks(P), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), gm, used, cbase, ng, P, f_open, f_close);
 			HIP_TRY(hipGetLastError());
-			prim::select(s, c->d_gv_tmp, rocprim::counting_iterator<u64>(0), f_open, c->d_gv_open.as<u64>(), c->d_gv_count.as<u64>(), (size_t)P);
-			prim::select(s, c->d_gv_tmp, rocprim::counting_iterator<u64>(0), f_close, c->d_gv_close.as<u64>(), c->d_gv_count.as<u64>() + 1, (size_t)P);
-			HIP_TRY(hipMemcpyAsync(count, c->d_gv_count.p, 16, hipMemcpyDeviceToHost, s));
+			prim::select(s, c->d_gm_tmp, rocprim::counting_iterator<u64>(0), f_open, c->d_gv_open.as<u64>(), c->d_gm_count.as<u64>(), (size_t)P);
+			prim::select(s, c->d_gm_tmp, rocprim::counting_iterator<u64>(0), f_close, c->d_gv_close.as<u64>(), c->d_gm_count.as<u64>() + 1, (size_t)P);
+			HIP_TRY(hipMemcpyAsync(count, c->d_gm_count.p, 16, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
 			SBL_CHECK(count[0] == count[1], SBL_ERR_INTERNAL, "the segments of the alignments do not close");
 			nseg = count[0];
@@ -191,11 +160,10 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 			c->d_gv_seg.ensure((size_t)nseg * sizeof(sbl_group_segment)); c->d_gv_slice.ensure((size_t)nseg * sizeof(GvSlice));
 			c->gv_segs.resize((size_t)nseg);
 			std::vector<GvSlice> slices((size_t)nseg);
-			k_segment_fill<<<gv_blocks(nseg), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), c->d_gm_slot.as<GmSlot>(), c->d_gv_group.as<GvGroup>(),
-			                                                      c->d_gv_cbase.as<u64>(), ng, c->d_gv_open.as<u64>(), c->d_gv_close.as<u64>(), nseg,
-			                                                      c->d_gv_seg.as<sbl_group_segment>(), c->d_gv_slice.as<GvSlice>());
+			k_segment_fill<<<gm_blocks(nseg), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), c->d_gm_group.as<GmGroup>(), c->d_gm_slot.as<GmSlot>(), used, cbase, ng,
+			                                                      c->d_gv_open.as<u64>(), c->d_gv_close.as<u64>(), nseg, c->d_gv_seg.as<sbl_group_segment>(), c->d_gv_slice.as<GvSlice>());
 			HIP_TRY(hipGetLastError());
-			k_segment_gapped<<<gv_blocks(P), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), P, c->d_gv_open.as<u64>(), nseg, c->d_gv_seg.as<sbl_group_segment>());
+			k_segment_gapped<<<gm_blocks(P), GV_THREADS, 0, s>>>(c->d_gv_class.as<uint8_t>(), P, c->d_gv_open.as<u64>(), nseg, c->d_gv_seg.as<sbl_group_segment>());
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipEventRecord(c->ev[2], s));
 			HIP_TRY(hipMemcpyAsync(c->gv_segs.data(), c->d_gv_seg.p, (size_t)nseg * sizeof(sbl_group_segment), hipMemcpyDeviceToHost, s));
@@ -214,7 +182,7 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 			c->d_gv_text.ensure(padded);
 			c->gv_text.resize(padded);
 			HIP_TRY(hipEventRecord(c->ev[3], s));
-			k_gather_slices<<<gv_blocks(padded / 16), GV_THREADS, 0, s>>>(c->d_ga_text.as<uint8_t>(), text_bytes, c->d_gv_slice.as<GvSlice>(), c->d_gv_toff.as<u64>(), nseg, total,
+			k_gather_slices<<<gm_blocks(padded / 16), GV_THREADS, 0, s>>>(c->d_ga_text.as<uint8_t>(), text_bytes, c->d_gv_slice.as<GvSlice>(), c->d_gv_toff.as<u64>(), nseg, total,
 			                                                              c->d_gv_text.as<uint4>());
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipEventRecord(c->ev[4], s));

@@ -1,5 +1,5 @@
 // sbl_align.h -- what boundary_align.hip and block_align.hip share: the scores, the read of a base on its strand, the timed launch, the
-// argument checks, the walk over the instances of one block and the group tables of the row speller.
+// argument checks and the walk over the instances of one block.  What the rows of the groups need is in sbl_groups.h.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -25,10 +25,6 @@ template <class F> __device__ inline u64 ga_find(u64 lo, u64 hi, F le)   // larg
 	}
 	return lo;
 }
-
-// the tables k_spell_groups spells the rows of the groups from (block_align.hip); group_variants.hip reads the rows through them
-struct GmSlot { u64 col; unsigned p, G; };                                    // gap slot p: G columns from column col = p + the G of the slots before it
-struct GmGroup { u64 toff, L, first_inst, first_slot; unsigned ninst, nslots; };      // toff: the group's text (ninst L bytes); slot 0 always listed
 
 // `launch` between ev[0] and ev[1], `bytes` of its results back to the host and one synchronise -> the milliseconds between the events
 template <class F> float al_timed_launch(sbl_ctx *c, F launch, void *back, const void *d_from, size_t bytes)
@@ -61,28 +57,6 @@ inline void check_range(const sbl_ctx *c, uint32_t chr, uint64_t start, uint64_t
 	SBL_CHECK(chr < c->nchr, SBL_ERR_BAD_ARG, no_record);
 	SBL_CHECK(end >= start, SBL_ERR_BAD_ARG, "a range ends before it starts");
 	SBL_CHECK(end <= (uint64_t)(c->orig_sepidx[chr + 1] - c->orig_sepidx[chr] - 1), SBL_ERR_BAD_ARG, "a range runs beyond its record");
-}
-
-// what sbl_group_variants and sbl_group_distances ask for first: the rows of the last groups call are still on the device
-inline void require_group_rows(const sbl_ctx *c)
-{
-	SBL_CHECK(c->gv_rows_valid, SBL_ERR_BAD_ARG, "no rows of groups on the device: the last sbl_align_* call must be sbl_align_groups or sbl_align_block_groups");
-}
-
-// f(g, r, dg) for every wanted group g (want: null or one byte per group) that has rows to compare with each other; r: its result, dg: its
-// place in d_gm_group, which lists the aligned groups with L > 0 in order.  Returns how many those are and where their rows end in d_ga_text
-struct GmListed { u64 n, text_end; };
-template <class F> GmListed for_each_wanted_group(const sbl_ctx *c, const uint8_t *want, F f)
-{
-	GmListed l{0, 0};
-	for (size_t g = 0; g < c->gm_res.size(); g++) {
-		const sbl_group_result &r = c->gm_res[g];
-		if (r.status != SBL_GALIGN_OK || r.L == 0) continue;
-		l.text_end = std::max<u64>(l.text_end, r.row_off + (u64)r.ninst * r.L);
-		if (r.ninst >= 2 && (!want || want[g])) f(g, r, l.n);
-		l.n++;
-	}
-	return l;
 }
 
 // f(i, j) for every run v[i .. j) of equal |id| of a list sorted by |id|; f may change the run it is given

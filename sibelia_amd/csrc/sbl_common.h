@@ -87,6 +87,31 @@ struct DevBuf {
 	template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// Grow-only host buffer for text that the device made: pinned, or pageable when pinning fails (a host that cannot pin that much still
+// gets its text).  Owns its memory like DevBuf; ensure() does not keep the contents.  what: the words of its out-of-memory error.
+struct HostText {
+	char *p = nullptr;
+	size_t cap = 0;
+	bool pinned = true;
+	HostText() = default;
+	HostText(const HostText &) = delete;
+	~HostText() { release(); }
+	void ensure(size_t bytes, const char *what)
+	{
+		if (bytes <= cap) return;
+		release();
+		const size_t want = bytes + bytes / 16 + 4096;
+		pinned = hipHostMalloc((void **)&p, want) == hipSuccess;
+		if (!pinned) {
+			(void)hipGetLastError();
+			p = (char *)malloc(want);
+			if (!p) throw SblError{SBL_ERR_OOM, what};
+		}
+		cap = want;
+	}
+	void release() { if (p) { if (pinned) (void)hipHostFree(p); else free(p); } p = nullptr; cap = 0; }
+};
+
 // glibc rand() (TYPE_3 additive feedback, r[i] = r[i-3] + r[i-31], srandom(1)): the reference calls the
 // unseeded process-global rand() when it replaces non-ACGT characters (reference src/indexedsequence.cpp:31-37).
 struct GlibcRand {

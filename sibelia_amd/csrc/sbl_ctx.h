@@ -61,8 +61,6 @@ struct sbl_ctx {
 	{
 		host_free(h_ch, h_pinned); host_free(h_opos, h_pinned); host_free(h_old_ch, h_old_pinned); host_free(h_old_opos, h_old_pinned);
 		h_ch = h_old_ch = nullptr; h_opos = h_old_opos = nullptr; h_cap = 0;
-		host_free(h_bs_text, h_bs_pinned); h_bs_text = nullptr; h_bs_cap = 0;
-		host_free(h_gc_text, h_gc_pinned); h_gc_text = nullptr; h_gc_cap = 0;
 	}
 
 	// ---- enumeration workspace
@@ -93,12 +91,10 @@ struct sbl_ctx {
 	std::string gff_text, coords_text;   // sbl_blocks_gff, sbl_blocks_coords
 
 	// sbl_spell_pieces (spell_text.hip), for sbl_blocks_sequences and sbl_spell_text: descriptors, text offsets, blob of literals and
-	// the text on the device; the text comes back through ONE pinned staging buffer (pageable when the pinned allocation fails:
-	// h_bs_pinned), freed with the context.  The times of the last launch, per entry point
+	// the text on the device; the text comes back through ONE staging buffer (HostText: pinned where that can be had), freed with the
+	// context.  The times of the last launch, per entry point
 	DevBuf d_bs_desc, d_bs_off, d_bs_hdr, d_bs_text;
-	char *h_bs_text = nullptr;
-	size_t h_bs_cap = 0;
-	bool h_bs_pinned = true;
+	HostText h_bs_text;
 	SblTimes bs_times, st_times;
 
 	// sbl_uncovered_calls (uncovered.hip): what it hands out
@@ -127,30 +123,29 @@ struct sbl_ctx {
 	std::vector<sbl_group_inst> gm_inst;
 	std::vector<sbl_group_result> gm_res;
 	std::vector<sbl_member_result> gm_members;
-	// sbl_group_variants (group_variants.hip): reads d_ga_text and d_gm_group / d_gm_slot as the last groups call left them -- valid while
-	// gv_rows_valid holds (set by gm_run, cleared wherever those buffers are reused: gm_spell).  Group and column tables, class bytes,
-	// open / close flags and the compacted columns, segments, slice tables and the packed slices on the device; the slices come back
-	// into a host buffer of their own (NOT h_bs_text: the rows of the groups call stay where they are)
+	// The readers of those rows (sbl_groups.h): sbl_group_variants, sbl_group_distances and sbl_group_concat read d_ga_text and
+	// d_gm_group / d_gm_slot as the last groups call left them -- valid while gv_rows_valid holds (set by gm_run, cleared wherever those
+	// buffers are reused: gm_spell).  They run one after the other on one stream and share what each fills anew: the used groups, the
+	// prefix of their padded columns, two counters and the workspace of the compactions.  None of them writes h_bs_text
 	bool gv_rows_valid = false;
-	DevBuf d_gv_group, d_gv_cbase, d_gv_class, d_gv_flag, d_gv_open, d_gv_close, d_gv_count, d_gv_seg, d_gv_slice, d_gv_toff, d_gv_text, d_gv_tmp;
+	DevBuf d_gm_used, d_gm_cbase, d_gm_count, d_gm_tmp;
+	// sbl_group_variants (group_variants.hip): class bytes, open / close flags and the compacted columns, segments, slice tables and the
+	// packed slices on the device; the slices come back into a host buffer of their own
+	DevBuf d_gv_class, d_gv_flag, d_gv_open, d_gv_close, d_gv_seg, d_gv_slice, d_gv_toff, d_gv_text;
 	std::vector<sbl_group_segment> gv_segs;
 	std::vector<char> gv_text;
 	SblTimes gv_times;                   // the kernels / the copy of the slices
-	// sbl_group_distances (group_distances.hip): reads d_ga_text under the same rule (gv_rows_valid) and nothing of sbl_group_variants':
-	// work items, the classes of the instances and the class matrix on the device; the matrix comes back into a host buffer of its own
+	// sbl_group_distances (group_distances.hip): work items, the classes of the instances and the class matrix; the matrix comes back into gd_counts
 	DevBuf d_gd_item, d_gd_cls, d_gd_mat;
 	std::vector<sbl_pair_counts> gd_counts;
 	SblTimes gd_times;                   // clearing the matrix and the kernel / the copy of the matrix
-	// sbl_group_concat (group_concat.hip): reads d_ga_text and d_gm_group / d_gm_slot under the same rule (gv_rows_valid).  Used groups,
-	// padded column prefix, row starts per (used group, class), first kept column per part, header blob and class text offsets; site
-	// flags, compacted columns, sites and the text on the device.  The text comes back through a pinned buffer of its own (pageable when
-	// pinning fails: h_gc_pinned), freed with the context -- NOT h_bs_text, which holds the rows of the groups call
-	DevBuf d_gc_group, d_gc_cbase, d_gc_roff, d_gc_first, d_gc_hdr, d_gc_coff, d_gc_flag, d_gc_x, d_gc_count, d_gc_site, d_gc_pick, d_gc_text, d_gc_tmp;
+	// sbl_group_concat (group_concat.hip): row starts per (used group, class), first kept column per part, header blob and class text
+	// offsets; site flags, compacted columns, sites and the text on the device.  The text comes back through a staging buffer of its
+	// own (HostText), freed with the context -- NOT h_bs_text, which holds the rows of the groups call
+	DevBuf d_gc_roff, d_gc_first, d_gc_hdr, d_gc_coff, d_gc_flag, d_gc_x, d_gc_site, d_gc_pick, d_gc_text;
 	std::vector<sbl_concat_part> gc_parts;
 	std::vector<sbl_concat_site> gc_sites;
-	char *h_gc_text = nullptr;
-	size_t h_gc_cap = 0;
-	bool h_gc_pinned = true;
+	HostText h_gc_text;
 	SblTimes gc_times;                   // the kernels / the copy of the text
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
@@ -241,8 +236,8 @@ void sbl_render_reports(sbl_ctx *c, const char *const *names);   // report[0..2]
 void sbl_sort_by_id(std::vector<sbl_block> &v);   // the one unstable sort by |id| the reference's writers apply to a copy of the list
 // implemented in blockseq.hip
 void sbl_check_blocks(const sbl_ctx *c, const sbl_block *b, uint64_t n);   // a caller's block list against the loaded records (throws SBL_ERR_BAD_ARG)
-// implemented in spell_text.hip
-void sbl_text_staging(sbl_ctx *c, size_t bytes);   // h_bs_text, the pinned staging buffer of device-made text, grown to `bytes`
+// h_bs_text, the staging buffer of device-made text (spell_text.hip, blockseq.hip, block_align.hip), grown to `bytes`
+inline void sbl_text_staging(sbl_ctx *c, size_t bytes) { c->h_bs_text.ensure(bytes, "host staging buffer for device-made text"); }
 // implemented in simplify.hip
 void sbl_simplify_run(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t max_iter, sbl_progress_fn progress, void *user, uint64_t *bulges);
 void sbl_simplify_free(sbl_ctx *c);

@@ -1,6 +1,6 @@
 // sbl_text.h -- the text kernel's tools (spell_text.hip: k_spell_text): the search of a text offset in the offsets of the pieces, and
 // 16 bytes of text held in two registers -- cut out of two aligned source words (gv_load16: the readers of the alignment rows,
-// group_variants.hip and group_distances.hip), complemented, opened for a line feed.  And the pieces k_spell_text spells, with the one
+// sbl_groups.h), complemented, opened for a line feed, stored as one vector (store16).  And the pieces k_spell_text spells, with the one
 // host function that launches it for sbl_spell_text (spell_text.hip) and sbl_blocks_sequences (blockseq.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -42,8 +42,7 @@ template <class P> __device__ inline unsigned bs_find(P off, unsigned long long 
 __device__ inline u64 zero8(u64 v) { return ~(((v & 0x7F7F7F7F7F7F7F7Full) + 0x7F7F7F7F7F7F7F7Full) | v) & 0x8080808080808080ull; }
 // 0x80 in every byte of v that is not zero
 __device__ inline u64 nonzero8(u64 v) { return ~zero8(v) & 0x8080808080808080ull; }
-// 0x80 in every byte of v that is one of A C G T, 0x40 in every byte that is '-' (the readers of the alignment rows: group_distances.hip,
-// group_concat.hip)
+// 0x80 in every byte of v that is one of A C G T, 0x40 in every byte that is '-' (group_distances.hip, group_concat.hip)
 __device__ inline u64 base_flags8(u64 v)
 {
 	const u64 base = zero8(v ^ 0x4141414141414141ull) | zero8(v ^ 0x4343434343434343ull) | zero8(v ^ 0x4747474747474747ull) | zero8(v ^ 0x5454545454545454ull);
@@ -60,6 +59,8 @@ __device__ inline u64 complement8(u64 x)
 }
 
 struct B16 { u64 lo, hi; };
+// the one vector store of an output-stationary lane: w as the 16-byte word `word` of out
+__device__ inline void store16(uint4 *__restrict__ out, u64 word, B16 w) { out[word] = make_uint4((unsigned)w.lo, (unsigned)(w.lo >> 32), (unsigned)w.hi, (unsigned)(w.hi >> 32)); }
 // bytes [sh, sh + 16) of the 32 bytes (a, b), sh in [0, 16)
 __device__ inline B16 window16(uint4 a, uint4 b, unsigned sh)
 {

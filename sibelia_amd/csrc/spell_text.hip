@@ -15,7 +15,7 @@
 //           wrapped range `line = off / (width + 1), col = off % (width + 1)` is derived once per lane.  Lanes on piece boundaries, in
 //           literals and in ranges wrapped narrower than 16 step byte by byte.
 //   host    sbl_spell_pieces: descriptors, offsets and blob go up once; the kernel and the copy back lie between event pairs
-//   back    through a pinned staging buffer owned by the context (sbl_text_staging; pageable when pinning fails, as sbl_get_state does).
+//   back    through a pinned staging buffer owned by the context (sbl_text_staging: HostText, pageable when pinning fails).
 #include <algorithm>
 
 #include "sbl_align.h"
@@ -113,26 +113,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_spell_text(const uint8_t *__rest
 			off++;
 		}
 	}
-	out[t0 / 16] = make_uint4((unsigned)w.lo, (unsigned)(w.lo >> 32), (unsigned)w.hi, (unsigned)(w.hi >> 32));
+	store16(out, t0 / 16, w);
 }
 
 }  // namespace
-
-// the context's pinned staging buffer for device-made text, at least `bytes` large (pageable when pinning fails)
-void sbl_text_staging(sbl_ctx *c, size_t bytes)
-{
-	if (bytes <= c->h_bs_cap) return;
-	c->host_free(c->h_bs_text, c->h_bs_pinned);
-	c->h_bs_text = nullptr; c->h_bs_cap = 0;
-	const size_t cap = bytes + bytes / 16 + 4096;
-	c->h_bs_pinned = hipHostMalloc((void **)&c->h_bs_text, cap) == hipSuccess;
-	if (!c->h_bs_pinned) {                                             // a host that cannot pin that much still gets its text
-		(void)hipGetLastError();
-		c->h_bs_text = (char *)malloc(cap);
-		if (!c->h_bs_text) throw SblError{SBL_ERR_OOM, "host staging buffer for device-made text"};
-	}
-	c->h_bs_cap = cap;
-}
 
 void sbl_spell_pieces(sbl_ctx *c, const std::vector<StDesc> &desc, const std::vector<u64> &toff, const char *blob, size_t blob_len, const char *too_large, SblTimes &t)
 {
@@ -152,7 +136,7 @@ void sbl_spell_pieces(sbl_ctx *c, const std::vector<StDesc> &desc, const std::ve
 		                                                   c->d_bs_hdr.as<char>(), total, c->d_bs_text.as<uint4>());
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(c->ev[1], s));
-		HIP_TRY(hipMemcpyAsync(c->h_bs_text, c->d_bs_text.p, padded, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(c->h_bs_text.p, c->d_bs_text.p, padded, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipEventRecord(c->ev[2], s));
 		HIP_TRY(hipStreamSynchronize(s));
 		t.kernel_ms = sbl_elapsed_ms(c, 0, 1); t.copy_ms = sbl_elapsed_ms(c, 1, 2);
@@ -188,7 +172,7 @@ extern "C" sbl_status sbl_spell_text(sbl_ctx *c, uint64_t npieces, const sbl_tex
 			toff.push_back(toff.back() + st_text_len(d.L, d.width));
 		}
 		sbl_spell_pieces(c, desc, toff, literals, literal_len, "text too large", c->st_times);
-		if (text) *text = toff.back() ? c->h_bs_text : "";
+		if (text) *text = toff.back() ? c->h_bs_text.p : "";
 		if (text_len) *text_len = toff.back();
 	});
 }

@@ -80,6 +80,11 @@ CORESITES_HELP = ("Two or more input files: write where every column of --coresn
                   "of the first file, 1-based position on it and strand of the block's instance there.")
 
 CORE_OPTIONS = (("--corealignment", "corealignment"), ("--corepartitions", "corepartitions"), ("--coresnps", "coresnps"), ("--coresites", "coresites"))
+# the options that name a file made from alignments, as (flag, attribute) in the order the files are written; those that read the
+# multiple alignments of the blocks (align_block_groups); those of them that compare the input files by their names
+FILE_OPTIONS = (("--maf", "maf"), ("--variants", "variants"), ("--unmapped", "unmapped"), ("--multimaf", "multimaf"), ("--multivariants", "multivariants"),
+                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS
+GROUP_OPTIONS, NAMED_FILE_OPTIONS = FILE_OPTIONS[3:], FILE_OPTIONS[5:]
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
@@ -255,9 +260,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         for a in sorted(set(samples)):
             if samples.count(a) > 1:
                 raise PipelineError("--multivariants names a sample by its file's base name: two files are called %s" % a)
-    for o, f in (("--distances", opt.distances), ("--distancecounts", opt.distancecounts)) + tuple((o, getattr(opt, a)) for o, a in CORE_OPTIONS):
-        if f is None:
-            continue
+    for o, _ in _given(opt, NAMED_FILE_OPTIONS):
         if len(opt.filenames) < 2:                             # before any file is read
             raise PipelineError("%s compares files: it needs at least two" % o)
         if opt.noblocks:
@@ -276,13 +279,13 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
     if opt.unmapped is not None and not opt.uncovered:
         raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
-    distances = opt.distances is not None or opt.distancecounts is not None or core_wanted(opt)      # what else aligns the groups
-    if opt.gapopen is not None and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None and not distances:
+    aligns = bool(_given(opt, FILE_OPTIONS))        # --unmapped is given with --variants only
+    if opt.gapopen is not None and not aligns:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
-    if opt.wideband and opt.maf is None and opt.variants is None and opt.multimaf is None and opt.multivariants is None and not distances:
+    if opt.wideband and not aligns:
         raise PipelineError("--wideband widens the bands of the alignments: it needs at least one of --maf, --variants, --multimaf and --multivariants")
-    if opt.maf is not None or opt.variants is not None or opt.multimaf is not None or opt.multivariants is not None or distances:
+    if aligns:
         _check_alignment_files(opt)
     return opt
 
@@ -297,17 +300,20 @@ def file_names(filenames: Sequence[str]) -> List[str]:
     return [os.path.basename(os.path.normpath(f)) for f in filenames]
 
 
+def _given(opt: argparse.Namespace, options) -> List[Tuple[str, str]]:
+    """(flag, file) of those of `options` ((flag, attribute) pairs) that are given, in their order."""
+    return [(o, getattr(opt, a)) for o, a in options if getattr(opt, a) is not None]
+
+
 def core_wanted(opt: argparse.Namespace) -> bool:
     """One of --corealignment / --corepartitions / --coresnps / --coresites is given."""
-    return any(getattr(opt, a) is not None for _, a in CORE_OPTIONS)
+    return bool(_given(opt, CORE_OPTIONS))
 
 
 def _check_alignment_files(opt: argparse.Namespace) -> None:
     """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts and the four --core options name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
-    given = [(o, f) for o, f in (("--maf", opt.maf), ("--variants", opt.variants), ("--unmapped", opt.unmapped), ("--multimaf", opt.multimaf),
-                                    ("--multivariants", opt.multivariants), ("--distances", opt.distances), ("--distancecounts", opt.distancecounts))
-                                   + tuple((o, getattr(opt, a)) for o, a in CORE_OPTIONS) if f is not None]
+    given = _given(opt, FILE_OPTIONS)
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -373,8 +379,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for f in (opt.maf, opt.variants, opt.unmapped, opt.multimaf, opt.multivariants, opt.distances, opt.distancecounts,
-                            opt.corealignment, opt.corepartitions, opt.coresnps, opt.coresites) if f is not None]      # relative names: under the output directory
+        out += [f for _, f in _given(opt, FILE_OPTIONS)]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -559,25 +564,6 @@ def uncovered_files(bf, opt: argparse.Namespace, names: Sequence[str], nfirst: i
     return out
 
 
-def qualifying_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
-    """The ids --multivariants calls from, on a block list (formats.BLOCK_DTYPE): EVERY instance of the id is at least min_block_size
-    long, there are at least two, exactly one lies on the records of the first file and at most one on those of each other file.  For
-    two files this is determine_unique_block (C-Sibelia.py:314-323)."""
-    import bisect
-    first = [0]
-    for n in file_records:
-        first.append(first[-1] + n)
-    by_id: Dict[int, List[Tuple[int, int]]] = {}
-    for b in blocks:
-        by_id.setdefault(abs(int(b["id"])), []).append((bisect.bisect_right(first, int(b["chr"])) - 1, int(b["end"]) - int(b["start"])))
-    out = []
-    for block, inst in sorted(by_id.items()):
-        files = [f for f, _ in inst]
-        if len(inst) >= 2 and all(n >= min_block_size for _, n in inst) and files.count(0) == 1 and len(set(files)) == len(files):
-            out.append(block)
-    return out
-
-
 def _file_of_record(file_records: Sequence[int]) -> Callable[[int], int]:
     import bisect
     first = [0]
@@ -586,35 +572,42 @@ def _file_of_record(file_records: Sequence[int]) -> Callable[[int], int]:
     return lambda c: bisect.bisect_right(first, int(c)) - 1
 
 
-def distance_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
-    """The ids --distances / --distancecounts count over, on a block list (formats.BLOCK_DTYPE): there are at least two instances of
-    the id, EVERY one is at least min_block_size long, and at most one lies on the records of each file.  Unlike qualifying_blocks it
-    does not ask for an instance in the first file."""
+def _instances_by_id(blocks, file_records: Sequence[int]) -> List[Tuple[int, List[Tuple[int, int]]]]:
+    """(id, [(file, length) per instance]) of a block list (formats.BLOCK_DTYPE), in ascending id."""
     file_of = _file_of_record(file_records)
     by_id: Dict[int, List[Tuple[int, int]]] = {}
     for b in blocks:
         by_id.setdefault(abs(int(b["id"])), []).append((file_of(b["chr"]), int(b["end"]) - int(b["start"])))
-    out = []
-    for block, inst in sorted(by_id.items()):
-        files = [f for f, _ in inst]
-        if len(inst) >= 2 and all(n >= min_block_size for _, n in inst) and len(set(files)) == len(files):
-            out.append(block)
-    return out
+    return sorted(by_id.items())
+
+
+def _once_per_file(inst: Sequence[Tuple[int, int]], min_block_size: int) -> bool:
+    """Every instance is at least min_block_size long and at most one lies on the records of each file."""
+    files = [f for f, _ in inst]
+    return all(n >= min_block_size for _, n in inst) and len(set(files)) == len(files)
+
+
+def qualifying_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
+    """The ids --multivariants calls from, on a block list (formats.BLOCK_DTYPE): EVERY instance of the id is at least min_block_size
+    long, there are at least two, exactly one lies on the records of the first file and at most one on those of each other file.  For
+    two files this is determine_unique_block (C-Sibelia.py:314-323)."""
+    return [block for block, inst in _instances_by_id(blocks, file_records)
+            if len(inst) >= 2 and _once_per_file(inst, min_block_size) and [f for f, _ in inst].count(0) == 1]
+
+
+def distance_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
+    """The ids --distances / --distancecounts count over, on a block list (formats.BLOCK_DTYPE): there are at least two instances of
+    the id, EVERY one is at least min_block_size long, and at most one lies on the records of each file.  Unlike qualifying_blocks it
+    does not ask for an instance in the first file."""
+    return [block for block, inst in _instances_by_id(blocks, file_records) if len(inst) >= 2 and _once_per_file(inst, min_block_size)]
 
 
 def core_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> List[int]:
     """The ids of the core blocks of a block list (formats.BLOCK_DTYPE), what the four --core options concatenate: the id has exactly
     one instance on the records of EACH input file -- as many instances as there are files -- and every one is at least min_block_size
     long.  The subset of distance_blocks that reaches every file; for two files the two are the same."""
-    file_of = _file_of_record(file_records)
-    by_id: Dict[int, List[Tuple[int, int]]] = {}
-    for b in blocks:
-        by_id.setdefault(abs(int(b["id"])), []).append((file_of(b["chr"]), int(b["end"]) - int(b["start"])))
-    out = []
-    for block, inst in sorted(by_id.items()):
-        if all(n >= min_block_size for _, n in inst) and sorted(f for f, _ in inst) == list(range(len(file_records))):
-            out.append(block)
-    return out
+    return [block for block, inst in _instances_by_id(blocks, file_records)
+            if all(n >= min_block_size for _, n in inst) and sorted(f for f, _ in inst) == list(range(len(file_records)))]
 
 
 def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[int], insts, aligned, core, complain: Callable[[str], None]) -> Dict[str, bytes]:
@@ -687,7 +680,6 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     instance sorts first, so it is the centre and its alleles are REF.
     --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two.
     --corealignment / --corepartitions / --coresnps / --coresites: the concatenation of the same alignments (core_files), after those."""
-    import bisect
     from . import formats
     from .api import GALIGN_OK, SibeliaError
     try:
@@ -716,16 +708,14 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
             segments = bf.group_variants([block in qualify for block in ids])
         except SibeliaError as e:
             raise PipelineError(str(e))
-        first = [0]
-        for n in bf.file_records:
-            first.append(first[-1] + n)
+        file_of = _file_of_record(bf.file_records)
         by_group: Dict[int, list] = {}
         for seg in segments:
             by_group.setdefault(seg[0], []).append(seg)
         records = []
         for g, segs in sorted(by_group.items()):
             inst = insts[g]
-            row_of = {bisect.bisect_right(first, c) - 1: i for i, (c, _, _, _) in enumerate(inst)}      # file -> row (at most one each)
+            row_of = {file_of(c): i for i, (c, _, _, _) in enumerate(inst)}      # file -> row (at most one each)
             c0, s0, e0, rev0 = inst[0]
             for pos, alleles in formats.group_variants_records(segs, s0, e0, rev0):
                 records.append((names[c0], pos, ids[g], alleles[0],
@@ -806,7 +796,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 bf.set_wide(True)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
-            if opt.multimaf is not None or opt.multivariants is not None or opt.distances is not None or opt.distancecounts is not None or core_wanted(opt):      # likewise on the final list
+            if _given(opt, GROUP_OPTIONS):          # likewise on the final list
                 files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write, blocks))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))

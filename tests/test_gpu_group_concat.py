@@ -233,6 +233,41 @@ def test_any_order_with_variants_and_distances_leaves_the_rows():
     assert seen[0][2] == [CM.concat(all_rows, cls, 4, h, 80, mode) for mode in MODES]
 
 
+def test_readers_with_different_masks_share_their_tables():
+    """variants, concat VARIABLE, variants, distances, concat ALL on the rows of ONE groups call, with two masks in turn: the table of
+    used groups and the prefix of their padded columns are one set of device buffers for all readers, and one left over from the call
+    before has the wrong length and the wrong prefix.  Four groups of three rows with 15, 16, 17 and 33 columns, substitutions only:
+    the rows are the strings."""
+    import mvariants_model as MV
+    from sibelia_amd import BlockFinder
+    rng = np.random.default_rng(198)
+    groups = []
+    for n in (15, 16, 17, 33):
+        c = MC.rand(rng, n)
+        two, three = bytearray(c), bytearray(c)
+        two[n - 1], three[0], three[n // 2] = other(c[n - 1]), other(c[0]), other(c[n // 2])
+        groups.append([c, bytes(two), bytes(three)])
+    b = Groups(groups)
+    cls, h = [0, 1, 2, 2, 0, 1, 1, 2, 0, 0, 2, 1], headers_of(3)
+    A, B = [True, False, True, True], [False, True, True, False]
+    segments = lambda want: [(g, s, e, before, lead, slices) for g, rows in enumerate(groups) if want[g]      # noqa: E731
+                             for s, e, before, lead, _, slices in MV.segments(rows)]
+    bf = BlockFinder(b.records, device=0)
+    try:
+        assert [al.rows for al in bf.align_groups(b.desc)] == groups
+        v1 = bf.group_variants(A)
+        c1 = bf.group_concat(cls, 3, h, CM.VARIABLE, 80, B)
+        v2 = bf.group_variants(A)
+        d = bf.group_distances(cls, 3, B)
+        c2 = bf.group_concat(cls, 3, h, CM.ALL, 80, A)
+    finally:
+        bf.close()
+    assert v1 == v2 == segments(A) and {s[0] for s in v1} == {0, 2, 3}
+    assert c1 == CM.concat(groups, cls, 3, h, 80, CM.VARIABLE, B) and len(c1[2]) == 6
+    assert c2 == CM.concat(groups, cls, 3, h, 80, CM.ALL, A)
+    assert d.tolist() == DM.fold([DM.rows_counts(r) if w else DM.skipped(3) for r, w in zip(groups, B)], cls, 3).tolist()
+
+
 def test_two_calls_in_a_row():
     """ALL then VARIABLE on one context: the first result was copied, the second replaces what the context owns"""
     from sibelia_amd import BlockFinder
