@@ -508,6 +508,46 @@ sbl_status sbl_group_concat(sbl_ctx *ctx, const uint8_t *want, const uint32_t *c
                             const char **text, uint64_t *text_len);
 sbl_status sbl_group_concat_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 
+/* SNP-density mask of the multiple alignments (csrc/group_mask.hip), defined by this project: per member row of the groups
+ * of the context's LAST sbl_align_groups / sbl_align_block_groups call, the regions in which the row differs from the centre row more
+ * densely than the parameters allow, and the rows with those regions replaced by N.  Everything is bytes and integers.
+ * USED GROUPS.  A group is USED if want[g] != 0 (want: one byte per group, NULL: all), its status is SBL_GALIGN_OK, L > 0 and it has at
+ * least 2 rows.  There is no class argument: the reference row is the centre, row 0.
+ * DIFFERENCE.  Column c of a used group is a difference of member row i >= 1 if the centre byte and the row's byte are both one of the four
+ * upper-case bytes A C G T and are unequal: sbl_group_distances' `mismatch` of the pair (0, i).  The centre holds a base there, so
+ * p = before(c) -- sbl_group_segment's `before`, the centre bytes other than '-' in columns [0, c) -- is unique to c among the
+ * differences of the row.
+ * DENSE RUN.  window W >= 1, max_diff T >= 1.  With p_0 < p_1 < ... the centre indices of the differences of ONE member row of ONE group:
+ * every k with p_{k+T} - p_k < W masks the columns [col(p_k), col(p_{k+T})] of that row, inclusive -- T + 1 differences within W
+ * consecutive centre bases, "more than T SNPs in a window of W".
+ * INTERVAL.  The masked columns of a row are the union of those hulls, reported as maximal intervals; two hulls belong to one interval
+ * only if they share a difference.  Two dense runs whose last and first differences are merely neighbours (k' = k + T + 1) are two
+ * intervals and the columns between them stay.  The centre row is never masked.
+ * MASKED ROWS.  The rows of the groups call with every byte other than '-' inside an interval replaced by 'N': gap bytes stay '-',
+ * lower-case and ambiguous bytes become 'N', inserted columns (centre '-') inside an interval belong to it.  The rows of the groups the
+ * call does not use -- unwanted, skipped, L == 0, one row -- are copied unchanged.  No difference or no interval is a result: the masked
+ * rows then equal the rows.
+ * sbl_mask_interval, in ascending (group, row, first), owned by the ctx until the next sbl_group_mask: `group` indexes the groups of the
+ * groups call, row >= 1, [first, last] are columns of the group, inclusive, before_first / before_last their centre indices, ndiff
+ * the number of differences inside (at least T + 1).
+ * The masked rows go into a device buffer of the context's own with the layout of the rows (every row_off / L of sbl_group_result holds
+ * for it); the `rows` of the groups call and the rows on the device stay unchanged.  The call marks the mask valid; the next
+ * sbl_align_* call clears the mark.  Difference flags, their compaction, the run tests, a scan, the intervals and the masked rows are
+ * made by kernels; the host reads two counts.  All offsets are 64 bit.
+ * SBL_ERR_BAD_ARG, checked on the host before any launch: no groups call yet, or the last sbl_align_* call was sbl_align_pairs /
+ * sbl_align_unique_blocks; window == 0; max_diff == 0.  A refused call leaves an earlier mask valid.
+ * SBL_ERR_TOO_LARGE: rows beyond what one launch's grid covers.
+ * sbl_group_mask_times: device time of the last call's kernels and of the device-to-host copy of the intervals (event pairs).
+ * sbl_group_set_masked: with on = 1 every later sbl_group_variants, sbl_group_distances and sbl_group_concat call of the context reads
+ * the masked rows instead of the rows, and is SBL_ERR_BAD_ARG while no mask is valid; with 0 (the default) they behave as without this
+ * setting, byte for byte.  Anything but 0 / 1 is SBL_ERR_BAD_ARG and the value stays as it was. */
+typedef struct { uint64_t group, row, first, last, before_first, before_last, ndiff; } sbl_mask_interval;
+sbl_status sbl_group_mask(sbl_ctx *ctx, const uint8_t *want, uint32_t window, uint32_t max_diff,
+                          const sbl_mask_interval **intervals, uint64_t *nintervals);
+sbl_status sbl_group_mask_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
+sbl_status sbl_group_set_masked(sbl_ctx *ctx, uint32_t on);      /* 0 (default) | 1 */
+sbl_status sbl_group_get_masked(const sbl_ctx *ctx, uint32_t *on);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

@@ -32,7 +32,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
-           "sbl_group_concat", "sbl_group_concat_times", "sbl_tiny_index",
+           "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_tiny_index",
            "sbl_test_touched_list"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -145,6 +145,11 @@ class ConcatSite(C.Structure):                     # sbl_concat_site
 CONCAT_ALL, CONCAT_VARIABLE = 0, 1                 # SBL_CONCAT_ALL, SBL_CONCAT_VARIABLE
 
 
+class MaskInterval(C.Structure):                   # sbl_mask_interval
+    _fields_ = [("group", C.c_uint64), ("row", C.c_uint64), ("first", C.c_uint64), ("last", C.c_uint64),
+                ("before_first", C.c_uint64), ("before_last", C.c_uint64), ("ndiff", C.c_uint64)]
+
+
 class GroupAlignment:
     """One sbl_group_result: status (GALIGN_OK / GALIGN_SKIPPED), L, row_off, the rows (centre first, members in the order given) and
     per member (score, band_w, passes).  A skipped group has L = 0, no rows and member scores None."""
@@ -240,6 +245,10 @@ def load_library():
                                        C.POINTER(C.POINTER(ConcatPart)), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(ConcatSite)), C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_group_concat_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_mask.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(MaskInterval)), C.POINTER(C.c_uint64)]
+        L.sbl_group_mask_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_set_masked.argtypes = [C.c_void_p, C.c_uint32]
+        L.sbl_group_get_masked.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -604,6 +613,38 @@ class BlockFinder:
     def group_concat_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms of the text) of the last group_concat call, from event pairs."""
         return self._times("sbl_group_concat_times")
+
+    def group_mask(self, window: int, max_diff: int, want: Optional[Sequence[bool]] = None):
+        """The SNP-density mask of the groups of the LAST align_groups / align_block_groups call (csrc/group_mask.hip; defined in
+        include/sibelia_amd.h): per member row the maximal intervals in which more than max_diff differences from the
+        centre row lie within `window` consecutive centre bases.  The rows with those intervals replaced by N stay on the device, for
+        group_variants / group_distances / group_concat under set_masked(True).  want: one flag per group (None: all).
+        -> [(group, row, first, last, before_first, before_last, ndiff)] in ascending (group, row, first), a copy."""
+        mask = self._want_mask("group_mask", want)
+        if any(not 0 <= int(v) <= 2 ** 32 - 1 for v in (window, max_diff)):
+            raise SibeliaError("sbl_group_mask: bad argument (the window or the number of differences outside 32 bits)")
+        iv, n = C.POINTER(MaskInterval)(), C.c_uint64()
+        self._check(self.L.sbl_group_mask(self.h, mask, int(window), int(max_diff), C.byref(iv), C.byref(n)), "sbl_group_mask")
+        v = _view(C.cast(iv, C.c_void_p).value, n.value * 7, np.dtype("<u8")).reshape(-1, 7)
+        return [tuple(x) for x in v.tolist()]
+
+    def group_mask_times(self) -> Tuple[float, float]:
+        """(kernel ms, device-to-host copy ms of the intervals) of the last group_mask call, from event pairs."""
+        return self._times("sbl_group_mask_times")
+
+    def set_masked(self, on) -> None:
+        """True: every later group_variants / group_distances / group_concat call of this finder reads the masked rows of group_mask
+        instead of the rows, and is refused while no mask is valid.  False (the default): as without the setting.  Anything but 0 / 1 is
+        refused and the value stays as it was."""
+        if not 0 <= int(on) <= 2 ** 32 - 1:
+            raise SibeliaError("sbl_group_set_masked: bad argument (the masked rows setting is 0 or 1)")
+        self._check(self.L.sbl_group_set_masked(self.h, int(on)), "sbl_group_set_masked")
+
+    @property
+    def masked(self) -> int:
+        v = C.c_uint32()
+        self._check(self.L.sbl_group_get_masked(self.h, C.byref(v)), "sbl_group_get_masked")
+        return v.value
 
     def align_stats(self) -> dict:
         """Counters of the last align_pairs / align_unique_blocks / align_groups / align_block_groups: pairs, skipped, passes, launches,

@@ -634,6 +634,7 @@ u64 gm_spell(sbl_ctx *c, const std::vector<GaJob> &jobs, const std::vector<GmWan
 	std::vector<std::pair<unsigned, unsigned>> runs_d;                          // (slot, length) of the 'D' runs of a group's members
 	u64 total = 0;
 	c->gv_rows_valid = false;                                                 // the rows and tables sbl_group_variants reads are about to be replaced
+	c->gk_valid = false;                                                      // ... and with them what sbl_group_mask made of them
 	text.assign(want.size(), GmText{});
 	for (size_t g = 0; g < want.size(); g++) {
 		const GmWant &w = want[g];
@@ -727,6 +728,7 @@ void gm_run(sbl_ctx *c, u64 *rows_len)
 		}
 	}
 	c->gv_rows_valid = true;                                                  // d_ga_text / d_gm_* hold the rows of these groups until the next gm_spell
+	c->gk_valid = false;                                                      // new rows: no mask of them yet (sbl_group_mask)
 }
 
 void gm_check(const sbl_ctx *c, u64 ngroups, const uint64_t *first, const sbl_group_inst *inst)

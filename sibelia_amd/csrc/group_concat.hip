@@ -153,6 +153,7 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 {
 	return guarded(c, [&] {
 		require_group_rows(c);
+		const uint8_t *const rows = gm_reader_rows(c);
 		check_classes(c, cls, nclass);
 		SBL_CHECK(mode == SBL_CONCAT_ALL || mode == SBL_CONCAT_VARIABLE, SBL_ERR_BAD_ARG, "unknown mode of concatenation");
 		SBL_CHECK(width >= 1, SBL_ERR_BAD_ARG, "the width of a line must be at least 1");
@@ -178,7 +179,6 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 		});
 		const std::vector<GmUsed> &groups = cols.used;
 		const u64 ng = groups.size(), P = cols.cbase.back(), text_bytes = cols.text_bytes;
-		const uint8_t *rows = c->d_ga_text.as<uint8_t>();
 		u64 C = variable ? 0 : first.back();
 		float kernel_ms = 0;
 		if (variable && ng) {

@@ -110,6 +110,7 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 {
 	return guarded(c, [&] {
 		require_group_rows(c);
+		const uint8_t *const rows = gm_reader_rows(c);
 		check_classes(c, cls, nclass);
 		const size_t ninst = c->gm_inst.size();
 		hipStream_t s = c->stream;
@@ -151,7 +152,7 @@ extern "C" sbl_status sbl_group_distances(sbl_ctx *c, const uint8_t *want, const
 			c->d_gd_mat.ensure(cells * sizeof(sbl_pair_counts));
 			HIP_TRY(hipEventRecord(c->ev[0], s));
 			HIP_TRY(hipMemsetAsync(c->d_gd_mat.p, 0, cells * sizeof(sbl_pair_counts), s));
-			k_group_distances<<<(unsigned)items.size(), GD_THREADS, 0, s>>>(c->d_ga_text.as<uint8_t>(), text_bytes, c->d_gd_item.as<GdItem>(), c->d_gd_cls.as<unsigned>(), nclass,
+			k_group_distances<<<(unsigned)items.size(), GD_THREADS, 0, s>>>(rows, text_bytes, c->d_gd_item.as<GdItem>(), c->d_gd_cls.as<unsigned>(), nclass,
 			                                                                c->d_gd_mat.as<unsigned long long>());
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipEventRecord(c->ev[1], s));

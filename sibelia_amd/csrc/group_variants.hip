@@ -128,6 +128,7 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 {
 	return guarded(c, [&] {
 		require_group_rows(c);
+		const uint8_t *const rows = gm_reader_rows(c);
 		hipStream_t s = c->stream;
 		c->gv_segs.clear(); c->gv_text.clear();
 		c->gv_times = SblTimes{};
@@ -138,7 +139,6 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 		const u64 *const cbase = c->d_gm_cbase.as<u64>();
 		u64 nseg = 0, total = 0;
 		if (ng) {
-			const uint8_t *rows = c->d_ga_text.as<uint8_t>();
 			const GmGroup *gm = c->d_gm_group.as<GmGroup>();
 			c->d_gv_class.ensure((size_t)P); c->d_gv_flag.ensure((size_t)(2 * P));
 			c->d_gv_open.ensure((size_t)P * 8); c->d_gv_close.ensure((size_t)P * 8); c->d_gm_count.ensure(16);
@@ -182,7 +182,7 @@ extern "C" sbl_status sbl_group_variants(sbl_ctx *c, const uint8_t *want, const 
 			c->d_gv_text.ensure(padded);
 			c->gv_text.resize(padded);
 			HIP_TRY(hipEventRecord(c->ev[3], s));
-			k_gather_slices<<<gm_blocks(padded / 16), GV_THREADS, 0, s>>>(c->d_ga_text.as<uint8_t>(), text_bytes, c->d_gv_slice.as<GvSlice>(), c->d_gv_toff.as<u64>(), nseg, total,
+			k_gather_slices<<<gm_blocks(padded / 16), GV_THREADS, 0, s>>>(rows, text_bytes, c->d_gv_slice.as<GvSlice>(), c->d_gv_toff.as<u64>(), nseg, total,
 			                                                              c->d_gv_text.as<uint4>());
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipEventRecord(c->ev[4], s));

@@ -147,6 +147,16 @@ struct sbl_ctx {
 	std::vector<sbl_concat_site> gc_sites;
 	HostText h_gc_text;
 	SblTimes gc_times;                   // the kernels / the copy of the text
+	// sbl_group_mask (group_mask.hip): the prefix of the padded member rows per used group, difference flags, the compacted differences
+	// (flat index; row key, centre index, column), start flags and their scan, head / tail flags and the compacted heads and tails, the
+	// intervals and their byte ranges, and the masked rows: a buffer of the layout of d_ga_text, valid while gk_valid holds (set by
+	// sbl_group_mask, cleared wherever gv_rows_valid is set or cleared).  gk_masked (sbl_group_set_masked): the three readers read
+	// it instead of d_ga_text (gm_reader_rows, sbl_groups.h)
+	DevBuf d_gk_rbase, d_gk_flag, d_gk_x, d_gk_diff, d_gk_start, d_gk_scan, d_gk_end, d_gk_head, d_gk_tail, d_gk_iv, d_gk_range, d_gk_text;
+	std::vector<sbl_mask_interval> gk_intervals;
+	SblTimes gk_times;                   // the kernels / the copy of the intervals
+	bool gk_valid = false;
+	uint32_t gk_masked = 0;
 
 	// ---- multi-GPU enumeration (shard.hip): attached communicator + exchange buffers
 	struct SblComm *comm = nullptr;

@@ -26,6 +26,14 @@ inline void require_group_rows(const sbl_ctx *c)
 {
 	SBL_CHECK(c->gv_rows_valid, SBL_ERR_BAD_ARG, "no rows of groups on the device: the last sbl_align_* call must be sbl_align_groups or sbl_align_block_groups");
 }
+// the rows sbl_group_variants, sbl_group_distances and sbl_group_concat read, asked for before any launch: those of the groups call, or
+// with sbl_group_set_masked on the masked rows of sbl_group_mask (group_mask.hip), a buffer of the same layout
+inline const uint8_t *gm_reader_rows(const sbl_ctx *c)
+{
+	if (!c->gk_masked) return c->d_ga_text.as<uint8_t>();
+	SBL_CHECK(c->gk_valid, SBL_ERR_BAD_ARG, "the masked rows are asked for (sbl_group_set_masked) and no sbl_group_mask call has made them since the last groups call");
+	return c->d_gk_text.as<uint8_t>();
+}
 // ... and, once they know that they will launch: `listed` groups in d_gm_group, text_bytes of rows in d_ga_text
 inline void require_rows_on_device(const sbl_ctx *c, u64 text_bytes, u64 listed)
 {

@@ -298,6 +298,24 @@ def core_sites_text(rows: Sequence[Tuple[int, str, int, int, bool, int]], gap_op
     return ("\n".join(out) + "\n").encode("latin1")
 
 
+CORE_DENSE_COLUMNS = ("file", "block", "record", "first", "last", "strand", "differences", "first_column", "last_column")
+
+
+def core_dense_text(rows, window: int, max_diff: int, gap_open: int = 0) -> bytes:
+    """The file of --coredense: tab-separated; a line `# densitywindow=W densitymax=T`, a line `# gapopen=N` for
+    gap_open > 0, a line of column names, then one line per masked interval in the order BlockFinder.group_mask returns them.  rows:
+    (file name of the masked row, block id, record name, start, end, rev, before_first, before_last, differences, first column, last
+    column) -- the centre instance of the block (0-based, half-open, on the first file), the centre indices of the interval's first and
+    last column, and those columns in the concatenation counted from 0.  Positions are 1-based on the record by the rule of
+    core_sites_text -- start + before + 1 forward, end - before on a reverse instance, where the two swap so that first <= last; the
+    columns are written 1-based and inclusive."""
+    out = ["# densitywindow=%d densitymax=%d" % (window, max_diff)] + (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(CORE_DENSE_COLUMNS)]
+    for name, block, record, start, end, rev, before_first, before_last, ndiff, first_column, last_column in rows:
+        lo, hi = (end - before_last, end - before_first) if rev else (start + before_first + 1, start + before_last + 1)
+        out.append("%s\t%d\t%s\t%d\t%d\t%s\t%d\t%d\t%d" % (name, block, record, lo, hi, "-" if rev else "+", ndiff, first_column + 1, last_column + 1))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
 # ------------------------------------------------------------------------------------------ calls from uncovered regions (--uncovered, --unmapped)
 
 CALL_DELETION, CALL_INSERTION, CALL_UNMAPPED = 0, 1, 2      # SBL_CALL_* (include/sibelia_amd.h)

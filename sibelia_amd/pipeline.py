@@ -16,7 +16,9 @@ mismatches and gaps between every two input files over the blocks with at most o
 distance matrix and the counts behind it.  --corealignment / --corepartitions / --coresnps / --coresites (two or more
 input files) concatenate, on the device, the same alignments of the blocks with exactly one instance in every file into the core-genome
 alignment and its variable columns, one FASTA record per input file, with the tables that say where a block and a column come from
-(DESIGN.md 0.9).  --uncovered adds the rest of C-Sibelia's VCF to
+(DESIGN.md 0.9).  --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense (two or more input files) make the same files from
+the rows with every file's SNP-dense regions -- more than --densitymax differences from the first file within --densitywindow of its
+bases -- replaced by N, and the table of those regions; the mask is computed on the device.  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -79,11 +81,34 @@ CORESNPS_HELP = ("Two or more input files: write the variable columns of the cor
 CORESITES_HELP = ("Two or more input files: write where every column of --coresnps comes from as tab-separated text: column, block, record "
                   "of the first file, 1-based position on it and strand of the block's instance there.")
 
+COREFILTERED_HELP = ("Two or more input files: write the core-genome alignment of --corealignment with, in every file's record, the regions "
+                     "in which it differs from the first file more densely than --densitymax in --densitywindow replaced by N (gaps stay).  "
+                     "The columns are those of --corealignment, so --corepartitions describes this file too.  Such regions are "
+                     "typical of imported DNA (recombination, phage) and of misassembled repeats; SNP pipelines drop them before a tree "
+                     "is built.  The mask is computed on the device.")
+
+COREFILTEREDSNPS_HELP = ("Two or more input files: write the variable columns of the alignment of --corefiltered, as --coresnps does.  N is not "
+                         "one of A C G T, so a column masked in any file is dropped for all files.")
+
+COREFILTEREDSITES_HELP = "Two or more input files: write where every column of --corefilteredsnps comes from, as --coresites does."
+
+COREDENSE_HELP = ("Two or more input files: write the masked regions as tab-separated text, one line per region: the masked file, block, "
+                  "record of the first file with the first and last 1-based position of the region on it and the strand of the block's "
+                  "instance there, the differences inside, and the first and last column in the alignment of --corealignment, counted from 1.")
+
+DENSITY_MAX = 2 ** 32 - 1
+DENSITYWINDOW_DEFAULT, DENSITYMAX_DEFAULT = 1000, 3      # the defaults of CFSAN's SNP pipeline: a convention, not a measurement
+DENSITYWINDOW_HELP = ("With --corefiltered, --corefilteredsnps, --corefilteredsites or --coredense: the window of the density filter in bases of "
+                      "the first file, 1 .. 4294967295, default 1000.")
+DENSITYMAX_HELP = ("With the same options: the differences a window may hold, 1 .. 4294967295, default 3: a region is masked where more than "
+                   "this many differences lie within one window.")
+
 CORE_OPTIONS = (("--corealignment", "corealignment"), ("--corepartitions", "corepartitions"), ("--coresnps", "coresnps"), ("--coresites", "coresites"))
+DENSITY_OPTIONS = (("--corefiltered", "corefiltered"), ("--corefilteredsnps", "corefilteredsnps"), ("--corefilteredsites", "corefilteredsites"), ("--coredense", "coredense"))
 # the options that name a file made from alignments, as (flag, attribute) in the order the files are written; those that read the
 # multiple alignments of the blocks (align_block_groups); those of them that compare the input files by their names
 FILE_OPTIONS = (("--maf", "maf"), ("--variants", "variants"), ("--unmapped", "unmapped"), ("--multimaf", "multimaf"), ("--multivariants", "multivariants"),
-                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS
+                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS + DENSITY_OPTIONS
 GROUP_OPTIONS, NAMED_FILE_OPTIONS = FILE_OPTIONS[3:], FILE_OPTIONS[5:]
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
@@ -194,6 +219,13 @@ def _gap_open(s: str) -> int:
     return v
 
 
+def _density(s: str) -> int:
+    v = int(s)
+    if v < 1 or v > DENSITY_MAX:
+        raise argparse.ArgumentTypeError("integer from 1 to %d expected" % DENSITY_MAX)
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = _Parser(prog="python -m sibelia_amd", description="Program for finding synteny blocks in closely related genomes "
                 "(Sibelia 3.0.7's command line over the MI355X library).  " + NOT_WRITTEN)
@@ -230,6 +262,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--corepartitions", default=None, metavar="FILE", help=COREPARTITIONS_HELP)
     p.add_argument("--coresnps", default=None, metavar="FILE", help=CORESNPS_HELP)
     p.add_argument("--coresites", default=None, metavar="FILE", help=CORESITES_HELP)
+    p.add_argument("--corefiltered", default=None, metavar="FILE", help=COREFILTERED_HELP)
+    p.add_argument("--corefilteredsnps", default=None, metavar="FILE", help=COREFILTEREDSNPS_HELP)
+    p.add_argument("--corefilteredsites", default=None, metavar="FILE", help=COREFILTEREDSITES_HELP)
+    p.add_argument("--coredense", default=None, metavar="FILE", help=COREDENSE_HELP)
+    p.add_argument("--densitywindow", type=_density, default=None, metavar="W", help=DENSITYWINDOW_HELP)
+    p.add_argument("--densitymax", type=_density, default=None, metavar="T", help=DENSITYMAX_HELP)
     p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
     p.add_argument("--wideband", action="store_true", help=WIDEBAND_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
@@ -279,6 +317,11 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         raise PipelineError("--uncovered reads the blocks of every stage: it needs --allstages")
     if opt.unmapped is not None and not opt.uncovered:
         raise PipelineError("--unmapped takes the insertions that --uncovered finds: it needs --uncovered")
+    for o, v in (("--densitywindow", opt.densitywindow), ("--densitymax", opt.densitymax)):
+        if v is not None and not density_wanted(opt):
+            raise PipelineError("%s sets the density filter: it needs at least one of --corefiltered, --corefilteredsnps, --corefilteredsites and --coredense" % o)
+    opt.densitywindow = opt.densitywindow or DENSITYWINDOW_DEFAULT
+    opt.densitymax = opt.densitymax or DENSITYMAX_DEFAULT
     aligns = bool(_given(opt, FILE_OPTIONS))        # --unmapped is given with --variants only
     if opt.gapopen is not None and not aligns:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
@@ -310,8 +353,13 @@ def core_wanted(opt: argparse.Namespace) -> bool:
     return bool(_given(opt, CORE_OPTIONS))
 
 
+def density_wanted(opt: argparse.Namespace) -> bool:
+    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given."""
+    return bool(_given(opt, DENSITY_OPTIONS))
+
+
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts and the four --core options name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts, the four --core options and the four of the density filter name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
     given = _given(opt, FILE_OPTIONS)
     for o, f in given:
@@ -614,13 +662,19 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     """--corealignment / --corepartitions / --coresnps / --coresites from the alignments of one align_block_groups call: the class of an
     instance is the file of its record, the wanted groups are the aligned blocks of `core` (core_blocks); the rows are concatenated and
     filtered on the device (BlockFinder.group_concat), one call per mode.  The first file's instance of a core block
-    sorts first, so it is the centre: the positions of --coresites are read on it."""
+    sorts first, so it is the centre: the positions of --coresites are read on it.
+    --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense, after those: the density mask of the same wanted groups
+    against their centre -- the first file -- on the device (BlockFinder.group_mask), then the same two concatenations
+    of the masked rows (set_masked); in a core block row i is file i's."""
     from . import formats
     from .api import CONCAT_ALL, CONCAT_VARIABLE, GALIGN_OK, SibeliaError
     file_of = _file_of_record(bf.file_records)
     n = len(bf.file_records)
     cls = [file_of(c) for inst in insts for c, _, _, _ in inst]
     want = [block in core and al.status == GALIGN_OK for block, al in zip(ids, aligned)]
+    flat = [0]                                          # the first instance of every group in cls
+    for inst in insts:
+        flat.append(flat[-1] + len(inst))
     if not any(want):
         complain("no core block: no block has exactly one instance of at least %d bases in every input file and was aligned\n" % opt.minblocksize)
     headers = [b">" + a.encode("latin1") + b"\n" for a in file_names(opt.filenames)]
@@ -638,9 +692,32 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                 out[opt.coresnps] = text
             if opt.coresites is not None:
                 out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+        if density_wanted(opt):
+            intervals = bf.group_mask(opt.densitywindow, opt.densitymax, want)
+            bf.set_masked(True)
+            try:
+                if opt.corefiltered is not None:
+                    out[opt.corefiltered] = bf.group_concat(cls, n, headers, CONCAT_ALL, formats.CORE_WIDTH, want)[0]
+                if opt.corefilteredsnps is not None or opt.corefilteredsites is not None:
+                    text, _, sites = bf.group_concat(cls, n, headers, CONCAT_VARIABLE, formats.CORE_WIDTH, want)
+                    if opt.corefilteredsnps is not None:
+                        out[opt.corefilteredsnps] = text
+                    if opt.corefilteredsites is not None:
+                        out[opt.corefilteredsites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+            finally:
+                bf.set_masked(False)
+            if opt.coredense is not None:
+                first, at = {}, 0                       # the first column of every wanted group in the concatenation: the parts of mode ALL
+                for g, al in enumerate(aligned):
+                    if want[g] and al.L:
+                        first[g], at = at, at + al.L
+                files = file_names(opt.filenames)
+                out[opt.coredense] = formats.core_dense_text(
+                    [(files[cls[flat[g] + row]], ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before_lo, before_hi, ndiff, first[g] + lo, first[g] + hi)
+                     for g, row, lo, hi, before_lo, before_hi, ndiff in intervals], opt.densitywindow, opt.densitymax, opt.gapopen)
     except SibeliaError as e:
         raise PipelineError(str(e))
-    return {f: out[f] for f in (opt.corealignment, opt.corepartitions, opt.coresnps, opt.coresites) if f is not None}
+    return {f: out[f] for _, f in _given(opt, CORE_OPTIONS + DENSITY_OPTIONS)}
 
 
 def distance_files(bf, opt: argparse.Namespace, ids: Sequence[int], insts, aligned, used, complain: Callable[[str], None]) -> Dict[str, bytes]:
@@ -679,7 +756,8 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     DESIGN.md 0.6) for the qualifying blocks of the final list `blocks` (qualifying_blocks) as a multi-sample VCF; the first-file
     instance sorts first, so it is the centre and its alleles are REF.
     --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two.
-    --corealignment / --corepartitions / --coresnps / --coresites: the concatenation of the same alignments (core_files), after those."""
+    --corealignment / --corepartitions / --coresnps / --coresites: the concatenation of the same alignments (core_files), after those;
+    --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense: the same of their masked rows (core_files), last."""
     from . import formats
     from .api import GALIGN_OK, SibeliaError
     try:
@@ -690,7 +768,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     qualify = set(qualifying_blocks(blocks, bf.file_records, opt.minblocksize)) if opt.multivariants is not None else set()
     distances = opt.distances is not None or opt.distancecounts is not None
     used = set(distance_blocks(blocks, bf.file_records, opt.minblocksize)) if distances else set()
-    core = set(core_blocks(blocks, bf.file_records, opt.minblocksize)) if core_wanted(opt) else set()
+    core = set(core_blocks(blocks, bf.file_records, opt.minblocksize)) if core_wanted(opt) or density_wanted(opt) else set()
     groups = []
     for block, inst, al in zip(ids, insts, aligned):
         if al.status != GALIGN_OK:
@@ -723,7 +801,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
         out[opt.multivariants] = formats.multi_vcf_text(names[0], sample_names(opt.filenames), records, opt.gapopen)
     if distances:
         out.update(distance_files(bf, opt, ids, insts, aligned, used, complain))
-    if core_wanted(opt):
+    if core_wanted(opt) or density_wanted(opt):
         out.update(core_files(bf, opt, names, ids, insts, aligned, core, complain))
     return out
 
