@@ -538,7 +538,7 @@ sbl_status sbl_group_concat_times(const sbl_ctx *ctx, double *kernel_ms, double 
  * sbl_align_unique_blocks; window == 0; max_diff == 0.  A refused call leaves an earlier mask valid.
  * SBL_ERR_TOO_LARGE: rows beyond what one launch's grid covers.
  * sbl_group_mask_times: device time of the last call's kernels and of the device-to-host copy of the intervals (event pairs).
- * sbl_group_set_masked: with on = 1 every later sbl_group_variants, sbl_group_distances and sbl_group_concat call of the context reads
+ * sbl_group_set_masked: with on = 1 every later sbl_group_variants, sbl_group_distances, sbl_group_concat and sbl_group_bootstrap call of the context reads
  * the masked rows instead of the rows, and is SBL_ERR_BAD_ARG while no mask is valid; with 0 (the default) they behave as without this
  * setting, byte for byte.  Anything but 0 / 1 is SBL_ERR_BAD_ARG and the value stays as it was. */
 typedef struct { uint64_t group, row, first, last, before_first, before_last, ndiff; } sbl_mask_interval;
@@ -547,6 +547,37 @@ sbl_status sbl_group_mask(sbl_ctx *ctx, const uint8_t *want, uint32_t window, ui
 sbl_status sbl_group_mask_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 sbl_status sbl_group_set_masked(sbl_ctx *ctx, uint32_t on);      /* 0 (default) | 1 */
 sbl_status sbl_group_get_masked(const sbl_ctx *ctx, uint32_t *on);
+
+/* Bootstrap pair counts of the core-genome alignment (csrc/group_boot.hip), defined by this project: what a distance
+ * tree of the classes (the pipeline: the input files) with bootstrap support needs from the rows of the groups of the context's LAST
+ * sbl_align_groups / sbl_align_block_groups call, counted where that call left them on the device.  Everything is integers.
+ * USED GROUPS.  want, cls and nclass mean what they mean for sbl_group_concat, the rule that a used group holds every class exactly once
+ * included: it is checked on the host before any launch, with the same messages.
+ * SITES.  The kept columns of SBL_CONCAT_VARIABLE over the used groups in call order, numbered 0 .. C - 1: every row holds one of A C G T
+ * and the rows are not all equal.  *nsites = C.  *nclean = K, the columns of the used groups in which every row holds one of A C G T,
+ * variable or not: the denominator of a proportion of differing sites.
+ * DRAWS.  Every replicate r = 1 .. replicates makes n = draws ? draws : C draws (the pipeline passes 0).  Draw i = 0 .. n - 1 of replicate r
+ * picks the site, in unsigned 64-bit arithmetic that wraps,
+ *     ctr = (r << 32) | i;  z = seed + 0x9E3779B97F4A7C15 * (ctr + 1);
+ *     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31;
+ *     site = ((z >> 32) * C) >> 32
+ * a function of (seed, r, i, C) alone: no state, the same on any device and in any order of work.
+ * COUNTS.  uint64 M[replicates + 1][nclass][nclass], row-major, owned by the ctx until the next sbl_group_bootstrap.  M[0][f][g]: the
+ * sites in which the rows of classes f and g differ.  M[r][f][g], r >= 1: the draws of replicate r whose site has them differing (a site
+ * drawn w times counts w times).  Every slab is symmetric with a zero diagonal; the values are exact for any weight a site can reach
+ * (all draws on one site included).  C == 0 gives all zeros and is a result.
+ * Site flags, their compaction, the packed sites (2 bits per class) and all counts are made by kernels; the replicates run in batches
+ * whose count slabs fit 64 MiB of device memory, one launch and one host synchronisation per batch.  The rows stay unchanged, and this
+ * call, sbl_group_variants, sbl_group_distances and sbl_group_concat may follow one groups call in any order with the same results.
+ * Under sbl_group_set_masked(1) the rows are the masked rows, as for those three.
+ * SBL_ERR_BAD_ARG, checked on the host before any launch: everything sbl_group_concat refuses for want / cls / nclass / the class rule and
+ * the missing groups call; replicates > 100000; counts == NULL; the masked setting on without a valid mask.
+ * SBL_ERR_TOO_LARGE: (replicates + 1) * nclass^2 > 2^27 cells (1 GiB of counts), refused before anything is allocated; C >= 2^32.
+ * sbl_group_bootstrap_times: device time of the last call's kernels (flags, compaction, packing and counts) and of the device-to-host
+ * copies of the counts (event pairs). */
+sbl_status sbl_group_bootstrap(sbl_ctx *ctx, const uint8_t *want, const uint32_t *cls, uint32_t nclass, uint32_t replicates, uint64_t seed, uint32_t draws,
+                               const uint64_t **counts, uint64_t *nsites, uint64_t *nclean);
+sbl_status sbl_group_bootstrap_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is

@@ -32,7 +32,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_groups", "sbl_align_block_groups", "sbl_align_set_gap_open", "sbl_align_get_gap_open",
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
-           "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_tiny_index",
+           "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_group_bootstrap", "sbl_group_bootstrap_times", "sbl_tiny_index",
            "sbl_test_touched_list"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -245,6 +245,9 @@ def load_library():
                                        C.POINTER(C.POINTER(ConcatPart)), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(ConcatSite)), C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_group_concat_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_bootstrap.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                          C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.sbl_group_bootstrap_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_group_mask.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(MaskInterval)), C.POINTER(C.c_uint64)]
         L.sbl_group_mask_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_group_set_masked.argtypes = [C.c_void_p, C.c_uint32]
@@ -613,6 +616,27 @@ class BlockFinder:
     def group_concat_times(self) -> Tuple[float, float]:
         """(kernel ms, device-to-host copy ms of the text) of the last group_concat call, from event pairs."""
         return self._times("sbl_group_concat_times")
+
+    def group_bootstrap(self, cls: Sequence[int], nclass: int, replicates: int, seed: int, draws: int = 0, want: Optional[Sequence[bool]] = None):
+        """The bootstrap pair counts of the groups of the LAST align_groups / align_block_groups call (csrc/group_boot.hip; defined in
+        include/sibelia_amd.h) over the variable columns of group_concat's mode CONCAT_VARIABLE, counted on the rows that
+        call left on the device.  cls, nclass, want: as for group_concat; replicates: 0 .. 100000; seed: 64 bits; draws: draws per
+        replicate, 0 for as many as there are sites.
+        -> (uint64 array of shape (replicates + 1, nclass, nclass), a copy: [0] the sites in which two classes differ, [r] the draws of
+        replicate r in which they do; C, the number of sites; K, the number of columns in which every row holds one of A C G T)."""
+        mask = self._want_mask("group_bootstrap", want)
+        arr = self._class_array("group_bootstrap", cls, (nclass, replicates, draws), "a class, their number, the replicates or the draws")
+        if not 0 <= int(seed) <= 2 ** 64 - 1:
+            raise SibeliaError("sbl_group_bootstrap: bad argument (the seed outside 64 bits)")
+        out, nsites, nclean = C.POINTER(C.c_uint64)(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.sbl_group_bootstrap(self.h, mask, arr, int(nclass), int(replicates), int(seed), int(draws), C.byref(out), C.byref(nsites), C.byref(nclean)),
+                    "sbl_group_bootstrap")
+        n, b = int(nclass), int(replicates) + 1
+        return _view(C.cast(out, C.c_void_p).value, b * n * n, np.dtype("<u8")).reshape(b, n, n), nsites.value, nclean.value
+
+    def group_bootstrap_times(self) -> Tuple[float, float]:
+        """(kernel ms of all phases, device-to-host copy ms of the counts) of the last group_bootstrap call, from event pairs."""
+        return self._times("sbl_group_bootstrap_times")
 
     def group_mask(self, window: int, max_diff: int, want: Optional[Sequence[bool]] = None):
         """The SNP-density mask of the groups of the LAST align_groups / align_block_groups call (csrc/group_mask.hip; defined in

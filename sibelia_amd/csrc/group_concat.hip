@@ -4,7 +4,7 @@
 // not all the same (SBL_CONCAT_VARIABLE).  The text is classes x columns bytes, the order of the rows themselves, and the rows lie on
 // the device (d_ga_text): a column filter and a transposing gather, so they run where the rows are and only the text comes back.
 //
-//   flags     (VARIABLE) k_site_flags, the column walk of sbl_groups.h (gm_walk16: a lane owns 16 columns of ONE group, every group padded
+//   flags     (VARIABLE) k_site_flags of sbl_groups.h, its column walk (gm_walk16: a lane owns 16 columns of ONE group, every group padded
 //             to a multiple of 16 columns) with "every row holds one of A C G T" (base_flags8) gathered next to "differs from row 0": 16
 //             flag bytes per lane.  Padding columns get flag 0.
 //   sites     (VARIABLE) the flagged columns are compacted in ascending order by rocPRIM's select (sbl_prim.h); the host reads their
@@ -35,23 +35,6 @@ namespace {
 constexpr unsigned GC_THREADS = GM_THREADS, GC_SPAN = GC_THREADS * 16;
 
 struct GcPick { u64 ug, col; };                        // a kept column: its used group and its column there
-
-// gm_walk16's reader of the flags: 0x80 in every byte whose column holds one of A C G T in all of the group's rows
-struct GcFlags {
-	unsigned nclass;                                                          // a used group has nclass rows
-	u64 alo, ahi;
-	__device__ unsigned rows(const GmGroup &) const { return nclass; }
-	__device__ void first(B16 ref) { alo = base_flags8(ref.lo); ahi = base_flags8(ref.hi); }
-	__device__ void next(B16 w) { alo &= base_flags8(w.lo); ahi &= base_flags8(w.hi); }
-	__device__ B16 bytes(u64 ulo, u64 uhi) const { return {(ulo & alo) >> 7, (uhi & ahi) >> 7}; }
-};
-
-__global__ __launch_bounds__(GC_THREADS) void k_site_flags(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
-                                                           const GmUsed *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
-                                                           u64 padded_cols, unsigned nclass, uint4 *__restrict__ flags)
-{
-	gm_walk16(text, text_bytes, gm, groups, cbase, ngroups, padded_cols, GcFlags{nclass, 0, 0}, flags);
-}
 
 __global__ __launch_bounds__(GC_THREADS) void k_site_fill(const GmGroup *__restrict__ gm, const GmSlot *__restrict__ slots, const GmUsed *__restrict__ groups,
                                                           const u64 *__restrict__ cbase, u64 ngroups, const u64 *__restrict__ xs, u64 nsites,
@@ -137,13 +120,6 @@ __global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__res
 	store16(out, t0 / 16, w);
 }
 
-[[noreturn]] void gc_bad_group(size_t g, const char *what)
-{
-	char b[160];
-	snprintf(b, sizeof b, "group %zu %s: a used group holds every class exactly once", g, what);
-	throw SblError{SBL_ERR_BAD_ARG, b};
-}
-
 }  // namespace
 
 extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const uint32_t *cls, uint32_t nclass, uint32_t mode, uint32_t width,
@@ -165,18 +141,8 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 		c->gc_times = SblTimes{};
 		// the used groups -- one row is enough where there is one class --, where the row of every class starts and the parts of mode ALL;
 		// with VARIABLE the used groups and the padded prefix of their columns go up (d_gm_used, d_gm_cbase)
-		std::vector<u64> roff, first(1, 0);
-		const GmColumns cols = gm_columns(c, want, 1, variable, [&](size_t g, const sbl_group_result &r, u64) {
-			if (r.ninst != nclass) gc_bad_group(g, r.ninst < nclass ? "has fewer instances than there are classes" : "has more instances than there are classes");
-			const size_t at = roff.size();
-			roff.resize(at + nclass, ~0ull);
-			for (u64 i = 0; i < r.ninst; i++) {
-				u64 &slot = roff[at + cls[c->gm_first[g] + i]];
-				if (slot != ~0ull) gc_bad_group(g, "holds a class twice");
-				slot = r.row_off + i * r.L;
-			}
-			first.push_back(first.back() + r.L);
-		});
+		std::vector<u64> roff, first;
+		const GmColumns cols = gm_class_columns(c, want, cls, nclass, variable, roff, first);
 		const std::vector<GmUsed> &groups = cols.used;
 		const u64 ng = groups.size(), P = cols.cbase.back(), text_bytes = cols.text_bytes;
 		u64 C = variable ? 0 : first.back();
@@ -185,7 +151,7 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 			// ---- the kept columns, ascending, and their number
 			c->d_gc_flag.ensure((size_t)P); c->d_gc_x.ensure((size_t)P * 8); c->d_gm_count.ensure(16);
 			HIP_TRY(hipEventRecord(c->ev[0], s));
-			k_site_flags<<<gm_blocks(P / 16), GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gm_used.as<GmUsed>(), c->d_gm_cbase.as<u64>(), ng, P, nclass,
+			k_site_flags<false><<<gm_blocks(P / 16), GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gm_used.as<GmUsed>(), c->d_gm_cbase.as<u64>(), ng, P, nclass,
 			                                                      c->d_gc_flag.as<uint4>());
 			HIP_TRY(hipGetLastError());
 			prim::select(s, c->d_gm_tmp, rocprim::counting_iterator<u64>(0), c->d_gc_flag.as<uint8_t>(), c->d_gc_x.as<u64>(), c->d_gm_count.as<u64>(), (size_t)P);

@@ -147,6 +147,11 @@ struct sbl_ctx {
 	std::vector<sbl_concat_site> gc_sites;
 	HostText h_gc_text;
 	SblTimes gc_times;                   // the kernels / the copy of the text
+	// sbl_group_bootstrap (group_boot.hip): the packed sites and the count slabs of one batch of replicates; flags, compacted columns and
+	// row starts go through sbl_group_concat's d_gc_flag / d_gc_x / d_gc_roff, which every call fills anew.  All slabs come back into gb_counts
+	DevBuf d_gb_pack, d_gb_mat;
+	std::vector<uint64_t> gb_counts;
+	SblTimes gb_times;                   // the kernels of all phases / the copies of the slabs
 	// sbl_group_mask (group_mask.hip): the prefix of the padded member rows per used group, difference flags, the compacted differences
 	// (flat index; row key, centre index, column), start flags and their scan, head / tail flags and the compacted heads and tails, the
 	// intervals and their byte ranges, and the masked rows: a buffer of the layout of d_ga_text, valid while gk_valid holds (set by

@@ -1,7 +1,10 @@
-// sbl_groups.h -- what the readers of the rows of the groups (group_variants.hip, group_distances.hip, group_concat.hip) share with each
-// other and with k_spell_groups (block_align.hip), which spells those rows: the tables they are spelled from, the host's walk over the
-// groups of the last groups call, its checks and tables; on the device the column walk, the tail cut and the centre bases before a column.
+// sbl_groups.h -- what the readers of the rows of the groups (group_variants.hip, group_distances.hip, group_concat.hip, group_boot.hip)
+// share with each other and with k_spell_groups (block_align.hip), which spells those rows: the tables they are spelled from, the host's
+// walk over the groups of the last groups call, its checks and tables; on the device the column walk, the tail cut, the centre bases
+// before a column and the site flags of the two readers that take one row per class (k_site_flags).
 #pragma once
+#include <cstdio>
+
 #include "sbl_align.h"
 #include "sbl_text.h"
 
@@ -86,6 +89,31 @@ template <class F> GmColumns gm_columns(sbl_ctx *c, const uint8_t *want, unsigne
 	return t;
 }
 
+// The used groups of the readers that take one row per class (group_concat.hip, group_boot.hip): a used group holds every class exactly
+// once, refused here before any launch.  roff[ug * nclass + f]: where the row of class f of used group ug starts in the rows; first: the
+// nused + 1 prefix of the groups' columns.  One row is enough where there is one class
+[[noreturn]] inline void gm_bad_class_group(size_t g, const char *what)
+{
+	char b[160];
+	snprintf(b, sizeof b, "group %zu %s: a used group holds every class exactly once", g, what);
+	throw SblError{SBL_ERR_BAD_ARG, b};
+}
+inline GmColumns gm_class_columns(sbl_ctx *c, const uint8_t *want, const uint32_t *cls, uint32_t nclass, bool upload, std::vector<u64> &roff, std::vector<u64> &first)
+{
+	roff.clear(); first.assign(1, 0);
+	return gm_columns(c, want, 1, upload, [&](size_t g, const sbl_group_result &r, u64) {
+		if (r.ninst != nclass) gm_bad_class_group(g, r.ninst < nclass ? "has fewer instances than there are classes" : "has more instances than there are classes");
+		const size_t at = roff.size();
+		roff.resize(at + nclass, ~0ull);
+		for (u64 i = 0; i < r.ninst; i++) {
+			u64 &slot = roff[at + cls[c->gm_first[g] + i]];
+			if (slot != ~0ull) gm_bad_class_group(g, "holds a class twice");
+			slot = r.row_off + i * r.L;
+		}
+		first.push_back(first.back() + r.L);
+	});
+}
+
 // the first n bytes of w (0 < n < 16), `fill` (one byte, eight times) in every byte behind them
 __device__ inline B16 keep16(B16 w, unsigned n, u64 fill)
 {
@@ -136,4 +164,27 @@ template <class R> __device__ inline void gm_walk16(const uint8_t *__restrict__ 
 	B16 o = reader.bytes(nonzero8(dlo), nonzero8(dhi));
 	if (n < 16) o = keep16(o, n, 0);
 	store16(out, x0 / 16, o);
+}
+
+// gm_walk16's reader of the site flags: bit 0 of a byte is set where the column holds one of A C G T in all of the group's rows and the
+// rows are not all equal (SBL_CONCAT_VARIABLE's kept columns); with CLEAN, bit 1 where it holds one of A C G T in all rows, equal or not
+template <bool CLEAN> struct GcFlags {
+	unsigned nclass;                                                          // a used group has nclass rows
+	u64 alo, ahi;
+	__device__ unsigned rows(const GmGroup &) const { return nclass; }
+	__device__ void first(B16 ref) { alo = base_flags8(ref.lo); ahi = base_flags8(ref.hi); }
+	__device__ void next(B16 w) { alo &= base_flags8(w.lo); ahi &= base_flags8(w.hi); }
+	__device__ B16 bytes(u64 ulo, u64 uhi) const
+	{
+		const u64 m = 0x8080808080808080ull;
+		return {(ulo & alo) >> 7 | (CLEAN ? (alo & m) >> 6 : 0), (uhi & ahi) >> 7 | (CLEAN ? (ahi & m) >> 6 : 0)};
+	}
+};
+
+template <bool CLEAN>
+__global__ __launch_bounds__(GM_THREADS) void k_site_flags(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
+                                                           const GmUsed *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
+                                                           u64 padded_cols, unsigned nclass, uint4 *__restrict__ flags)
+{
+	gm_walk16(text, text_bytes, gm, groups, cbase, ngroups, padded_cols, GcFlags<CLEAN>{nclass, 0, 0}, flags);
 }

@@ -18,7 +18,10 @@ input files) concatenate, on the device, the same alignments of the blocks with 
 alignment and its variable columns, one FASTA record per input file, with the tables that say where a block and a column come from
 (DESIGN.md 0.9).  --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense (two or more input files) make the same files from
 the rows with every file's SNP-dense regions -- more than --densitymax differences from the first file within --densitywindow of its
-bases -- replaced by N, and the table of those regions; the mask is computed on the device.  --uncovered adds the rest of C-Sibelia's VCF to
+bases -- replaced by N, and the table of those regions; the mask is computed on the device.  --coretree /
+--corefilteredtree (three or more input files) write the neighbour-joining tree of the input files from the variable columns of those
+two alignments in Newick format, with --bootstrap B the support of B replicates whose pair counts are made on the device (DESIGN.md 0.11;
+`tree.py`).  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -103,12 +106,27 @@ DENSITYWINDOW_HELP = ("With --corefiltered, --corefilteredsnps, --corefilteredsi
 DENSITYMAX_HELP = ("With the same options: the differences a window may hold, 1 .. 4294967295, default 3: a region is masked where more than "
                    "this many differences lie within one window.")
 
+CORETREE_HELP = ("Three or more input files: write the neighbour-joining tree of the input files in Newick format, one line, the files named "
+                 "by their base names.  The distance of two files is the number of columns of --coresnps in which they differ over the number "
+                 "of columns of --corealignment in which every file holds one of A C G T (--treemodel).  The tree is unrooted and written "
+                 "from the node next to the first file, branch lengths with 9 decimals.  Not written where there is no such column.")
+COREFILTEREDTREE_HELP = "Three or more input files: write the same tree from the alignment of --corefiltered, its dense regions masked."
+BOOTSTRAP_MAX = 100000
+BOOTSTRAP_HELP = ("With --coretree or --corefilteredtree: label every inner branch with the percentage of B bootstrap replicates that hold it, "
+                  "0 .. 100000, default 0: no labels.  A replicate draws as many columns as --coresnps has, with replacement; the counts of "
+                  "all replicates are made on the device.")
+BOOTSEED_MAX = 2 ** 64 - 1
+BOOTSEED_HELP = "With the same options: the seed of the draws, 0 .. 18446744073709551615, default 1.  The same seed gives the same file."
+TREEMODEL_HELP = ("With the same options: p, the proportion of differing columns (default), or jc, Jukes and Cantor's correction "
+                  "-3/4 ln(1 - 4p/3); a tree with two files at p >= 0.75 is then not written.")
+
 CORE_OPTIONS = (("--corealignment", "corealignment"), ("--corepartitions", "corepartitions"), ("--coresnps", "coresnps"), ("--coresites", "coresites"))
 DENSITY_OPTIONS = (("--corefiltered", "corefiltered"), ("--corefilteredsnps", "corefilteredsnps"), ("--corefilteredsites", "corefilteredsites"), ("--coredense", "coredense"))
+TREE_OPTIONS = (("--coretree", "coretree"), ("--corefilteredtree", "corefilteredtree"))
 # the options that name a file made from alignments, as (flag, attribute) in the order the files are written; those that read the
 # multiple alignments of the blocks (align_block_groups); those of them that compare the input files by their names
 FILE_OPTIONS = (("--maf", "maf"), ("--variants", "variants"), ("--unmapped", "unmapped"), ("--multimaf", "multimaf"), ("--multivariants", "multivariants"),
-                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS + DENSITY_OPTIONS
+                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS + DENSITY_OPTIONS + TREE_OPTIONS
 GROUP_OPTIONS, NAMED_FILE_OPTIONS = FILE_OPTIONS[3:], FILE_OPTIONS[5:]
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
@@ -226,6 +244,15 @@ def _density(s: str) -> int:
     return v
 
 
+def _bounded(lo: int, hi: int):
+    def conv(s: str) -> int:
+        v = int(s)
+        if v < lo or v > hi:
+            raise argparse.ArgumentTypeError("integer from %d to %d expected" % (lo, hi))
+        return v
+    return conv
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = _Parser(prog="python -m sibelia_amd", description="Program for finding synteny blocks in closely related genomes "
                 "(Sibelia 3.0.7's command line over the MI355X library).  " + NOT_WRITTEN)
@@ -268,6 +295,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--coredense", default=None, metavar="FILE", help=COREDENSE_HELP)
     p.add_argument("--densitywindow", type=_density, default=None, metavar="W", help=DENSITYWINDOW_HELP)
     p.add_argument("--densitymax", type=_density, default=None, metavar="T", help=DENSITYMAX_HELP)
+    p.add_argument("--coretree", default=None, metavar="FILE", help=CORETREE_HELP)
+    p.add_argument("--corefilteredtree", default=None, metavar="FILE", help=COREFILTEREDTREE_HELP)
+    p.add_argument("--bootstrap", type=_bounded(0, BOOTSTRAP_MAX), default=None, metavar="B", help=BOOTSTRAP_HELP)
+    p.add_argument("--bootseed", type=_bounded(0, BOOTSEED_MAX), default=None, metavar="S", help=BOOTSEED_HELP)
+    p.add_argument("--treemodel", choices=("p", "jc"), default=None, help=TREEMODEL_HELP)
     p.add_argument("--gapopen", type=_gap_open, default=None, metavar="N", help=GAPOPEN_HELP)
     p.add_argument("--wideband", action="store_true", help=WIDEBAND_HELP)
     p.add_argument("--device", type=int, default=-1, metavar="N", help="HIP device to run on (default: the current one)")
@@ -311,6 +343,20 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
             for a in names:
                 if a != "".join(a.split()):
                     raise PipelineError("--distances writes PHYLIP, which separates by blanks: the file name '%s' holds white space" % a)
+    for o, _ in _given(opt, TREE_OPTIONS):
+        if len(opt.filenames) < 3:                             # two files have one distance and no tree
+            raise PipelineError("%s builds a tree: it needs at least three input files" % o)
+        from . import tree
+        try:
+            tree.check_names(file_names(opt.filenames))
+        except ValueError as e:
+            raise PipelineError("%s names a file by its base name: %s" % (o, e))
+    for o, v in (("--bootstrap", opt.bootstrap), ("--bootseed", opt.bootseed), ("--treemodel", opt.treemodel)):
+        if v is not None and not tree_wanted(opt):
+            raise PipelineError("%s is a setting of the tree: it needs at least one of --coretree and --corefilteredtree" % o)
+    opt.bootstrap = opt.bootstrap or 0
+    opt.bootseed = 1 if opt.bootseed is None else opt.bootseed
+    opt.treemodel = opt.treemodel or "p"
     if opt.uncovered and opt.variants is None:
         raise PipelineError("--uncovered adds its records to the file of --variants: it needs --variants")
     if opt.uncovered and not opt.allstages:
@@ -354,12 +400,17 @@ def core_wanted(opt: argparse.Namespace) -> bool:
 
 
 def density_wanted(opt: argparse.Namespace) -> bool:
-    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given."""
-    return bool(_given(opt, DENSITY_OPTIONS))
+    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given, or --corefilteredtree, which reads the same masked rows."""
+    return bool(_given(opt, DENSITY_OPTIONS)) or opt.corefilteredtree is not None
+
+
+def tree_wanted(opt: argparse.Namespace) -> bool:
+    """One of --coretree / --corefilteredtree is given."""
+    return bool(_given(opt, TREE_OPTIONS))
 
 
 def _check_alignment_files(opt: argparse.Namespace) -> None:
-    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts, the four --core options and the four of the density filter name files of their own: not each other and not a file the run writes anyway."""
+    """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts, the four --core options, the four of the density filter and the two trees name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
     given = _given(opt, FILE_OPTIONS)
     for o, f in given:
@@ -665,8 +716,10 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     sorts first, so it is the centre: the positions of --coresites are read on it.
     --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense, after those: the density mask of the same wanted groups
     against their centre -- the first file -- on the device (BlockFinder.group_mask), then the same two concatenations
-    of the masked rows (set_masked); in a core block row i is file i's."""
-    from . import formats
+    of the masked rows (set_masked); in a core block row i is file i's.
+    --coretree / --corefilteredtree: one BlockFinder.group_bootstrap call each on the rows / the masked rows and the
+    tree of its counts (tree.py); a tree that cannot be built is named through `complain` and its file is absent from the result."""
+    from . import formats, tree
     from .api import CONCAT_ALL, CONCAT_VARIABLE, GALIGN_OK, SibeliaError
     file_of = _file_of_record(bf.file_records)
     n = len(bf.file_records)
@@ -679,6 +732,18 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
         complain("no core block: no block has exactly one instance of at least %d bases in every input file and was aligned\n" % opt.minblocksize)
     headers = [b">" + a.encode("latin1") + b"\n" for a in file_names(opt.filenames)]
     out = {}
+
+    def tree_file(o: str):
+        if not any(want):                               # no core block: said above
+            return
+        counts, nsites, nclean = bf.group_bootstrap(cls, n, opt.bootstrap, opt.bootseed, 0, want)
+        if nsites == 0:
+            complain("%s not written: no variable column in the core-genome alignment\n" % o)
+            return
+        try:
+            out[getattr(opt, o[2:])] = tree.tree_text(counts, nclean, opt.treemodel, file_names(opt.filenames)).encode("latin1")
+        except tree.Saturated as e:
+            complain("%s not written: %s\n" % (o, e))
     try:
         if opt.corealignment is not None or opt.corepartitions is not None:
             text, parts, _ = bf.group_concat(cls, n, headers, CONCAT_ALL, formats.CORE_WIDTH, want)
@@ -692,6 +757,8 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                 out[opt.coresnps] = text
             if opt.coresites is not None:
                 out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+        if opt.coretree is not None:
+            tree_file("--coretree")
         if density_wanted(opt):
             intervals = bf.group_mask(opt.densitywindow, opt.densitymax, want)
             bf.set_masked(True)
@@ -704,6 +771,8 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                         out[opt.corefilteredsnps] = text
                     if opt.corefilteredsites is not None:
                         out[opt.corefilteredsites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+                if opt.corefilteredtree is not None:
+                    tree_file("--corefilteredtree")
             finally:
                 bf.set_masked(False)
             if opt.coredense is not None:
@@ -717,7 +786,9 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                      for g, row, lo, hi, before_lo, before_hi, ndiff in intervals], opt.densitywindow, opt.densitymax, opt.gapopen)
     except SibeliaError as e:
         raise PipelineError(str(e))
-    return {f: out[f] for _, f in _given(opt, CORE_OPTIONS + DENSITY_OPTIONS)}
+    made = {f: out[f] for _, f in _given(opt, CORE_OPTIONS + DENSITY_OPTIONS)}
+    made.update({f: out[f] for _, f in _given(opt, TREE_OPTIONS) if f in out})      # a tree that could not be built was named and is absent
+    return made
 
 
 def distance_files(bf, opt: argparse.Namespace, ids: Sequence[int], insts, aligned, used, complain: Callable[[str], None]) -> Dict[str, bytes]:
@@ -757,7 +828,8 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     instance sorts first, so it is the centre and its alleles are REF.
     --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two.
     --corealignment / --corepartitions / --coresnps / --coresites: the concatenation of the same alignments (core_files), after those;
-    --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense: the same of their masked rows (core_files), last."""
+    --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense: the same of their masked rows (core_files);
+    --coretree / --corefilteredtree: the trees of the two (core_files), last."""
     from . import formats
     from .api import GALIGN_OK, SibeliaError
     try:
@@ -768,7 +840,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     qualify = set(qualifying_blocks(blocks, bf.file_records, opt.minblocksize)) if opt.multivariants is not None else set()
     distances = opt.distances is not None or opt.distancecounts is not None
     used = set(distance_blocks(blocks, bf.file_records, opt.minblocksize)) if distances else set()
-    core = set(core_blocks(blocks, bf.file_records, opt.minblocksize)) if core_wanted(opt) or density_wanted(opt) else set()
+    core = set(core_blocks(blocks, bf.file_records, opt.minblocksize)) if core_wanted(opt) or density_wanted(opt) or tree_wanted(opt) else set()
     groups = []
     for block, inst, al in zip(ids, insts, aligned):
         if al.status != GALIGN_OK:
@@ -801,7 +873,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
         out[opt.multivariants] = formats.multi_vcf_text(names[0], sample_names(opt.filenames), records, opt.gapopen)
     if distances:
         out.update(distance_files(bf, opt, ids, insts, aligned, used, complain))
-    if core_wanted(opt) or density_wanted(opt):
+    if core_wanted(opt) or density_wanted(opt) or tree_wanted(opt):
         out.update(core_files(bf, opt, names, ids, insts, aligned, core, complain))
     return out
 
@@ -880,7 +952,8 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
     finally:
         bf.close()
-    assert list(files) == planned_files(opt, len(stages), outdir_exists)
+    unbuilt = [f for _, f in _given(opt, TREE_OPTIONS) if f not in files]      # a tree that could not be built was named on standard error
+    assert list(files) == [f for f in planned_files(opt, len(stages), outdir_exists) if f not in unbuilt]
     return 0, files, "".join(printed)
 
 
