@@ -339,8 +339,11 @@ __device__ __forceinline__ void wave_collapse(const GraphView &g, Txn &t, BulgeW
 //   3  the stamp words of every id it will erase or copy, and the two pool allocations, in one batch;
 //   4  checks, then nothing but stores (erase, characters, links, new elements, positions), the AddPoint list, and the AddPoints.
 // Same effect as wave_collapse (the two erase loops fuse: the flank marks of the first are a subset of the range of the second, and
-// the order of erasure is unobservable -- lazy-erase chain and list sizes are order-free).  NC = 64-step chunks per window (1 or 3).
-#define GATHER_CHUNKS_MAX 1
+// the order of erasure is unobservable -- lazy-erase chain and list sizes are order-free).  NC = 64-step chunks per window, 1 to 3:
+// a collapse looks at span = max(dS, dT) + k + 1 steps of a window, so NC chunks hold every branch of up to 64 NC - k - 1 steps (k = 25:
+// a lone SNP is 26 steps and fits one chunk, two SNPs 13 or more bases apart and most indels do not).  wave_collapse_any chooses; the
+// largest NC is the calling kernel's (the one-chunk limit used to be global, after a three-chunk k_commit was measured at 504 B of
+// scratch and 40 -> 52 ms: that was the compiler's private copy of the GraphView argument, see k_commit, not these registers).
 template <int NC>
 __device__ __forceinline__ unsigned gsel(const unsigned (&r)[NC], unsigned x)      // r "at step x": every lane must take part
 {
@@ -590,16 +593,35 @@ __device__ __forceinline__ void wave_collapse_g(const GraphView &g, Txn &t, Bulg
 	WSYNC();
 	PC_ADD(15);
 }
-// the collapse of an ordered round / chain transaction: gather-first where the walks fit the register chunks
+// SBL_PHASES: the collapses of the timed transactions by the form they took (wave_collapse_g<1>, <2>, <3>, wave_collapse), by
+// dS == dT / dS > dT / dS < dT and by span (255: that or more), and per form their number and summed cycles
+__device__ unsigned g_collapse_hist[4][3][256];
+__device__ unsigned long long g_collapse_form[4][2];
+extern "C" void sbl_collapse_hist(unsigned *out /* [4][3][256] */)
+{
+	(void)hipDeviceSynchronize();
+	(void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_collapse_hist), sizeof g_collapse_hist);
+}
+// the collapse of an ordered round / chain transaction: gather-first where the walks fit GMAX register chunks of 64 steps.
+// GMAX is the caller's: every instantiation is inlined into its kernel.  k_commit (waves_per_eu 4: 128 registers) pays nothing for the
+// two-chunk form and 64 B of scratch (200 -> 264 B) for the three-chunk one, and was measured faster with each (docs/history/
+// gather_chunks.md); k_chain with all three forms inlined goes from 56 to 392 B of scratch -- the chain keeps one chunk.
+template <int GMAX>
 __device__ __forceinline__ void wave_collapse_any(const GraphView &g, Txn &t, BulgeWork &w, unsigned lane, unsigned stampv, const int prof)
 {
+	static_assert(GMAX >= 1 && GMAX <= 3, "wave_collapse_g and gsel are written for one to three chunks");
 	const unsigned span = (w.c_dT > w.c_dS ? w.c_dT : w.c_dS) + g.k + 1u;
-	// (one chunk only: the three-chunk instantiation needs ~60 more registers, and inlined into k_commit it made EVERY transaction spill --
-	// 504 B of scratch, commit 40 -> 52 ms; longer branches keep the round-3 form)
-	if (prof && lane == 0 && span > 64u * GATHER_CHUNKS_MAX) w.nold++;
-	if (span > 64u * GATHER_CHUNKS_MAX) wave_collapse(g, t, w, lane, stampv, prof);
-	else if (span <= 64u) wave_collapse_g<1>(g, t, w, lane, stampv, prof);
-	else wave_collapse_g<GATHER_CHUNKS_MAX>(g, t, w, lane, stampv, prof);
+	const unsigned form = span <= 64u ? 0u : (GMAX >= 2 && span <= 128u) ? 1u : (GMAX >= 3 && span <= 192u) ? 2u : 3u;
+	const unsigned long long c0 = prof ? __builtin_readcyclecounter() : 0ull;
+	if (prof && lane == 0) {
+		if (form == 3u) w.nold++;
+		atomicAdd(&g_collapse_hist[form][w.c_dS == w.c_dT ? 0 : w.c_dS > w.c_dT ? 1 : 2][span < 255u ? span : 255u], 1u);
+	}
+	if (form == 0u) wave_collapse_g<1>(g, t, w, lane, stampv, prof);
+	else if (form == 1u) wave_collapse_g<(GMAX >= 2 ? 2 : 1)>(g, t, w, lane, stampv, prof);
+	else if (form == 2u) wave_collapse_g<(GMAX >= 3 ? 3 : 1)>(g, t, w, lane, stampv, prof);
+	else wave_collapse(g, t, w, lane, stampv, prof);
+	if (prof && lane == 0) { atomicAdd(&g_collapse_form[form][0], 1ull); atomicAdd(&g_collapse_form[form][1], __builtin_readcyclecounter() - c0); }
 }
 
 // ---- the caller side of BulgeWork::jscan: next member of [idJ, group end) that is still valid and whose endChar differs from I's
@@ -1227,6 +1249,8 @@ __device__ __forceinline__ bool park_load(const GraphView &g, Txn &t, BulgeWork 
 // The transaction proper (RemoveBulges for one id) on one wave; t, w, flag, absh and fast live in LDS.
 // solo: 0 = ordered round (the probe found bulges, the entry owns its claims), 1 = the id runs with nothing else in flight
 // (big-arena solo round, or the serial chain: stampv == BT_NONE, no reservation exists and none is checked).
+// GMAX: the most register chunks a gather-first collapse may take in this kernel (wave_collapse_any).
+template <int GMAX>
 __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWork &w, int &flag, ABShared &absh, uint8_t *fast, unsigned fast_bytes,
                                             unsigned wi, unsigned id, unsigned stampv, int solo, bool prepass, uint8_t *mine, unsigned arena_bytes, int prof,
                                             const unsigned *sepl = nullptr /* LDS copy of the separators' slots (SepBounds), or none */,
@@ -1349,7 +1373,7 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 			}
 #endif
 			if (w.lazy) {
-				wave_collapse_any(g, t, w, lane, stampv, prof);
+				wave_collapse_any<GMAX>(g, t, w, lane, stampv, prof);
 				PH_ADD(5);
 				if (t.err) break;
 				wave_publish_collapse(g, id, t.push_e, t.push_d, t.push_len, lane, sepl);
@@ -1407,7 +1431,7 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 				}
 			}
 			PH_ADD(4);
-			wave_collapse_any(g, t, w, lane, stampv, prof);
+			wave_collapse_any<GMAX>(g, t, w, lane, stampv, prof);
 			PH_ADD(5);
 			if (t.err) break;
 			if (lane == 0 && w.c_dT > w.c_dS) {
@@ -1484,6 +1508,9 @@ __device__ __forceinline__ void commit_body(const GraphView &g, Txn &t, BulgeWor
 // loops -- the longest transactions of the round, so they start first; workgroup nres + wi is window entry wi.  Both kinds ran side by
 // side before (two kernels on two streams), so one grid adds no interleaving.  What the body needs to know about a resumed transaction
 // after park_load is in BulgeWork::resumed / can_park (LDS), not in registers.
+#ifndef COMMIT_GATHER_CHUNKS
+#define COMMIT_GATHER_CHUNKS 3                 // spans up to 192 gather-first (wave_collapse_any): every span at D = 150, k = 25 (at most D + k = 175)
+#endif
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_commit(GraphView g_arg, unsigned nwin, uint8_t *arena, unsigned arena_bytes, int solo, const unsigned *claims, const uint8_t *live, int prof_every)
 {
 	// The view is read where the dispatch put it: the first kernel argument, at offset 0 of the kernel argument segment.  Through the
@@ -1544,7 +1571,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 			if (__builtin_amdgcn_readfirstlane((int)g.slice_busy[g.shadow_base + 64u + wi]) != 0) slice = g.shadow_base + wi; else own_slice = true;
 		}
 	}
-	commit_body(g, t, w, flag, absh, fast, (unsigned)sizeof fast, wi, id, stampv, solo, solo != 0, arena + (size_t)slice * arena_bytes, arena_bytes, prof, sepl, own_slice, resume);
+	commit_body<COMMIT_GATHER_CHUNKS>(g, t, w, flag, absh, fast, (unsigned)sizeof fast, wi, id, stampv, solo, solo != 0, arena + (size_t)slice * arena_bytes, arena_bytes, prof, sepl, own_slice, resume);
 }
 
 // finished markers of park_of (bit 31 | round tag) are only read in the round they were written in; the tag is 11 bits of a 12-bit round,
@@ -1595,7 +1622,7 @@ __global__ void __launch_bounds__(64) k_chain(GraphView g, uint8_t *arena, unsig
 		done++;
 		WSYNC();
 		if (lane == 0) g.big[id] = 0;                                   // the chain always runs in the big arena
-		commit_body(g, t, w, flag, absh, fast, (unsigned)sizeof fast, 0u, id, BT_NONE, 1, !known_live, arena, arena_bytes, prof);
+		commit_body<1>(g, t, w, flag, absh, fast, (unsigned)sizeof fast, 0u, id, BT_NONE, 1, !known_live, arena, arena_bytes, prof);      // (one chunk: wave_collapse_any)
 		WSYNC();
 		cur = (unsigned long long)id + 1;
 		__threadfence();
@@ -1731,6 +1758,7 @@ void sbl_commit_prof_reset()
 	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_txn_hist), z, 64 * 8));
 	HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_txn_max), z, 16));
 	{ std::vector<unsigned long long> zz(4096, 0); HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_round_max), zz.data(), 4096 * 8)); }
+	{ std::vector<unsigned> zz(4 * 3 * 256, 0); HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_collapse_hist), zz.data(), zz.size() * 4)); HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_collapse_form), z, 8 * 8)); }
 	{ std::vector<unsigned long long> zz(4096 * 2, 0); HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_round_few), zz.data(), 4096 * 2 * 8)); }
 	{ std::vector<unsigned long long> zz(4096 * 3, 0); for (unsigned r = 0; r < 4096; r++) zz[3 * r] = ~0ull; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_round_span), zz.data(), 4096 * 3 * 8)); }
 }
@@ -1773,7 +1801,21 @@ void sbl_commit_prof_report(unsigned ts_round)
 			fprintf(stderr, "[sbl] %u commit launches: owners' span %.1f us in total, slowest transactions %.1f us, their start offsets %.1f us\n", nl, span, slow, off);
 		}
 		fprintf(stderr, "[sbl] slowest transaction of every launch (kcycles/instances/old-form collapses/collapses):");
-		for (unsigned r = 0; r < 4096 && r < ts_round; r++) if (rm[r]) fprintf(stderr, " %llu/%llu/%llu/%llu", (rm[r] >> 24) / 1000, (rm[r] >> 16) & 255, (rm[r] >> 8) & 255, rm[r] & 255);
+		unsigned nlaunch = 0, nlaunch_old = 0;
+		for (unsigned r = 0; r < 4096 && r < ts_round; r++) if (rm[r]) { nlaunch++; nlaunch_old += ((rm[r] >> 8) & 255) != 0; fprintf(stderr, " %llu/%llu/%llu/%llu", (rm[r] >> 24) / 1000, (rm[r] >> 16) & 255, (rm[r] >> 8) & 255, rm[r] & 255); }
 		fprintf(stderr, "\n");
+		fprintf(stderr, "[sbl] launches whose slowest timed transaction made an old-form collapse: %u of %u\n", nlaunch_old, nlaunch);
+		// every collapse of the timed transactions, by the form it took
+		static unsigned hist[4][3][256];
+		unsigned long long cf[4][2];
+		HIP_TRY(hipMemcpyFromSymbol(hist, HIP_SYMBOL(g_collapse_hist), sizeof hist));
+		HIP_TRY(hipMemcpyFromSymbol(cf, HIP_SYMBOL(g_collapse_form), sizeof cf));
+		const char *fn[4] = {"gather-first, 1 chunk", "gather-first, 2 chunks", "gather-first, 3 chunks", "old form"};
+		for (int f = 0; f < 4; f++) {
+			unsigned long long by[3] = {0, 0, 0}, cls[4] = {0, 0, 0, 0};
+			for (int r = 0; r < 3; r++) for (int sp = 0; sp < 256; sp++) { by[r] += hist[f][r][sp]; cls[sp <= 64 ? 0 : sp <= 128 ? 1 : sp <= 192 ? 2 : 3] += hist[f][r][sp]; }
+			fprintf(stderr, "[sbl] collapses, %-22s %8llu (dS == dT %llu, dS > dT %llu, dS < dT %llu; span <= 64: %llu, <= 128: %llu, <= 192: %llu, longer: %llu), %.3f Mcycles, %.0f cycles each\n",
+			        fn[f], cf[f][0], by[0], by[1], by[2], cls[0], cls[1], cls[2], cls[3], cf[f][1] / 1e6, cf[f][0] ? (double)cf[f][1] / (double)cf[f][0] : 0.0);
+		}
 	}
 }
