@@ -201,6 +201,21 @@ sbl_status sbl_tiny_index(sbl_ctx *ctx, uint64_t nblocks, const uint64_t *block_
  * need_after: nid + 1 bytes each, what the kernel leaves in the two flag arrays (0 everywhere). */
 sbl_status sbl_test_touched_list(sbl_ctx *ctx, const uint8_t *touch, uint32_t nid, uint32_t *list, uint32_t *out, uint8_t *touch_after, uint8_t *need_after);
 
+/* TEST ENTRY POINT: the set-up of a simplification stage for (k, D) on the loaded state, one GPU -- enumeration, compact marks, instance
+ * lists, positional order of the ids, block index -- and nothing after it: the state is left as it is.
+ * out[0 .. 5]: ids, marks of strand 0, marks of strand 1, blocks of the block index (0: the stage keeps none), elements, 1 if the
+ * index records came from the marks pass.  The arrays stay on the device until the next stage or set-up; sbl_test_graph_fetch copies the
+ * first `bytes` bytes of one of them (SBL_ERR_BAD_ARG: more than it holds):
+ *   0 melem[strand]   1 mid[strand]   2 maux[strand]        (uint32 per mark of the strand, ascending element)
+ *   3 head[strand]    4 lsize[strand]                       (uint32 per id: first node of its list or 0xFFFFFFFF, instances)
+ *   5 nnext           6 nslot          9 nidst   10 nmark   (uint32 per node: next node of the list or 0xFFFFFFFF, element slot,
+ *                                                            (id << 1) | strand, index of its mark in the strand's compact arrays)
+ *   7 perm                                                  (uint32 per id: the ids in positional order)
+ *   8 block index                                           (4 x uint64 per block of 64 slots)
+ *   11 nodeof[strand]                                       (uint32 per element slot: its node or 0xFFFFFFFF) */
+sbl_status sbl_test_graph_build(sbl_ctx *ctx, uint32_t k, uint32_t D, uint32_t *out);
+sbl_status sbl_test_graph_fetch(sbl_ctx *ctx, int what, int strand, void *dst, uint64_t bytes);
+
 /* what the reference's main runs after GenerateSyntenyBlocks (src/sibelia.cpp:287-315) on the blocks of the last
  * sbl_generate_blocks: Postprocessor::GlueStripes (src/postprocessor.cpp:37-154; skipped when glue == 0) and the texts of
  * blocks_coords.txt (OutputGenerator::ListBlocksIndices, src/outputgenerator.cpp:227-233), genomes_permutations.txt

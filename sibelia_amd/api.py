@@ -33,7 +33,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
            "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_group_bootstrap", "sbl_group_bootstrap_times", "sbl_tiny_index",
-           "sbl_test_touched_list"]
+           "sbl_test_touched_list", "sbl_test_graph_build", "sbl_test_graph_fetch"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
 
@@ -209,6 +209,8 @@ def load_library():
         L.sbl_generate_blocks.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.sbl_synteny_stats.argtypes = [C.c_void_p, C.POINTER(SyntenyStats)]
         L.sbl_test_touched_list.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sbl_test_graph_build.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.sbl_test_graph_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64]
         L.sbl_tiny_index.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(TinyRange), C.c_uint32, C.c_int,
                                      C.POINTER(C.POINTER(TinyResult)), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sbl_postprocess.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
@@ -418,6 +420,40 @@ class BlockFinder:
                     "sbl_test_touched_list")
         assert out[0] <= nid, "k_touched_list counted %d of %d ids" % (out[0], nid)
         return lst[:int(out[0])].copy(), int(out[1]), ta, na
+
+    def test_graph_build(self, k: int, D: int) -> dict:
+        """TEST ENTRY POINT (sbl_test_graph_build / sbl_test_graph_fetch, include/sibelia_amd.h): the set-up of a simplification stage
+        for (k, D) on the loaded state, which stays as it is.  -> nid, E, nblk, index_from_marks; melem / mid / maux (per strand);
+        lists[strand][id] = the element slots of the id's instances in list order (lsize[strand][id] of them); nidst and nmark along
+        the lists; perm; bidx (nblk x 4 uint64)."""
+        out = np.zeros(8, dtype=np.uint32)
+        self._check(self.L.sbl_test_graph_build(self.h, k, D, out.ctypes.data), "sbl_test_graph_build")
+        nid, n, nblk, E = int(out[0]), (int(out[1]), int(out[2])), int(out[3]), int(out[4])
+
+        def fetch(what, strand, count, dtype=np.uint32):
+            a = np.empty(count, dtype=dtype)
+            self._check(self.L.sbl_test_graph_fetch(self.h, what, strand, a.ctypes.data, a.nbytes), "sbl_test_graph_fetch")
+            return a
+        r = {"nid": nid, "E": E, "nblk": nblk, "index_from_marks": bool(out[5]),
+             "melem": [fetch(0, t, n[t]) for t in (0, 1)], "mid": [fetch(1, t, n[t]) for t in (0, 1)], "maux": [fetch(2, t, n[t]) for t in (0, 1)],
+             "head": [fetch(3, t, nid) for t in (0, 1)], "lsize": [fetch(4, t, nid) for t in (0, 1)],
+             "perm": fetch(7, 0, nid), "bidx": fetch(8, 0, 4 * nblk, np.uint64).reshape(nblk, 4),
+             "nodeof": [fetch(11, t, E) for t in (0, 1)]}
+        ninst = n[0] + n[1]
+        nnext, nslot, nidst, nmark = (fetch(w, 0, ninst) for w in (5, 6, 9, 10))
+        r["nslot"], r["nidst"], r["nmark"] = nslot, nidst, nmark
+        lists, nodes = [[], []], [[], []]
+        for t in (0, 1):
+            for i in range(nid):
+                nd, chain = int(r["head"][t][i]), []
+                while nd != 0xFFFFFFFF:
+                    assert nd < ninst and len(chain) <= ninst, "instance list of id %d, strand %d leaves the nodes or loops" % (i, t)
+                    chain.append(nd)
+                    nd = int(nnext[nd])
+                nodes[t].append(np.array(chain, dtype=np.int64))
+                lists[t].append(nslot[chain] if chain else np.empty(0, dtype=np.uint32))
+        r["lists"], r["nodes"] = lists, nodes
+        return r
 
     def _names_array(self, what: str, names: Optional[Sequence[str]]):
         """`names` as the `const char *const *` of the C entry points, which read one name per loaded record (include/sibelia_amd.h);

@@ -41,10 +41,10 @@ struct SimplifyState : SimplifyHandles {
 	DevBuf ctr, need, big, touch, ck_touch, own, lock, rmax, wmax, win;
 	DevBuf arena, snap_arena, big_arena, claims, live, robuf, bidx, instbuf, walk_list, snap_list, snap_live, park_of, slice_busy, park_list;
 	DevBuf ck_ch, ck_op, ck_nx, ck_pv, ck_bif[2], ck_nodeof[2], ck_nslot, ck_nnext, ck_ndead, ck_head[2], ck_lsize[2];
-	DevBuf keys, skeys, selem, sorttmp, scantmp, perm, permin;
+	DevBuf keys, skeys, selem, sorttmp, scantmp, perm, permin, lbound;
 	DevBuf nmark, maux[2], iota, sel, tstamp;
 	DevBuf lin, elin, lmpos[2], lmid[2], cnt1k, off1k;      // linearised marks of the later snapshots
-	DevBuf flag, segidx, seg_head, seg_len, seg_succ_elem, succ[2], dist[2], newidx, ch_out, op_out;
+	DevBuf segmask, segcnt, segoff, seg_head, seg_len, seg_succ_elem, succ[2], dist[2], newidx, ch_out, op_out;
 };
 void sbl_simplify_free(sbl_ctx *c)
 {
@@ -127,6 +127,7 @@ struct DeviceBackend {
 	// block index of the original slots (GraphView::bidx): read by the probe and the reservation, maintained by the transactions
 	bool use_index;                                                   // off: every window is walked (StageSwitches::no_block_index; the one-launch path reads no index)
 	uint32_t idx_nblk = 0;
+	bool index_from_marks = false;                                    // the marks pass of the stage start wrote the index (StageAttempt::compact_marks)
 	// k_probe_idx's LDS by the instances an id has (set with rsv_waves): a handful -- 256-slot verdict table, 64 instances, 64 walked marks = 3.1 KB;
 	// dozens (many strains) -- 1024 slots, 256 instances, 192 marks = 12 KB.  An entry that does not fit goes to the walking probe.
 	unsigned pidx_vbits = 9, pidx_inst = 256, pidx_marks = 192;
@@ -225,23 +226,24 @@ struct DeviceBackend {
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		parked_known = 0;                                           // (reset_round_state clears the device side before the first round)
 	}
-	// segment ranking of the current list (the later snapshots and the copy-back): returns the list length, leaves flag / segidx / seg_head / dist[cur] filled
+	// segment ranking of the current list (the later snapshots and the copy-back): returns the list length, leaves segmask / segoff / seg_head / dist[cur] filled
 	unsigned long long rank_segments(unsigned ne, int *cur_out)
 	{
 		hipStream_t s = c->stream;
-		st->flag.ensure((size_t)ne * 4 + 16); st->segidx.ensure((size_t)ne * 4 + 16);
-		k_seg_flags<<<(ne + 255) / 256, 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->flag.as<unsigned>());
-		prim::exclusive_scan(s, st->scantmp, st->flag.as<unsigned>(), st->segidx.as<unsigned>(), 0u, (size_t)ne + 1, rocprim::plus<unsigned>());
+		const size_t nb = ((size_t)ne + 63) / 64;                   // head flags: one 64-bit mask and one count per 64 slots
+		st->segmask.ensure(nb * 8 + 16); st->segcnt.ensure(nb * 4 + 16); st->segoff.ensure(nb * 4 + 16);
+		k_seg_flags<<<nblocks(nblocks(ne, MARK_CHUNK), 4), 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->segmask.as<unsigned long long>(), st->segcnt.as<unsigned>());
+		prim::exclusive_scan(s, st->scantmp, st->segcnt.as<unsigned>(), st->segoff.as<unsigned>(), 0u, nb + 1, rocprim::plus<unsigned>());
 		unsigned nseg = 0;
-		HIP_TRY(hipMemcpyAsync(&nseg, st->segidx.as<unsigned>() + ne, 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(&nseg, st->segoff.as<unsigned>() + nb, 4, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		SBL_CHECK(nseg >= 1, SBL_ERR_INTERNAL, "segment ranking: empty list");
 		st->seg_head.ensure((size_t)nseg * 4); st->seg_len.ensure((size_t)nseg * 4); st->seg_succ_elem.ensure((size_t)nseg * 4);
 		for (int t = 0; t < 2; t++) { st->succ[t].ensure((size_t)nseg * 4); st->dist[t].ensure((size_t)nseg * 8); }
-		k_seg_tails<<<(ne + 255) / 256, 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->flag.as<unsigned>(), st->segidx.as<unsigned>(),
+		k_seg_tails<<<(ne + 255) / 256, 256, 0, s>>>(st->ch.as<uint8_t>(), st->nx.as<unsigned>(), ne, st->segmask.as<unsigned long long>(), st->segoff.as<unsigned>(),
 		                                            st->seg_head.as<unsigned>(), st->seg_len.as<unsigned>(), st->seg_succ_elem.as<unsigned>());
 		k_seg_finish<<<(nseg + 255) / 256, 256, 0, s>>>(nseg, st->seg_head.as<unsigned>(), st->seg_len.as<unsigned>(), st->seg_succ_elem.as<unsigned>(),
-		                                               st->flag.as<unsigned>(), st->segidx.as<unsigned>(), st->succ[0].as<unsigned>(), st->dist[0].as<unsigned long long>());
+		                                               st->segmask.as<unsigned long long>(), st->segoff.as<unsigned>(), st->succ[0].as<unsigned>(), st->dist[0].as<unsigned long long>());
 		int cur = 0;
 		for (unsigned span = 1; span < nseg; span <<= 1, cur ^= 1)
 			k_seg_jump<<<(nseg + 255) / 256, 256, 0, s>>>(nseg, st->succ[cur].as<unsigned>(), st->dist[cur].as<unsigned long long>(),
@@ -260,7 +262,7 @@ struct DeviceBackend {
 		int cur = 0;
 		const unsigned long long total = rank_segments(ne, &cur);
 		st->lin.ensure((size_t)ne * 4 + 16); st->elin.ensure((size_t)total * 4 + 16);
-		k_lin_positions<<<(ne + 255) / 256, 256, 0, s>>>(st->ch.as<uint8_t>(), ne, st->flag.as<unsigned>(), st->segidx.as<unsigned>(), st->seg_head.as<unsigned>(),
+		k_lin_positions<<<(ne + 255) / 256, 256, 0, s>>>(st->ch.as<uint8_t>(), ne, st->segmask.as<unsigned long long>(), st->segoff.as<unsigned>(), st->seg_head.as<unsigned>(),
 		                                                st->dist[cur].as<unsigned long long>(), total, st->lin.as<unsigned>(), st->elin.as<unsigned>());
 		const unsigned nchunks = (unsigned)((total + 1023) / 1024);
 		st->cnt1k.ensure((size_t)(nchunks + 1) * 4); st->off1k.ensure((size_t)(nchunks + 1) * 4);
@@ -692,6 +694,31 @@ struct StageAttempt {
 
 	bool many_instances() const { return ninst > 12 * (size_t)std::max<uint32_t>(1, be.nid_); }      // instances per id: a handful, or dozens (many strains)
 
+	// ---- ordered compaction of both strands' marks into (element, id) arrays (what sbl_compact_marks does strand by strand) in one
+	// counting pass, one scan, one host wait and one writing pass; the counting pass has the ballots of the block index in hand and
+	// writes its records on the way (DeviceBackend::index_from_marks: the stage start then needs no k_build_blkidx)
+	void compact_marks()
+	{
+		if (c->marks_compact_ready) return;                          // (the enumeration sorted its few member positions instead of scanning every element)
+		const unsigned nchunks = nblocks(E, MARK_CHUNK);
+		c->d_chunkcnt.ensure(((size_t)2 * nchunks + 1) * 4); c->d_chunkoff.ensure(((size_t)2 * nchunks + 1) * 4);
+		unsigned *cnt = c->d_chunkcnt.as<unsigned>(), *off = c->d_chunkoff.as<unsigned>();
+		unsigned long long *bidx = be.idx_nblk ? st->bidx.as<unsigned long long>() : nullptr;
+		k_count_marks2<<<nblocks(nchunks, 4), 256, 0, s>>>(c->d_bif[0].as<unsigned>(), c->d_bif[1].as<unsigned>(), c->d_ch.as<uint8_t>(), E, nchunks, cnt, bidx);
+		prim::exclusive_scan(s, c->d_scantmp, cnt, off, 0u, (size_t)2 * nchunks + 1, rocprim::plus<unsigned>());
+		unsigned tot[2] = {0, 0};                                    // marks of strand 0, marks of both
+		HIP_TRY(hipMemcpyAsync(&tot[0], off + nchunks, 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(&tot[1], off + 2 * (size_t)nchunks, 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		c->nmarks[0] = tot[0]; c->nmarks[1] = tot[1] - tot[0];
+		for (int t = 0; t < 2; t++) { c->d_melem[t].ensure((size_t)c->nmarks[t] * 4 + 16); c->d_mid[t].ensure((size_t)c->nmarks[t] * 4 + 16); }
+		if (tot[1])
+			k_write_marks2<<<nblocks(nchunks, 4), 256, 0, s>>>(c->d_bif[0].as<unsigned>(), c->d_bif[1].as<unsigned>(), E, nchunks, off, c->d_melem[0].as<unsigned>(), c->d_mid[0].as<unsigned>(),
+			                                                  c->d_melem[1].as<unsigned>(), c->d_mid[1].as<unsigned>());
+		HIP_TRY(hipGetLastError());
+		be.index_from_marks = bidx != nullptr;
+	}
+
 	// ---- E1, E2: enumeration into mark arrays with room for inserted elements, graph arrays, instance lists in the reference's initial order
 	void setup_graph(bool allow_dense, bool force_dense, bool may_switch)
 	{
@@ -715,15 +742,18 @@ struct StageAttempt {
 		k_init_links<<<nblocks(cap_e, 256), 256, 0, s>>>(st->nx.as<unsigned>(), st->pv.as<unsigned>(), st->nodeof[0].as<unsigned>(), st->nodeof[1].as<unsigned>(),
 		                                                st->ch.as<uint8_t>(), E, cap_e);
 
+		const size_t dense_max = force_dense ? DENSE_SWITCH_MAX_ELEMS : DENSE_MAX_ELEMS;
+		dense = allow_dense && E <= dense_max && be.nid_ > 0 && !sw.no_dense_path;
+		if (dense) be.use_index = false;                                   // (the one-launch path reads no index: nothing to maintain)
+		be.idx_nblk = be.use_index ? (uint32_t)((E + 63) / 64) : 0u;
+		if (be.idx_nblk) st->bidx.ensure((size_t)be.idx_nblk * BT_IDX_WORDS * 8);
+
 		// ---- E2
-		sbl_compact_marks(c, 0);
-		sbl_compact_marks(c, 1);
+		compact_marks();
 		n0 = c->nmarks[0];
 		const size_t n1 = c->nmarks[1];
 		ninst = n0 + n1;
 		c->stats.instances = ninst;
-		const size_t dense_max = force_dense ? DENSE_SWITCH_MAX_ELEMS : DENSE_MAX_ELEMS;
-		dense = allow_dense && E <= dense_max && be.nid_ > 0 && !sw.no_dense_path;
 		// (a job on several GPUs never switches: the decision is timed, and the ranks must stay in step)
 		be.may_try_dense = may_switch && !dense && !c->comm && E <= DENSE_SWITCH_MAX_ELEMS && !sw.no_dense_path && !sw.no_dense_switch;
 		be.max_iter_ = max_iter ? max_iter : 1u;
@@ -740,22 +770,24 @@ struct StageAttempt {
 			HIP_TRY(hipMemsetAsync(st->head[t].p, 0xFF, nidp * 4, s));
 			HIP_TRY(hipMemsetAsync(st->lsize[t].p, 0, nidp * 4, s));
 		}
-		const size_t nmax = std::max(n0, n1);
-		st->keys.ensure(nmax * 8 + 16); st->skeys.ensure(nmax * 8 + 16); st->selem.ensure(nmax * 4 + 16); st->iota.ensure(nmax * 4 + 16);
+		// one sort for both strands' lists: every mark at its rank in list order (k_instance_input), keys (strand << idbits) | id, stable
+		const unsigned idbits = prim::bits_of(be.nid_);
+		SBL_CHECK(idbits <= 31, SBL_ERR_TOO_LARGE, "too many bifurcation ids for the instance sort");
+		st->keys.ensure(ninst * 4 + 16); st->skeys.ensure(ninst * 4 + 16); st->selem.ensure(ninst * 4 + 16); st->iota.ensure(ninst * 4 + 16);
 		st->nmark.ensure(cap_n * 4);
-		for (int t = 0; t < 2; t++) st->maux[t].ensure(16);
-		const unsigned ordbits = prim::bits_of(2ull * E), idbits = prim::bits_of(be.nid_);      // sort keys of id_bits + ordbits bits (48 on the benchmark workload: 6 radix passes, not 8)
-		for (int t = 0; t < 2; t++) {
-			unsigned n = c->nmarks[t];
-			if (!n) continue;
-			k_instance_keys<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[t].as<unsigned>(), c->d_mid[t].as<unsigned>(), n, (unsigned)t,
-			                                               c->d_sepidx.as<unsigned>(), c->nchr, (unsigned)E, ordbits, st->keys.as<unsigned long long>(), st->iota.as<unsigned>());
-			prim::sort_pairs(s, st->sorttmp, st->keys.as<unsigned long long>(), st->skeys.as<unsigned long long>(), st->iota.as<unsigned>(), st->selem.as<unsigned>(), n, 0, std::min(64u, idbits + ordbits));
-			k_build_lists<<<nblocks(n, 256), 256, 0, s>>>(st->skeys.as<unsigned long long>(), st->selem.as<unsigned>(), c->d_melem[t].as<unsigned>(), n, t ? (unsigned)n0 : 0u, (unsigned)t, ordbits,
+		st->lbound.ensure(((size_t)c->nchr + 2) * 4);
+		for (int t = 0; t < 2; t++) st->maux[t].ensure((size_t)c->nmarks[t] * 4 + 16);
+		if (ninst) {
+			const unsigned n = (unsigned)ninst;
+			k_mark_bounds<<<nblocks((size_t)c->nchr + 1, 64), 64, 0, s>>>(c->d_melem[1].as<unsigned>(), (unsigned)n1, c->d_sepidx.as<unsigned>(), c->nchr, st->lbound.as<unsigned>());
+			k_instance_input<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[0].as<unsigned>(), c->d_mid[0].as<unsigned>(), c->d_melem[1].as<unsigned>(), c->d_mid[1].as<unsigned>(),
+			                                                (unsigned)n0, (unsigned)n1, c->d_sepidx.as<unsigned>(), c->nchr, st->lbound.as<unsigned>(), c->d_ch.as<uint8_t>(), k, idbits,
+			                                                st->keys.as<unsigned>(), st->iota.as<unsigned>(), st->maux[0].as<unsigned>(), st->maux[1].as<unsigned>());
+			prim::sort_pairs(s, st->sorttmp, st->keys.as<unsigned>(), st->skeys.as<unsigned>(), st->iota.as<unsigned>(), st->selem.as<unsigned>(), n, 0, idbits + 1);
+			k_build_lists<<<nblocks(n, 256), 256, 0, s>>>(st->skeys.as<unsigned>(), st->selem.as<unsigned>(), c->d_melem[0].as<unsigned>(), c->d_melem[1].as<unsigned>(), n, idbits,
 			                                             st->nslot.as<unsigned>(), st->nnext.as<unsigned>(), st->nidst.as<unsigned>(), st->ndead.as<uint8_t>(),
-			                                             st->head[t].as<unsigned>(), st->lsize[t].as<unsigned>(), st->nodeof[t].as<unsigned>(), st->nmark.as<unsigned>());
-			st->maux[t].ensure((size_t)n * 4 + 16);
-			k_mark_aux<<<nblocks(n, 256), 256, 0, s>>>(c->d_melem[t].as<unsigned>(), n, (unsigned)t, c->d_sepidx.as<unsigned>(), c->nchr, c->d_ch.as<uint8_t>(), k, st->maux[t].as<unsigned>());
+			                                             st->head[0].as<unsigned>(), st->head[1].as<unsigned>(), st->lsize[0].as<unsigned>(), st->lsize[1].as<unsigned>(),
+			                                             st->nodeof[0].as<unsigned>(), st->nodeof[1].as<unsigned>(), st->nmark.as<unsigned>());
 		}
 		HIP_TRY(hipGetLastError());
 		// positional order of the ids for the snapshot kernel
@@ -875,9 +907,6 @@ struct StageAttempt {
 		be.ev_phase = c->stage_seq++;
 		be.prof = sw.phases;
 		if (be.prof) sbl_commit_prof_reset();
-		if (dense) be.use_index = false;                                   // (the one-launch path reads no index: nothing to maintain)
-		be.idx_nblk = be.use_index ? (uint32_t)((E + 63) / 64) : 0u;
-		if (be.idx_nblk) st->bidx.ensure((size_t)be.idx_nblk * BT_IDX_WORDS * 8);
 		be.bind();
 		be.g.k = k; be.g.D = D;
 	}
@@ -947,13 +976,14 @@ struct StageAttempt {
 		int cur = 0;
 		total = be.rank_segments(ne, &cur);                             // segment 0 starts with element 0 (the first '$'): the new total length
 		const size_t Enew = (size_t)total, Epad = (Enew + 31) / 32 * 32 + 64;
-		st->newidx.ensure((size_t)ne * 4 + 16);
+		if (sw.check_dictionary) st->newidx.ensure((size_t)ne * 4 + 16);      // (old slot -> new slot of EVERY element: only k_dict_check reads it)
 		st->ch_out.ensure(Epad); st->op_out.ensure(Enew * 4 + 16);
-		k_scatter_linear<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), st->op.as<unsigned>(), ne, st->flag.as<unsigned>(), st->segidx.as<unsigned>(),
+		k_scatter_linear<<<nblocks(ne, 256), 256, 0, s>>>(st->ch.as<uint8_t>(), st->op.as<unsigned>(), ne, st->segmask.as<unsigned long long>(), st->segoff.as<unsigned>(),
 		                                                 st->seg_head.as<unsigned>(), st->dist[cur].as<unsigned long long>(), total,
-		                                                 st->ch_out.as<uint8_t>(), st->op_out.as<unsigned>(), st->newidx.as<unsigned>());
+		                                                 st->ch_out.as<uint8_t>(), st->op_out.as<unsigned>(), sw.check_dictionary ? st->newidx.as<unsigned>() : nullptr);
 		k_fill_bytes<<<nblocks(Epad - Enew, 256), 256, 0, s>>>(st->ch_out.as<uint8_t>(), (uint8_t)'$', Enew, Epad);
-		k_remap_seps<<<nblocks(c->nchr + 1, 64), 64, 0, s>>>(st->newidx.as<unsigned>(), c->d_sepidx.as<unsigned>(), c->nchr + 1);
+		k_remap_seps<<<nblocks(c->nchr + 1, 64), 64, 0, s>>>(st->segmask.as<unsigned long long>(), st->segoff.as<unsigned>(), st->seg_head.as<unsigned>(),
+		                                                    st->dist[cur].as<unsigned long long>(), total, c->d_sepidx.as<unsigned>(), c->nchr + 1);
 		k_sep_positions<<<nblocks(c->nchr, 64), 64, 0, s>>>(c->d_sepidx.as<unsigned>(), c->nchr, st->op_out.as<unsigned>());
 		HIP_TRY(hipGetLastError());
 	}
@@ -1032,7 +1062,7 @@ static int simplify_run_impl(sbl_ctx *c, const StageSwitches &sw, uint32_t k, ui
 	be.g.test_flags = sw.test_flags;
 	be.g.tstamp = nullptr; be.g.tslot = 0;
 	be.g.sep = c->d_sepidx.as<unsigned>(); be.g.nsep = c->nchr + 1; be.g.norig = (uint32_t)a.E;
-	be.index_build();
+	if (!be.index_from_marks) be.index_build();                         // (marks that came ready-made from the enumeration: no marks pass wrote it)
 	if (!a.dense) be.stamps_init();
 	HIP_TRY(hipEventRecord(c->ev[3], s));
 
@@ -1114,6 +1144,57 @@ extern "C" sbl_status sbl_test_touched_list(sbl_ctx *c, const uint8_t *touch, ui
 		HIP_TRY(hipMemcpyAsync(list, d_list.p, nidp * 4, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpyAsync(touch_after, d_touch.p, nidp, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpyAsync(need_after, d_need.p, nidp, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	});
+}
+
+// TEST ENTRY POINT (include/sibelia_amd.h): the set-up of a stage for (k, D) on the loaded state, as simplify_run_impl runs it up to the
+// first snapshot -- enumeration, marks, instance lists, positional order, block index -- and nothing after it: the state stays as it is.
+// The arrays stay on the device for sbl_test_graph_fetch.
+extern "C" sbl_status sbl_test_graph_build(sbl_ctx *c, uint32_t k, uint32_t D, uint32_t *out)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(out, SBL_ERR_BAD_ARG, "null pointer");
+		SBL_CHECK(!c->comm, SBL_ERR_BAD_ARG, "sbl_test_graph_build: one GPU only");
+		if (!c->simp) {
+			c->simp = new SimplifyState();
+			HIP_TRY(hipHostMalloc((void **)&c->simp->h_ctr, (CTR_COUNT + 16) * 4, hipHostMallocMapped | hipHostMallocCoherent));
+			memset(c->simp->h_ctr, 0, (CTR_COUNT + 16) * 4);
+			if (hipHostGetDevicePointer((void **)&c->simp->d_hctr, c->simp->h_ctr, 0) != hipSuccess) { (void)hipGetLastError(); c->simp->d_hctr = nullptr; }
+		}
+		const StageSwitches sw = read_switches();
+		StageAttempt a(c, sw, k, D, 1);
+		a.setup_graph(false, false, false);
+		a.size_buffers(true);
+		a.be.g.norig = (uint32_t)a.E;
+		if (!a.be.index_from_marks) a.be.index_build();
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		out[0] = a.be.nid_; out[1] = c->nmarks[0]; out[2] = c->nmarks[1]; out[3] = a.be.idx_nblk; out[4] = (uint32_t)a.E; out[5] = a.be.index_from_marks ? 1u : 0u;
+	});
+}
+extern "C" sbl_status sbl_test_graph_fetch(sbl_ctx *c, int what, int strand, void *dst, uint64_t bytes)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(c->simp && dst && (strand == 0 || strand == 1), SBL_ERR_BAD_ARG, "sbl_test_graph_fetch: no stage set-up, null pointer or bad strand");
+		SimplifyState *st = c->simp;
+		const DevBuf *b = nullptr;
+		switch (what) {
+			case 0: b = &c->d_melem[strand]; break;
+			case 1: b = &c->d_mid[strand]; break;
+			case 2: b = &st->maux[strand]; break;
+			case 3: b = &st->head[strand]; break;
+			case 4: b = &st->lsize[strand]; break;
+			case 5: b = &st->nnext; break;
+			case 6: b = &st->nslot; break;
+			case 7: b = &st->perm; break;
+			case 8: b = &st->bidx; break;
+			case 9: b = &st->nidst; break;
+			case 10: b = &st->nmark; break;
+			case 11: b = &st->nodeof[strand]; break;
+			default: SBL_CHECK(false, SBL_ERR_BAD_ARG, "sbl_test_graph_fetch: unknown array");
+		}
+		SBL_CHECK(bytes <= b->cap, SBL_ERR_BAD_ARG, "sbl_test_graph_fetch: more bytes than the array holds");
+		if (bytes) HIP_TRY(hipMemcpyAsync(dst, b->p, bytes, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 	});
 }

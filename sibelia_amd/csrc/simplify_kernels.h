@@ -23,20 +23,27 @@ void sbl_rounds_stats_report();                                      // test_fla
 
 __global__ void __launch_bounds__(256) k_init_links(unsigned *__restrict__ nx, unsigned *__restrict__ pv, unsigned *__restrict__ nodeof0,
                                                     unsigned *__restrict__ nodeof1, uint8_t *__restrict__ ch, size_t E, size_t cap);
-__global__ void __launch_bounds__(256) k_instance_keys(const unsigned *__restrict__ elem, const unsigned *__restrict__ id, unsigned n, unsigned strand,
-                                                       const unsigned *__restrict__ sepidx, unsigned nchr, unsigned E, unsigned ordbits,
-                                                       unsigned long long *__restrict__ keys, unsigned *__restrict__ midx);
-__global__ void __launch_bounds__(256) k_build_lists(const unsigned long long *__restrict__ skeys, const unsigned *__restrict__ smidx, const unsigned *__restrict__ melem, unsigned n,
-                                                     unsigned node_base, unsigned strand, unsigned ordbits, unsigned *__restrict__ nslot, unsigned *__restrict__ nnext, unsigned *__restrict__ nidst,
-                                                     uint8_t *__restrict__ ndead, unsigned *__restrict__ head, unsigned *__restrict__ lsize,
-                                                     unsigned *__restrict__ nodeof, unsigned *__restrict__ nmark);
+#define MARK_CHUNK 256u                      // slots a wave of k_count_marks2 / k_write_marks2 takes: four blocks of the block index
+__global__ void __launch_bounds__(256) k_count_marks2(const unsigned *__restrict__ bif0, const unsigned *__restrict__ bif1, const uint8_t *__restrict__ ch, size_t E,
+                                                      unsigned nchunks, unsigned *__restrict__ cnt, unsigned long long *__restrict__ bidx);
+__global__ void __launch_bounds__(256) k_write_marks2(const unsigned *__restrict__ bif0, const unsigned *__restrict__ bif1, size_t E, unsigned nchunks,
+                                                      const unsigned *__restrict__ off, unsigned *__restrict__ melem0, unsigned *__restrict__ mid0,
+                                                      unsigned *__restrict__ melem1, unsigned *__restrict__ mid1);
+__global__ void __launch_bounds__(64) k_mark_bounds(const unsigned *__restrict__ melem1, unsigned n1, const unsigned *__restrict__ sepidx, unsigned nchr, unsigned *__restrict__ lb);
+__global__ void __launch_bounds__(256) k_instance_input(const unsigned *__restrict__ melem0, const unsigned *__restrict__ mid0, const unsigned *__restrict__ melem1,
+                                                        const unsigned *__restrict__ mid1, unsigned n0, unsigned n1, const unsigned *__restrict__ sepidx, unsigned nchr,
+                                                        const unsigned *__restrict__ lb, const uint8_t *__restrict__ ch, unsigned k, unsigned idbits,
+                                                        unsigned *__restrict__ keys, unsigned *__restrict__ midx, unsigned *__restrict__ aux0, unsigned *__restrict__ aux1);
+__global__ void __launch_bounds__(256) k_build_lists(const unsigned *__restrict__ skeys, const unsigned *__restrict__ smidx, const unsigned *__restrict__ melem0,
+                                                     const unsigned *__restrict__ melem1, unsigned n, unsigned idbits, unsigned *__restrict__ nslot, unsigned *__restrict__ nnext,
+                                                     unsigned *__restrict__ nidst, uint8_t *__restrict__ ndead, unsigned *__restrict__ head0, unsigned *__restrict__ head1,
+                                                     unsigned *__restrict__ lsize0, unsigned *__restrict__ lsize1, unsigned *__restrict__ nodeof0, unsigned *__restrict__ nodeof1,
+                                                     unsigned *__restrict__ nmark);
 __global__ void __launch_bounds__(256) k_id_position_keys(const unsigned *__restrict__ head0, const unsigned *__restrict__ head1, const unsigned *__restrict__ nslot,
                                                           unsigned nid, unsigned long long *__restrict__ keys, unsigned *__restrict__ ids);
 __global__ void __launch_bounds__(256) k_max_instances(const unsigned *__restrict__ l0, const unsigned *__restrict__ l1, unsigned nid, unsigned *__restrict__ out);
-__global__ void __launch_bounds__(256) k_mark_aux(const unsigned *__restrict__ melem, unsigned n, unsigned strand, const unsigned *__restrict__ sepidx, unsigned nchr,
-                                                  const uint8_t *__restrict__ ch, unsigned k, unsigned *__restrict__ aux);
 __global__ void __launch_bounds__(64) k_snapshot_first(GraphView g, MarkStream ms, const unsigned *__restrict__ nmark, const unsigned *__restrict__ perm, unsigned plo, unsigned phi);
-__global__ void __launch_bounds__(256) k_lin_positions(const uint8_t *__restrict__ ch, unsigned ne, const unsigned *__restrict__ flag, const unsigned *__restrict__ segidx,
+__global__ void __launch_bounds__(256) k_lin_positions(const uint8_t *__restrict__ ch, unsigned ne, const unsigned long long *__restrict__ segmask, const unsigned *__restrict__ segoff,
                                                        const unsigned *__restrict__ seg_head, const unsigned long long *__restrict__ dist, unsigned long long total,
                                                        unsigned *__restrict__ lin, unsigned *__restrict__ elin);
 __global__ void __launch_bounds__(256) k_count_marks_lin(const unsigned *__restrict__ bif, const unsigned *__restrict__ elin, size_t n, unsigned *__restrict__ chunkcnt);
@@ -69,21 +76,23 @@ __global__ void __launch_bounds__(64) k_dense_stage(GraphView g, uint8_t *arena,
 __global__ void __launch_bounds__(256) k_count_touched(const uint8_t *__restrict__ touch, unsigned nid, unsigned *__restrict__ out);
 __global__ void __launch_bounds__(256) k_touched_list(uint8_t *__restrict__ touch, uint8_t *__restrict__ need, unsigned nid, unsigned *__restrict__ list, unsigned *__restrict__ count,
                                                       unsigned *__restrict__ wcount);
-__global__ void __launch_bounds__(256) k_seg_flags(const uint8_t *__restrict__ ch, const unsigned *__restrict__ nx, unsigned ne, unsigned *__restrict__ flag);
+__global__ void __launch_bounds__(256) k_seg_flags(const uint8_t *__restrict__ ch, const unsigned *__restrict__ nx, unsigned ne, unsigned long long *__restrict__ segmask,
+                                                   unsigned *__restrict__ segcnt);
 __global__ void __launch_bounds__(256) k_seg_tails(const uint8_t *__restrict__ ch, const unsigned *__restrict__ nx, unsigned ne,
-                                                   const unsigned *__restrict__ flag, const unsigned *__restrict__ segidx /* exclusive scan */,
+                                                   const unsigned long long *__restrict__ segmask, const unsigned *__restrict__ segoff /* exclusive scan */,
                                                    unsigned *__restrict__ seg_head, unsigned *__restrict__ seg_len, unsigned *__restrict__ seg_succ_elem);
 __global__ void __launch_bounds__(256) k_seg_finish(unsigned nseg, const unsigned *__restrict__ seg_head, unsigned *__restrict__ seg_len,
-                                                    const unsigned *__restrict__ seg_succ_elem, const unsigned *__restrict__ flag,
-                                                    const unsigned *__restrict__ segidx, unsigned *__restrict__ succ, unsigned long long *__restrict__ dist);
+                                                    const unsigned *__restrict__ seg_succ_elem, const unsigned long long *__restrict__ segmask,
+                                                    const unsigned *__restrict__ segoff, unsigned *__restrict__ succ, unsigned long long *__restrict__ dist);
 __global__ void __launch_bounds__(256) k_seg_jump(unsigned nseg, const unsigned *__restrict__ succ_in, const unsigned long long *__restrict__ dist_in,
                                                   unsigned *__restrict__ succ_out, unsigned long long *__restrict__ dist_out);
 __global__ void __launch_bounds__(256) k_scatter_linear(const uint8_t *__restrict__ ch, const unsigned *__restrict__ op, unsigned ne,
-                                                        const unsigned *__restrict__ flag, const unsigned *__restrict__ segidx,
+                                                        const unsigned long long *__restrict__ segmask, const unsigned *__restrict__ segoff,
                                                         const unsigned *__restrict__ seg_head, const unsigned long long *__restrict__ dist,
                                                         unsigned long long total, uint8_t *__restrict__ ch_out, unsigned *__restrict__ op_out,
                                                         unsigned *__restrict__ newidx);
-__global__ void k_remap_seps(const unsigned *__restrict__ newidx, unsigned *__restrict__ sepidx, unsigned n);
+__global__ void k_remap_seps(const unsigned long long *__restrict__ segmask, const unsigned *__restrict__ segoff, const unsigned *__restrict__ seg_head,
+                             const unsigned long long *__restrict__ dist, unsigned long long total, unsigned *__restrict__ sepidx, unsigned n);
 __global__ void k_sep_positions(const unsigned *__restrict__ sepidx, unsigned nchr, unsigned *__restrict__ op);
 __global__ void __launch_bounds__(256) k_dict_check(const uint8_t *__restrict__ ch, unsigned ne, const unsigned *__restrict__ newidx, const uint8_t *__restrict__ ch_out, unsigned long long total,
                                                     const unsigned *__restrict__ bif0, const unsigned *__restrict__ bif1, const unsigned long long *__restrict__ dict, unsigned nd, unsigned k,

@@ -10,24 +10,8 @@
 // At the start of iteration 1 the list is still position-linear (element index = position) and the compacted marks of the
 // enumeration (melem / mid per strand, ascending element) ARE every window: instance j of strand 0 sees the marks j+1, j+2, ...
 // while melem - pos < min(D, distance to the chromosome end), strand 1 the marks j-1, j-2, ... -- a dozen consecutive 8-byte
-// records instead of 150 x (link + character + mark) per instance.  k_mark_aux adds, per mark, the endChar of the instance
-// (bulgeremoval.cpp:340-347) and its distance to the end of the chromosome in walk direction.
-__global__ void __launch_bounds__(256) k_mark_aux(const unsigned *__restrict__ melem, unsigned n, unsigned strand, const unsigned *__restrict__ sepidx, unsigned nchr,
-                                                  const uint8_t *__restrict__ ch, unsigned k, unsigned *__restrict__ aux)
-{
-	unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const unsigned e = melem[i], c = chr_of(sepidx, nchr, e);
-	const unsigned dist = strand == 0 ? sepidx[c + 1] - e : e - sepidx[c];      // valid steps from the instance (inclusive) to the separator
-	unsigned bit = 0;
-	if (dist >= k + 1) {                                                         // ProperKMer(k + 1): endChar = character at step k, oriented
-		const uint8_t x = strand == 0 ? ch[e + k] : ch[e - k];
-		const unsigned code = x == 'A' ? 0u : x == 'C' ? 1u : x == 'G' ? 2u : 3u;
-		bit = 1u << (strand == 0 ? code : 3u - code);
-	}
-	aux[i] = (bit << 24) | (dist < 0xFFFFFFu ? dist : 0xFFFFFFu);
-}
-
+// records instead of 150 x (link + character + mark) per instance.  k_instance_input (graphbuild.hip) adds, per mark, the endChar of
+// the instance (bulgeremoval.cpp:340-347) and its distance to the end of the chromosome in walk direction.
 
 // AnyBulges verdict (see wave_verdict) of every id on the pristine graph; need[id] = 2 (known live) / 0 (clean) / 1 (the LDS
 // table could not decide: the probe of its round does).  Four instances per step, 16 lanes each.
@@ -105,17 +89,7 @@ __global__ void __launch_bounds__(64) k_snapshot_first(GraphView g, MarkStream m
 // the copy-back (k_seg_*) gives every live element its position in the list; elin[] is the inverse map.  The marks are then
 // compacted in list order (mpos = list position, mid = id; nmark[node] = index of the instance's mark) and the verdict
 // kernel is the stream again -- with the instance lists followed through their links, since they are no longer runs of nodes.
-__global__ void __launch_bounds__(256) k_lin_positions(const uint8_t *__restrict__ ch, unsigned ne, const unsigned *__restrict__ flag, const unsigned *__restrict__ segidx,
-                                                       const unsigned *__restrict__ seg_head, const unsigned long long *__restrict__ dist, unsigned long long total,
-                                                       unsigned *__restrict__ lin, unsigned *__restrict__ elin)
-{
-	unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-	if (e >= ne) return;
-	if (ch[e] == BT_DEAD_CHAR) { lin[e] = SBL_NONE; return; }
-	unsigned seg = segidx[e] + flag[e] - 1;
-	unsigned pos = (unsigned)(total - dist[seg] + (e - seg_head[seg]));
-	lin[e] = pos; elin[pos] = e;
-}
+// (k_lin_positions stands with the ranking it reads: graphbuild.hip)
 __global__ void __launch_bounds__(256) k_count_marks_lin(const unsigned *__restrict__ bif, const unsigned *__restrict__ elin, size_t n, unsigned *__restrict__ chunkcnt)
 {
 	__shared__ unsigned cnt;
@@ -146,7 +120,7 @@ __global__ void __launch_bounds__(256) k_write_marks_lin(const unsigned *__restr
 #pragma unroll
 	for (int i = 0; i < 4; i++) if (ids[i] != SBL_NONE) { out_pos[off] = (unsigned)(base + i); out_id[off] = ids[i]; nmark[nodeof[el[i]]] = off; off++; }
 }
-// k_mark_aux in list coordinates: chromosome ends = list positions of the separators, characters through elin[]
+// the aux word of k_instance_input (graphbuild.hip) in list coordinates: chromosome ends = list positions of the separators, characters through elin[]
 __global__ void __launch_bounds__(256) k_mark_aux_lin(const unsigned *__restrict__ mpos, unsigned n, unsigned strand, const unsigned *__restrict__ sepelem, unsigned nchr,
                                                       const unsigned *__restrict__ lin, const unsigned *__restrict__ elin, const uint8_t *__restrict__ ch, unsigned k, unsigned *__restrict__ aux)
 {
