@@ -594,6 +594,28 @@ sbl_status sbl_group_bootstrap(sbl_ctx *ctx, const uint8_t *want, const uint32_t
                                const uint64_t **counts, uint64_t *nsites, uint64_t *nclean);
 sbl_status sbl_group_bootstrap_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
 
+/* Partial groups: the soft core (csrc/sbl_groups.h, group_concat.hip, group_boot.hip), defined by this project.
+ * sbl_group_set_partial: with on = 1 the class rule of every later sbl_group_concat and sbl_group_bootstrap call of the context is "a
+ * used group holds every class AT MOST once": a group with fewer instances than classes is used, a group of one row included; a group
+ * that holds a class twice, a class not below nclass and a group with more instances than classes are refused with the messages of the
+ * strict rule.  A class that no used group holds is legal.  With 0 (the default) every entry point behaves as without this setting, byte
+ * for byte.  Anything but 0 / 1 is SBL_ERR_BAD_ARG and the value stays as it was.  sbl_group_mask, sbl_group_variants and
+ * sbl_group_distances take no class rule and do not look at the setting; sbl_group_set_masked combines with it freely.
+ * With P the classes a used group holds:
+ *   ALL        the row of a class outside P is L bytes of '-'.
+ *   CLEAN      a column is clean if every row of P holds one of A C G T.
+ *   VARIABLE   a column is kept (a SITE) if it is clean and the rows of P are not all equal; a group of one row has none.  In the text
+ *              of SBL_CONCAT_VARIABLE the byte of a class outside P is '-'.  `before`, parts and sites are as without the setting.
+ *   COUNTS     M[r][f][g] of sbl_group_bootstrap counts the draws (slab 0: the sites) whose site's group holds both f and g and in
+ *              which the two differ.  *nclean is the sum of the clean columns of the used groups.  Draw rule, batches and limits stay.
+ * sbl_group_bootstrap_pairs: clean[nclass][nclass] of the LAST successful sbl_group_bootstrap call, row-major, owned by the ctx until
+ * the next one: clean[f][g] is the clean columns of the used groups that hold both f and g (clean[f][f]: that hold f), the denominator
+ * of the pair's proportion of differing sites; symmetric.  After a call with the setting off every cell equals that call's *nclean.
+ * SBL_ERR_BAD_ARG before any sbl_group_bootstrap call has succeeded, and for clean == NULL. */
+sbl_status sbl_group_set_partial(sbl_ctx *ctx, uint32_t on);      /* 0 (default) | 1 */
+sbl_status sbl_group_get_partial(const sbl_ctx *ctx, uint32_t *on);
+sbl_status sbl_group_bootstrap_pairs(sbl_ctx *ctx, const uint64_t **clean /* nclass * nclass, row-major, owned by ctx */);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

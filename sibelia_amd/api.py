@@ -33,6 +33,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
            "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_group_bootstrap", "sbl_group_bootstrap_times", "sbl_tiny_index",
+           "sbl_group_set_partial", "sbl_group_get_partial", "sbl_group_bootstrap_pairs",
            "sbl_test_touched_list", "sbl_test_graph_build", "sbl_test_graph_fetch"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -253,6 +254,9 @@ def load_library():
         L.sbl_group_mask.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(MaskInterval)), C.POINTER(C.c_uint64)]
         L.sbl_group_mask_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_group_set_masked.argtypes = [C.c_void_p, C.c_uint32]
+        L.sbl_group_set_partial.argtypes = [C.c_void_p, C.c_uint32]
+        L.sbl_group_get_partial.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.sbl_group_bootstrap_pairs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64))]
         L.sbl_group_get_masked.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -668,11 +672,35 @@ class BlockFinder:
         self._check(self.L.sbl_group_bootstrap(self.h, mask, arr, int(nclass), int(replicates), int(seed), int(draws), C.byref(out), C.byref(nsites), C.byref(nclean)),
                     "sbl_group_bootstrap")
         n, b = int(nclass), int(replicates) + 1
+        self._boot_nclass = n
         return _view(C.cast(out, C.c_void_p).value, b * n * n, np.dtype("<u8")).reshape(b, n, n), nsites.value, nclean.value
 
     def group_bootstrap_times(self) -> Tuple[float, float]:
         """(kernel ms of all phases, device-to-host copy ms of the counts) of the last group_bootstrap call, from event pairs."""
         return self._times("sbl_group_bootstrap_times")
+
+    def group_bootstrap_pairs(self) -> np.ndarray:
+        """The clean columns per pair of classes of the last group_bootstrap call (include/sibelia_amd.h): [f, g] the
+        columns of the used groups that hold both f and g in which every present row holds one of A C G T; without set_partial every
+        cell is that call's K.  -> uint64 array of shape (nclass, nclass), a copy.  Refused before any group_bootstrap call."""
+        out = C.POINTER(C.c_uint64)()
+        self._check(self.L.sbl_group_bootstrap_pairs(self.h, C.byref(out)), "sbl_group_bootstrap_pairs")
+        n = self._boot_nclass
+        return _view(C.cast(out, C.c_void_p).value, n * n, np.dtype("<u8")).reshape(n, n)
+
+    def set_partial(self, on) -> None:
+        """True: every later group_concat / group_bootstrap call of this finder uses the groups that hold every class AT MOST once (the
+        soft core): an absent class's row is gaps, columns are judged on the present rows, pairs are counted where both are present.
+        False (the default): as without the setting.  Anything but 0 / 1 is refused and the value stays as it was."""
+        if not 0 <= int(on) <= 2 ** 32 - 1:
+            raise SibeliaError("sbl_group_set_partial: bad argument (the partial groups setting is 0 or 1)")
+        self._check(self.L.sbl_group_set_partial(self.h, int(on)), "sbl_group_set_partial")
+
+    @property
+    def partial(self) -> int:
+        v = C.c_uint32()
+        self._check(self.L.sbl_group_get_partial(self.h, C.byref(v)), "sbl_group_get_partial")
+        return v.value
 
     def group_mask(self, window: int, max_diff: int, want: Optional[Sequence[bool]] = None):
         """The SNP-density mask of the groups of the LAST align_groups / align_block_groups call (csrc/group_mask.hip; defined in

@@ -23,6 +23,8 @@
 //             used when there is one class), tables up; event pairs around the kernels and around the copy back; the text comes back
 //             into a pinned buffer of its own that grows on demand (h_gc_text), sites into gc_sites; the parts of mode VARIABLE are
 //             counted on the host from the sites.
+//   partial   under sbl_group_set_partial a used group holds every class at most once: k_site_flags<.., true> walks the
+//             rows the group has, and k_concat_text<.., true> writes '-' for a class the group does not hold (roff == ~0).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -53,7 +55,9 @@ __global__ __launch_bounds__(GC_THREADS) void k_site_fill(const GmGroup *__restr
 // coff: the nclass + 1 text offsets of the class rows; row f is its header -- hdr[coff[f] - f S ...), S = st_text_len(C, width) -- and the
 // S bytes of its C kept columns in lines.  roff[ug * nclass + f]: where the row of class f of used group ug starts in `text`.
 // ALL: first[ug] (nused + 1): the first column of the used group in the concatenation.  VARIABLE: picks[C].
-template <bool VARIABLE>
+// PARTIAL (sbl_group_set_partial): roff == ~0 says that the used group does not hold the class; its bytes are '-'
+constexpr u64 GC_GAPS = 0x2D2D2D2D2D2D2D2Dull;         // eight '-'
+template <bool VARIABLE, bool PARTIAL = false>
 __global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__restrict__ text, u64 text_bytes, const u64 *__restrict__ roff,
                                                             const u64 *__restrict__ first, u64 nused, const GcPick *__restrict__ picks,
                                                             const u64 *__restrict__ coff, unsigned nclass, const char *__restrict__ hdr,
@@ -94,7 +98,8 @@ __global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__res
 			fast = c + (nl < 16 ? 15 : 16) <= first[g + 1];                   // all of them in one group's row
 		}
 		if (fast) {
-			w = gv_load16(text, text_bytes, roff[g * nclass + f0 + fi] + (c - first[g]));
+			const u64 r = roff[g * nclass + f0 + fi];
+			w = PARTIAL && r == ~0ull ? B16{GC_GAPS, GC_GAPS} : gv_load16(text, text_bytes, r + (c - first[g]));
 			if (nl < 16) w = insert_newline(w, nl);
 		}
 	}
@@ -109,8 +114,10 @@ __global__ __launch_bounds__(GC_THREADS) void k_concat_text(const uint8_t *__res
 			if (off < hlen) ch = (unsigned char)hdr[s_off[fi] - f * S + off];
 			else if (off + 1 == rlen || col == width) { ch = '\n'; col = 0; }
 			else {
-				if (VARIABLE) { const GcPick p = picks[c]; ch = text[roff[p.ug * nclass + f] + p.col]; }
-				else { while (c >= first[g + 1]) g++; ch = text[roff[g * nclass + f] + (c - first[g])]; }
+				u64 r, at;
+				if (VARIABLE) { const GcPick p = picks[c]; r = roff[p.ug * nclass + f]; at = p.col; }
+				else { while (c >= first[g + 1]) g++; r = roff[g * nclass + f]; at = c - first[g]; }
+				ch = PARTIAL && r == ~0ull ? '-' : text[r + at];
 				c++; col++;
 			}
 			if (j < 8) w.lo |= (u64)ch << (8 * j); else w.hi |= (u64)ch << (8 * (j - 8));
@@ -135,7 +142,7 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 		SBL_CHECK(width >= 1, SBL_ERR_BAD_ARG, "the width of a line must be at least 1");
 		SBL_CHECK(headers && header_first, SBL_ERR_BAD_ARG, "null headers");
 		for (uint32_t f = 0; f < nclass; f++) SBL_CHECK(header_first[f] <= header_first[f + 1], SBL_ERR_BAD_ARG, "descending header offsets");
-		const bool variable = mode == SBL_CONCAT_VARIABLE;
+		const bool variable = mode == SBL_CONCAT_VARIABLE, partial = c->gp_partial != 0;
 		hipStream_t s = c->stream;
 		c->gc_parts.clear(); c->gc_sites.clear();
 		c->gc_times = SblTimes{};
@@ -151,8 +158,8 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 			// ---- the kept columns, ascending, and their number
 			c->d_gc_flag.ensure((size_t)P); c->d_gc_x.ensure((size_t)P * 8); c->d_gm_count.ensure(16);
 			HIP_TRY(hipEventRecord(c->ev[0], s));
-			k_site_flags<false><<<gm_blocks(P / 16), GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gm_used.as<GmUsed>(), c->d_gm_cbase.as<u64>(), ng, P, nclass,
-			                                                      c->d_gc_flag.as<uint4>());
+			(partial ? k_site_flags<false, true> : k_site_flags<false, false>)<<<gm_blocks(P / 16), GC_THREADS, 0, s>>>(
+				rows, text_bytes, c->d_gm_group.as<GmGroup>(), c->d_gm_used.as<GmUsed>(), c->d_gm_cbase.as<u64>(), ng, P, nclass, c->d_gc_flag.as<uint4>());
 			HIP_TRY(hipGetLastError());
 			prim::select(s, c->d_gm_tmp, rocprim::counting_iterator<u64>(0), c->d_gc_flag.as<uint8_t>(), c->d_gc_x.as<u64>(), c->d_gm_count.as<u64>(), (size_t)P);
 			HIP_TRY(hipEventRecord(c->ev[1], s));
@@ -186,11 +193,13 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 					                                                c->d_gc_x.as<u64>(), C, c->d_gc_site.as<sbl_concat_site>(), c->d_gc_pick.as<GcPick>());
 					HIP_TRY(hipGetLastError());
 				}
-				k_concat_text<true><<<blocks, GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gc_roff.as<u64>(), nullptr, ng, c->d_gc_pick.as<GcPick>(), c->d_gc_coff.as<u64>(), nclass,
-				                                                  c->d_gc_hdr.as<char>(), C, S, width, total, c->d_gc_text.as<uint4>());
+				(partial ? k_concat_text<true, true> : k_concat_text<true, false>)<<<blocks, GC_THREADS, 0, s>>>(
+					rows, text_bytes, c->d_gc_roff.as<u64>(), nullptr, ng, c->d_gc_pick.as<GcPick>(), c->d_gc_coff.as<u64>(), nclass, c->d_gc_hdr.as<char>(), C, S, width, total,
+					c->d_gc_text.as<uint4>());
 			} else
-				k_concat_text<false><<<blocks, GC_THREADS, 0, s>>>(rows, text_bytes, c->d_gc_roff.as<u64>(), c->d_gc_first.as<u64>(), ng, nullptr, c->d_gc_coff.as<u64>(), nclass,
-				                                                   c->d_gc_hdr.as<char>(), C, S, width, total, c->d_gc_text.as<uint4>());
+				(partial ? k_concat_text<false, true> : k_concat_text<false, false>)<<<blocks, GC_THREADS, 0, s>>>(
+					rows, text_bytes, c->d_gc_roff.as<u64>(), c->d_gc_first.as<u64>(), ng, nullptr, c->d_gc_coff.as<u64>(), nclass, c->d_gc_hdr.as<char>(), C, S, width, total,
+					c->d_gc_text.as<uint4>());
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipEventRecord(c->ev[3], s));
 			HIP_TRY(hipMemcpyAsync(c->h_gc_text.p, c->d_gc_text.p, padded, hipMemcpyDeviceToHost, s));
@@ -217,6 +226,21 @@ extern "C" sbl_status sbl_group_concat(sbl_ctx *c, const uint8_t *want, const ui
 		if (text) *text = total ? c->h_gc_text.p : "";
 		if (text_len) *text_len = total;
 	});
+}
+
+extern "C" sbl_status sbl_group_set_partial(sbl_ctx *c, uint32_t on)
+{
+	return guarded(c, [&] {
+		SBL_CHECK(on <= 1, SBL_ERR_BAD_ARG, "the partial groups setting is 0 or 1");
+		c->gp_partial = on;
+	});
+}
+
+extern "C" sbl_status sbl_group_get_partial(const sbl_ctx *c, uint32_t *on)
+{
+	if (!c || !on) return SBL_ERR_BAD_ARG;
+	*on = c->gp_partial;
+	return SBL_OK;
 }
 
 extern "C" sbl_status sbl_group_concat_times(const sbl_ctx *c, double *kernel_ms, double *copyback_ms)

@@ -149,8 +149,13 @@ struct sbl_ctx {
 	SblTimes gc_times;                   // the kernels / the copy of the text
 	// sbl_group_bootstrap (group_boot.hip): the packed sites and the count slabs of one batch of replicates; flags, compacted columns and
 	// row starts go through sbl_group_concat's d_gc_flag / d_gc_x / d_gc_roff, which every call fills anew.  All slabs come back into gb_counts
-	DevBuf d_gb_pack, d_gb_mat;
-	std::vector<uint64_t> gb_counts;
+	// gp_partial (sbl_group_set_partial): a used group of sbl_group_concat / sbl_group_bootstrap holds every class at most once.  gb_pairs:
+	// the clean columns per pair of classes of the last bootstrap call (sbl_group_bootstrap_pairs), folded on the host from d_gb_gclean,
+	// one count per used group
+	DevBuf d_gb_pack, d_gb_mat, d_gb_gclean;
+	std::vector<uint64_t> gb_counts, gb_pairs;
+	bool gb_pairs_valid = false;
+	uint32_t gp_partial = 0;
 	SblTimes gb_times;                   // the kernels of all phases / the copies of the slabs
 	// sbl_group_mask (group_mask.hip): the prefix of the padded member rows per used group, difference flags, the compacted differences
 	// (flat index; row key, centre index, column), start flags and their scan, head / tail flags and the compacted heads and tails, the

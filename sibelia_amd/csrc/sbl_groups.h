@@ -91,7 +91,9 @@ template <class F> GmColumns gm_columns(sbl_ctx *c, const uint8_t *want, unsigne
 
 // The used groups of the readers that take one row per class (group_concat.hip, group_boot.hip): a used group holds every class exactly
 // once, refused here before any launch.  roff[ug * nclass + f]: where the row of class f of used group ug starts in the rows; first: the
-// nused + 1 prefix of the groups' columns.  One row is enough where there is one class
+// nused + 1 prefix of the groups' columns.  One row is enough where there is one class.  Under sbl_group_set_partial (gp_partial, DESIGN.md
+// 0.12) a used group holds every class AT MOST once: a group with fewer instances than classes is used, the roff of an absent class stays
+// ~0 and the kernels' partial instantiations read it as "absent"; a class twice and more instances than classes are refused as before
 [[noreturn]] inline void gm_bad_class_group(size_t g, const char *what)
 {
 	char b[160];
@@ -102,7 +104,8 @@ inline GmColumns gm_class_columns(sbl_ctx *c, const uint8_t *want, const uint32_
 {
 	roff.clear(); first.assign(1, 0);
 	return gm_columns(c, want, 1, upload, [&](size_t g, const sbl_group_result &r, u64) {
-		if (r.ninst != nclass) gm_bad_class_group(g, r.ninst < nclass ? "has fewer instances than there are classes" : "has more instances than there are classes");
+		if (r.ninst > nclass) gm_bad_class_group(g, "has more instances than there are classes");
+		if (r.ninst < nclass && !c->gp_partial) gm_bad_class_group(g, "has fewer instances than there are classes");
 		const size_t at = roff.size();
 		roff.resize(at + nclass, ~0ull);
 		for (u64 i = 0; i < r.ninst; i++) {
@@ -167,11 +170,12 @@ template <class R> __device__ inline void gm_walk16(const uint8_t *__restrict__ 
 }
 
 // gm_walk16's reader of the site flags: bit 0 of a byte is set where the column holds one of A C G T in all of the group's rows and the
-// rows are not all equal (SBL_CONCAT_VARIABLE's kept columns); with CLEAN, bit 1 where it holds one of A C G T in all rows, equal or not
-template <bool CLEAN> struct GcFlags {
+// rows are not all equal (SBL_CONCAT_VARIABLE's kept columns); with CLEAN, bit 1 where it holds one of A C G T in all rows, equal or not.
+// PARTIAL (sbl_group_set_partial): the group's rows are the rows of the classes it holds, Q.ninst of them
+template <bool CLEAN, bool PARTIAL = false> struct GcFlags {
 	unsigned nclass;                                                          // a used group has nclass rows
 	u64 alo, ahi;
-	__device__ unsigned rows(const GmGroup &) const { return nclass; }
+	__device__ unsigned rows(const GmGroup &Q) const { return PARTIAL ? Q.ninst : nclass; }
 	__device__ void first(B16 ref) { alo = base_flags8(ref.lo); ahi = base_flags8(ref.hi); }
 	__device__ void next(B16 w) { alo &= base_flags8(w.lo); ahi &= base_flags8(w.hi); }
 	__device__ B16 bytes(u64 ulo, u64 uhi) const
@@ -181,10 +185,10 @@ template <bool CLEAN> struct GcFlags {
 	}
 };
 
-template <bool CLEAN>
+template <bool CLEAN, bool PARTIAL = false>
 __global__ __launch_bounds__(GM_THREADS) void k_site_flags(const uint8_t *__restrict__ text, u64 text_bytes, const GmGroup *__restrict__ gm,
                                                            const GmUsed *__restrict__ groups, const u64 *__restrict__ cbase, u64 ngroups,
                                                            u64 padded_cols, unsigned nclass, uint4 *__restrict__ flags)
 {
-	gm_walk16(text, text_bytes, gm, groups, cbase, ngroups, padded_cols, GcFlags<CLEAN>{nclass, 0, 0}, flags);
+	gm_walk16(text, text_bytes, gm, groups, cbase, ngroups, padded_cols, GcFlags<CLEAN, PARTIAL>{nclass, 0, 0}, flags);
 }

@@ -278,21 +278,28 @@ def core_headers(names: Sequence[str]) -> Tuple[bytes, List[int]]:
     return bytes(blob), first
 
 
-def core_partitions_text(rows: Sequence[Tuple[int, int, int]], gap_open: int = 0) -> bytes:
+def _core_comments(gap_open: int, coremin: int) -> List[str]:
+    """the comment lines of the --core files: `# gapopen=N` for gap_open > 0 (--gapopen), then `# coremin=M` for coremin > 0 (--coremin
+    below the number of files: the soft core)"""
+    return (["# gapopen=%d" % gap_open] if gap_open else []) + (["# coremin=%d" % coremin] if coremin else [])
+
+
+def core_partitions_text(rows: Sequence[Tuple[int, int, int]], gap_open: int = 0, coremin: int = 0) -> bytes:
     """The file of --corepartitions: tab-separated, a line of column names, then one line per used block in ascending
     id.  rows: (block id, first column, number of columns) with the first column counted from 0 as BlockFinder.group_concat returns the
-    parts; written 1-based and inclusive.  gap_open > 0 (--gapopen) is recorded in a line `# gapopen=N` before the column names."""
-    out = (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(CORE_PARTITIONS_COLUMNS)]
+    parts; written 1-based and inclusive.  gap_open > 0 (--gapopen) is recorded in a line `# gapopen=N` before the column names, coremin > 0
+    in a line `# coremin=M` after it."""
+    out = _core_comments(gap_open, coremin) + ["\t".join(CORE_PARTITIONS_COLUMNS)]
     out += ["%d\t%d\t%d" % (block, first + 1, first + ncols) for block, first, ncols in rows]
     return ("\n".join(out) + "\n").encode("latin1")
 
 
-def core_sites_text(rows: Sequence[Tuple[int, str, int, int, bool, int]], gap_open: int = 0) -> bytes:
+def core_sites_text(rows: Sequence[Tuple[int, str, int, int, bool, int]], gap_open: int = 0, coremin: int = 0) -> bytes:
     """The file of --coresites: tab-separated, a line of column names, then one line per column of --coresnps, numbered
     from 1.  rows: (block id, record name, start, end, rev, before) -- the centre instance of the block (0-based, half-open, on the
     first file) and the index of the column's base in it; the position is 1-based on the record: start + before + 1 for a forward
-    instance, end - before for a reverse one.  gap_open > 0 is recorded as for core_partitions_text."""
-    out = (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(CORE_SITES_COLUMNS)]
+    instance, end - before for a reverse one.  gap_open > 0 and coremin > 0 are recorded as for core_partitions_text."""
+    out = _core_comments(gap_open, coremin) + ["\t".join(CORE_SITES_COLUMNS)]
     for i, (block, record, start, end, rev, before) in enumerate(rows):
         out.append("%d\t%d\t%s\t%d\t%s" % (i + 1, block, record, end - before if rev else start + before + 1, "-" if rev else "+"))
     return ("\n".join(out) + "\n").encode("latin1")
@@ -301,18 +308,27 @@ def core_sites_text(rows: Sequence[Tuple[int, str, int, int, bool, int]], gap_op
 CORE_DENSE_COLUMNS = ("file", "block", "record", "first", "last", "strand", "differences", "first_column", "last_column")
 
 
-def core_dense_text(rows, window: int, max_diff: int, gap_open: int = 0) -> bytes:
+def core_dense_text(rows, window: int, max_diff: int, gap_open: int = 0, coremin: int = 0) -> bytes:
     """The file of --coredense: tab-separated; a line `# densitywindow=W densitymax=T`, a line `# gapopen=N` for
-    gap_open > 0, a line of column names, then one line per masked interval in the order BlockFinder.group_mask returns them.  rows:
+    gap_open > 0, a line `# coremin=M` for coremin > 0, a line of column names, then one line per masked interval in the order BlockFinder.group_mask returns them.  rows:
     (file name of the masked row, block id, record name, start, end, rev, before_first, before_last, differences, first column, last
     column) -- the centre instance of the block (0-based, half-open, on the first file), the centre indices of the interval's first and
     last column, and those columns in the concatenation counted from 0.  Positions are 1-based on the record by the rule of
     core_sites_text -- start + before + 1 forward, end - before on a reverse instance, where the two swap so that first <= last; the
     columns are written 1-based and inclusive."""
-    out = ["# densitywindow=%d densitymax=%d" % (window, max_diff)] + (["# gapopen=%d" % gap_open] if gap_open else []) + ["\t".join(CORE_DENSE_COLUMNS)]
+    out = ["# densitywindow=%d densitymax=%d" % (window, max_diff)] + _core_comments(gap_open, coremin) + ["\t".join(CORE_DENSE_COLUMNS)]
     for name, block, record, start, end, rev, before_first, before_last, ndiff, first_column, last_column in rows:
         lo, hi = (end - before_last, end - before_first) if rev else (start + before_first + 1, start + before_last + 1)
         out.append("%s\t%d\t%s\t%d\t%d\t%s\t%d\t%d\t%d" % (name, block, record, lo, hi, "-" if rev else "+", ndiff, first_column + 1, last_column + 1))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
+def core_presence_text(names: Sequence[str], rows: Sequence[Tuple[int, Sequence[bool]]], gap_open: int = 0, coremin: int = 0) -> bytes:
+    """The file of --corepresence: tab-separated; the comment lines of core_partitions_text, a line `block` and the
+    files' base names, then one line per used block in ascending id: the id and, per input file, 1 where the block has its instance in
+    the file and 0 where it has none.  rows: (block id, one flag per file)."""
+    out = _core_comments(gap_open, coremin) + ["\t".join(["block"] + list(names))]
+    out += ["\t".join(["%d" % block] + ["1" if x else "0" for x in held]) for block, held in rows]
     return ("\n".join(out) + "\n").encode("latin1")
 
 

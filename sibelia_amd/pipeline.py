@@ -18,7 +18,9 @@ input files) concatenate, on the device, the same alignments of the blocks with 
 alignment and its variable columns, one FASTA record per input file, with the tables that say where a block and a column come from
 (DESIGN.md 0.9).  --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense (two or more input files) make the same files from
 the rows with every file's SNP-dense regions -- more than --densitymax differences from the first file within --densitywindow of its
-bases -- replaced by N, and the table of those regions; the mask is computed on the device.  --coretree /
+bases -- replaced by N, and the table of those regions; the mask is computed on the device.  --coremin M
+turns the core of all of these into the soft core -- blocks with instances in at least M files, gaps for the files without one -- and
+--corepresence lists which files every used block is in.  --coretree /
 --corefilteredtree (three or more input files) write the neighbour-joining tree of the input files from the variable columns of those
 two alignments in Newick format, with --bootstrap B the support of B replicates whose pair counts are made on the device (DESIGN.md 0.11;
 `tree.py`).  --uncovered adds the rest of C-Sibelia's VCF to
@@ -120,13 +122,24 @@ BOOTSEED_HELP = "With the same options: the seed of the draws, 0 .. 184467440737
 TREEMODEL_HELP = ("With the same options: p, the proportion of differing columns (default), or jc, Jukes and Cantor's correction "
                   "-3/4 ln(1 - 4p/3); a tree with two files at p >= 0.75 is then not written.")
 
+COREMIN_HELP = ("With any of the --core..., --corefiltered... and tree options or --corepresence: the soft core.  Use the blocks with instances "
+                "in at least M input files, 2 .. the number of files, default the number of files: the strict core.  Below it a block is "
+                "used if all its instances are at least the minimum block size long, exactly one lies in the first file, at most one in "
+                "each other file and they reach at least M files.  A file without an instance of a block gets gaps in the alignments; "
+                "a column counts as variable or as comparable by the files that are there, and a tree takes the distance of two files "
+                "over the columns of the blocks that both have.  A tree is not written where two files share no such column.  "
+                "The tab-separated files record M in a line `# coremin=M`.")
+COREPRESENCE_HELP = ("Two or more input files: write which input files every used block has an instance in as tab-separated text: a line "
+                     "`block` and the files' base names, then the block and 1 or 0 per file, in ascending block id.")
+
 CORE_OPTIONS = (("--corealignment", "corealignment"), ("--corepartitions", "corepartitions"), ("--coresnps", "coresnps"), ("--coresites", "coresites"))
 DENSITY_OPTIONS = (("--corefiltered", "corefiltered"), ("--corefilteredsnps", "corefilteredsnps"), ("--corefilteredsites", "corefilteredsites"), ("--coredense", "coredense"))
 TREE_OPTIONS = (("--coretree", "coretree"), ("--corefilteredtree", "corefilteredtree"))
+PRESENCE_OPTIONS = (("--corepresence", "corepresence"),)
 # the options that name a file made from alignments, as (flag, attribute) in the order the files are written; those that read the
 # multiple alignments of the blocks (align_block_groups); those of them that compare the input files by their names
 FILE_OPTIONS = (("--maf", "maf"), ("--variants", "variants"), ("--unmapped", "unmapped"), ("--multimaf", "multimaf"), ("--multivariants", "multivariants"),
-                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS + DENSITY_OPTIONS + TREE_OPTIONS
+                ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS + DENSITY_OPTIONS + PRESENCE_OPTIONS + TREE_OPTIONS
 GROUP_OPTIONS, NAMED_FILE_OPTIONS = FILE_OPTIONS[3:], FILE_OPTIONS[5:]
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
@@ -297,6 +310,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--densitymax", type=_density, default=None, metavar="T", help=DENSITYMAX_HELP)
     p.add_argument("--coretree", default=None, metavar="FILE", help=CORETREE_HELP)
     p.add_argument("--corefilteredtree", default=None, metavar="FILE", help=COREFILTEREDTREE_HELP)
+    p.add_argument("--coremin", type=_unsigned, default=None, metavar="M", help=COREMIN_HELP)
+    p.add_argument("--corepresence", default=None, metavar="FILE", help=COREPRESENCE_HELP)
     p.add_argument("--bootstrap", type=_bounded(0, BOOTSTRAP_MAX), default=None, metavar="B", help=BOOTSTRAP_HELP)
     p.add_argument("--bootseed", type=_bounded(0, BOOTSEED_MAX), default=None, metavar="S", help=BOOTSEED_HELP)
     p.add_argument("--treemodel", choices=("p", "jc"), default=None, help=TREEMODEL_HELP)
@@ -366,6 +381,14 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
     for o, v in (("--densitywindow", opt.densitywindow), ("--densitymax", opt.densitymax)):
         if v is not None and not density_wanted(opt):
             raise PipelineError("%s sets the density filter: it needs at least one of --corefiltered, --corefilteredsnps, --corefilteredsites and --coredense" % o)
+    if opt.coremin is not None:
+        if not concat_wanted(opt):
+            raise PipelineError("--coremin sets which blocks the core-genome files are made of: it needs at least one of the --core..., "
+                                "--corefiltered... and tree options and --corepresence")
+        if not 2 <= opt.coremin <= len(opt.filenames):
+            raise PipelineError("--coremin is the number of input files a block must reach: 2 .. %d for these input files" % len(opt.filenames))
+    else:
+        opt.coremin = len(opt.filenames)
     opt.densitywindow = opt.densitywindow or DENSITYWINDOW_DEFAULT
     opt.densitymax = opt.densitymax or DENSITYMAX_DEFAULT
     aligns = bool(_given(opt, FILE_OPTIONS))        # --unmapped is given with --variants only
@@ -407,6 +430,16 @@ def density_wanted(opt: argparse.Namespace) -> bool:
 def tree_wanted(opt: argparse.Namespace) -> bool:
     """One of --coretree / --corefilteredtree is given."""
     return bool(_given(opt, TREE_OPTIONS))
+
+
+def presence_wanted(opt: argparse.Namespace) -> bool:
+    """--corepresence is given."""
+    return bool(_given(opt, PRESENCE_OPTIONS))
+
+
+def concat_wanted(opt: argparse.Namespace) -> bool:
+    """One of the options that core_files serves is given."""
+    return core_wanted(opt) or density_wanted(opt) or tree_wanted(opt) or presence_wanted(opt)
 
 
 def _check_alignment_files(opt: argparse.Namespace) -> None:
@@ -709,6 +742,15 @@ def core_blocks(blocks, file_records: Sequence[int], min_block_size: int) -> Lis
             if all(n >= min_block_size for _, n in inst) and sorted(f for f, _ in inst) == list(range(len(file_records)))]
 
 
+def soft_core_blocks(blocks, file_records: Sequence[int], min_block_size: int, coremin: int) -> List[int]:
+    """The ids of the soft-core blocks of a block list (formats.BLOCK_DTYPE), what the --core options concatenate under --coremin: every
+    instance of the id is at least min_block_size long, exactly one lies on the records of the first file, at most one on those of each
+    other file, and they lie in at least `coremin` files -- qualifying_blocks with a floor on the number of files, so the first file's
+    instance stays the centre.  With coremin the number of files these are core_blocks."""
+    return [block for block, inst in _instances_by_id(blocks, file_records)
+            if len(inst) >= max(coremin, 1) and _once_per_file(inst, min_block_size) and [f for f, _ in inst].count(0) == 1]
+
+
 def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[int], insts, aligned, core, complain: Callable[[str], None]) -> Dict[str, bytes]:
     """--corealignment / --corepartitions / --coresnps / --coresites from the alignments of one align_block_groups call: the class of an
     instance is the file of its record, the wanted groups are the aligned blocks of `core` (core_blocks); the rows are concatenated and
@@ -718,7 +760,10 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     against their centre -- the first file -- on the device (BlockFinder.group_mask), then the same two concatenations
     of the masked rows (set_masked); in a core block row i is file i's.
     --coretree / --corefilteredtree: one BlockFinder.group_bootstrap call each on the rows / the masked rows and the
-    tree of its counts (tree.py); a tree that cannot be built is named through `complain` and its file is absent from the result."""
+    tree of its counts (tree.py); a tree that cannot be built is named through `complain` and its file is absent from the result.
+    --coremin below the number of files: `core` holds soft_core_blocks, all of the above runs inside a set_partial
+    section, the tables get their `# coremin=M` line and the trees divide by group_bootstrap_pairs, the clean columns per pair of files.
+    --corepresence: which files every wanted and aligned block has an instance in, from `cls`."""
     from . import formats, tree
     from .api import CONCAT_ALL, CONCAT_VARIABLE, GALIGN_OK, SibeliaError
     file_of = _file_of_record(bf.file_records)
@@ -728,8 +773,14 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     flat = [0]                                          # the first instance of every group in cls
     for inst in insts:
         flat.append(flat[-1] + len(inst))
+    soft = opt.coremin < n                              # the soft core: partial groups on the device, comment lines in the files
+    coremin = opt.coremin if soft else 0
     if not any(want):
-        complain("no core block: no block has exactly one instance of at least %d bases in every input file and was aligned\n" % opt.minblocksize)
+        if soft:
+            complain("no core block: no block has exactly one instance of at least %d bases in the first input file, at most one in each other "
+                     "and instances in at least %d input files (--coremin %d), and was aligned\n" % (opt.minblocksize, opt.coremin, opt.coremin))
+        else:
+            complain("no core block: no block has exactly one instance of at least %d bases in every input file and was aligned\n" % opt.minblocksize)
     headers = [b">" + a.encode("latin1") + b"\n" for a in file_names(opt.filenames)]
     out = {}
 
@@ -741,22 +792,27 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
             complain("%s not written: no variable column in the core-genome alignment\n" % o)
             return
         try:
-            out[getattr(opt, o[2:])] = tree.tree_text(counts, nclean, opt.treemodel, file_names(opt.filenames)).encode("latin1")
-        except tree.Saturated as e:
+            out[getattr(opt, o[2:])] = tree.tree_text(counts, bf.group_bootstrap_pairs() if soft else nclean, opt.treemodel, file_names(opt.filenames)).encode("latin1")
+        except (tree.Saturated, tree.NoSharedColumn) as e:
             complain("%s not written: %s\n" % (o, e))
     try:
+        if soft:
+            bf.set_partial(True)
+        if opt.corepresence is not None:
+            out[opt.corepresence] = formats.core_presence_text(
+                file_names(opt.filenames), [(ids[g], [f in cls[flat[g]:flat[g + 1]] for f in range(n)]) for g in range(len(ids)) if want[g] and aligned[g].L], opt.gapopen, coremin)
         if opt.corealignment is not None or opt.corepartitions is not None:
             text, parts, _ = bf.group_concat(cls, n, headers, CONCAT_ALL, formats.CORE_WIDTH, want)
             if opt.corealignment is not None:
                 out[opt.corealignment] = text
             if opt.corepartitions is not None:
-                out[opt.corepartitions] = formats.core_partitions_text([(ids[g], first, ncols) for g, first, ncols in parts], opt.gapopen)
+                out[opt.corepartitions] = formats.core_partitions_text([(ids[g], first, ncols) for g, first, ncols in parts], opt.gapopen, coremin)
         if opt.coresnps is not None or opt.coresites is not None:
             text, _, sites = bf.group_concat(cls, n, headers, CONCAT_VARIABLE, formats.CORE_WIDTH, want)
             if opt.coresnps is not None:
                 out[opt.coresnps] = text
             if opt.coresites is not None:
-                out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+                out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen, coremin)
         if opt.coretree is not None:
             tree_file("--coretree")
         if density_wanted(opt):
@@ -770,7 +826,7 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                     if opt.corefilteredsnps is not None:
                         out[opt.corefilteredsnps] = text
                     if opt.corefilteredsites is not None:
-                        out[opt.corefilteredsites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen)
+                        out[opt.corefilteredsites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen, coremin)
                 if opt.corefilteredtree is not None:
                     tree_file("--corefilteredtree")
             finally:
@@ -783,10 +839,13 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                 files = file_names(opt.filenames)
                 out[opt.coredense] = formats.core_dense_text(
                     [(files[cls[flat[g] + row]], ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before_lo, before_hi, ndiff, first[g] + lo, first[g] + hi)
-                     for g, row, lo, hi, before_lo, before_hi, ndiff in intervals], opt.densitywindow, opt.densitymax, opt.gapopen)
+                     for g, row, lo, hi, before_lo, before_hi, ndiff in intervals], opt.densitywindow, opt.densitymax, opt.gapopen, coremin)
     except SibeliaError as e:
         raise PipelineError(str(e))
-    made = {f: out[f] for _, f in _given(opt, CORE_OPTIONS + DENSITY_OPTIONS)}
+    finally:
+        if soft:
+            bf.set_partial(False)
+    made = {f: out[f] for _, f in _given(opt, CORE_OPTIONS + DENSITY_OPTIONS + PRESENCE_OPTIONS)}
     made.update({f: out[f] for _, f in _given(opt, TREE_OPTIONS) if f in out})      # a tree that could not be built was named and is absent
     return made
 
@@ -840,7 +899,10 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     qualify = set(qualifying_blocks(blocks, bf.file_records, opt.minblocksize)) if opt.multivariants is not None else set()
     distances = opt.distances is not None or opt.distancecounts is not None
     used = set(distance_blocks(blocks, bf.file_records, opt.minblocksize)) if distances else set()
-    core = set(core_blocks(blocks, bf.file_records, opt.minblocksize)) if core_wanted(opt) or density_wanted(opt) or tree_wanted(opt) else set()
+    core = set()
+    if concat_wanted(opt):
+        soft = opt.coremin < len(bf.file_records)
+        core = set(soft_core_blocks(blocks, bf.file_records, opt.minblocksize, opt.coremin) if soft else core_blocks(blocks, bf.file_records, opt.minblocksize))
     groups = []
     for block, inst, al in zip(ids, insts, aligned):
         if al.status != GALIGN_OK:
@@ -873,7 +935,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
         out[opt.multivariants] = formats.multi_vcf_text(names[0], sample_names(opt.filenames), records, opt.gapopen)
     if distances:
         out.update(distance_files(bf, opt, ids, insts, aligned, used, complain))
-    if core_wanted(opt) or density_wanted(opt) or tree_wanted(opt):
+    if concat_wanted(opt):
         out.update(core_files(bf, opt, names, ids, insts, aligned, core, complain))
     return out
 

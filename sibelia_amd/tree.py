@@ -22,6 +22,15 @@ class Saturated(ValueError):
         self.pair = (f, g)
 
 
+class NoSharedColumn(ValueError):
+    """a pair of files without a column to compare them in (a denominator of 0 in a matrix K); .pair = (f, g)"""
+
+    def __init__(self, f: int, g: int, names: Optional[Sequence[str]] = None):
+        a, b = (names[f], names[g]) if names is not None else ("%d" % f, "%d" % g)
+        ValueError.__init__(self, "files %s and %s share no column in which both hold one of A C G T: they have no distance" % (a, b))
+        self.pair = (f, g)
+
+
 class Tree:
     def __init__(self, n: int, edges):
         self.n, self.edges = n, list(edges)
@@ -34,11 +43,22 @@ def check_names(names: Sequence[str]) -> None:
             raise ValueError("the name %r cannot stand in a Newick tree: it is empty or holds one of ( ) [ ] : ; , a quote or white space" % name)
 
 
-def distances(M, K: int, model: str = "p") -> np.ndarray:
-    """counts of differing columns M (files x files) over K columns -> distances: the proportion p, or Jukes and Cantor's correction"""
+def distances(M, K, model: str = "p", names: Optional[Sequence[str]] = None) -> np.ndarray:
+    """counts of differing columns M (files x files) over K columns -> distances: the proportion p, or Jukes and Cantor's correction.
+    K: one number, or a matrix files x files with the columns of every pair (the soft core): a pair of two files with
+    K[f][g] == 0 raises NoSharedColumn, which names them (by `names` where given)"""
     if model not in MODELS:
         raise ValueError("unknown model %r" % (model,))
-    p = np.asarray(M).astype(np.float64) / K
+    if np.ndim(K) == 0:
+        p = np.asarray(M).astype(np.float64) / K
+    else:
+        K = np.asarray(K).astype(np.float64)
+        if K.shape != np.shape(M):
+            raise ValueError("the columns per pair must have the shape of the counts")
+        bad = np.argwhere((K == 0) & ~np.eye(len(K), dtype=bool))
+        if len(bad):
+            raise NoSharedColumn(int(bad[0][0]), int(bad[0][1]), names)
+        p = np.asarray(M).astype(np.float64) / np.where(K == 0, 1.0, K)              # a diagonal cell: 0 over anything
     if model == "p":
         return p
     bad = np.argwhere(p >= 0.75)
@@ -160,10 +180,10 @@ def newick(tree: Tree, names: Sequence[str], support: Optional[Dict[int, int]] =
     return text[r.top]
 
 
-def tree_text(counts, K: int, model: str, names: Sequence[str]) -> str:
-    """counts: (B + 1, files, files), slab 0 of all sites and one slab per replicate; K: the columns they were taken from -> the Newick
-    text of slab 0's tree with the support of the B replicate trees"""
+def tree_text(counts, K, model: str, names: Sequence[str]) -> str:
+    """counts: (B + 1, files, files), slab 0 of all sites and one slab per replicate; K: the columns they were taken from, one number
+    or one per pair of files (distances) -> the Newick text of slab 0's tree with the support of the B replicate trees"""
     B = len(counts) - 1
-    main = neighbour_joining(distances(counts[0], K, model))
-    reps = [neighbour_joining(distances(counts[r], K, model)) for r in range(1, B + 1)]
+    main = neighbour_joining(distances(counts[0], K, model, names))
+    reps = [neighbour_joining(distances(counts[r], K, model, names)) for r in range(1, B + 1)]
     return newick(main, names, support(main, reps) if B else None, B)
