@@ -616,6 +616,34 @@ sbl_status sbl_group_set_partial(sbl_ctx *ctx, uint32_t on);      /* 0 (default)
 sbl_status sbl_group_get_partial(const sbl_ctx *ctx, uint32_t *on);
 sbl_status sbl_group_bootstrap_pairs(sbl_ctx *ctx, const uint64_t **clean /* nclass * nclass, row-major, owned by ctx */);
 
+/* Neighbour joining of a batch of distance matrices (csrc/tree_nj.hip), defined by this project: the trees of the
+ * replicates of a bootstrap, one workgroup per matrix, the matrix in LDS.  D holds ntrees matrices of n x n doubles, row-major, in host
+ * memory.  The call needs no records and no groups call, and it reads and writes nothing the sbl_group_* calls own.
+ * THE TREE of a matrix is Studier and Keppler's neighbour joining as sibelia_amd/tree.py's neighbour_joining computes it, in the same
+ * float64 operations, so the lengths are the same bit for bit.  Leaves are 0 .. n - 1; join s = 0 .. n - 4 makes node n + s, the last three
+ * rows hang from node 2 n - 3.  With m = n - s rows left, in the order that deleting the joined rows leaves, and a row's sum r taken over
+ * those m cells (diagonal included) in this order -- m < 8: from 0.0 left to right; m >= 8: eight partial sums r[k] = a[k],
+ * r[k] += a[i + k] for i = 8, 16, .. < m - m % 8, then ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the m % 8 tail cells left to
+ * right, then 0.0 + that --
+ *     Q[i][j] = ((double)(m - 2) * D[i][j] - r[i]) - r[j]; the pair is the first of the smallest Q over i < j, row-major
+ *     li = dij / 2 + (r[i] - r[j]) / (double)(2 * (m - 2)), lj = dij - li; li < 0: (0, dij); else lj < 0: (dij, 0)
+ *     the new row ((D[i][k] + D[j][k]) - dij) / 2 takes row and column i, D[i][i] = 0, row and column j leave
+ *     the last three: ((D01 + D02) - D12) / 2, ((D01 + D12) - D02) / 2, ((D02 + D12) - D01) / 2, each x > 0 ? x : 0.0
+ * with no fused multiply-add and IEEE divisions.
+ * EDGES.  2 n - 3 per matrix, in the order of tree.py's Tree.edges: per join (n + s, node of row i, li), (n + s, node of row j, lj), then
+ * the three edges of the last node.  SPLITS.  n - 3 per matrix (none for n == 3): splits[s] holds the leaves below node n + s as a bit
+ * mask, complemented within n bits where it holds leaf 0 -- the convention of tree.py's bipartitions.
+ * Both arrays are owned by the ctx until the next sbl_nj_batch.  Matrices go up and results come back in batches of 64 MiB / (8 n^2)
+ * matrices, one launch and one host synchronisation per batch.  ntrees == 0 is a result: nothing is launched.
+ * SBL_ERR_BAD_ARG, checked on the host before any launch: n < 3; edges or splits NULL; D NULL with ntrees > 0; a cell that is not finite;
+ * a matrix that is not symmetric bit for bit; a diagonal cell that is not 0.  SBL_ERR_TOO_LARGE: n > 64 (the mask is one word).  A
+ * refused call leaves the result of an earlier call valid.
+ * sbl_nj_batch_times: device time of the last call's kernels and of its copies, uploads and copies back together (event pairs). */
+typedef struct { uint32_t parent, child; double length; } sbl_nj_edge;
+sbl_status sbl_nj_batch(sbl_ctx *ctx, const double *D /* ntrees * n * n, row-major, host */, uint32_t n, uint32_t ntrees,
+                        const sbl_nj_edge **edges /* ntrees * (2n - 3) */, const uint64_t **splits /* ntrees * (n - 3) */);
+sbl_status sbl_nj_batch_times(const sbl_ctx *ctx, double *kernel_ms, double *copy_ms /* upload + copy-back */);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

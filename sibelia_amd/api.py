@@ -33,7 +33,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
            "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_group_bootstrap", "sbl_group_bootstrap_times", "sbl_tiny_index",
-           "sbl_group_set_partial", "sbl_group_get_partial", "sbl_group_bootstrap_pairs",
+           "sbl_group_set_partial", "sbl_group_get_partial", "sbl_group_bootstrap_pairs", "sbl_nj_batch", "sbl_nj_batch_times",
            "sbl_test_touched_list", "sbl_test_graph_build", "sbl_test_graph_fetch"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -151,6 +151,13 @@ class MaskInterval(C.Structure):                   # sbl_mask_interval
                 ("before_first", C.c_uint64), ("before_last", C.c_uint64), ("ndiff", C.c_uint64)]
 
 
+class NjEdge(C.Structure):                         # sbl_nj_edge
+    _fields_ = [("parent", C.c_uint32), ("child", C.c_uint32), ("length", C.c_double)]
+
+
+NJ_EDGE_DTYPE = np.dtype([("parent", "<u4"), ("child", "<u4"), ("length", "<f8")])      # tree.EDGE_RECORD
+
+
 class GroupAlignment:
     """One sbl_group_result: status (GALIGN_OK / GALIGN_SKIPPED), L, row_off, the rows (centre first, members in the order given) and
     per member (score, band_w, passes).  A skipped group has L = 0, no rows and member scores None."""
@@ -258,6 +265,8 @@ def load_library():
         L.sbl_group_get_partial.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sbl_group_bootstrap_pairs.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64))]
         L.sbl_group_get_masked.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.sbl_nj_batch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(NjEdge)), C.POINTER(C.POINTER(C.c_uint64))]
+        L.sbl_nj_batch_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -687,6 +696,29 @@ class BlockFinder:
         self._check(self.L.sbl_group_bootstrap_pairs(self.h, C.byref(out)), "sbl_group_bootstrap_pairs")
         n = self._boot_nclass
         return _view(C.cast(out, C.c_void_p).value, n * n, np.dtype("<u8")).reshape(n, n)
+
+    def nj_batch(self, D):
+        """The neighbour-joining trees of a batch of distance matrices (csrc/tree_nj.hip; defined in include/sibelia_amd.h, DESIGN.md
+        0.13), one workgroup per matrix: bit for bit the trees of tree.neighbour_joining.  D: array of shape (ntrees, n, n), 3 <= n <= 64,
+        finite, every matrix symmetric with a zero diagonal.  Needs no groups call and leaves what the group_* calls own alone.
+        -> (structured array of shape (ntrees, 2n - 3) with parent, child, length: the edges in the order of Tree.edges;
+        uint64 array of shape (ntrees, n - 3): per join the leaves below the new node as a bit mask, complemented where it holds file 0,
+        the convention of tree.bipartitions).  Both are copies."""
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.ndim != 3 or D.shape[1] != D.shape[2]:
+            raise SibeliaError("sbl_nj_batch: bad argument (the matrices must have the shape (trees, files, files))")
+        ntrees, n = int(D.shape[0]), int(D.shape[1])
+        if ntrees > 2 ** 32 - 1:
+            raise SibeliaError("sbl_nj_batch: bad argument (the number of matrices outside 32 bits)")
+        edges, splits = C.POINTER(NjEdge)(), C.POINTER(C.c_uint64)()
+        self._check(self.L.sbl_nj_batch(self.h, D.ctypes.data_as(C.POINTER(C.c_double)) if D.size else None, n, ntrees, C.byref(edges), C.byref(splits)), "sbl_nj_batch")
+        ne, ns = 2 * n - 3, n - 3
+        return (_view(C.cast(edges, C.c_void_p).value, ntrees * ne, NJ_EDGE_DTYPE).reshape(ntrees, ne),
+                _view(C.cast(splits, C.c_void_p).value, ntrees * ns, np.dtype("<u8")).reshape(ntrees, ns))
+
+    def nj_batch_times(self) -> Tuple[float, float]:
+        """(kernel ms, ms of the uploads of the matrices and the copies of the results) of the last nj_batch call, from event pairs."""
+        return self._times("sbl_nj_batch_times")
 
     def set_partial(self, on) -> None:
         """True: every later group_concat / group_bootstrap call of this finder uses the groups that hold every class AT MOST once (the

@@ -157,6 +157,12 @@ struct sbl_ctx {
 	bool gb_pairs_valid = false;
 	uint32_t gp_partial = 0;
 	SblTimes gb_times;                   // the kernels of all phases / the copies of the slabs
+	// sbl_nj_batch (tree_nj.hip): the matrices, edges and splits of one batch on the device; the edges and splits of all matrices of the
+	// last call.  Nothing here is shared with the sbl_group_* calls
+	DevBuf d_nj_in, d_nj_edges, d_nj_splits;
+	std::vector<sbl_nj_edge> nj_edges;
+	std::vector<uint64_t> nj_splits;
+	SblTimes nj_times;                   // the kernels / the uploads of the matrices and the copies of the results
 	// sbl_group_mask (group_mask.hip): the prefix of the padded member rows per used group, difference flags, the compacted differences
 	// (flat index; row key, centre index, column), start flags and their scan, head / tail flags and the compacted heads and tails, the
 	// intervals and their byte ranges, and the masked rows: a buffer of the layout of d_ga_text, valid while gk_valid holds (set by

@@ -23,7 +23,9 @@ turns the core of all of these into the soft core -- blocks with instances in at
 --corepresence lists which files every used block is in.  --coretree /
 --corefilteredtree (three or more input files) write the neighbour-joining tree of the input files from the variable columns of those
 two alignments in Newick format, with --bootstrap B the support of B replicates whose pair counts are made on the device (DESIGN.md 0.11;
-`tree.py`).  --uncovered adds the rest of C-Sibelia's VCF to
+`tree.py`).  --coreconsensus / --corefilteredconsensus write the majority-rule consensus of those B replicate trees and --coreboottrees /
+--corefilteredboottrees the replicate trees themselves; all B + 1 matrices of a run are joined on the device in one call, up to 64 input
+files.  --uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -114,13 +116,22 @@ CORETREE_HELP = ("Three or more input files: write the neighbour-joining tree of
                  "from the node next to the first file, branch lengths with 9 decimals.  Not written where there is no such column.")
 COREFILTEREDTREE_HELP = "Three or more input files: write the same tree from the alignment of --corefiltered, its dense regions masked."
 BOOTSTRAP_MAX = 100000
-BOOTSTRAP_HELP = ("With --coretree or --corefilteredtree: label every inner branch with the percentage of B bootstrap replicates that hold it, "
+BOOTSTRAP_HELP = ("With --coretree or --corefilteredtree, or with the consensus and replicate tree files, which are made of the replicates: label every inner branch with the percentage of B bootstrap replicates that hold it, "
                   "0 .. 100000, default 0: no labels.  A replicate draws as many columns as --coresnps has, with replacement; the counts of "
                   "all replicates are made on the device.")
 BOOTSEED_MAX = 2 ** 64 - 1
 BOOTSEED_HELP = "With the same options: the seed of the draws, 0 .. 18446744073709551615, default 1.  The same seed gives the same file."
 TREEMODEL_HELP = ("With the same options: p, the proportion of differing columns (default), or jc, Jukes and Cantor's correction "
                   "-3/4 ln(1 - 4p/3); a tree with two files at p >= 0.75 is then not written.")
+
+CORECONSENSUS_HELP = ("Three or more input files, with --bootstrap B of 1 or more: write the majority-rule consensus of the B replicate trees of "
+                      "--coretree in Newick format, one line: the branches that more than half of the replicates hold, each labelled with the "
+                      "percentage that holds it and as long as its mean length in those replicates.  Without such a branch the tree is a star.  "
+                      "The replicate trees are built on the device for up to 64 input files.")
+COREFILTEREDCONSENSUS_HELP = "The same consensus from the replicates of --corefilteredtree."
+COREBOOTTREES_HELP = ("Three or more input files, with --bootstrap B of 1 or more: write the B replicate trees of --coretree in Newick format, one "
+                      "line each in the order of the replicates, without labels: the input of an external consensus or summary program.")
+COREFILTEREDBOOTTREES_HELP = "The same replicate trees from the replicates of --corefilteredtree."
 
 COREMIN_HELP = ("With any of the --core..., --corefiltered... and tree options or --corepresence: the soft core.  Use the blocks with instances "
                 "in at least M input files, 2 .. the number of files, default the number of files: the strict core.  Below it a block is "
@@ -140,7 +151,14 @@ PRESENCE_OPTIONS = (("--corepresence", "corepresence"),)
 # multiple alignments of the blocks (align_block_groups); those of them that compare the input files by their names
 FILE_OPTIONS = (("--maf", "maf"), ("--variants", "variants"), ("--unmapped", "unmapped"), ("--multimaf", "multimaf"), ("--multivariants", "multivariants"),
                 ("--distances", "distances"), ("--distancecounts", "distancecounts")) + CORE_OPTIONS + DENSITY_OPTIONS + PRESENCE_OPTIONS + TREE_OPTIONS
-GROUP_OPTIONS, NAMED_FILE_OPTIONS = FILE_OPTIONS[3:], FILE_OPTIONS[5:]
+# the files made of the bootstrap replicates' trees, written after all of those: the consensus of the plain and of the masked rows, then the
+# replicate trees of the two.  ROWS_TREE_OPTIONS: per kind of rows its tree, consensus and replicate trees
+REPLICATE_OPTIONS = (("--coreconsensus", "coreconsensus"), ("--corefilteredconsensus", "corefilteredconsensus"),
+                     ("--coreboottrees", "coreboottrees"), ("--corefilteredboottrees", "corefilteredboottrees"))
+ALL_TREE_OPTIONS = TREE_OPTIONS + REPLICATE_OPTIONS
+ROWS_TREE_OPTIONS = {False: (TREE_OPTIONS[0], REPLICATE_OPTIONS[0], REPLICATE_OPTIONS[2]), True: (TREE_OPTIONS[1], REPLICATE_OPTIONS[1], REPLICATE_OPTIONS[3])}
+ALL_FILE_OPTIONS = FILE_OPTIONS + REPLICATE_OPTIONS
+GROUP_OPTIONS, NAMED_FILE_OPTIONS = ALL_FILE_OPTIONS[3:], ALL_FILE_OPTIONS[5:]
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
@@ -310,6 +328,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--densitymax", type=_density, default=None, metavar="T", help=DENSITYMAX_HELP)
     p.add_argument("--coretree", default=None, metavar="FILE", help=CORETREE_HELP)
     p.add_argument("--corefilteredtree", default=None, metavar="FILE", help=COREFILTEREDTREE_HELP)
+    p.add_argument("--coreconsensus", default=None, metavar="FILE", help=CORECONSENSUS_HELP)
+    p.add_argument("--corefilteredconsensus", default=None, metavar="FILE", help=COREFILTEREDCONSENSUS_HELP)
+    p.add_argument("--coreboottrees", default=None, metavar="FILE", help=COREBOOTTREES_HELP)
+    p.add_argument("--corefilteredboottrees", default=None, metavar="FILE", help=COREFILTEREDBOOTTREES_HELP)
     p.add_argument("--coremin", type=_unsigned, default=None, metavar="M", help=COREMIN_HELP)
     p.add_argument("--corepresence", default=None, metavar="FILE", help=COREPRESENCE_HELP)
     p.add_argument("--bootstrap", type=_bounded(0, BOOTSTRAP_MAX), default=None, metavar="B", help=BOOTSTRAP_HELP)
@@ -358,7 +380,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
             for a in names:
                 if a != "".join(a.split()):
                     raise PipelineError("--distances writes PHYLIP, which separates by blanks: the file name '%s' holds white space" % a)
-    for o, _ in _given(opt, TREE_OPTIONS):
+    for o, _ in _given(opt, ALL_TREE_OPTIONS):
         if len(opt.filenames) < 3:                             # two files have one distance and no tree
             raise PipelineError("%s builds a tree: it needs at least three input files" % o)
         from . import tree
@@ -369,6 +391,9 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
     for o, v in (("--bootstrap", opt.bootstrap), ("--bootseed", opt.bootseed), ("--treemodel", opt.treemodel)):
         if v is not None and not tree_wanted(opt):
             raise PipelineError("%s is a setting of the tree: it needs at least one of --coretree and --corefilteredtree" % o)
+    for o, _ in _given(opt, REPLICATE_OPTIONS):
+        if not opt.bootstrap:
+            raise PipelineError("%s is made of the trees of the bootstrap replicates: it needs --bootstrap B with B of 1 or more" % o)
     opt.bootstrap = opt.bootstrap or 0
     opt.bootseed = 1 if opt.bootseed is None else opt.bootseed
     opt.treemodel = opt.treemodel or "p"
@@ -391,7 +416,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         opt.coremin = len(opt.filenames)
     opt.densitywindow = opt.densitywindow or DENSITYWINDOW_DEFAULT
     opt.densitymax = opt.densitymax or DENSITYMAX_DEFAULT
-    aligns = bool(_given(opt, FILE_OPTIONS))        # --unmapped is given with --variants only
+    aligns = bool(_given(opt, ALL_FILE_OPTIONS))    # --unmapped is given with --variants only
     if opt.gapopen is not None and not aligns:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
@@ -423,13 +448,14 @@ def core_wanted(opt: argparse.Namespace) -> bool:
 
 
 def density_wanted(opt: argparse.Namespace) -> bool:
-    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given, or --corefilteredtree, which reads the same masked rows."""
-    return bool(_given(opt, DENSITY_OPTIONS)) or opt.corefilteredtree is not None
+    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given, or --corefilteredtree, --corefilteredconsensus or
+    --corefilteredboottrees, which read the same masked rows."""
+    return bool(_given(opt, DENSITY_OPTIONS)) or bool(_given(opt, ROWS_TREE_OPTIONS[True]))
 
 
 def tree_wanted(opt: argparse.Namespace) -> bool:
-    """One of --coretree / --corefilteredtree is given."""
-    return bool(_given(opt, TREE_OPTIONS))
+    """One of --coretree / --corefilteredtree or of the four files made of their replicates is given."""
+    return bool(_given(opt, ALL_TREE_OPTIONS))
 
 
 def presence_wanted(opt: argparse.Namespace) -> bool:
@@ -445,7 +471,7 @@ def concat_wanted(opt: argparse.Namespace) -> bool:
 def _check_alignment_files(opt: argparse.Namespace) -> None:
     """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts, the four --core options, the four of the density filter and the two trees name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
-    given = _given(opt, FILE_OPTIONS)
+    given = _given(opt, ALL_FILE_OPTIONS)
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -511,7 +537,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for _, f in _given(opt, FILE_OPTIONS)]      # relative names: under the output directory
+        out += [f for _, f in _given(opt, ALL_FILE_OPTIONS)]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -761,6 +787,8 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     of the masked rows (set_masked); in a core block row i is file i's.
     --coretree / --corefilteredtree: one BlockFinder.group_bootstrap call each on the rows / the masked rows and the
     tree of its counts (tree.py); a tree that cannot be built is named through `complain` and its file is absent from the result.
+    --coreconsensus / --coreboottrees and --corefilteredconsensus / --corefilteredboottrees: from the same call as the tree of their rows,
+    whose B + 1 matrices go through one BlockFinder.nj_batch call (tree.tree_files); absent with their tree.
     --coremin below the number of files: `core` holds soft_core_blocks, all of the above runs inside a set_partial
     section, the tables get their `# coremin=M` line and the trees divide by group_bootstrap_pairs, the clean columns per pair of files.
     --corepresence: which files every wanted and aligned block has an instance in, from `cls`."""
@@ -784,17 +812,27 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     headers = [b">" + a.encode("latin1") + b"\n" for a in file_names(opt.filenames)]
     out = {}
 
-    def tree_file(o: str):
-        if not any(want):                               # no core block: said above
+    def tree_files(masked: bool):
+        """the tree, the consensus and the replicate trees wanted of the rows (masked: of the masked rows): one group_bootstrap call, and
+        in tree.tree_files one nj_batch call -- a finder without one (more than 64 files go the same way) has its trees joined there"""
+        kinds = ("tree", "consensus", "boottrees")     # the texts of tree.tree_files, in its order
+        given = [(kind, o, getattr(opt, a)) for kind, (o, a) in zip(kinds, ROWS_TREE_OPTIONS[masked]) if getattr(opt, a) is not None]
+        if not given or not any(want):                  # no core block: said above
             return
         counts, nsites, nclean = bf.group_bootstrap(cls, n, opt.bootstrap, opt.bootseed, 0, want)
-        if nsites == 0:
-            complain("%s not written: no variable column in the core-genome alignment\n" % o)
+        why = "no variable column in the core-genome alignment" if nsites == 0 else None
+        if why is None:
+            try:
+                texts = tree.tree_files(counts, bf.group_bootstrap_pairs() if soft else nclean, opt.treemodel, file_names(opt.filenames), getattr(bf, "nj_batch", None),
+                                        [kind for kind, _, _ in given])
+            except (tree.Saturated, tree.NoSharedColumn) as e:
+                why = str(e)
+        if why is not None:
+            for _, o, _ in given:
+                complain("%s not written: %s\n" % (o, why))
             return
-        try:
-            out[getattr(opt, o[2:])] = tree.tree_text(counts, bf.group_bootstrap_pairs() if soft else nclean, opt.treemodel, file_names(opt.filenames)).encode("latin1")
-        except (tree.Saturated, tree.NoSharedColumn) as e:
-            complain("%s not written: %s\n" % (o, e))
+        for kind, _, f in given:
+            out[f] = texts[kinds.index(kind)].encode("latin1")
     try:
         if soft:
             bf.set_partial(True)
@@ -813,8 +851,7 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                 out[opt.coresnps] = text
             if opt.coresites is not None:
                 out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen, coremin)
-        if opt.coretree is not None:
-            tree_file("--coretree")
+        tree_files(False)
         if density_wanted(opt):
             intervals = bf.group_mask(opt.densitywindow, opt.densitymax, want)
             bf.set_masked(True)
@@ -827,8 +864,7 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                         out[opt.corefilteredsnps] = text
                     if opt.corefilteredsites is not None:
                         out[opt.corefilteredsites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen, coremin)
-                if opt.corefilteredtree is not None:
-                    tree_file("--corefilteredtree")
+                tree_files(True)
             finally:
                 bf.set_masked(False)
             if opt.coredense is not None:
@@ -846,7 +882,7 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
         if soft:
             bf.set_partial(False)
     made = {f: out[f] for _, f in _given(opt, CORE_OPTIONS + DENSITY_OPTIONS + PRESENCE_OPTIONS)}
-    made.update({f: out[f] for _, f in _given(opt, TREE_OPTIONS) if f in out})      # a tree that could not be built was named and is absent
+    made.update({f: out[f] for _, f in _given(opt, ALL_TREE_OPTIONS) if f in out})      # a tree that could not be built was named and is absent
     return made
 
 
@@ -888,7 +924,7 @@ def align_block_groups(bf, opt: argparse.Namespace, names: Sequence[str], compla
     --distances / --distancecounts: the pairwise counts of the same alignments (distance_files), written after the two.
     --corealignment / --corepartitions / --coresnps / --coresites: the concatenation of the same alignments (core_files), after those;
     --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense: the same of their masked rows (core_files);
-    --coretree / --corefilteredtree: the trees of the two (core_files), last."""
+    --coretree / --corefilteredtree: the trees of the two (core_files); the consensus and the replicate trees of the two, last."""
     from . import formats
     from .api import GALIGN_OK, SibeliaError
     try:
@@ -1014,7 +1050,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))
     finally:
         bf.close()
-    unbuilt = [f for _, f in _given(opt, TREE_OPTIONS) if f not in files]      # a tree that could not be built was named on standard error
+    unbuilt = [f for _, f in _given(opt, ALL_TREE_OPTIONS) if f not in files]      # a tree that could not be built was named on standard error
     assert list(files) == [f for f in planned_files(opt, len(stages), outdir_exists) if f not in unbuilt]
     return 0, files, "".join(printed)
 

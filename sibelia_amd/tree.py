@@ -2,6 +2,9 @@
 distances from counts, neighbour joining (Studier and Keppler's form of Saitou and Nei's method), the bipartitions of a tree, bootstrap
 support and the canonical Newick text.  numpy only: matrices of files x files belong on the host.  Everything is one fixed sequence of
 float64 operations on integers, so the same counts give the same text, byte for byte.
+--coreconsensus / --coreboottrees: the tally of the replicates' bipartitions, the majority-rule consensus and tree_files,
+which makes every text of one set of counts and may be handed a callable that joins all matrices at once (BlockFinder.nj_batch, the
+same float64 operations on the device); this module never loads the library itself.
 
 A tree is unrooted: leaves 0 .. n - 1 (the files), internal nodes n .., and `edges`, a list of (node, node, length)."""
 from __future__ import annotations
@@ -34,6 +37,16 @@ class NoSharedColumn(ValueError):
 class Tree:
     def __init__(self, n: int, edges):
         self.n, self.edges = n, list(edges)
+
+    @classmethod
+    def of_records(cls, records) -> "Tree":
+        """the tree of one tree's edge records (EDGE_RECORD: 2 n - 3 of them, in the order of `edges`)"""
+        return cls((len(records) + 3) // 2, [(int(u), int(v), float(ln)) for u, v, ln in zip(records["parent"].tolist(), records["child"].tolist(), records["length"].tolist())])
+
+
+# one edge of a tree as the neighbour joining of a batch hands it out (BlockFinder.nj_batch): parent, child, length
+EDGE_RECORD = np.dtype([("parent", "<u4"), ("child", "<u4"), ("length", "<f8")])
+NJ_BATCH_MAX_FILES = 64                            # a callable `nj` takes matrices of at most this many files: its splits are 64-bit masks
 
 
 def check_names(names: Sequence[str]) -> None:
@@ -187,3 +200,103 @@ def tree_text(counts, K, model: str, names: Sequence[str]) -> str:
     main = neighbour_joining(distances(counts[0], K, model, names))
     reps = [neighbour_joining(distances(counts[r], K, model, names)) for r in range(1, B + 1)]
     return newick(main, names, support(main, reps) if B else None, B)
+
+
+def split_tally(splits) -> Dict[int, int]:
+    """the bipartitions of a set of trees, one row of masks per tree (bipartitions' convention: the side without file 0; a tree holds a
+    bipartition once) -> bipartition -> the number of trees that hold it"""
+    flat = np.asarray(splits).ravel()
+    if not len(flat):
+        return {}
+    masks, held = np.unique(flat, return_counts=True)
+    return {int(b): int(k) for b, k in zip(masks.tolist(), held.tolist())}
+
+
+def _edge_lengths_of_records(records):
+    """edge records of shape (trees, 2 n - 3), n <= 64 -> (n, per internal edge of every tree its bipartition as uint64 and its length,
+    both of shape (trees, n - 3); the lengths of the leaf edges, (trees, n)).  Join s = 0 .. n - 4 of a tree is records 2 s and 2 s + 1, whose
+    parent is node n + s: the leaves below a node are those below the two children of its join"""
+    B, ne = records.shape
+    n = (ne + 3) // 2
+    child = records["child"].astype(np.int64)
+    rows = np.arange(B)
+    below = np.zeros((B, 2 * n - 2), dtype=np.uint64)
+    below[:, :n] = np.uint64(1) << np.arange(n, dtype=np.uint64)
+    for s in range(n - 3):
+        below[:, n + s] = below[rows, child[:, 2 * s]] | below[rows, child[:, 2 * s + 1]]
+    full = np.uint64((1 << n) - 1)
+    side = np.take_along_axis(below, child, axis=1)
+    side = np.where(side & np.uint64(1) != 0, full ^ side, side)                # the side without file 0
+    order = np.argsort(child, axis=1, kind="stable")                            # the leaf edges by leaf, then the internal edges by node
+    length = np.take_along_axis(records["length"], order, axis=1)
+    return n, np.take_along_axis(side, order, axis=1)[:, n:], length[:, n:], length[:, :n]
+
+
+def consensus(replicates, B: int):
+    """The majority-rule consensus of B replicate trees: `replicates` is a sequence of B Trees or their edge records of shape
+    (B, 2 n - 3) (EDGE_RECORD).  Its internal edges are the bipartitions that strictly more than half of the replicates hold
+    (2 * count > B); they are pairwise compatible, so they nest by inclusion under a top node that carries file 0.  An edge is as long as
+    the mean of its length in the replicates that hold it (a leaf edge: in all of them), the sum taken with math.fsum, which does not
+    depend on the order of the replicates.  No such bipartition: the star.
+    -> (the tree, {bipartition: the replicates that hold it} for its internal edges): what newick takes as tree and support"""
+    import math
+    if B < 1 or len(replicates) != B:
+        raise ValueError("a consensus takes the %d replicate trees" % B if B >= 1 else "a consensus takes one replicate at least")
+    held: Dict[int, list] = {}                          # a majority bipartition -> its lengths
+    if isinstance(replicates, np.ndarray):
+        n, masks, lengths, leaf_lengths = _edge_lengths_of_records(replicates)
+        uniq, inverse, count = np.unique(masks.ravel(), return_inverse=True, return_counts=True)
+        inverse = np.asarray(inverse).ravel()
+        flat = lengths.ravel()
+        for u in np.nonzero(2 * count > B)[0].tolist():
+            held[int(uniq[u])] = flat[inverse == u].tolist()
+        leaves = [leaf_lengths[:, f].tolist() for f in range(n)]
+    else:
+        n = replicates[0].n
+        leaves = [[] for _ in range(n)]
+        every: Dict[int, list] = {}
+        for t in replicates:
+            r = _Rooted(t)
+            for v in r.internal:
+                every.setdefault(r.mask[v], []).append(r.length[v])
+            for f in range(n):
+                leaves[f].append(r.length[f])
+        held = {b: ls for b, ls in every.items() if 2 * len(ls) > B}
+    inner = sorted(held, key=lambda b: (bin(b).count("1"), b))                  # a bipartition lies inside a later one or beside it
+    node = {b: n + k for k, b in enumerate(inner)}
+    top = n + len(inner)
+
+    def parent(b: int, after: int) -> int:
+        return next((node[c] for c in inner[after:] if b & c == b), top)
+    edges = [(parent(1 << f, 0) if f else top, f, math.fsum(leaves[f]) / B) for f in range(n)]
+    edges += [(parent(b, k + 1), node[b], math.fsum(held[b]) / len(held[b])) for k, b in enumerate(inner)]
+    return Tree(n, edges), {b: len(held[b]) for b in inner}
+
+
+def tree_files(counts, K, model: str, names: Sequence[str], nj=None, want: Sequence[str] = ("tree", "consensus", "boottrees")):
+    """counts, K, model, names: as for tree_text -> (the text of tree_text; the consensus of the B replicate trees as newick writes it
+    with their support; B lines, the unlabelled newick of replicate 1 .. B), None for a text that `want` does not name, and for the
+    consensus without replicates.  nj: a callable, matrices of shape (trees, files, files) -> (edge records (trees, 2 files - 3),
+    bipartitions (trees, files - 3)) that joins like neighbour_joining, bit for bit (BlockFinder.nj_batch): it gets all B + 1 matrices
+    in one call.  Without it, and above 64 files, every matrix goes through neighbour_joining here: the same texts, byte for byte.  The
+    distances are made here either way, slab after slab, so Saturated and NoSharedColumn rise as they do from tree_text"""
+    B = len(counts) - 1
+    D = np.stack([distances(counts[r], K, model, names) for r in range(B + 1)])
+    n = D.shape[1]
+    boot = B and "boottrees" in want
+    if nj is not None and n <= NJ_BATCH_MAX_FILES:
+        records, splits = nj(D)
+        main = Tree.of_records(records[0])
+        tally = split_tally(splits[1:]) if "tree" in want else {}
+        reps = [Tree.of_records(records[r]) for r in range(1, B + 1)] if boot else records[1:]
+    else:
+        trees = [neighbour_joining(D[r]) for r in range(B + 1)]
+        main, reps = trees[0], trees[1:]
+        tally = split_tally(np.array([b for t in reps for b in bipartitions(t)], dtype=object)) if "tree" in want else {}
+    text = newick(main, names, {b: tally.get(b, 0) for b in bipartitions(main)} if B else None, B) if "tree" in want else None
+    majority = None
+    if B and "consensus" in want:
+        ctree, held = consensus(reps, B)
+        majority = newick(ctree, names, held, B)
+    lines = "".join(newick(t, names) for t in reps) if boot else None
+    return text, majority, lines
