@@ -644,6 +644,39 @@ sbl_status sbl_nj_batch(sbl_ctx *ctx, const double *D /* ntrees * n * n, row-maj
                         const sbl_nj_edge **edges /* ntrees * (2n - 3) */, const uint64_t **splits /* ntrees * (n - 3) */);
 sbl_status sbl_nj_batch_times(const sbl_ctx *ctx, double *kernel_ms, double *copy_ms /* upload + copy-back */);
 
+/* Fitch parsimony of the sites on a tree (csrc/group_parsimony.hip), defined by this project: which site changes on
+ * which branch.  The SITES 0 .. C - 1 are those of the context's LAST successful sbl_group_bootstrap call, read where that call left
+ * them packed on the device (2 bits per class, presence words under sbl_group_set_partial); its nclass, C and partial setting are taken
+ * from the context.  sbl_group_concat, sbl_group_variants, sbl_group_distances, sbl_group_mask and sbl_nj_batch may run in between
+ * without changing the result.  Everything is integers.
+ * THE TREE.  Unrooted and binary over leaves 0 .. n - 1 (the classes) and internal nodes n .. 2 n - 3, given as 2 n - 3 edges; an edge's
+ * two nodes may stand in either order and its length is ignored.  It is read from leaf 0: `top` is the internal node next to leaf 0,
+ * every node but leaf 0 has a parent, parent(top) is leaf 0, every internal node has two children.
+ * SETS.  The code of a base is (ch >> 1) & 3: A = 0, C = 1, T = 2, G = 3.  A present leaf's set is 1 << code; under the partial setting a
+ * leaf whose class the site's group does not hold has the set 0xF.
+ * BOTTOM-UP.  Internal v with children a, b: S(v) = S(a) & S(b) if that is not 0, else S(a) | S(b) and the site takes one step.  Then,
+ * with R = S(leaf 0), the site takes one more step if R & S(top) == 0.
+ * TOP-DOWN.  The state of leaf 0 is its base; of an absent leaf 0, the lowest code in S(top).  Every other node takes its parent's state
+ * if S(v) holds it, else the lowest code in S(v): an absent leaf takes its parent's state and carries no change.
+ * CHANGES.  One lies on the edge (parent(v), v) at a site iff the two states differ; from is the parent's state -- the side of leaf 0 --
+ * and to the child's.  A site has as many changes as steps.  changes: all of them in ascending (site, edge), edge the index into the
+ * caller's edges.  edge_counts[edge][from * 4 + to]: the changes of the edge by kind, the diagonal 0.  steps[site]; minsteps[site]: the
+ * distinct bases among the site's present leaves minus 1 (none present: 0); a site with steps > minsteps is homoplasic.
+ * One lane per site: k_fitch_steps (sets in LDS, steps and minsteps), an exclusive scan of the steps to the offsets of the sites'
+ * records, k_fitch_changes (bottom-up again, top-down, the records and a histogram per workgroup, flushed with 64-bit integer adds).
+ * All four arrays are owned by the ctx until the next successful sbl_group_parsimony.  C == 0 is a result: nothing is launched, steps,
+ * minsteps and changes are empty and the counts 0.  A refused call leaves the result of an earlier call valid.
+ * SBL_ERR_BAD_ARG, checked on the host before any launch: no successful sbl_group_bootstrap call; n is not that call's nclass; n < 3; an
+ * out pointer or edges is NULL; an edge names a node >= 2 n - 2; the edges are not a tree in which every leaf has degree 1 and every
+ * internal node degree 3.  SBL_ERR_TOO_LARGE: n > 64 (the limit of sbl_nj_batch and of 64-bit file masks), before any launch; a change
+ * list above 1 GiB (2^26 changes), known after the first pass and the scan.
+ * sbl_group_parsimony_times: device time of the last call's two passes and scan and of the device-to-host copies (event pairs). */
+typedef struct { uint64_t site; uint32_t edge; uint8_t from, to, pad_[2]; } sbl_parsimony_change;
+sbl_status sbl_group_parsimony(sbl_ctx *ctx, const sbl_nj_edge *edges /* 2n - 3 */, uint32_t n,
+                               const uint64_t **edge_counts /* (2n - 3) * 16 */, const uint8_t **steps /* C */, const uint8_t **minsteps /* C */,
+                               const sbl_parsimony_change **changes, uint64_t *nchanges);
+sbl_status sbl_group_parsimony_times(const sbl_ctx *ctx, double *kernel_ms, double *copyback_ms);
+
 /* The calls C-Sibelia.py makes from the regions no block covers (src/csibelia/C-Sibelia.py:325-338, :373-427), by
  * interval bookkeeping on the host (csrc/uncovered.hip).  `blocks` holds nlists block lists one after the other -- list l is
  * blocks[list_first[l], list_first[l + 1]) (nlists + 1 ascending offsets, the first one 0) -- the lists of the stages in order, the LAST

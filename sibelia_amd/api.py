@@ -33,7 +33,7 @@ EXPORTS = ["sbl_create", "sbl_destroy", "sbl_load", "sbl_enumerate", "sbl_simpli
            "sbl_align_set_wide", "sbl_align_get_wide", "sbl_align_wide_stats",
            "sbl_uncovered_calls", "sbl_spell_text", "sbl_spell_text_times", "sbl_group_variants", "sbl_group_variants_times", "sbl_group_distances", "sbl_group_distances_times",
            "sbl_group_concat", "sbl_group_concat_times", "sbl_group_mask", "sbl_group_mask_times", "sbl_group_set_masked", "sbl_group_get_masked", "sbl_group_bootstrap", "sbl_group_bootstrap_times", "sbl_tiny_index",
-           "sbl_group_set_partial", "sbl_group_get_partial", "sbl_group_bootstrap_pairs", "sbl_nj_batch", "sbl_nj_batch_times",
+           "sbl_group_set_partial", "sbl_group_get_partial", "sbl_group_bootstrap_pairs", "sbl_nj_batch", "sbl_nj_batch_times", "sbl_group_parsimony", "sbl_group_parsimony_times",
            "sbl_test_touched_list", "sbl_test_graph_build", "sbl_test_graph_fetch"]
 
 ALIGN_MAX_LEN = 2047                               # SBL_ALIGN_MAX_LEN
@@ -158,6 +158,13 @@ class NjEdge(C.Structure):                         # sbl_nj_edge
 NJ_EDGE_DTYPE = np.dtype([("parent", "<u4"), ("child", "<u4"), ("length", "<f8")])      # tree.EDGE_RECORD
 
 
+class ParsimonyChange(C.Structure):                # sbl_parsimony_change
+    _fields_ = [("site", C.c_uint64), ("edge", C.c_uint32), ("from_", C.c_uint8), ("to", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+PARSIMONY_CHANGE_DTYPE = np.dtype([("site", "<u8"), ("edge", "<u4"), ("from", "u1"), ("to", "u1"), ("pad_", "u1", (2,))])
+
+
 class GroupAlignment:
     """One sbl_group_result: status (GALIGN_OK / GALIGN_SKIPPED), L, row_off, the rows (centre first, members in the order given) and
     per member (score, band_w, passes).  A skipped group has L = 0, no rows and member scores None."""
@@ -267,6 +274,9 @@ def load_library():
         L.sbl_group_get_masked.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.sbl_nj_batch.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(NjEdge)), C.POINTER(C.POINTER(C.c_uint64))]
         L.sbl_nj_batch_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.sbl_group_parsimony.argtypes = [C.c_void_p, C.POINTER(NjEdge), C.c_uint32, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint8)),
+                                          C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(ParsimonyChange)), C.POINTER(C.c_uint64)]
+        L.sbl_group_parsimony_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.sbl_comm_unique_id.argtypes = [C.c_void_p]
         L.sbl_comm_attach_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.sbl_group_create_local.argtypes = [C.c_uint32]
@@ -681,7 +691,7 @@ class BlockFinder:
         self._check(self.L.sbl_group_bootstrap(self.h, mask, arr, int(nclass), int(replicates), int(seed), int(draws), C.byref(out), C.byref(nsites), C.byref(nclean)),
                     "sbl_group_bootstrap")
         n, b = int(nclass), int(replicates) + 1
-        self._boot_nclass = n
+        self._boot_nclass, self._boot_sites = n, nsites.value
         return _view(C.cast(out, C.c_void_p).value, b * n * n, np.dtype("<u8")).reshape(b, n, n), nsites.value, nclean.value
 
     def group_bootstrap_times(self) -> Tuple[float, float]:
@@ -719,6 +729,34 @@ class BlockFinder:
     def nj_batch_times(self) -> Tuple[float, float]:
         """(kernel ms, ms of the uploads of the matrices and the copies of the results) of the last nj_batch call, from event pairs."""
         return self._times("sbl_nj_batch_times")
+
+    def group_parsimony(self, edges):
+        """Fitch parsimony of the sites of the LAST group_bootstrap call on a tree (csrc/group_parsimony.hip; defined in
+        include/sibelia_amd.h), read from the packed sites that call left on the device.  edges: the 2 n - 3 edges of an
+        unrooted binary tree over leaves 0 .. n - 1 (that call's classes) and internal nodes n .. 2 n - 3: a structured array with parent
+        and child (NJ_EDGE_DTYPE, a row of nj_batch) or a sequence of (node, node[, length]); lengths are ignored, 3 <= n <= 64.
+        -> (uint64 array (2 n - 3, 4, 4): per edge the changes [from, to], from on the side of leaf 0, bases coded A C T G = 0 1 2 3;
+        uint8 array (C,): the steps of every site; uint8 array (C,): the least steps its bases allow; structured array
+        (PARSIMONY_CHANGE_DTYPE: site, edge, from, to) of all changes in ascending (site, edge)).  All are copies."""
+        if isinstance(edges, np.ndarray) and edges.dtype.names:
+            pairs = list(zip(edges["parent"].tolist(), edges["child"].tolist()))
+        else:
+            pairs = [(e[0], e[1]) for e in edges]
+        if (len(pairs) + 3) % 2 or any(not 0 <= int(x) <= 2 ** 32 - 1 for e in pairs for x in e):
+            raise SibeliaError("sbl_group_parsimony: bad argument (a tree of n leaves has 2 n - 3 edges between nodes of 32 bits)")
+        n = (len(pairs) + 3) // 2
+        arr = (NjEdge * max(1, len(pairs)))(*[NjEdge(int(u), int(v), 0.0) for u, v in pairs])
+        counts, steps, least, changes = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint8)(), C.POINTER(ParsimonyChange)()
+        nchanges = C.c_uint64()
+        self._check(self.L.sbl_group_parsimony(self.h, arr, n, C.byref(counts), C.byref(steps), C.byref(least), C.byref(changes), C.byref(nchanges)), "sbl_group_parsimony")
+        nsites = self._boot_sites                                                # the sites of the last successful group_bootstrap call
+        return (_view(C.cast(counts, C.c_void_p).value, (2 * n - 3) * 16, np.dtype("<u8")).reshape(2 * n - 3, 4, 4),
+                _view(C.cast(steps, C.c_void_p).value, nsites, np.dtype("u1")), _view(C.cast(least, C.c_void_p).value, nsites, np.dtype("u1")),
+                _view(C.cast(changes, C.c_void_p).value, nchanges.value, PARSIMONY_CHANGE_DTYPE))
+
+    def group_parsimony_times(self) -> Tuple[float, float]:
+        """(kernel ms of the two passes and the scan, device-to-host copy ms of the four arrays) of the last group_parsimony call."""
+        return self._times("sbl_group_parsimony_times")
 
     def set_partial(self, on) -> None:
         """True: every later group_concat / group_bootstrap call of this finder uses the groups that hold every class AT MOST once (the

@@ -22,7 +22,9 @@
 //   host      every argument is checked before any launch (the checks and the walk of sbl_groups.h); the slabs of a batch live in a device
 //             buffer of at most GB_BUDGET bytes (SBL_TEST_BOOT_BUDGET_KB: test switch) and come back into the context's host array batch
 //             after batch; one synchronise per batch, none per replicate.  SBL_TEST_BOOT_MAX_SITES: test switch, the limit on C.  Both
-//             switches are for the tests only: read per call, a value below 1 or not a number counts as 1.
+//             switches are for the tests only: read per call, a value below 1 or not a number counts as 1.  The packed sites stay in
+//             d_gb_pack after the call, with their classes, their number and the partial setting recorded in the context
+//             (gb_pack_valid): sbl_group_parsimony (group_parsimony.hip) reads them, no other call writes that buffer.
 //   partial   under sbl_group_set_partial a used group holds every class at most once: the flags walk the rows the group
 //             has, k_boot_clean_groups counts the clean columns per used group (the host folds them into the clean columns per pair of
 //             classes, sbl_group_bootstrap_pairs), k_boot_pack<true> writes a presence word beside every base word and k_boot_count<true>
@@ -263,6 +265,7 @@ extern "C" sbl_status sbl_group_bootstrap(sbl_ctx *c, const uint8_t *want, const
 			// a batch: whole slabs within the budget (one at least) and within one launch's grid
 			const u64 batch = std::max<u64>(1, std::min(gb_env("SBL_TEST_BOOT_BUDGET_KB", 1024, GB_BUDGET) / (cells * 8), GB_MAX_BLOCKS / nchunks));
 			al_upload(c, c->d_gc_roff, roff);
+			c->gb_pack_valid = false;                                            // the packed sites of the call before are written over from here on
 			c->d_gb_pack.ensure((size_t)(C * W) * (partial ? 16 : 8));
 			const auto pack = partial ? k_boot_pack<true> : k_boot_pack<false>;
 			const auto count = partial ? k_boot_count<true> : k_boot_count<false>;
@@ -308,6 +311,8 @@ extern "C" sbl_status sbl_group_bootstrap(sbl_ctx *c, const uint8_t *want, const
 			}
 		}
 		c->gb_pairs_valid = true;
+		c->gb_pack_valid = true;                                                // d_gb_pack holds the C sites of this call: what sbl_group_parsimony reads
+		c->gb_pack_nclass = nclass; c->gb_pack_partial = partial; c->gb_pack_sites = C;
 		c->stats.device_bytes = sbl_devbuf_total().load();
 		*counts = c->gb_counts.data();
 		if (nsites) *nsites = C;

@@ -157,6 +157,18 @@ struct sbl_ctx {
 	bool gb_pairs_valid = false;
 	uint32_t gp_partial = 0;
 	SblTimes gb_times;                   // the kernels of all phases / the copies of the slabs
+	// sbl_group_parsimony (group_parsimony.hip) reads d_gb_pack as the last successful sbl_group_bootstrap call left it: no other call
+	// writes that buffer, and sbl_group_bootstrap clears gb_pack_valid before it packs anew and sets it, with the classes, the sites and
+	// the partial setting of the packed words, where it succeeds.  The schedule of the tree, steps (one byte behind the sites: a 0 for the
+	// scan's total), minsteps, offsets, changes and the counts per edge on the device; what the last successful call hands out
+	bool gb_pack_valid = false;
+	uint32_t gb_pack_nclass = 0, gb_pack_partial = 0;
+	uint64_t gb_pack_sites = 0;
+	DevBuf d_gf_sched, d_gf_steps, d_gf_min, d_gf_off, d_gf_changes, d_gf_counts, d_gf_tmp;
+	std::vector<uint64_t> gf_counts;
+	std::vector<uint8_t> gf_steps, gf_min;
+	std::vector<sbl_parsimony_change> gf_changes;
+	SblTimes gf_times;                   // the two passes and the scan / the copies of the four arrays
 	// sbl_nj_batch (tree_nj.hip): the matrices, edges and splits of one batch on the device; the edges and splits of all matrices of the
 	// last call.  Nothing here is shared with the sbl_group_* calls
 	DevBuf d_nj_in, d_nj_edges, d_nj_splits;

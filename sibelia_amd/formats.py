@@ -305,6 +305,44 @@ def core_sites_text(rows: Sequence[Tuple[int, str, int, int, bool, int]], gap_op
     return ("\n".join(out) + "\n").encode("latin1")
 
 
+CORE_BRANCHES_COLUMNS = ("branch", "files", "length", "support", "changes", "transitions", "transversions")
+CORE_BRANCH_SITES_COLUMNS = CORE_SITES_COLUMNS + ("branch", "from", "to", "steps", "minsteps")
+PARSIMONY_BASES = "ACTG"                          # the base of a code (ch >> 1) & 3
+PARSIMONY_TRANSITIONS = ((0, 3), (3, 0), (1, 2), (2, 1))      # A <-> G, C <-> T as (from, to)
+
+
+def parsimony_summary(steps, minsteps) -> str:
+    """the line `# sites=C steps=S minsteps=M homoplasic=H ci=X` of --corebranches / --corebranchsites: the sums over the sites, the
+    sites with more steps than their bases need, and the consistency index M / S by the rounding of p_distance_text, nan for S = 0"""
+    S, M = sum(int(x) for x in steps), sum(int(x) for x in minsteps)
+    H = sum(int(a) > int(b) for a, b in zip(steps, minsteps))
+    return "# sites=%d steps=%d minsteps=%d homoplasic=%d ci=%s" % (len(steps), S, M, H, p_distance_text(S - M, M))
+
+
+def core_branches_text(rows, steps, minsteps, gap_open: int = 0, coremin: int = 0) -> bytes:
+    """The file of --corebranches: tab-separated; the comment lines of core_partitions_text, the line of
+    parsimony_summary, a line of column names, then one line per branch in the order given, numbered from 1.  rows: (the names of the
+    files below the branch, its length, its support label or None, its 4 x 4 counts of changes [from][to])."""
+    out = _core_comments(gap_open, coremin) + [parsimony_summary(steps, minsteps), "\t".join(CORE_BRANCHES_COLUMNS)]
+    for i, (files, length, label, counts) in enumerate(rows):
+        changes = sum(int(x) for row in counts for x in row)
+        transitions = sum(int(counts[a][b]) for a, b in PARSIMONY_TRANSITIONS)
+        out.append("%d\t%s\t%.9f\t%s\t%d\t%d\t%d" % (i + 1, ",".join(files), length, "." if label is None else label, changes, transitions, changes - transitions))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
+def core_branch_sites_text(site_rows, changes, steps, minsteps, gap_open: int = 0, coremin: int = 0) -> bytes:
+    """The file of --corebranchsites: tab-separated; the same comment lines and summary, a line of column names, then
+    one line per change in the order given (column, then branch).  site_rows: the rows of core_sites_text, whose fields open the line;
+    changes: (site counted from 0, branch counted from 1, code from, code to)."""
+    out = _core_comments(gap_open, coremin) + [parsimony_summary(steps, minsteps), "\t".join(CORE_BRANCH_SITES_COLUMNS)]
+    for site, branch, a, b in changes:
+        block, record, start, end, rev, before = site_rows[site]
+        out.append("%d\t%d\t%s\t%d\t%s\t%d\t%s\t%s\t%d\t%d" % (site + 1, block, record, end - before if rev else start + before + 1, "-" if rev else "+", branch,
+                                                                 PARSIMONY_BASES[a], PARSIMONY_BASES[b], steps[site], minsteps[site]))
+    return ("\n".join(out) + "\n").encode("latin1")
+
+
 CORE_DENSE_COLUMNS = ("file", "block", "record", "first", "last", "strand", "differences", "first_column", "last_column")
 
 

@@ -25,7 +25,10 @@ turns the core of all of these into the soft core -- blocks with instances in at
 two alignments in Newick format, with --bootstrap B the support of B replicates whose pair counts are made on the device (DESIGN.md 0.11;
 `tree.py`).  --coreconsensus / --corefilteredconsensus write the majority-rule consensus of those B replicate trees and --coreboottrees /
 --corefilteredboottrees the replicate trees themselves; all B + 1 matrices of a run are joined on the device in one call, up to 64 input
-files.  --uncovered adds the rest of C-Sibelia's VCF to
+files.  --corebranches / --corebranchsites / --coresnptree and their
+--corefiltered... twins (three to 64 input files) map the columns of --coresnps onto the branches of that tree by Fitch parsimony on the
+device: a table of the branches with their changes, a table of the changes, and the tree with the changes as lengths.
+--uncovered adds the rest of C-Sibelia's VCF to
 the file of --variants: the deletions and insertions read off the regions no block covers and the breakend records of the insertions
 that cannot be placed (--unmapped FILE: those as FASTA instead); the alleles are spelled on the device (`uncovered_files`).
 
@@ -133,6 +136,23 @@ COREBOOTTREES_HELP = ("Three or more input files, with --bootstrap B of 1 or mor
                       "line each in the order of the replicates, without labels: the input of an external consensus or summary program.")
 COREFILTEREDBOOTTREES_HELP = "The same replicate trees from the replicates of --corefilteredtree."
 
+PARSIMONY_MAX_FILES = 64
+COREBRANCHES_HELP = ("Three to 64 input files: map the columns of --coresnps onto the tree of --coretree by Fitch parsimony, on the device, and write "
+                     "one line per branch as tab-separated text, in the order the tree's text visits them: its number, the files below it, its "
+                     "length and support as in --coretree ('.' on a branch to a file and without --bootstrap), and the changes it carries, split "
+                     "into transitions (A-G, C-T) and transversions.  The tree is read from the first file; where several bases are equally "
+                     "good for an inner node it takes its parent's, else the first of A C T G.  A comment line gives the sites, their steps, the "
+                     "least their bases allow, the homoplasic sites (more steps than that) and the consistency index.  Not written "
+                     "where --coretree is not.")
+COREFILTEREDBRANCHES_HELP = "The same table from the columns of --corefilteredsnps on the tree of --corefilteredtree."
+COREBRANCHSITES_HELP = ("Three to 64 input files: write the changes themselves as tab-separated text, one line per change by column, then branch: "
+                        "the column's fields of --coresites, the branch as numbered in --corebranches, the base on the side of the first file, "
+                        "the base on the other side, and the column's steps and least steps.")
+COREFILTEREDBRANCHSITES_HELP = "The same table for --corefilteredsnps, its leading fields those of --corefilteredsites."
+CORESNPTREE_HELP = ("Three to 64 input files: write the tree of --coretree, same order and support labels, with every branch as long as the "
+                    "number of changes it carries: a SNP-scaled tree.")
+COREFILTEREDSNPTREE_HELP = "The same tree from --corefilteredtree and --corefilteredsnps."
+
 COREMIN_HELP = ("With any of the --core..., --corefiltered... and tree options or --corepresence: the soft core.  Use the blocks with instances "
                 "in at least M input files, 2 .. the number of files, default the number of files: the strict core.  Below it a block is "
                 "used if all its instances are at least the minimum block size long, exactly one lies in the first file, at most one in "
@@ -155,10 +175,18 @@ FILE_OPTIONS = (("--maf", "maf"), ("--variants", "variants"), ("--unmapped", "un
 # replicate trees of the two.  ROWS_TREE_OPTIONS: per kind of rows its tree, consensus and replicate trees
 REPLICATE_OPTIONS = (("--coreconsensus", "coreconsensus"), ("--corefilteredconsensus", "corefilteredconsensus"),
                      ("--coreboottrees", "coreboottrees"), ("--corefilteredboottrees", "corefilteredboottrees"))
-ALL_TREE_OPTIONS = TREE_OPTIONS + REPLICATE_OPTIONS
+# the files of the parsimony mapping on the tree, written after all of those: the branch tables of the plain and of the
+# masked rows, then the change tables, then the SNP-scaled trees.  ROWS_BRANCH_OPTIONS: per kind of rows its three
+BRANCH_OPTIONS = (("--corebranches", "corebranches"), ("--corefilteredbranches", "corefilteredbranches"),
+                  ("--corebranchsites", "corebranchsites"), ("--corefilteredbranchsites", "corefilteredbranchsites"),
+                  ("--coresnptree", "coresnptree"), ("--corefilteredsnptree", "corefilteredsnptree"))
+ALL_TREE_OPTIONS = TREE_OPTIONS + REPLICATE_OPTIONS + BRANCH_OPTIONS
 ROWS_TREE_OPTIONS = {False: (TREE_OPTIONS[0], REPLICATE_OPTIONS[0], REPLICATE_OPTIONS[2]), True: (TREE_OPTIONS[1], REPLICATE_OPTIONS[1], REPLICATE_OPTIONS[3])}
+ROWS_BRANCH_OPTIONS = {False: BRANCH_OPTIONS[0::2], True: BRANCH_OPTIONS[1::2]}
 ALL_FILE_OPTIONS = FILE_OPTIONS + REPLICATE_OPTIONS
 GROUP_OPTIONS, NAMED_FILE_OPTIONS = ALL_FILE_OPTIONS[3:], ALL_FILE_OPTIONS[5:]
+# ... and with the files of the mapping: every file made from alignments, in the order they are written
+EVERY_FILE_OPTIONS = ALL_FILE_OPTIONS + BRANCH_OPTIONS
 
 UNCOVERED_HELP = ("With --variants and --allstages: add what the reference's comparison tool calls from the regions that no block with an "
                   "instance in both input files covers, at any stage: a region of the first file longer than the minimum block size as "
@@ -332,6 +360,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--corefilteredconsensus", default=None, metavar="FILE", help=COREFILTEREDCONSENSUS_HELP)
     p.add_argument("--coreboottrees", default=None, metavar="FILE", help=COREBOOTTREES_HELP)
     p.add_argument("--corefilteredboottrees", default=None, metavar="FILE", help=COREFILTEREDBOOTTREES_HELP)
+    p.add_argument("--corebranches", default=None, metavar="FILE", help=COREBRANCHES_HELP)
+    p.add_argument("--corefilteredbranches", default=None, metavar="FILE", help=COREFILTEREDBRANCHES_HELP)
+    p.add_argument("--corebranchsites", default=None, metavar="FILE", help=COREBRANCHSITES_HELP)
+    p.add_argument("--corefilteredbranchsites", default=None, metavar="FILE", help=COREFILTEREDBRANCHSITES_HELP)
+    p.add_argument("--coresnptree", default=None, metavar="FILE", help=CORESNPTREE_HELP)
+    p.add_argument("--corefilteredsnptree", default=None, metavar="FILE", help=COREFILTEREDSNPTREE_HELP)
     p.add_argument("--coremin", type=_unsigned, default=None, metavar="M", help=COREMIN_HELP)
     p.add_argument("--corepresence", default=None, metavar="FILE", help=COREPRESENCE_HELP)
     p.add_argument("--bootstrap", type=_bounded(0, BOOTSTRAP_MAX), default=None, metavar="B", help=BOOTSTRAP_HELP)
@@ -367,7 +401,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         for a in sorted(set(samples)):
             if samples.count(a) > 1:
                 raise PipelineError("--multivariants names a sample by its file's base name: two files are called %s" % a)
-    for o, _ in _given(opt, NAMED_FILE_OPTIONS):
+    for o, _ in _given(opt, NAMED_FILE_OPTIONS + BRANCH_OPTIONS):
         if len(opt.filenames) < 2:                             # before any file is read
             raise PipelineError("%s compares files: it needs at least two" % o)
         if opt.noblocks:
@@ -388,6 +422,9 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
             tree.check_names(file_names(opt.filenames))
         except ValueError as e:
             raise PipelineError("%s names a file by its base name: %s" % (o, e))
+    for o, _ in _given(opt, BRANCH_OPTIONS):
+        if len(opt.filenames) > PARSIMONY_MAX_FILES:           # before anything runs: the mapping on the device takes 64-bit file masks
+            raise PipelineError("%s maps the changes onto the tree on the device, which takes at most %d input files: %d are given" % (o, PARSIMONY_MAX_FILES, len(opt.filenames)))
     for o, v in (("--bootstrap", opt.bootstrap), ("--bootseed", opt.bootseed), ("--treemodel", opt.treemodel)):
         if v is not None and not tree_wanted(opt):
             raise PipelineError("%s is a setting of the tree: it needs at least one of --coretree and --corefilteredtree" % o)
@@ -416,7 +453,7 @@ def parse_args(argv: Sequence[str]) -> argparse.Namespace:
         opt.coremin = len(opt.filenames)
     opt.densitywindow = opt.densitywindow or DENSITYWINDOW_DEFAULT
     opt.densitymax = opt.densitymax or DENSITYMAX_DEFAULT
-    aligns = bool(_given(opt, ALL_FILE_OPTIONS))    # --unmapped is given with --variants only
+    aligns = bool(_given(opt, EVERY_FILE_OPTIONS))    # --unmapped is given with --variants only
     if opt.gapopen is not None and not aligns:
         raise PipelineError("--gapopen sets a cost of the alignments: it needs at least one of --maf, --variants and --multimaf")
     opt.gapopen = opt.gapopen or 0                  # not given: 0, the linear gap cost
@@ -448,13 +485,13 @@ def core_wanted(opt: argparse.Namespace) -> bool:
 
 
 def density_wanted(opt: argparse.Namespace) -> bool:
-    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given, or --corefilteredtree, --corefilteredconsensus or
-    --corefilteredboottrees, which read the same masked rows."""
-    return bool(_given(opt, DENSITY_OPTIONS)) or bool(_given(opt, ROWS_TREE_OPTIONS[True]))
+    """One of --corefiltered / --corefilteredsnps / --corefilteredsites / --coredense is given, or --corefilteredtree, --corefilteredconsensus,
+    --corefilteredboottrees or one of --corefilteredbranches / --corefilteredbranchsites / --corefilteredsnptree, which read the same masked rows."""
+    return bool(_given(opt, DENSITY_OPTIONS)) or bool(_given(opt, ROWS_TREE_OPTIONS[True] + ROWS_BRANCH_OPTIONS[True]))
 
 
 def tree_wanted(opt: argparse.Namespace) -> bool:
-    """One of --coretree / --corefilteredtree or of the four files made of their replicates is given."""
+    """One of --coretree / --corefilteredtree, of the four files made of their replicates or of the six of the parsimony mapping is given."""
     return bool(_given(opt, ALL_TREE_OPTIONS))
 
 
@@ -471,7 +508,7 @@ def concat_wanted(opt: argparse.Namespace) -> bool:
 def _check_alignment_files(opt: argparse.Namespace) -> None:
     """--maf / --variants / --unmapped / --multimaf / --multivariants / --distances / --distancecounts, the four --core options, the four of the density filter and the two trees name files of their own: not each other and not a file the run writes anyway."""
     where = lambda f: os.path.normpath(os.path.join(os.path.abspath(opt.outdir), f))      # noqa: E731
-    given = _given(opt, ALL_FILE_OPTIONS)
+    given = _given(opt, EVERY_FILE_OPTIONS)
     for o, f in given:
         if not f or f.endswith(("/", os.sep)) or os.path.basename(os.path.normpath(f)) in ("", ".", ".."):
             raise PipelineError("%s needs a file name, not '%s'" % (o, f))
@@ -537,7 +574,7 @@ def planned_files(opt: argparse.Namespace, nstages: int, outdir_exists: bool = F
         out += ["genomes_permutations.txt", "coverage_report.txt"]
         if opt.sequencesfile:
             out.append("blocks_sequences.fasta")
-        out += [f for _, f in _given(opt, ALL_FILE_OPTIONS)]      # relative names: under the output directory
+        out += [f for _, f in _given(opt, EVERY_FILE_OPTIONS)]      # relative names: under the output directory
     if opt.graphfile:
         out.append("de_bruijn_graph%s.dot" % (str(nstages) if opt.allstages else ""))
     return out
@@ -791,7 +828,9 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
     whose B + 1 matrices go through one BlockFinder.nj_batch call (tree.tree_files); absent with their tree.
     --coremin below the number of files: `core` holds soft_core_blocks, all of the above runs inside a set_partial
     section, the tables get their `# coremin=M` line and the trees divide by group_bootstrap_pairs, the clean columns per pair of files.
-    --corepresence: which files every wanted and aligned block has an instance in, from `cls`."""
+    --corepresence: which files every wanted and aligned block has an instance in, from `cls`.
+    --corebranches / --corebranchsites / --coresnptree and their filtered twins: after the tree of their rows, from the same group_bootstrap
+    call and its main tree, one BlockFinder.group_parsimony call; absent with their tree."""
     from . import formats, tree
     from .api import CONCAT_ALL, CONCAT_VARIABLE, GALIGN_OK, SibeliaError
     file_of = _file_of_record(bf.file_records)
@@ -817,22 +856,49 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
         in tree.tree_files one nj_batch call -- a finder without one (more than 64 files go the same way) has its trees joined there"""
         kinds = ("tree", "consensus", "boottrees")     # the texts of tree.tree_files, in its order
         given = [(kind, o, getattr(opt, a)) for kind, (o, a) in zip(kinds, ROWS_TREE_OPTIONS[masked]) if getattr(opt, a) is not None]
-        if not given or not any(want):                  # no core block: said above
+        mapped = [(kind, o, getattr(opt, a)) for kind, (o, a) in zip(("branches", "branchsites", "snptree"), ROWS_BRANCH_OPTIONS[masked]) if getattr(opt, a) is not None]
+        if not (given or mapped) or not any(want):      # no core block: said above
             return
         counts, nsites, nclean = bf.group_bootstrap(cls, n, opt.bootstrap, opt.bootseed, 0, want)
         why = "no variable column in the core-genome alignment" if nsites == 0 else None
+        keep = {}
         if why is None:
             try:
                 texts = tree.tree_files(counts, bf.group_bootstrap_pairs() if soft else nclean, opt.treemodel, file_names(opt.filenames), getattr(bf, "nj_batch", None),
-                                        [kind for kind, _, _ in given])
+                                        [kind for kind, _, _ in given] + (["tree"] if mapped else []), keep)
             except (tree.Saturated, tree.NoSharedColumn) as e:
                 why = str(e)
         if why is not None:
-            for _, o, _ in given:
+            for _, o, _ in given + mapped:
                 complain("%s not written: %s\n" % (o, why))
             return
         for kind, _, f in given:
             out[f] = texts[kinds.index(kind)].encode("latin1")
+        if mapped:
+            branch_files(keep["tree"], keep["support"], site_rows.get(masked), mapped)
+
+    def branch_files(main, held, rows, mapped):
+        """the branch table, the change table and the SNP-scaled tree of the main tree: one BlockFinder.group_parsimony
+        call on the sites the group_bootstrap call before it left packed on the device, with the edges of the tree that call's counts gave"""
+        ecounts, steps, least, changes = bf.group_parsimony([(u, v) for u, v, _ in main.edges])
+        order = tree.branches(main)
+        files = file_names(opt.filenames)
+        number = {e: k + 1 for k, (_, e, _, _) in enumerate(order)}
+        steps, least = steps.tolist(), least.tolist()
+        for kind, _, f in mapped:
+            if kind == "branches":
+                out[f] = formats.core_branches_text(
+                    [([files[x] for x in range(n) if mask >> x & 1], length, tree.support_label(held.get(mask, 0), opt.bootstrap) if held is not None and v >= n else None,
+                      ecounts[e].tolist()) for v, e, mask, length in order], steps, least, opt.gapopen, coremin)
+            elif kind == "branchsites":
+                found = sorted(zip(changes["site"].tolist(), [number[e] for e in changes["edge"].tolist()], changes["from"].tolist(), changes["to"].tolist()))
+                out[f] = formats.core_branch_sites_text(rows, found, steps, least, opt.gapopen, coremin)
+            else:
+                out[f] = tree.newick(main, files, held, opt.bootstrap, {v: int(ecounts[e].sum()) for v, e, _, _ in order}).encode("latin1")
+
+    def site_rows_of(sites):
+        return [(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites]
+    site_rows = {}                                      # masked -> the rows of formats.core_sites_text of that kind of rows
     try:
         if soft:
             bf.set_partial(True)
@@ -845,12 +911,13 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
                 out[opt.corealignment] = text
             if opt.corepartitions is not None:
                 out[opt.corepartitions] = formats.core_partitions_text([(ids[g], first, ncols) for g, first, ncols in parts], opt.gapopen, coremin)
-        if opt.coresnps is not None or opt.coresites is not None:
+        if opt.coresnps is not None or opt.coresites is not None or opt.corebranchsites is not None:
             text, _, sites = bf.group_concat(cls, n, headers, CONCAT_VARIABLE, formats.CORE_WIDTH, want)
+            site_rows[False] = site_rows_of(sites)
             if opt.coresnps is not None:
                 out[opt.coresnps] = text
             if opt.coresites is not None:
-                out[opt.coresites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen, coremin)
+                out[opt.coresites] = formats.core_sites_text(site_rows[False], opt.gapopen, coremin)
         tree_files(False)
         if density_wanted(opt):
             intervals = bf.group_mask(opt.densitywindow, opt.densitymax, want)
@@ -858,12 +925,13 @@ def core_files(bf, opt: argparse.Namespace, names: Sequence[str], ids: Sequence[
             try:
                 if opt.corefiltered is not None:
                     out[opt.corefiltered] = bf.group_concat(cls, n, headers, CONCAT_ALL, formats.CORE_WIDTH, want)[0]
-                if opt.corefilteredsnps is not None or opt.corefilteredsites is not None:
+                if opt.corefilteredsnps is not None or opt.corefilteredsites is not None or opt.corefilteredbranchsites is not None:
                     text, _, sites = bf.group_concat(cls, n, headers, CONCAT_VARIABLE, formats.CORE_WIDTH, want)
+                    site_rows[True] = site_rows_of(sites)
                     if opt.corefilteredsnps is not None:
                         out[opt.corefilteredsnps] = text
                     if opt.corefilteredsites is not None:
-                        out[opt.corefilteredsites] = formats.core_sites_text([(ids[g], names[insts[g][0][0]]) + tuple(insts[g][0][1:]) + (before,) for g, _, before in sites], opt.gapopen, coremin)
+                        out[opt.corefilteredsites] = formats.core_sites_text(site_rows[True], opt.gapopen, coremin)
                 tree_files(True)
             finally:
                 bf.set_masked(False)
@@ -1044,7 +1112,7 @@ def run(argv: Sequence[str], write: Optional[Callable[[str], None]] = None, outd
                 bf.set_wide(True)
             if opt.maf is not None or opt.variants is not None:      # on the final list: after the boundary correction, if that ran
                 files.update(align_unique_blocks(bf, opt, names, nfirst, sys.stderr.write, history))
-            if _given(opt, GROUP_OPTIONS):          # likewise on the final list
+            if _given(opt, GROUP_OPTIONS + BRANCH_OPTIONS):          # likewise on the final list
                 files.update(align_block_groups(bf, opt, names if names is not None else bf.record_names(), sys.stderr.write, blocks))
         if opt.graphfile:
             files["de_bruijn_graph%s.dot" % (str(len(stages)) if opt.allstages else "")] = formats.dot_text(bf.list_edges(last_k))

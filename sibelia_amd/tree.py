@@ -167,19 +167,26 @@ def support(tree: Tree, replicate_trees) -> Dict[int, int]:
     return out
 
 
-def newick(tree: Tree, names: Sequence[str], support: Optional[Dict[int, int]] = None, B: int = 0) -> str:
+def support_label(held: int, B: int) -> str:
+    """the label of an internal edge that `held` of B replicates hold: the percentage, a tie going up"""
+    return "%d" % ((200 * held + B) // (2 * B))
+
+
+def newick(tree: Tree, names: Sequence[str], support: Optional[Dict[int, int]] = None, B: int = 0, lengths: Optional[Dict[int, int]] = None) -> str:
     """the canonical text: from the internal node next to file 0, children by their smallest file, lengths %.9f; with B > 0 every internal
-    node but the top one carries its edge's support in percent, ties going up.  One line, ';' and a line feed"""
+    node but the top one carries its edge's support in percent, ties going up.  One line, ';' and a line feed.  lengths: node -> an
+    integer written in place of the length of the edge above it (--coresnptree: the changes of branches)"""
     check_names(names)
     if len(names) != tree.n:
         raise ValueError("%d names for %d files" % (len(names), tree.n))
     r = _Rooted(tree)
+    above = (lambda v: "%.9f" % r.length[v]) if lengths is None else (lambda v: "%d" % lengths[v])
     text: Dict[int, str] = {}
     stack = [(r.top, False)]
     while stack:
         v, done = stack.pop()
         if v < tree.n:
-            text[v] = "%s:%.9f" % (names[v], r.length[v])
+            text[v] = "%s:%s" % (names[v], above(v))
         elif not done:
             stack.append((v, True))
             stack += [(w, False) for w in r.children[v]]
@@ -188,9 +195,26 @@ def newick(tree: Tree, names: Sequence[str], support: Optional[Dict[int, int]] =
             if v == r.top:
                 text[v] = inner + ";\n"
             else:
-                label = "%d" % ((200 * (support or {}).get(r.mask[v], 0) + B) // (2 * B)) if B > 0 else ""
-                text[v] = "%s%s:%.9f" % (inner, label, r.length[v])
+                label = support_label((support or {}).get(r.mask[v], 0), B) if B > 0 else ""
+                text[v] = "%s%s:%s" % (inner, label, above(v))
     return text[r.top]
+
+
+def branches(tree: Tree):
+    """the edges of a tree in the order its newick text visits the node below them -- preorder from the internal node next to file 0,
+    children by their smallest file, so the edge to file 0 comes first -- as (node below the edge, index of the edge in tree.edges, the
+    files on the side away from the top node as a bit mask, length).  Branch k + 1 of --corebranches is entry k"""
+    r = _Rooted(tree)
+    index = {}
+    for e, (u, v, _) in enumerate(tree.edges):
+        index[(u, v)] = index[(v, u)] = e
+    parent = {w: v for v, kids in r.children.items() for w in kids}
+    out, stack = [], list(reversed(r.children[r.top]))
+    while stack:
+        v = stack.pop()
+        out.append((v, index[(parent[v], v)], r.mask[v], r.length[v]))
+        stack += reversed(r.children[v])
+    return out
 
 
 def tree_text(counts, K, model: str, names: Sequence[str]) -> str:
@@ -273,13 +297,15 @@ def consensus(replicates, B: int):
     return Tree(n, edges), {b: len(held[b]) for b in inner}
 
 
-def tree_files(counts, K, model: str, names: Sequence[str], nj=None, want: Sequence[str] = ("tree", "consensus", "boottrees")):
+def tree_files(counts, K, model: str, names: Sequence[str], nj=None, want: Sequence[str] = ("tree", "consensus", "boottrees"), keep: Optional[dict] = None):
     """counts, K, model, names: as for tree_text -> (the text of tree_text; the consensus of the B replicate trees as newick writes it
     with their support; B lines, the unlabelled newick of replicate 1 .. B), None for a text that `want` does not name, and for the
     consensus without replicates.  nj: a callable, matrices of shape (trees, files, files) -> (edge records (trees, 2 files - 3),
     bipartitions (trees, files - 3)) that joins like neighbour_joining, bit for bit (BlockFinder.nj_batch): it gets all B + 1 matrices
     in one call.  Without it, and above 64 files, every matrix goes through neighbour_joining here: the same texts, byte for byte.  The
-    distances are made here either way, slab after slab, so Saturated and NoSharedColumn rise as they do from tree_text"""
+    distances are made here either way, slab after slab, so Saturated and NoSharedColumn rise as they do from tree_text.  keep: a dict
+    that receives the main tree as "tree" and, where "tree" is wanted and there are replicates, the support of its internal edges as
+    "support" -- what a caller needs to map changes onto the branches of the text without a second neighbour joining"""
     B = len(counts) - 1
     D = np.stack([distances(counts[r], K, model, names) for r in range(B + 1)])
     n = D.shape[1]
@@ -293,7 +319,10 @@ def tree_files(counts, K, model: str, names: Sequence[str], nj=None, want: Seque
         trees = [neighbour_joining(D[r]) for r in range(B + 1)]
         main, reps = trees[0], trees[1:]
         tally = split_tally(np.array([b for t in reps for b in bipartitions(t)], dtype=object)) if "tree" in want else {}
-    text = newick(main, names, {b: tally.get(b, 0) for b in bipartitions(main)} if B else None, B) if "tree" in want else None
+    held = {b: tally.get(b, 0) for b in bipartitions(main)} if B and "tree" in want else None
+    if keep is not None:
+        keep["tree"], keep["support"] = main, held
+    text = newick(main, names, held, B) if "tree" in want else None
     majority = None
     if B and "consensus" in want:
         ctree, held = consensus(reps, B)
